@@ -15,10 +15,17 @@ them and relays rank 0's line (the parent never initialises HIP).  Every rank pr
 (independent work, no collective in the data path; a gloo group carries the barrier, the max-over-ranks
 time and the per-rank reports only).
 
-Prints ONE JSON line (rank 0).  Beside the headline (`value`, BASELINE configs[1]) the line carries
-`roofline` (blur kernel, live HIP events), `roofline_step`, `config3` (32 x 256^3 volumes dealt i % N,
-strong scaling), `config5` (streaming epoch, CPU-tensor contract and device-resident), `ranks`, and at
-N = 1 `blur_microbench`, `config4_sr`, `cpu_baseline`.
+Prints ONE JSON line (rank 0).  A plain run sets up, warms up, times the K steps and reports the headline
+(`value`, BASELINE configs[1]) with `ms_per_step`, `roofline_step` (computed from the timed steps) and `ranks`.
+`--full` adds what takes work of its own: `roofline` (blur kernel, HIP events around the blur launches of every
+4th timed sample), `roofline_kernels` (16 untimed traced samples), `config3` (32 x 256^3 volumes dealt i % N,
+strong scaling), `config5` (streaming epoch, CPU-tensor contract and device-resident), and at N = 1
+`blur_microbench`, `config4_sr`, `cpu_baseline`; the `--no-*` options leave single parts of it out.
+
+`--dump-outputs DIR`: after the timed steps, rank 0 writes the image and labels of its last timed step as
+DIR/image.npy and DIR/labels.npy (float32, flattened; above 2^22 voxels the same fixed, seeded sample of 2^22
+voxels in every run).  The inputs and the sample keys depend only on the arguments, so two builds can be
+compared output for output.
 
 `--dry-plan`: no GPU work at all -- every rank only draws the host plans of its samples (what the Python
 side does per sample); used by the CPU test of the N-rank launcher and as a host-cost probe.
@@ -66,6 +73,11 @@ def parse_args(argv=None):
     ap.add_argument("--no-look-ahead", dest="look_ahead", action="store_false",
                     help="keyed mode: do not name the next sample (its draw job then runs as a launch of its own)")
     ap.add_argument("--dry-plan", action="store_true", help="host plans only, no GPU (launcher test / host-cost probe)")
+    ap.add_argument("--full", action="store_true",
+                    help="also the side measurements: blur roofline, per-launch figures, config3, config5, and at N = 1 the blur "
+                         "microbench, config4_sr and the CPU baseline (a plain run times the headline only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's image and labels (rank 0) to DIR/image.npy, DIR/labels.npy (float32)")
     return ap.parse_args(argv)
 
 
@@ -410,6 +422,40 @@ def cpu_baseline(shape, threads):
             "reference_anchor": REFERENCE_ANCHOR}
 
 
+DUMP_VOXELS = 1 << 22  # voxels per dumped array: 16 MiB of float32 each, 32 MiB for image + labels
+
+
+def dump_outputs(directory, image, labels):
+    """The arrays the timed path handed back in its last step, as float32 .npy files, flattened.  A volume above DUMP_VOXELS
+    voxels is sampled at DUMP_VOXELS sorted flat indices drawn by a fixed seed (the same indices in every run of that size)."""
+    import numpy as np
+    import torch
+
+    out = Path(directory)
+    out.mkdir(parents=True, exist_ok=True)
+    n = image.numel()
+    sel = None
+    if n > DUMP_VOXELS:
+        idx = np.sort(np.random.default_rng(20240601).choice(n, DUMP_VOXELS, replace=False))
+        sel = torch.from_numpy(idx).to(image.device)
+    for name, t in (("image", image), ("labels", labels)):
+        flat = t.reshape(-1)
+        if sel is not None:
+            flat = flat.index_select(0, sel)
+        np.save(out / f"{name}.npy", flat.to(torch.float32).cpu().numpy())
+
+
+def seed_volumes(shape, variants):
+    """make_seed_volumes for several variants at once: the numpy work of one variant is single-threaded and releases the GIL,
+    so one thread per variant cuts that part of a 256^3 run's start-up about fourfold (same arrays)."""
+    from concurrent.futures import ThreadPoolExecutor
+
+    from fetalsyngen_amd.phantom import make_seed_volumes
+
+    with ThreadPoolExecutor(max_workers=len(variants)) as pool:
+        return list(pool.map(lambda v: make_seed_volumes(shape, variant=v), variants))
+
+
 # ----------------------------------------------------------------------------------------------------
 class Ranks:
     """The little cross-rank traffic a benchmark of independent replicas needs (gloo): barrier, max of a time, gather of
@@ -508,7 +554,6 @@ def run(args, rank, world, local):
     from fetalsyngen_amd import sharding
     from fetalsyngen_amd.data.datasets import MemorySynthDataset, SeedBank
     from fetalsyngen_amd.data.staging import PrefetchingStream
-    from fetalsyngen_amd.phantom import make_seed_volumes
 
     _lib.load()  # fail loudly if the HIP library is missing
     if args.tune:
@@ -528,10 +573,12 @@ def run(args, rank, world, local):
     # inputs resident in HBM before any timed region: 4 distinct label volumes (the same four on every rank, so that
     # the batch of config3 does not depend on N); further "subjects" are cheap on-device transforms of these
     base_banks, base_segs = [], []
-    for v in range(4):
-        seg, seeds = make_seed_volumes(shape, variant=v)
+    host = seed_volumes(shape, range(4))
+    while host:
+        seg, seeds = host.pop(0)
         base_banks.append(SeedBank(seeds, device))
         base_segs.append(torch.from_numpy(seg).to(device))
+    del seg, seeds
 
     def subject(k):
         """Label volumes of synthetic subject k: base variant k % 4, rolled 8*(k//4) voxels along y, mirrored in z for odd k//4."""
@@ -547,7 +594,7 @@ def run(args, rank, world, local):
         gen.reserve(shape, samples_in_flight=12)  # memory pool sized for the samples the host keeps in flight
 
     result_extra = {}
-    if rank == 0 and not args.no_microbench:
+    if args.full and rank == 0 and not args.no_microbench:
         result_extra["blur_microbench"] = blur_microbench(shape, device)
 
     streams = [torch.cuda.Stream(device=device) for _ in range(args.streams)] if args.streams > 1 else [None]
@@ -574,8 +621,8 @@ def run(args, rank, world, local):
         return out, seg_d, p
 
     # ---- headline: BASELINE configs[1], W untimed + K timed steps, barrier + synchronize on both sides ----------
-    # blur timing inside the timed region: HIP events recorded on the launch stream around the blur launches of every 4th
-    # sample, inside fsg_sample_run (FetalSynthGen.blur_events / blur_events_every)
+    # --full only: blur timing inside the timed region, HIP events recorded on the launch stream around the blur launches of
+    # every 4th sample, inside fsg_sample_run (FetalSynthGen.blur_events / blur_events_every)
     # Setup, untimed and outside the W warm-up steps the caller asked for: the first sample loads every code object (~240 ms),
     # the next dozen still run with cold interpreter / allocator / clock state (host 300-400 us per sample against 260 later:
     # gpurun_out r4m, tools/warmup_curve.py).  Like prewarm() and reserve() above this is one-off process start-up, so a short
@@ -589,12 +636,14 @@ def run(args, rank, world, local):
     import gc
     gc.collect()
     gc.freeze()
-    gen.blur_events = []
-    gen.blur_events_every = 4  # every 4th sample: each event record is a barrier packet in the launch queue (~5.5 us of bubble)
+    if args.full:
+        gen.blur_events = []
+        gen.blur_events_every = 4  # every 4th sample: each event record is a barrier packet in the launch queue (~5.5 us of bubble)
     for i in range(args.warmup):
         step(i)
     torch.cuda.synchronize()
-    _drop_events(gen.blur_events)
+    if args.full:
+        _drop_events(gen.blur_events)
     R.barrier()
     torch.cuda.synchronize()
     edge = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) if os.environ.get("FSG_BENCH_EDGES") else None
@@ -602,7 +651,7 @@ def run(args, rank, world, local):
     if edge:
         edge[0].record()
     for i in range(args.steps):
-        _o, _s, p = step(args.warmup + i)
+        out_last, seg_last, p = step(args.warmup + i)
         mus_seen.append(p["resample_params"]["spacing"])
     if edge:
         edge[1].record()
@@ -616,100 +665,11 @@ def run(args, rank, world, local):
         print(json.dumps({"edges": {"wall_ms": round(dt_rank * 1e3, 3), "enqueue_done_ms": round(t_enq * 1e3, 3), "sync_done_ms": round(t_sync * 1e3, 3),
                                     "gpu_span_ms": round(edge[0].elapsed_time(edge[1]), 3)}}), file=sys.stderr, flush=True)
 
-    # ---- per-launch times of the same samples' kind, UNTIMED: HIP events behind every launch of 16 further samples ------------
-    gen.blur_events_save, gen.blur_events = gen.blur_events, None
-    gen.stage_traces = []
-    for i in range(16):
-        step(20_000_000 + i)
-    torch.cuda.synchronize()
-    traces, gen.stage_traces = gen.stage_traces, None
-    gen.blur_events = gen.blur_events_save
-    roofline_kernels = stage_rooflines(traces, nvox)
-    for tr in traces:
-        tr.close()
-    # what one event record costs the launch stream by itself (a barrier packet): 33 back-to-back records, median gap.
-    # `us_net` = `us` minus that bubble; the net figures add up to the un-instrumented step (cross-check below).
-    from fetalsyngen_amd import kernels as _K
-    evs = [_lib.load().fsg_event_create() for _ in range(33)]
-    st_raw = _K._stream(torch.device(device))
-    torch.cuda.synchronize()
-    for e in evs:
-        _lib.load().fsg_event_record(e, st_raw)
-    torch.cuda.synchronize()
-    gaps, ms_ = [], ctypes.c_float()
-    for e0, e1 in zip(evs, evs[1:]):
-        _lib.check(_lib.load().fsg_event_elapsed_ms(e0, e1, ctypes.byref(ms_)), "fsg_event_elapsed_ms")
-        gaps.append(ms_.value * 1e3)
-    for e in evs:
-        _lib.load().fsg_event_destroy(e)
-    bubble = float(np.median(gaps))
-    net = 0.0
-    for k_, v_ in roofline_kernels.items():
-        if isinstance(v_, dict):
-            v_["us_net"] = round(max(v_["us"] - bubble, 0.0), 2)
-            v_["frac_net"] = (round(v_["algorithmic_bytes"] / v_["us_net"] / 1e3 / HBM_PEAK_GBS, 4) if v_["us_net"] > 0 else None)
-            net += v_["us_net"] * v_["launches_per_sample"]
-    roofline_kernels["_event_bubble_us"] = round(bubble, 2)
-    roofline_kernels["_sum_us_net_per_sample"] = round(net, 2)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, out_last, seg_last)
+    del out_last, seg_last
 
-    lib = _lib.load()
-    blur_total_ms, sections, lows = 0.0, [], []
-    ms = ctypes.c_float()
-    for e0, e1, pl, low in gen.blur_events:
-        _lib.check(lib.fsg_event_elapsed_ms(e0, e1, ctypes.byref(ms)), "fsg_event_elapsed_ms")
-        blur_total_ms += ms.value
-        sections.append(pl)
-        lows.append(low)
-    _drop_events(gen.blur_events)
-    gen.blur_events = None
-    # What the events bracket.  r03 default: the FUSED pair (csrc/fsg_blur_rs.hip) -- blur and down-sampling of an axis as one
-    # operator: x launch reads N, writes N m0/n0; y,z launch reads N m0/n0, writes M (+ the noise draw).  Unfused
-    # (--tune 16384, or a configuration outside the fused domain): x pass + fused y,z pass, 8 B/voxel each.
     size_v = float(args.size)
-    fused = [bool(lib.fsg_blur_resample_supported(args.size, args.size, args.size, lo[0], lo[1], lo[2],
-                                                  *[2 * dict(sec).get(a_, 0) + 1 for a_ in range(3)])) for sec, lo in zip(sections, lows)]
-    alg_bytes, traffic_bytes, nlaunch, npass = 0.0, 0.0, 0, 0
-    rs_table = None
-    rs_files = sorted((REPO / "profiles").glob("r*_blur_rs_pmc.json"))
-    if rs_files:
-        rs_table = json.loads(rs_files[-1].read_text())["sizes"].get(str(args.size))
-
-    def rs_ratio(prefix, radius):
-        if not rs_table:
-            return None
-        pts = {int(k[len(prefix):].split(",")[0].rstrip(">")): v["traffic_over_algorithmic"] for k, v in rs_table.items()
-               if k.startswith(prefix)}
-        return pts[min(pts, key=lambda r_: abs(r_ - radius))] if pts else None
-
-    traffic_known = True
-    for sec, lo, fz in zip(sections, lows, fused):
-        npass += len(sec)
-        if fz:
-            bx = 4.0 * nvox + 4.0 * nvox * lo[0] / size_v
-            byz = 4.0 * nvox * lo[0] / size_v + 4.0 * lo[0] * lo[1] * lo[2]
-            alg_bytes += bx + byz
-            nlaunch += 2
-            radii = dict(sec)
-            rx = rs_ratio("blur_rs_x_kernel<", radii.get(0, 1))
-            ryz = rs_ratio("blur_rs_yz_kernel<", max(radii.get(1, 1), radii.get(2, 1)))
-            if rx is None or ryz is None:
-                traffic_known = False
-            else:
-                traffic_bytes += rx * bx + ryz * byz
-        else:
-            launches = _blur_launch_plan(sec)
-            alg_bytes += 8.0 * nvox * len(launches)
-            nlaunch += len(launches)
-            t_l, _n = blur_traffic([sec], args.size)
-            if t_l is None:
-                traffic_known = False
-            else:
-                traffic_bytes += t_l * len(launches)
-    us_launch = blur_total_ms * 1e3 / max(nlaunch, 1)
-    bytes_launch = alg_bytes / max(nlaunch, 1)
-    traffic_launch = traffic_bytes / max(nlaunch, 1) if (traffic_known and nlaunch) else None
-    achieved = bytes_launch / us_launch / 1e3 if nlaunch else 0.0
-    n_fused = sum(fused)
     # whole step: SURVEY 8(d) per-kernel algorithmic bytes with the fusions as built (gamma/bias in the warp epilogue: 0; blur
     # and down-sampling per axis; K9+K10 one evaluation): K1 5 + warp 8 (image) + 5 (uint8 label read, float32 label write)
     # + x launch (4 + 4 mu_x) + y,z launch (4 mu_x + 4 mu) + K9 (4 mu + 4) B/voxel, mu_x = m/n, mu = M/N
@@ -737,38 +697,132 @@ def run(args, rank, world, local):
                    "outputs": "fp32 [0,1] image + fp32 labels in HBM", "volumes_per_rank": args.steps,
                    "parallelism": f"{world} independent replicas (no collective)", "streams_per_gpu": args.streams,
                    **({"tuning_flags": args.tune} if args.tune else {})},
-        "roofline": {"bound": "hbm",
-                     "kernel": ("separable blur, fused per axis with the down-sampling (csrc/fsg_blur_rs.hip): x launch "
-                                "(blur_rs_x_kernel) + y,z launch with the noise epilogue (blur_rs_yz_kernel)"
-                                if n_fused == len(sections) and sections else
-                                "separable 3-pass blur = x pass (blur_strided_v4) + fused y,z pass (blur_yz_fused_kernel)")
-                               + "; HIP events on the launch stream around those launches of every 4th timed sample (rank 0)",
-                     "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                     "frac": round(achieved / HBM_PEAK_GBS, 4),
-                     "traffic": (None if traffic_launch is None else int(traffic_launch)),
-                     "us_per_launch": round(us_launch, 2), "launches_timed": nlaunch,
-                     "algorithmic_bytes_per_launch": int(bytes_launch),
-                     "accounting": "bytes one launch must move, averaged over the timed launches: fused x launch 4N + 4N m/n "
-                                   "(volume read once, x-resampled volume written once), fused y,z launch 4N m/n + 4M (M = "
-                                   "low-res voxels of that sample); unfused launches 8 B/voxel.  traffic = those bytes x the "
-                                   "traffic/algorithmic ratio of the launch's kernel in the committed PMC table "
-                                   f"(profiles/{rs_files[-1].name if rs_files else 'none'}: 1.00-1.03)",
-                     "samples_fused": n_fused, "samples_timed": len(sections),
-                     "axis_passes_per_sample": round(npass / max(len(sections), 1), 2),
-                     "launches_per_sample": round(nlaunch / max(len(sections), 1), 2)},
         "roofline_step": {"bound": "hbm", "bytes_per_voxel": "26 + 8*mu_x + 8*mu (K1 5, warp 8 image + 1 uint8 label read + 4 float32 label write, "
                                                              "blur+resample x 4+4mu_x, y,z 4mu_x+4mu, K9/K10 4+4mu)",
                           "mu_mean": round(mu, 4), "mu_x_mean": round(mu_x, 4), "algorithmic_bytes_per_step": int(step_bytes),
                           "achieved": round(step_bytes / (dt / args.steps) / 1e9, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
                           "frac": round(step_bytes / (dt / args.steps) / 1e9 / HBM_PEAK_GBS, 4)},
     }
-    roofline_kernels["_check_sum_net_le_step"] = bool(roofline_kernels["_sum_us_net_per_sample"] <= dt / args.steps * 1e6 * 1.03)
-    result["roofline_kernels"] = roofline_kernels
+    if args.full:
+        # ---- per-launch times of the same samples' kind, UNTIMED: HIP events behind every launch of 16 further samples ------------
+        gen.blur_events_save, gen.blur_events = gen.blur_events, None
+        gen.stage_traces = []
+        for i in range(16):
+            step(20_000_000 + i)
+        torch.cuda.synchronize()
+        traces, gen.stage_traces = gen.stage_traces, None
+        gen.blur_events = gen.blur_events_save
+        roofline_kernels = stage_rooflines(traces, nvox)
+        for tr in traces:
+            tr.close()
+        # what one event record costs the launch stream by itself (a barrier packet): 33 back-to-back records, median gap.
+        # `us_net` = `us` minus that bubble; the net figures add up to the un-instrumented step (cross-check below).
+        from fetalsyngen_amd import kernels as _K
+        evs = [_lib.load().fsg_event_create() for _ in range(33)]
+        st_raw = _K._stream(torch.device(device))
+        torch.cuda.synchronize()
+        for e in evs:
+            _lib.load().fsg_event_record(e, st_raw)
+        torch.cuda.synchronize()
+        gaps, ms_ = [], ctypes.c_float()
+        for e0, e1 in zip(evs, evs[1:]):
+            _lib.check(_lib.load().fsg_event_elapsed_ms(e0, e1, ctypes.byref(ms_)), "fsg_event_elapsed_ms")
+            gaps.append(ms_.value * 1e3)
+        for e in evs:
+            _lib.load().fsg_event_destroy(e)
+        bubble = float(np.median(gaps))
+        net = 0.0
+        for k_, v_ in roofline_kernels.items():
+            if isinstance(v_, dict):
+                v_["us_net"] = round(max(v_["us"] - bubble, 0.0), 2)
+                v_["frac_net"] = (round(v_["algorithmic_bytes"] / v_["us_net"] / 1e3 / HBM_PEAK_GBS, 4) if v_["us_net"] > 0 else None)
+                net += v_["us_net"] * v_["launches_per_sample"]
+        roofline_kernels["_event_bubble_us"] = round(bubble, 2)
+        roofline_kernels["_sum_us_net_per_sample"] = round(net, 2)
+
+        lib = _lib.load()
+        blur_total_ms, sections, lows = 0.0, [], []
+        ms = ctypes.c_float()
+        for e0, e1, pl, low in gen.blur_events:
+            _lib.check(lib.fsg_event_elapsed_ms(e0, e1, ctypes.byref(ms)), "fsg_event_elapsed_ms")
+            blur_total_ms += ms.value
+            sections.append(pl)
+            lows.append(low)
+        _drop_events(gen.blur_events)
+        gen.blur_events = None
+        # What the events bracket.  r03 default: the FUSED pair (csrc/fsg_blur_rs.hip) -- blur and down-sampling of an axis as one
+        # operator: x launch reads N, writes N m0/n0; y,z launch reads N m0/n0, writes M (+ the noise draw).  Unfused
+        # (--tune 16384, or a configuration outside the fused domain): x pass + fused y,z pass, 8 B/voxel each.
+        fused = [bool(lib.fsg_blur_resample_supported(args.size, args.size, args.size, lo[0], lo[1], lo[2],
+                                                      *[2 * dict(sec).get(a_, 0) + 1 for a_ in range(3)])) for sec, lo in zip(sections, lows)]
+        alg_bytes, traffic_bytes, nlaunch, npass = 0.0, 0.0, 0, 0
+        rs_table = None
+        rs_files = sorted((REPO / "profiles").glob("r*_blur_rs_pmc.json"))
+        if rs_files:
+            rs_table = json.loads(rs_files[-1].read_text())["sizes"].get(str(args.size))
+
+        def rs_ratio(prefix, radius):
+            if not rs_table:
+                return None
+            pts = {int(k[len(prefix):].split(",")[0].rstrip(">")): v["traffic_over_algorithmic"] for k, v in rs_table.items()
+                   if k.startswith(prefix)}
+            return pts[min(pts, key=lambda r_: abs(r_ - radius))] if pts else None
+
+        traffic_known = True
+        for sec, lo, fz in zip(sections, lows, fused):
+            npass += len(sec)
+            if fz:
+                bx = 4.0 * nvox + 4.0 * nvox * lo[0] / size_v
+                byz = 4.0 * nvox * lo[0] / size_v + 4.0 * lo[0] * lo[1] * lo[2]
+                alg_bytes += bx + byz
+                nlaunch += 2
+                radii = dict(sec)
+                rx = rs_ratio("blur_rs_x_kernel<", radii.get(0, 1))
+                ryz = rs_ratio("blur_rs_yz_kernel<", max(radii.get(1, 1), radii.get(2, 1)))
+                if rx is None or ryz is None:
+                    traffic_known = False
+                else:
+                    traffic_bytes += rx * bx + ryz * byz
+            else:
+                launches = _blur_launch_plan(sec)
+                alg_bytes += 8.0 * nvox * len(launches)
+                nlaunch += len(launches)
+                t_l, _n = blur_traffic([sec], args.size)
+                if t_l is None:
+                    traffic_known = False
+                else:
+                    traffic_bytes += t_l * len(launches)
+        us_launch = blur_total_ms * 1e3 / max(nlaunch, 1)
+        bytes_launch = alg_bytes / max(nlaunch, 1)
+        traffic_launch = traffic_bytes / max(nlaunch, 1) if (traffic_known and nlaunch) else None
+        achieved = bytes_launch / us_launch / 1e3 if nlaunch else 0.0
+        n_fused = sum(fused)
+        result["roofline"] = {"bound": "hbm",
+                              "kernel": ("separable blur, fused per axis with the down-sampling (csrc/fsg_blur_rs.hip): x launch "
+                                         "(blur_rs_x_kernel) + y,z launch with the noise epilogue (blur_rs_yz_kernel)"
+                                         if n_fused == len(sections) and sections else
+                                         "separable 3-pass blur = x pass (blur_strided_v4) + fused y,z pass (blur_yz_fused_kernel)")
+                                        + "; HIP events on the launch stream around those launches of every 4th timed sample (rank 0)",
+                              "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                              "frac": round(achieved / HBM_PEAK_GBS, 4),
+                              "traffic": (None if traffic_launch is None else int(traffic_launch)),
+                              "us_per_launch": round(us_launch, 2), "launches_timed": nlaunch,
+                              "algorithmic_bytes_per_launch": int(bytes_launch),
+                              "accounting": "bytes one launch must move, averaged over the timed launches: fused x launch 4N + 4N m/n "
+                                            "(volume read once, x-resampled volume written once), fused y,z launch 4N m/n + 4M (M = "
+                                            "low-res voxels of that sample); unfused launches 8 B/voxel.  traffic = those bytes x the "
+                                            "traffic/algorithmic ratio of the launch's kernel in the committed PMC table "
+                                            f"(profiles/{rs_files[-1].name if rs_files else 'none'}: 1.00-1.03)",
+                              "samples_fused": n_fused, "samples_timed": len(sections),
+                              "axis_passes_per_sample": round(npass / max(len(sections), 1), 2),
+                              "launches_per_sample": round(nlaunch / max(len(sections), 1), 2)}
+        roofline_kernels["_check_sum_net_le_step"] = bool(roofline_kernels["_sum_us_net_per_sample"] <= dt / args.steps * 1e6 * 1.03)
+        result["roofline_kernels"] = roofline_kernels
     result.update(result_extra)
 
     # ---- config3: a batch of B volumes dealt i % N (strong scaling), per-sample keys independent of N -------------
     c3 = None
-    if not args.no_config3:
+    if args.full and not args.no_config3:
         B = args.batch_volumes
         mine = list(sharding.shard(B, rank, world))
         subj = {i: subject(i) for i in mine}
@@ -805,7 +859,7 @@ def run(args, rank, world, local):
 
     # ---- config5: streaming epoch into a consumer, (a) reference contract on the CPU, (b) device-resident ----------
     c5 = None
-    if not args.no_config5:
+    if args.full and not args.no_config5:
         ds = MemorySynthDataset(gen, base_segs, base_banks)
         n_stream = args.stream_volumes
         idx = [rank + world * j for j in range(n_stream)]
@@ -856,9 +910,9 @@ def run(args, rank, world, local):
         if c5 is not None:
             result["config5"] = c5
             result["value_cpu_contract"] = c5["cpu_contract"]["volumes_per_s"]
-        if world == 1 and not args.no_sr:
+        if args.full and world == 1 and not args.no_sr:
             result["config4_sr"] = config4_sr(device)
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             threads = min(os.cpu_count() or 1, 16)
             result["cpu_baseline"] = cpu_baseline(shape, threads)
             result["gpu_over_cpu"] = round(result["value"] / result["cpu_baseline"]["value"], 1)
@@ -873,6 +927,8 @@ def main(argv=None):
     args = parse_args(argv)
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if args.steps < 1:
+        raise SystemExit("--steps must be >= 1")
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         return launch_ranks(args, argv)  # parent of N ranks: no GPU call in this process
     rank = int(os.environ.get("RANK", "0"))

@@ -3,8 +3,9 @@
 Pins:
   * tests/golden/inputs_sta21.npz -- header fields, label histogram, voxel sum and a decimated copy of two of the
     reference's bundled volumes (`sub-sta21` dseg, one seed file), written by tests/golden/make_golden.py with
-    its own independent reader.  Where /root/reference is present (the build container) `NiftiReader` reads
-    the very files and must reproduce the fixture.
+    its own independent reader.  The two volumes themselves are stored beside the fixture
+    (tests/golden/sub-sta21_rec-irtk_T2w_dseg*.nii.gz, data only): `NiftiReader` reads them and must
+    reproduce the fixture.
   * hand-built NIfTI-1 headers (LPS-coded, permuted axes, qform-only with qfac = -1, oblique) for
     `io_orientation` / `ras_reorient`, with the expected result written out by hand.
 SimpleITK / monai / nibabel are not importable here: anything beyond these pins is "parity unpinned"
@@ -23,7 +24,6 @@ from hypothesis import strategies as st
 from fetalsyngen_amd.utils.image_reading import NiftiReader, io_orientation, ras_reorient, read_nifti
 
 GOLD = Path(__file__).parent / "golden"
-REF = Path("/root/reference")
 
 
 def _write(path, arr, *, sform=None, qform=None, pixdim=(1.0, 1.0, 1.0), qfac=1.0, gz=True):
@@ -67,11 +67,10 @@ def test_fixture_of_the_reference_bundled_files():
     assert set(np.nonzero(g["seed_hist"])[0]) <= {0} | set(range(20, 30))  # meta label 2 -> sub-clusters 20..29
 
 
-@pytest.mark.skipif(not REF.exists(), reason="the reference's bundled data only exists in the build container")
 def test_reader_reproduces_the_bundled_files():
     g = np.load(GOLD / "inputs_sta21.npz")
     for key in ("dseg", "seed"):
-        path = REF / str(g[f"{key}_relpath"])
+        path = GOLD / Path(str(g[f"{key}_relpath"])).name  # the bundled file, stored as a fixture
         arr, affine, pixdim = read_nifti(path)
         np.testing.assert_array_equal(affine[:3, :], g[f"{key}_srow"].astype(np.float64))
         assert tuple(pixdim) == (0.5, 0.5, 0.5)

@@ -4,8 +4,8 @@
 tag=${1:-check}; out=gpurun_out/$tag; mkdir -p $out
 timeout -k 10 900 python -m pytest tests -m gpu -x -q > $out/tests.log 2>&1; echo "tests rc=$?"; tail -2 $out/tests.log
 bash tools/prof_bench.sh $tag > $out/prof.log 2>&1
-python bench.py --gpus 1 --steps 20 --warmup 5 > $out/bench_driver.json 2> $out/bench_driver.err; echo "driver rc=$?"
-FSG_BENCH_SHARE_GPU0=1 python bench.py --gpus 2 --steps 100 --warmup 10 --stream-volumes 400 > $out/bench_2rank.json 2> $out/bench_2rank.err; echo "2rank rc=$?"
+python bench.py --gpus 1 --steps 20 --warmup 5 --full > $out/bench_driver.json 2> $out/bench_driver.err; echo "driver rc=$?"
+FSG_BENCH_SHARE_GPU0=1 python bench.py --gpus 2 --steps 100 --warmup 10 --full --stream-volumes 400 > $out/bench_2rank.json 2> $out/bench_2rank.err; echo "2rank rc=$?"
 python tools/host_phases.py > $out/host_phases.txt 2>&1
 python - "$out" <<'PY'
 import json, sys
