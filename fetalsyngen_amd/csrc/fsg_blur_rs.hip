@@ -12,8 +12,11 @@
 //        unfused (r02):  blur x 8N + blur y,z 8N + K7 (4N + 4M)            = 21 B/voxel at mu = 0.3
 //        here:           x pass 4N + 4N (m/n)  +  y,z pass 4N (m/n) + 4M   = 10.5 B/voxel
 // Rounding differs from the reference's order by a few ulp of the 0..255 values (the blur's own tolerance is atol 1e-3:
-// conv3d's summation order is unspecified); quirks kept: zero-padded un-renormalised borders, an output whose position is
-// outside (0, n-1] is 0 (lo < 0 in the table), noise added after, negatives clamped.
+// conv3d's summation order is unspecified); quirks kept: zero-padded un-renormalised borders, noise added after, negatives
+// clamped.  Domain: down-sampling tables with m < n on every axis and no output outside (0, n-1] (lo >= 0 throughout; lo
+// strictly increasing; hi = lo or lo + 1: kernels.DeviceTables checks them).  An output at position 0 (the first one of
+// m == n) is "outside" and 0 in the reference; these kernels never write it, so such tables take the unfused path (K7
+// writes it), which is why the entry points refuse m == n.
 //
 // Per axis the arithmetic is the reference's own: B[i] accumulated over ascending taps (fmaf, as fsg_blur.hip), then
 // w_lo * B[lo] + w_hi * B[hi] with separate multiplies and an add (fsg_mix, as fsg_zoom.hip); only the order ACROSS axes differs.
@@ -44,8 +47,8 @@ struct TapsK { float w[RS_KCAP + 3]; };
 
 
 // First output j (of m) whose lower neighbour lo[j] >= l0, for a table whose lo is non-decreasing in j (every plain
-// resampling table: positions delta + j * n / m).  Outputs with lo < 0 ("outside": value 0) sort first.  Wave-uniform
-// result; `guess` may be anything, a good one makes it one ballot.
+// resampling table: positions delta + j * n / m).  Wave-uniform result; `guess` may be anything, a good one makes it one
+// ballot.
 __device__ __forceinline__ int rs_first_output(const fsg_tap* __restrict__ tab, int m, int l0, int guess) {
   const int lane = threadIdx.x & 63;
   int jg = min(max(guess, 0), m);
@@ -106,7 +109,8 @@ __device__ __forceinline__ float rs_rl(float v, int q) {
 
 // A row of the blur's input through a raw buffer descriptor: a row outside the axis (negative offset -> wraps past the
 // descriptor's size, or beyond its end) comes back as zeros from the range check -- the blur's zero padding without a clamped
-// address and four selects per row (descriptor sizes < 2^31 bytes: fsg_blur_resample_supported).
+// address and four selects per row.  Holds only while no offset the kernel forms wraps modulo 2^32 back into range
+// (rs_x_offsets_fit; the y,z kernel's rows are at most 2 KiB, its planes < 2^31 bytes).
 // (the builtin's result is cast as a whole: element access on it directly compiles to a ONE-dword load, hipcc 7.2)
 typedef float rs_f4 __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ float4 rs_row_load(__amdgpu_buffer_rsrc_t r, unsigned byte_offset) {
@@ -152,20 +156,15 @@ __global__ __launch_bounds__(256) void blur_rs_x_kernel(const float4* __restrict
       }
     }
   }
-  // Outputs whose lower neighbour is in [l0, l0 + TL); chunk 0 also owns the "outside" outputs (lo < 0 -> 0).  The tables
-  // are down-sampling tables (m <= n: positions at least one input row apart), so an input row is the lower neighbour of AT
-  // MOST ONE output: a static walk over the chunk's rows with a uniform "does an output sit here" test keeps every register
-  // index a compile-time constant (a switch over the row index is turned into a dynamic index by the optimiser and the
-  // accumulators land in scratch memory).
+  // Outputs whose lower neighbour is in [l0, l0 + TL).  The tables are down-sampling tables (m < n: positions at least one
+  // input row apart, none outside), so an input row is the lower neighbour of AT MOST ONE output: a static walk over the
+  // chunk's rows with a uniform "does an output sit here" test keeps every register index a compile-time constant (a switch
+  // over the row index is turned into a dynamic index by the optimiser and the accumulators land in scratch memory).
   const ChunkTaps ct = rs_chunk_resolve(tab, m, l0, l0 + TL, jg, lt0);
   const LaneTaps lt = ct.t;
   const int jb = ct.jb - ct.shift;  // output of lane 0
   float4* d = dst + c;
   int q = ct.shift;
-  while (q < 63 && rs_rl(lt.lo, q) < 0) {  // outside outputs (only ever at the start of the axis)
-    if (live) d[(size_t)(jb + q) * inner4] = make_float4(0.f, 0.f, 0.f, 0.f);
-    ++q;
-  }
 #pragma unroll
   for (int o = 0; o < TL; ++o) {
     if (rs_rl(lt.lo, q) == l0 + o) {
@@ -191,7 +190,7 @@ __global__ __launch_bounds__(256) void blur_rs_x_kernel(const float4* __restrict
 #define FSG_RSY_BATCH 4
 #endif
 constexpr int RSY_BATCH = FSG_RSY_BATCH;
-constexpr int RSY_TL = FSG_RSY_TL, RSY_NW = FSG_RSY_NW, RSY_IN = RSY_NW * RSY_TL, RSY_WROWS = RSY_TL + 1;  // input y rows per wave / workgroup; output rows a wave can emit (m <= n, + an "outside" one)
+constexpr int RSY_TL = FSG_RSY_TL, RSY_NW = FSG_RSY_NW, RSY_IN = RSY_NW * RSY_TL, RSY_WROWS = RSY_TL + 1;  // input y rows per wave / workgroup; output rows a wave can emit (m < n: at most TL; one spare)
 
 struct NoiseK {
   int mode;  // 0 none, 1 pointer, 2 Philox
@@ -296,10 +295,6 @@ __global__ __launch_bounds__(64 * RSY_NW) void blur_rs_yz_kernel(const float4* _
     jb = ct.jb;
     nrows = min(ct.je - ct.jb, RSY_WROWS);
     int q = ct.shift;  // static walk over the chunk's rows, as in blur_rs_x_kernel
-    while (q < 63 && rs_rl(lt.lo, q) < 0) {
-      if (live && jl0 + q - jb < RSY_WROWS) reinterpret_cast<float4*>(rows + (size_t)(jl0 + q - jb) * pitch + RP)[c] = make_float4(0.f, 0.f, 0.f, 0.f);
-      ++q;
-    }
 #pragma unroll
     for (int o = 0; o < TL; ++o) {
       if (rs_rl(lt.lo, q) == l0 + o) {
@@ -451,6 +446,15 @@ int rs_fill_taps(const float* taps_host, int ntaps, int R, TapsK& K) {
   return 0;
 }
 
+// The x kernel's row offsets (unsigned)l * rowb + colb, colb < rowb = 4 n1 n2 bytes, for l in [-R, 16 ceil(n0 / 16) + R]
+// (chunk l0 loads rows l0 - R .. l0 + TL + R; the last chunk starts at 16 (ceil(n0 / 16) - 1)): the zero padding needs every
+// one outside [0, n0 rowb) that belongs there.  Rows past the end stay past it iff (16 ceil(n0 / 16) + R + 1) rowb <= 2^32;
+// rows before the start land at 2^32 - |l| rowb + colb >= n0 rowb iff (n0 + R) rowb <= 2^32, implied by the first.
+bool rs_x_offsets_fit(int n0, long long inner, int R) {
+  const unsigned long long rows = (unsigned long long)RSX_TL * (unsigned long long)((n0 + RSX_TL - 1) / RSX_TL) + (unsigned)R + 1u;
+  return rows * (unsigned long long)inner * 4ull <= (1ull << 32);
+}
+
 }  // namespace
 
 extern "C" {
@@ -458,11 +462,14 @@ extern "C" {
 int fsg_blur_resample_supported(int n0, int n1, int n2, int m0, int m1, int m2, int ntaps_x, int ntaps_y, int ntaps_z) {
   if (g_tuning_flags & FSG_TUNE_NO_BLUR_RS) return 0;  // A/B switch: every caller then takes the unfused sequence
   if (n0 <= 0 || n1 <= 0 || n2 <= 0 || m0 <= 0 || m1 <= 0 || m2 <= 0) return 0;
-  if (m0 > n0 || m1 > n1 || m2 > n2) return 0;  // down-sampling tables (lo non-decreasing, at most one output per input row + 1)
+  // down-sampling tables (lo strictly increasing: at most one output per input row); m == n would put output 0 at position
+  // 0, "outside", which these kernels never write
+  if (m0 >= n0 || m1 >= n1 || m2 >= n2) return 0;
   for (int nt : {ntaps_x, ntaps_y, ntaps_z})
     if (nt < 3 || (nt & 1) == 0 || nt > RS_KCAP) return 0;
   if ((n2 & 3) || n2 > 512 || ((long long)n1 * n2 & 3)) return 0;
   if ((size_t)n0 * n1 * n2 > ((size_t)1 << 29)) return 0;  // rows are addressed by 32-bit byte offsets in a buffer descriptor < 2^31 bytes
+  if (!rs_x_offsets_fit(n0, (long long)n1 * n2, ntaps_x >> 1)) return 0;  // ... none of which may wrap back into range
   const int Ryz = (ntaps_y > ntaps_z ? ntaps_y : ntaps_z) >> 1;
   if (rs_yz_lds(n2, m2, Ryz) > 64000) return 0;
   return 1;
@@ -472,7 +479,7 @@ int fsg_blur_resample_x_f32(const float* src, int n0, int n1, int n2, const fsg_
                             int ntaps, float* dst, void* stream) {
   if (!src || !dst || src == dst || !tx) return FSG_E_BADARG;
   if (n0 <= 0 || n1 <= 0 || n2 <= 0 || m0 <= 0) return FSG_E_BADARG;
-  if (m0 > n0) return FSG_E_ALIGN;
+  if (m0 >= n0) return FSG_E_ALIGN;
   const int R = ntaps >> 1;
   TapsK K;
   int rc = rs_fill_taps(taps_host, ntaps, R, K);
@@ -480,6 +487,7 @@ int fsg_blur_resample_x_f32(const float* src, int n0, int n1, int n2, const fsg_
   const long long inner = (long long)n1 * n2;
   if ((inner & 3) || ((((uintptr_t)src) | ((uintptr_t)dst)) & 15)) return FSG_E_ALIGN;
   if ((size_t)n0 * inner > ((size_t)1 << 29)) return FSG_E_TOOBIG;  // 32-bit byte offsets in a descriptor < 2^31 bytes
+  if (!rs_x_offsets_fit(n0, inner, R)) return FSG_E_TOOBIG;          // ... that never wrap back into range
   const int inner4 = (int)(inner >> 2);
   hipStream_t st = fsg_stream(stream);
   switch (R) {
@@ -502,7 +510,7 @@ int fsg_blur_resample_yz_noise_f32(const float* src, int m0, int n1, int n2, con
   if (!src || !dst || src == dst || !ty || !tz) return FSG_E_BADARG;
   if (m0 <= 0 || n1 <= 0 || n2 <= 0 || m1 <= 0 || m2 <= 0 || noise_mode < 0 || noise_mode > 2) return FSG_E_BADARG;
   if (noise_mode == 1 && !noise) return FSG_E_BADARG;
-  if (m1 > n1 || m2 > n2) return FSG_E_ALIGN;
+  if (m1 >= n1 || m2 >= n2) return FSG_E_ALIGN;
   const int R = (ntaps_y > ntaps_z ? ntaps_y : ntaps_z) >> 1;  // one radius for both axes: the narrower tap set is zero-padded
   TapsK Ky, Kz;
   int rc = rs_fill_taps(taps_y_host, ntaps_y, R, Ky);

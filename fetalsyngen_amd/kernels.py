@@ -11,7 +11,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .tables import Arena, TAP_DTYPE
+from .tables import Arena, TAP_DTYPE, is_down_table
 
 F32 = torch.float32
 
@@ -92,6 +92,20 @@ def _device_table(tab, device):
     return d
 
 
+_DOWN_INFO: dict = {}  # id(host table) -> (tables.is_down_table, rows it reads: max hi + 1, host table kept alive)
+
+
+def _down_info(tab):
+    hit = _DOWN_INFO.get(id(tab))
+    if hit is not None and hit[2] is tab:
+        return hit[0], hit[1]
+    info = (is_down_table(tab), int(tab["hi"].max()) + 1 if len(tab) else 0)
+    if len(_DOWN_INFO) >= _DEV_TABLES_MAX:
+        _DOWN_INFO.pop(next(iter(_DOWN_INFO)))
+    _DOWN_INFO[id(tab)] = (*info, tab)
+    return info
+
+
 # Bumped by FetalSynthGen once per sample.  A DeviceTables object remembers the epoch it was built in: its upload was enqueued
 # on the launch stream during THAT sample's host phase, so work that is ordered only behind the previous sample (the head of a
 # sample on the library's side stream, fsg_sample_plan::overlap) may read it from the next sample on, not before.
@@ -102,10 +116,15 @@ class DeviceTables:
     """Three per-axis tap tables resident on the device.
 
     Tables produced by the cached builders in `tables.py` are uploaded once per device and reused
-    (the host array object is the cache key); ad-hoc tables are uploaded on first use."""
+    (the host array object is the cache key); ad-hoc tables are uploaded on first use.  `down` / `reach`: per axis, whether
+    the host table is a down-sampling table (tables.is_down_table: what the fused blur + resample kernels assume) and how
+    many source rows it reads."""
 
     def __init__(self, tabs, device, arena: Arena | None = None):
         self.lengths = tuple(len(t) for t in tabs)
+        info = [_down_info(t) for t in tabs]
+        self.down = tuple(i[0] for i in info)
+        self.reach = tuple(i[1] for i in info)
         self.born = _EPOCH[0]
         self._dev = [_device_table(t, device) for t in tabs]
         self.ptrs = tuple(C.c_void_p(d.data_ptr()) for d in self._dev)  # the device copies never move
@@ -550,10 +569,13 @@ def blur_yz(x, taps_y: np.ndarray, taps_z: np.ndarray):
 
 def blur_resample(x, tabs: DeviceTables, taps, noise_std=0.0, noise=None, seed=None, stream_id=0, keep_mid=False):
     """K6 + K7 (+ K8) as the fused pair of launches (fsg_blur_resample_x_f32, fsg_blur_resample_yz_noise_f32): `taps` = the
-    three per-axis Gaussian tap arrays.  None when the configuration is outside the fused kernels' domain."""
+    three per-axis Gaussian tap arrays.  None when the configuration is outside the fused kernels' domain: shapes and radii
+    (fsg_blur_resample_supported), tables that are not down-sampling tables of these axes, an input not 16-byte aligned."""
     _need_gpu(x, noise)
     n0, n1, n2 = _dims3(_f32(x))
     m0, m1, m2 = tabs.lengths
+    if not all(tabs.down) or any(r > n for r, n in zip(tabs.reach, (n0, n1, n2))) or x.data_ptr() & 15:
+        return None
     tp = [np.ascontiguousarray(t, dtype=np.float32) for t in taps]
     lib = _lib.load()
     if not lib.fsg_blur_resample_supported(n0, n1, n2, m0, m1, m2, len(tp[0]), len(tp[1]), len(tp[2])):

@@ -80,6 +80,15 @@ def position_table(pos64: np.ndarray, n_src: int) -> np.ndarray:
     return _pack(lo.numpy(), hi.numpy(), w_lo.numpy(), w_hi.numpy())
 
 
+def is_down_table(tab: np.ndarray) -> bool:
+    """The precondition of the fused blur + down-sampling kernels (csrc/fsg_blur_rs.hip) on one axis's table: every output
+    inside (lo >= 0), lo strictly increasing (an input row is the lower neighbour of at most one output), hi = lo or lo + 1.
+    RandResample's tables for m < n pass; m == n puts output 0 at position 0, outside."""
+    lo = tab["lo"].astype(np.int64)
+    hi = tab["hi"].astype(np.int64)
+    return bool(len(tab) > 0 and lo[0] >= 0 and (np.diff(lo) > 0).all() and ((hi == lo) | (hi == lo + 1)).all())
+
+
 _LOG5 = np.log(5)
 
 

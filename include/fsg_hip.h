@@ -544,10 +544,14 @@ int fsg_sample_run_batch(const fsg_sample_plan* plans, int nplans, void* const* 
  * coefficients (w_lo k[.] + w_hi k[. - 1]) evaluated for the m low-res outputs only; the blurred full-resolution volume is
  * never formed.  Two launches: x (reads N, writes N m0/n0), then y + z + noise (reads N m0/n0, writes M).  Results equal
  * the unfused sequence (fsg_blur_axis_* x3, fsg_resample_noise_f32) up to float32 rounding of a re-ordered linear map --
- * within the blur's own tolerance (atol 1e-3 on the 0..255 scale).  Zero-padded un-renormalised borders, outputs whose
- * position is outside (0, n-1] are 0 (lo < 0 in the table), noise and the clamp at 0 after, as in the reference.
- * taps: odd counts 3..17 (radius 1..8) on all three axes; n2 % 4 == 0, n2 <= 512; otherwise FSG_E_ALIGN (callers then use
- * the unfused entry points).  fsg_blur_resample_supported: 1 when both launches accept the configuration (no GPU call). */
+ * within the blur's own tolerance (atol 1e-3 on the 0..255 scale).  Zero-padded un-renormalised borders, noise and the clamp
+ * at 0 after, as in the reference.  Tables: down-sampling, m < n on every axis (else FSG_E_ALIGN), every output inside
+ * (lo >= 0), lo strictly increasing, hi = lo or lo + 1 (not checked here: kernels.DeviceTables records it); an output
+ * outside (0, n-1] -- output 0 when m == n -- is never written.
+ * taps: odd counts 3..17 (radius 1..8) on all three axes; n2 % 4 == 0, n2 <= 512, the y,z launch's LDS <= 64000 bytes;
+ * otherwise FSG_E_ALIGN (callers then use the unfused entry points).  x launch: FSG_E_TOOBIG unless
+ * (16 ceil(n0 / 16) + R_x + 1) * n1 * n2 * 4 <= 2^32 (its 32-bit row offsets must not wrap).
+ * fsg_blur_resample_supported: 1 when both launches accept the configuration (no GPU call). */
 int fsg_blur_resample_supported(int n0, int n1, int n2, int m0, int m1, int m2, int ntaps_x, int ntaps_y, int ntaps_z);
 int fsg_blur_resample_x_f32(const float* src, int n0, int n1, int n2, const fsg_tap* tx, int m0, const float* taps_host,
                             int ntaps, float* dst, void* stream);

@@ -316,6 +316,26 @@ def test_blur_resample_fused_pair_equals_unfused_and_oracle(K):
     # outside the fused domain (an axis without blur: spacing <= resolution): the caller is told to use the unfused path
     stds, new, _fac, tabs = T.resample_plan((64, 64, 64), np.array([0.5] * 3), np.array([0.5] * 3), 0.5)
     assert K.blur_resample(torch.zeros(64, 64, 64, device=DEV), K.DeviceTables(tabs, DEV), [np.ones(1, np.float32)] * 3) is None
+    # m == n on an axis with a blur: output 0 sits at position 0, "outside" (0 in the reference), which the fused kernels
+    # never write -> refused; the unfused sequence matches the float64 reference and writes that output as exactly 0
+    from tests.util_resample64 import blur_resample64
+
+    shape = (40, 36, 28)
+    x = (rs.rand(*shape) * 255).astype(np.float32)
+    taps = [T.gaussian_taps(s_) for s_ in (1.1, 0.9, 1.3)]
+    for a in range(3):
+        m = [n_ // 2 for n_ in shape]
+        m[a] = shape[a]
+        tabs = [T._resample_axis_table(m[b], shape[b]) for b in range(3)]
+        rt = K.DeviceTables(tabs, DEV)
+        xd = dev(x)
+        assert K.blur_resample(xd, rt, taps) is None, a
+        y = xd
+        for axis in range(3):
+            y = K.blur_axis(y, axis, taps[axis])
+        unfused = host(K.resample_noise(y, rt))
+        np.testing.assert_allclose(unfused, blur_resample64(x, taps, tabs), rtol=RTOL, atol=ATOL)
+        assert (np.take(unfused, 0, axis=a) == 0).all(), a
 
 
 def test_zoom_tile_kernel_equals_row_kernels(K):
