@@ -12,7 +12,6 @@
 #include "fsg_ride.h"
 
 int g_tuning_flags = 0;  // FSG_TUNE_* bits, see fsg_set_tuning
-int g_warp_variant = 0;   // fsg_warp_set_variant
 
 namespace {
 
@@ -170,45 +169,6 @@ __device__ __forceinline__ void row_position(const FsgDeformK& D, const float* s
 }
 
 typedef float float2_u __attribute__((ext_vector_type(2), aligned(4)));
-
-// trilinear gather with the two z-neighbours fetched by one 8-byte load (needs n2 >= 2).
-// Same blend order as sample_linear; when z0 == n2-1 the ceil neighbour is clamped onto z0 as in the
-// reference (its weight is then exactly 0).
-__device__ __forceinline__ float sample_linear_pairs(const float* __restrict__ s, const FsgDeformK& D, float x,
-                                                     float y, float z) {
-  const float hx = (float)(D.n0 - 1), hy = (float)(D.n1 - 1), hz = (float)(D.n2 - 1);
-  const bool ok = (x > 0.f) && (y > 0.f) && (z > 0.f) && (x <= hx) && (y <= hy) && (z <= hz);
-  if (!ok) return 0.f;
-  const float fx = floorf(x), fy = floorf(y), fz = floorf(z);
-  const int x0 = (int)fx, y0 = (int)fy, z0 = (int)fz;
-  int x1 = min(x0 + 1, D.n0 - 1);
-  const int y1 = min(y0 + 1, D.n1 - 1);
-  const float bx = x - fx, by = y - fy, bz = z - fz;
-  const float ax = 1.f - bx, ay = 1.f - by, az = 1.f - bz;
-  int xs0 = x0, xs1 = x1;
-  if (D.flip) { xs0 = D.n0 - 1 - x0; xs1 = D.n0 - 1 - x1; }
-  const int zb = min(z0, D.n2 - 2);
-  const bool hi0 = z0 != zb;  // only when z0 == n2-1: both neighbours are the pair's upper element
-  const float* r00 = s + ((size_t)xs0 * D.n1 + y0) * D.n2 + zb;
-  const float* r10 = s + ((size_t)xs1 * D.n1 + y0) * D.n2 + zb;
-  const float* r01 = s + ((size_t)xs0 * D.n1 + y1) * D.n2 + zb;
-  const float* r11 = s + ((size_t)xs1 * D.n1 + y1) * D.n2 + zb;
-  const float2_u p00 = *reinterpret_cast<const float2_u*>(r00);
-  const float2_u p10 = *reinterpret_cast<const float2_u*>(r10);
-  const float2_u p01 = *reinterpret_cast<const float2_u*>(r01);
-  const float2_u p11 = *reinterpret_cast<const float2_u*>(r11);
-  const float c000 = hi0 ? p00.y : p00.x, c001 = p00.y;
-  const float c100 = hi0 ? p10.y : p10.x, c101 = p10.y;
-  const float c010 = hi0 ? p01.y : p01.x, c011 = p01.y;
-  const float c110 = hi0 ? p11.y : p11.x, c111 = p11.y;
-  const float c00 = c000 * ax + c100 * bx;
-  const float c01 = c001 * ax + c101 * bx;
-  const float c10 = c010 * ax + c110 * bx;
-  const float c11 = c011 * ax + c111 * bx;
-  const float c0 = c00 * ay + c10 * by;
-  const float c1 = c01 * ay + c11 * by;
-  return c0 * az + c1 * bz;
-}
 
 // logical tile id: hardware deals consecutive workgroups round-robin over the 8 XCDs; give every XCD a
 // contiguous range of tiles (= a slab of x planes) so the source planes it gathers from stay in ITS L2.
@@ -666,95 +626,6 @@ __global__ __launch_bounds__(256) void warp_rows_kernel(FsgDeformK D, const int3
   }
 }
 
-// ---- lean per-voxel body on buffer addressing (patch kernel) ------------------------------------------------
-// The patch kernel is instruction-issue bound (~290 wave-instructions per 64 voxels, one per quad-cycle per
-// SIMD; profiles/r01_pmc_warp.md), so this body spends as few instructions as the arithmetic allows:
-//   * raw buffer loads (SGPR descriptor + 32-bit byte offset): no 64-bit address arithmetic, and out-of-range
-//     offsets return 0 instead of faulting, so no index is ever clamped (indices are in range by construction;
-//     the clamp only guarded against NaN positions);
-//   * ONE base offset per voxel; the 2x2x2 neighbours are base +- plane stride, + row stride, and the upper z
-//     neighbour is the second half of each 8-byte load.  Where the reference clamps a neighbour onto the base
-//     (coordinate exactly on the last plane/row/column) its weight is exactly 0, so whichever finite value (or
-//     the 0 of an out-of-range read) sits there contributes +-0: same result.  Only the z edge is re-read with
-//     4-byte loads, because the 8-byte load of the buffer's very last element would straddle its end.
-struct WarpBuf {
-  __amdgpu_buffer_rsrc_t lin, nn;
-  unsigned sx, sy;   // element strides of x and y
-  int dx_bytes;      // +-plane stride in bytes (sign: flip)
-};
-
-template <typename LT>
-__device__ __forceinline__ LT buf_load_label(__amdgpu_buffer_rsrc_t r, unsigned elem);
-template <>
-__device__ __forceinline__ float buf_load_label<float>(__amdgpu_buffer_rsrc_t r, unsigned elem) {
-  return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(r, elem * 4u, 0, 0));
-}
-template <>
-__device__ __forceinline__ uint8_t buf_load_label<uint8_t>(__amdgpu_buffer_rsrc_t r, unsigned elem) {
-  return __builtin_amdgcn_raw_buffer_load_b8(r, elem, 0, 0);
-}
-
-template <typename LT, bool HAS_LIN, bool HAS_NN, bool FAST>
-__device__ __forceinline__ void warp_emit_buf(const FsgDeformK& D, const EpiK& E, const Margins& m, const WarpBuf& B,
-                                              const float* sm, int nf, int i, int j, int k, bool live,
-                                              const fsg_tap& c, const fsg_tap& cb, size_t row,
-                                              float* __restrict__ out_lin, LT* __restrict__ out_nn) {
-  typedef float f2v __attribute__((ext_vector_type(2)));
-  float x, y, z;
-  row_position(D, sm, i, j, k, c, x, y, z);
-  x = x - m.mx;
-  y = y - m.my;
-  z = z - m.mz;
-  if (HAS_NN) {
-    int xi = (int)rintf(x);
-    const int yi = (int)rintf(y), zi = (int)rintf(z);
-    if (D.flip) xi = D.n0 - 1 - xi;
-    const LT l = buf_load_label<LT>(B.nn, (unsigned)xi * B.sx + (unsigned)yi * B.sy + (unsigned)zi);
-    if (live) out_nn[row + k] = l;
-  }
-  if (HAS_LIN) {
-    const bool ok = (x > 0.f) && (y > 0.f) && (z > 0.f);  // x <= n-1 etc. hold by construction (clamped)
-    const float fx = floorf(x), fy = floorf(y), fz = floorf(z);
-    int x0 = (int)fx;
-    const int y0 = (int)fy, z0 = (int)fz;
-    const float bx = x - fx, by = y - fy, bz = z - fz;
-    const float ax = 1.f - bx, ay = 1.f - by, az = 1.f - bz;
-    if (D.flip) x0 = D.n0 - 1 - x0;
-    const unsigned o = ((unsigned)x0 * B.sx + (unsigned)y0 * B.sy + (unsigned)z0) * 4u;
-    const unsigned oy = B.sy * 4u;
-    f2v p00 = {0.f, 0.f}, p10 = {0.f, 0.f}, p01 = {0.f, 0.f}, p11 = {0.f, 0.f};
-    if (ok) {  // voxels that sample outside the volume (clamped onto a 0-face) need no data
-      p00 = __builtin_bit_cast(f2v, __builtin_amdgcn_raw_buffer_load_b64(B.lin, o, 0, 0));
-      p10 = __builtin_bit_cast(f2v, __builtin_amdgcn_raw_buffer_load_b64(B.lin, o + (unsigned)B.dx_bytes, 0, 0));
-      p01 = __builtin_bit_cast(f2v, __builtin_amdgcn_raw_buffer_load_b64(B.lin, o + oy, 0, 0));
-      p11 = __builtin_bit_cast(f2v, __builtin_amdgcn_raw_buffer_load_b64(B.lin, o + (unsigned)B.dx_bytes + oy, 0, 0));
-    }
-    if (ok && z0 >= D.n2 - 1) {  // rare (z exactly on the last column): single-element reads, upper neighbour unused
-      p00.x = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(B.lin, o, 0, 0));
-      p10.x = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(B.lin, o + (unsigned)B.dx_bytes, 0, 0));
-      p01.x = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(B.lin, o + oy, 0, 0));
-      p11.x = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(B.lin, o + (unsigned)B.dx_bytes + oy, 0, 0));
-      p00.y = p00.x; p10.y = p10.x; p01.y = p01.x; p11.y = p11.x;
-    }
-    const float c00 = p00.x * ax + p10.x * bx;
-    const float c01 = p00.y * ax + p10.y * bx;
-    const float c10 = p01.x * ax + p11.x * bx;
-    const float c11 = p01.y * ax + p11.y * bx;
-    const float c0 = c00 * ay + c10 * by;
-    const float c1 = c01 * ay + c11 * by;
-    float v = ok ? (c0 * az + c1 * bz) : 0.f;
-    if (E.gamma > 0.f) {
-      if (FAST) v = 300.0f * __builtin_amdgcn_exp2f(E.gamma * (__builtin_amdgcn_logf(v) - 8.2288186904958804f));
-      else v = 300.0f * powf(v / 300.0f, E.gamma);
-    }
-    if (E.bias) {
-      const float bval = fsg_mix(cb.w_lo, sm[nf + cb.lo], cb.w_hi, sm[nf + cb.hi]);
-      v = v * (FAST ? __builtin_amdgcn_exp2f(bval * 1.4426950408889634f) : expf(bval));
-    }
-    if (live) out_lin[row + k] = v;
-  }
-}
-
 // ---- patch variant: 16 waves sweep a 4 x 4 patch of adjacent rows in lockstep ----------------------------
 // Cost model (profiles/r01_gather_cost_ubench.txt): a gather costs ~10.7 cycles of the CU's fill path per
 // 128-B line that misses L1, whatever its width.  Output rows (i..i+3, j..j+3) read source rows that
@@ -769,7 +640,7 @@ constexpr int PATCH_ROWCAP = 128;
 constexpr int PATCH_NQ = FSG_PATCH_NQ;  // 64-voxel chunks per lane and lockstep step (2: 174 us against 135 us -- the L1 working set doubles)
 constexpr int PATCH_TZCAP = 512;  // z extent whose taps are staged in LDS (2 x 8 KB)
 
-template <typename LT, bool HAS_LIN, bool HAS_NN, bool FAST, bool BUF>
+template <typename LT, bool HAS_LIN, bool HAS_NN, bool FAST>
 __global__ __launch_bounds__(1024, 8) void warp_patch_kernel(FsgDeformK D, const int32_t* __restrict__ mm6,
                                                           const float* __restrict__ src_lin,
                                                           float* __restrict__ out_lin,
@@ -805,13 +676,6 @@ __global__ __launch_bounds__(1024, 8) void warp_patch_kernel(FsgDeformK D, const
   }
   __syncthreads();  // rows are wave-private, the z taps were written by every wave
   const size_t row = ((size_t)i * D.n1 + j) * D.n2;
-  const unsigned nvox = (unsigned)D.n0 * (unsigned)D.n1 * (unsigned)D.n2;
-  WarpBuf B;
-  B.lin = __builtin_amdgcn_make_buffer_rsrc((void*)src_lin, 0, HAS_LIN ? nvox * 4u : 0u, 0x00020000);
-  B.nn = __builtin_amdgcn_make_buffer_rsrc((void*)src_nn, 0, HAS_NN ? nvox * (unsigned)sizeof(LT) : 0u, 0x00020000);
-  B.sy = (unsigned)D.n2;
-  B.sx = (unsigned)D.n1 * (unsigned)D.n2;
-  B.dx_bytes = D.flip ? -(int)(B.sx * 4u) : (int)(B.sx * 4u);
   auto tap_at = [&](const int4* lds, const fsg_tap* tab, bool on, int k) {
     // NB: written as `if`, not `cond ? table[k] : none`: the ternary makes hipcc scalarise the 16-byte entry
     // into eight branchy dword loads (+35 % kernel time, measured)
@@ -822,102 +686,20 @@ __global__ __launch_bounds__(1024, 8) void warp_patch_kernel(FsgDeformK D, const
     }
     return c;
   };
-  if (BUF) {
-    for (int kb = 0; kb < D.n2; kb += FSG_WAVE) {
-      const int kk = kb + lane;
-      const int k = min(kk, D.n2 - 1);
-      const fsg_tap c = tap_at(s_tz, D.tz, D.field != nullptr, k), cb = tap_at(s_bz, E.bz, E.bias != nullptr, k);
-      warp_emit_buf<LT, HAS_LIN, HAS_NN, FAST>(D, E, m, B, sm, nf, i, j, k, live_row && kk < D.n2, c, cb, row, out_lin,
-                                               out_nn);
-      __syncthreads();  // keep the 16 waves on the same z chunk: bounded L1 working set, shared misses
-    }
-  } else {
-    // PATCH_NQ chunks of 64 voxels per step and lane: all their gathers are in flight before the first blend
-    for (int kb = 0; kb < D.n2; kb += PATCH_NQ * FSG_WAVE) {
-      const int kk = kb + lane;
-      fsg_tap ck[4] = {none, none, none, none}, cbk[4] = {none, none, none, none};
-#pragma unroll
-      for (int q = 0; q < PATCH_NQ; ++q) {
-        const int k = min(kk + 64 * q, D.n2 - 1);
-        ck[q] = tap_at(s_tz, D.tz, D.field != nullptr, k);
-        cbk[q] = tap_at(s_bz, E.bz, E.bias != nullptr, k);
-      }
-      if (live_row)
-        warp_emitN<LT, HAS_LIN, HAS_NN, FAST, 0, PATCH_NQ>(D, E, m, sm, nf, i, j, kk, ck, cbk, row, src_lin, out_lin, src_nn,
-                                                           out_nn);
-      __syncthreads();  // keep the 16 waves on the same z chunks: bounded L1 working set, shared misses
-    }
-  }
-}
-
-// ---- tile variant: the 16 waves sweep a PI x PJ patch of rows in lockstep, KZ voxels of every row per step ------
-// The patch kernel above gives a wave 64 consecutive z voxels of ONE row: at the rotations the generator draws
-// (<= 20 degrees about every axis) the source positions of such a run drift by up to 64 * sin(theta) = 13-20 source
-// rows in x and in y, so one gather touches ~30 different 128-B lines and uses a few voxels of each.  Here a wave
-// covers RJ = 64 / KZ adjacent rows x KZ voxels: the drift inside a step is KZ * sin(theta), the footprint of the
-// workgroup's PI x PJ x KZ brick of outputs is a compact block of source rows that the next step (same rows, next
-// KZ voxels) continues along the same cache lines.  Same per-voxel arithmetic (warp_emitN), bit-identical output.
-template <typename LT, bool HAS_LIN, bool HAS_NN, bool FAST, int KZ, int WI>
-__global__ __launch_bounds__(1024, 8) void warp_tile_kernel(FsgDeformK D, const int32_t* __restrict__ mm6,
-                                                         const float* __restrict__ src_lin,
-                                                         float* __restrict__ out_lin,
-                                                         const LT* __restrict__ src_nn, LT* __restrict__ out_nn,
-                                                         EpiK E) {
-  constexpr int RJ = 64 / KZ;   // rows (along j) per wave
-  constexpr int WJ = 16 / WI;   // waves along j
-  constexpr int PI = WI, PJ = WJ * RJ;
-  __shared__ float sm_all[PI * PJ][PATCH_ROWCAP];
-  __shared__ int4 s_tz[PATCH_TZCAP], s_bz[PATCH_TZCAP];
-  const bool taps_lds = D.n2 <= PATCH_TZCAP;
-  if (taps_lds) {
-    for (int t = threadIdx.x; t < D.n2; t += 1024) {
-      if (D.field) s_tz[t] = *reinterpret_cast<const int4*>(D.tz + t);
-      if (E.bias) s_bz[t] = *reinterpret_cast<const int4*>(E.bz + t);
-    }
-  }
-  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
-  const int tiles_j = (D.n1 + PJ - 1) / PJ;
-  const int tile = xcd_tile(blockIdx.x, gridDim.x);
-  const int wi = wave / WJ, wj = wave - wi * WJ;
-  const int i_raw = (tile / tiles_j) * PI + wi;
-  const int j_wave = (tile % tiles_j) * PJ + wj * RJ;
-  const int rj = lane / KZ, kz = lane - rj * KZ;
-  const int j_raw = j_wave + rj;
-  const bool live_row = i_raw < D.n0 && j_raw < D.n1;
-  const int i = min(i_raw, D.n0 - 1), j = min(j_raw, D.n1 - 1);
-  const Margins m = load_margins(mm6);
-  const int nf = D.field ? 3 * D.f2 : 0;
-  const int need = nf + (E.bias ? E.b2 : 0);
-  const fsg_tap none = fsg_tap{0, 0, 0.f, 0.f};
-  if (need) {
-    const bool onfly = D.rows == nullptr;
-    const fsg_tap ax = (onfly && D.field) ? uniform_tap(D.tx, i) : none;
-    const fsg_tap abx = (onfly && E.bias) ? uniform_tap(E.bx, i) : none;
-#pragma unroll
-    for (int r = 0; r < RJ; ++r)  // every row of the wave is staged by all 64 lanes
-      stage_row(D, E, i, min(j_wave + r, D.n1 - 1), nf, need, ax, abx, sm_all[wave * RJ + r], lane);
-  }
-  __syncthreads();
-  const float* sm = sm_all[wave * RJ + rj];
-  const size_t row = ((size_t)i * D.n1 + j) * D.n2;
-  auto tap_at = [&](const int4* lds, const fsg_tap* tab, bool on, int k) {
-    fsg_tap c = none;
-    if (on) {
-      if (taps_lds) { const int4 v = lds[k]; c = fsg_tap{v.x, v.y, __builtin_bit_cast(float, v.z), __builtin_bit_cast(float, v.w)}; }
-      else c = tab[k];
-    }
-    return c;
-  };
-  for (int kb = 0; kb < D.n2; kb += KZ) {
-    const int kk = kb + kz;
-    const int k = min(kk, D.n2 - 1);
+  // PATCH_NQ chunks of 64 voxels per step and lane: all their gathers are in flight before the first blend
+  for (int kb = 0; kb < D.n2; kb += PATCH_NQ * FSG_WAVE) {
+    const int kk = kb + lane;
     fsg_tap ck[4] = {none, none, none, none}, cbk[4] = {none, none, none, none};
-    ck[0] = tap_at(s_tz, D.tz, D.field != nullptr, k);
-    cbk[0] = tap_at(s_bz, E.bz, E.bias != nullptr, k);
-    // lanes past the end of the row or of the patch recompute a live voxel and do not store (kbase >= n2 disables stores)
-    warp_emitN<LT, HAS_LIN, HAS_NN, FAST, 0, 1>(D, E, m, sm, nf, i, j, (live_row && kk < D.n2) ? kk : (D.n2 + kk), ck, cbk, row,
-                                                src_lin, out_lin, src_nn, out_nn);
-    __syncthreads();  // the 16 waves stay on the same z slab: the brick's source block is what L1 holds
+#pragma unroll
+    for (int q = 0; q < PATCH_NQ; ++q) {
+      const int k = min(kk + 64 * q, D.n2 - 1);
+      ck[q] = tap_at(s_tz, D.tz, D.field != nullptr, k);
+      cbk[q] = tap_at(s_bz, E.bz, E.bias != nullptr, k);
+    }
+    if (live_row)
+      warp_emitN<LT, HAS_LIN, HAS_NN, FAST, 0, PATCH_NQ>(D, E, m, sm, nf, i, j, kk, ck, cbk, row, src_lin, out_lin, src_nn,
+                                                         out_nn);
+    __syncthreads();  // keep the 16 waves on the same z chunks: bounded L1 working set, shared misses
   }
 }
 
@@ -1039,331 +821,6 @@ __global__ __launch_bounds__(256) void warp_kernel(FsgDeformK D, const int32_t* 
   }
 }
 
-// =================================================================================================
-// Brick warp kernel: LDS staging of the source bounding box.
-//
-// A block of 256 threads produces an 8 x 8 x 16 brick of the output grid (4 consecutive z per thread):
-//   0. the brick's 8+8+16 table entries and the <= 4^3 coarse-grid nodes it touches go to LDS;
-//   1. every thread evaluates the sampling position of its 4 voxels (reference operation order) and the
-//      block reduces the integer bounding box of all 2x2x2 neighbourhoods (wave shuffles -> LDS atomics);
-//   2. the bounding box of the intensity volume (and of the uint8 label volume) is copied to LDS with
-//      coalesced 16-byte loads -- every source cache line is fetched once per brick instead of once per
-//      gather instruction that touches it (profiles/r01_pmc_warp.md);
-//   3. the trilinear neighbourhoods and the nearest label are read from LDS, blended in the reference's
-//      order, gamma/bias applied, and 4 voxels are stored with one 16-byte store.
-// Bricks whose box does not fit (extreme deformations) or whose coarse window exceeds 4 nodes per axis take
-// the same arithmetic through direct global gathers.  Results are bit-identical to the other warp kernels.
-// STATUS (r01): correct but not yet faster -- 255-265 us vs 175 us for the patch kernel at 256^3: with
-// 48 KiB of LDS only 3 workgroups fit a CU and each brick is a chain of 2 dependent global round trips
-// + 3 barriers, and an 8x8x16 brick's box is ~7x its own volume.  Opt-in via FSG_TUNE_BRICK; the plan in
-// DESIGN.md section 7 (persistent workgroups that prefetch the next brick's box) builds on this kernel.
-// =================================================================================================
-constexpr int BRI = 8, BRJ = 8, BRK = 16;
-constexpr int BR_CAP = 9216;   // floats of LDS for the intensity box (36 KiB)
-constexpr int BR_W = 4;        // coarse nodes per axis held in LDS
-
-struct BrickLds {
-  float box[BR_CAP];
-  uint32_t lab[BR_CAP / 4];
-  float nodes_f[BR_W * BR_W * BR_W * 3];
-  float nodes_b[BR_W * BR_W * BR_W];
-  fsg_tap tap[32];   // [0,8) x, [8,16) y, [16,32) z of the displacement tables
-  fsg_tap btap[32];  // same for the bias tables
-  int bb[6];         // min x,y,z, max x,y,z of the neighbourhoods
-};
-
-__device__ __forceinline__ float sel4(const float (&u)[BR_W], int idx) {
-  float r = u[0];
-  r = idx == 1 ? u[1] : r;
-  r = idx == 2 ? u[2] : r;
-  r = idx == 3 ? u[3] : r;
-  return r;
-}
-
-__device__ __forceinline__ int wave_min_i(int v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = min(v, __shfl_xor(v, o, FSG_WAVE));
-  return v;
-}
-__device__ __forceinline__ int wave_max_i(int v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = max(v, __shfl_xor(v, o, FSG_WAVE));
-  return v;
-}
-
-// x/y interpolation of the LDS node window for the nodes zs = 0..nzw-1 of one channel
-template <int NCH>
-__device__ __forceinline__ void window_xy(const float* nodes, int nyw, int nzw, int ch, const fsg_tap& a, int alo,
-                                          int ahi, const fsg_tap& b, int blo, int bhi, float (&u)[BR_W]) {
-#pragma unroll
-  for (int zs = 0; zs < BR_W; ++zs) {
-    u[zs] = 0.f;
-    if (zs < nzw) {
-      const float f00 = nodes[((alo * nyw + blo) * nzw + zs) * NCH + ch];
-      const float f10 = nodes[((ahi * nyw + blo) * nzw + zs) * NCH + ch];
-      const float f01 = nodes[((alo * nyw + bhi) * nzw + zs) * NCH + ch];
-      const float f11 = nodes[((ahi * nyw + bhi) * nzw + zs) * NCH + ch];
-      u[zs] = fsg_mix(b.w_lo, fsg_mix(a.w_lo, f00, a.w_hi, f10), b.w_hi, fsg_mix(a.w_lo, f01, a.w_hi, f11));
-    }
-  }
-}
-
-__device__ __forceinline__ void affine_clamp(const FsgDeformK& D, float px, float py, float pz, float& x, float& y,
-                                             float& z) {
-  x = D.A[0] * px + D.A[1] * py + D.A[2] * pz + D.c2[0];
-  y = D.A[3] * px + D.A[4] * py + D.A[5] * pz + D.c2[1];
-  z = D.A[6] * px + D.A[7] * py + D.A[8] * pz + D.c2[2];
-  const float hx = (float)(D.n0 - 1), hy = (float)(D.n1 - 1), hz = (float)(D.n2 - 1);
-  if (x < 0.f) x = 0.f;
-  if (y < 0.f) y = 0.f;
-  if (z < 0.f) z = 0.f;
-  if (x > hx) x = hx;
-  if (y > hy) y = hy;
-  if (z > hz) z = hz;
-}
-
-template <typename LD, bool HAS_LIN, bool HAS_NN, bool FAST>
-__global__ __launch_bounds__(256) void warp_brick_kernel(FsgDeformK D, const int32_t* __restrict__ mm6,
-                                                         const float* __restrict__ src_lin,
-                                                         float* __restrict__ out_lin,
-                                                         const uint8_t* __restrict__ src_nn,
-                                                         LD* __restrict__ out_nn, EpiK E) {
-  __shared__ __attribute__((aligned(16))) BrickLds S;
-  const int t = threadIdx.x;
-  const int nbk = (D.n2 + BRK - 1) / BRK, nbj = (D.n1 + BRJ - 1) / BRJ;
-  int tile = xcd_tile(blockIdx.x, gridDim.x);
-  const int kb = tile % nbk;
-  tile /= nbk;
-  const int jb = tile % nbj, ib = tile / nbj;
-  const int i0 = ib * BRI, j0 = jb * BRJ, k0 = kb * BRK;
-  const int k4 = t & 3, jj = (t >> 2) & 7, ii = t >> 5;
-  const int i = min(i0 + ii, D.n0 - 1), j = min(j0 + jj, D.n1 - 1);
-  const bool live_ij = (i0 + ii < D.n0) && (j0 + jj < D.n1);
-  const Margins m = load_margins(mm6);
-
-  // ---- 0. tables and coarse nodes of this brick -------------------------------------------------
-  if (t < 32) {
-    const fsg_tap none = fsg_tap{0, 0, 0.f, 0.f};
-    fsg_tap a = none, b = none;
-    if (t < 8) {
-      const int q = min(i0 + t, D.n0 - 1);
-      if (D.field) a = D.tx[q];
-      if (E.bias) b = E.bx[q];
-    } else if (t < 16) {
-      const int q = min(j0 + t - 8, D.n1 - 1);
-      if (D.field) a = D.ty[q];
-      if (E.bias) b = E.by[q];
-    } else {
-      const int q = min(k0 + t - 16, D.n2 - 1);
-      if (D.field) a = D.tz[q];
-      if (E.bias) b = E.bz[q];
-    }
-    S.tap[t] = a;
-    S.btap[t] = b;
-  }
-  if (t < 3) { S.bb[t] = 0x7FFFFFFF; S.bb[3 + t] = -1; }
-  __syncthreads();
-  // windows (tables are non-decreasing in the output index)
-  const int xw0 = S.tap[0].lo, yw0 = S.tap[8].lo, zw0 = S.tap[16].lo;
-  const int nxw = S.tap[7].hi - xw0 + 1, nyw = S.tap[15].hi - yw0 + 1, nzw = S.tap[31].hi - zw0 + 1;
-  const int bxw0 = S.btap[0].lo, byw0 = S.btap[8].lo, bzw0 = S.btap[16].lo;
-  const int nbxw = S.btap[7].hi - bxw0 + 1, nbyw = S.btap[15].hi - byw0 + 1, nbzw = S.btap[31].hi - bzw0 + 1;
-  const bool win_ok = (!D.field || (nxw <= BR_W && nyw <= BR_W && nzw <= BR_W)) &&
-                      (!E.bias || (nbxw <= BR_W && nbyw <= BR_W && nbzw <= BR_W));
-  if (win_ok) {
-    if (D.field) {
-      const int nn3 = nxw * nyw * nzw * 3;
-      if (t < nn3) {
-        const int c = t % 3;
-        int r = t / 3;
-        const int zz = r % nzw;
-        r /= nzw;
-        const int yy = r % nyw, xx = r / nyw;
-        S.nodes_f[t] = D.field[(((size_t)(xw0 + xx) * D.f1 + (yw0 + yy)) * D.f2 + (zw0 + zz)) * 3 + c];
-      }
-    }
-    if (E.bias) {
-      const int nb3 = nbxw * nbyw * nbzw;
-      if (t >= 192 && t - 192 < nb3) {
-        int r = t - 192;
-        const int zz = r % nbzw;
-        r /= nbzw;
-        const int yy = r % nbyw, xx = r / nbyw;
-        S.nodes_b[t - 192] = E.bias[((size_t)(bxw0 + xx) * E.b1 + (byw0 + yy)) * E.b2 + (bzw0 + zz)];
-      }
-    }
-  }
-  __syncthreads();
-
-  // ---- 1. positions of this thread's 4 voxels ------------------------------------------------------
-  float x[4], y[4], z[4], bval[4];
-  {
-    float ux[BR_W], uy[BR_W], uz[BR_W], ub[BR_W];
-    const fsg_tap a = S.tap[ii], b = S.tap[8 + jj];
-    if (D.field && win_ok) {
-      window_xy<3>(S.nodes_f, nyw, nzw, 0, a, a.lo - xw0, a.hi - xw0, b, b.lo - yw0, b.hi - yw0, ux);
-      window_xy<3>(S.nodes_f, nyw, nzw, 1, a, a.lo - xw0, a.hi - xw0, b, b.lo - yw0, b.hi - yw0, uy);
-      window_xy<3>(S.nodes_f, nyw, nzw, 2, a, a.lo - xw0, a.hi - xw0, b, b.lo - yw0, b.hi - yw0, uz);
-    }
-    if (E.bias && win_ok) {
-      const fsg_tap ab = S.btap[ii], bb = S.btap[8 + jj];
-      window_xy<1>(S.nodes_b, nbyw, nbzw, 0, ab, ab.lo - bxw0, ab.hi - bxw0, bb, bb.lo - byw0, bb.hi - byw0, ub);
-    }
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      const int kq = 4 * k4 + q;
-      const int k = min(k0 + kq, D.n2 - 1);
-      bval[q] = 0.f;
-      if (win_ok) {
-        float px = (float)i - D.cen[0], py = (float)j - D.cen[1], pz = (float)k - D.cen[2];
-        if (D.field) {
-          const fsg_tap c = S.tap[16 + kq];
-          const int cl = c.lo - zw0, ch = c.hi - zw0;
-          px = px + fsg_mix(c.w_lo, sel4(ux, cl), c.w_hi, sel4(ux, ch));
-          py = py + fsg_mix(c.w_lo, sel4(uy, cl), c.w_hi, sel4(uy, ch));
-          pz = pz + fsg_mix(c.w_lo, sel4(uz, cl), c.w_hi, sel4(uz, ch));
-        }
-        affine_clamp(D, px, py, pz, x[q], y[q], z[q]);
-        if (E.bias) {
-          const fsg_tap cb = S.btap[16 + kq];
-          bval[q] = fsg_mix(cb.w_lo, sel4(ub, cb.lo - bzw0), cb.w_hi, sel4(ub, cb.hi - bzw0));
-        }
-      } else {
-        fsg_position(D, i, j, k, x[q], y[q], z[q]);
-        if (E.bias) bval[q] = fsg_tab_interp<1>(E.bias, E.b1, E.b2, 0, E.bx[i], E.by[j], E.bz[k]);
-      }
-      x[q] = x[q] - m.mx;
-      y[q] = y[q] - m.my;
-      z[q] = z[q] - m.mz;
-    }
-  }
-
-  // ---- 1b. bounding box of all neighbourhoods --------------------------------------------------------
-  int lo0 = 0x7FFFFFFF, lo1 = 0x7FFFFFFF, lo2 = 0x7FFFFFFF, hi0 = -1, hi1 = -1, hi2 = -1;
-#pragma unroll
-  for (int q = 0; q < 4; ++q) {
-    const int a0 = min(max((int)floorf(x[q]), 0), D.n0 - 1), a1 = min(max((int)floorf(y[q]), 0), D.n1 - 1),
-              a2 = min(max((int)floorf(z[q]), 0), D.n2 - 1);
-    lo0 = min(lo0, a0); hi0 = max(hi0, min(a0 + 1, D.n0 - 1));
-    lo1 = min(lo1, a1); hi1 = max(hi1, min(a1 + 1, D.n1 - 1));
-    lo2 = min(lo2, a2); hi2 = max(hi2, min(a2 + 1, D.n2 - 1));
-  }
-  lo0 = wave_min_i(lo0); lo1 = wave_min_i(lo1); lo2 = wave_min_i(lo2);
-  hi0 = wave_max_i(hi0); hi1 = wave_max_i(hi1); hi2 = wave_max_i(hi2);
-  if ((t & 63) == 0) {
-    atomicMin(&S.bb[0], lo0); atomicMin(&S.bb[1], lo1); atomicMin(&S.bb[2], lo2);
-    atomicMax(&S.bb[3], hi0); atomicMax(&S.bb[4], hi1); atomicMax(&S.bb[5], hi2);
-  }
-  __syncthreads();
-  const int X0 = S.bb[0], Y0 = S.bb[1], Z0 = S.bb[2] & ~3;  // z start aligned to 16 bytes
-  const int ex = S.bb[3] - X0 + 1, ey = S.bb[4] - Y0 + 1;
-  const int ez4 = ((S.bb[5] - Z0) >> 2) + 1;                // 16-byte chunks per row
-  const int pitch = ez4 * 4;
-  const int nchunk = ex * ey * ez4;
-  const bool fits = nchunk * 4 <= BR_CAP;
-
-  // ---- 2. copy the box to LDS ----------------------------------------------------------------------------
-  if (fits) {
-    const float inv_e = 1.0f / (float)ez4, inv_y = 1.0f / (float)ey;
-    for (int c = t; c < nchunk; c += 256) {
-      int r = (int)((float)c * inv_e);
-      if (r * ez4 > c) --r; else if ((r + 1) * ez4 <= c) ++r;
-      const int q = c - r * ez4;
-      int rx = (int)((float)r * inv_y);
-      if (rx * ey > r) --rx; else if ((rx + 1) * ey <= r) ++rx;
-      const int ry = r - rx * ey;
-      int xs = X0 + rx;
-      if (D.flip) xs = D.n0 - 1 - xs;
-      const size_t g = ((size_t)xs * D.n1 + (Y0 + ry)) * D.n2 + Z0 + 4 * q;
-      if (HAS_LIN) reinterpret_cast<float4*>(S.box)[c] = *reinterpret_cast<const float4*>(src_lin + g);
-      if (HAS_NN) S.lab[c] = *reinterpret_cast<const uint32_t*>(src_nn + g);
-    }
-  }
-  __syncthreads();
-
-  // ---- 3. gather, blend, epilogue, store ------------------------------------------------------------------
-  const float hx = (float)(D.n0 - 1), hy = (float)(D.n1 - 1), hz = (float)(D.n2 - 1);
-  float v[4];
-  uint32_t lab4 = 0;
-#pragma unroll
-  for (int q = 0; q < 4; ++q) {
-    if (HAS_NN) {
-      int xi = (int)rintf(x[q]), yi = (int)rintf(y[q]), zi = (int)rintf(z[q]);
-      xi = min(max(xi, 0), D.n0 - 1);
-      yi = min(max(yi, 0), D.n1 - 1);
-      zi = min(max(zi, 0), D.n2 - 1);
-      uint32_t l;
-      if (fits) {
-        // (explicit LDS address space: with plain pointers the optimiser merges this branch and the global one below into ONE
-        // load through a selected generic pointer -- a flat instruction on the vector-memory path for every "LDS" read)
-        const int idx = ((xi - X0) * ey + (yi - Y0)) * pitch + (zi - Z0);
-        l = (((const __attribute__((address_space(3))) uint32_t*)S.lab)[idx >> 2] >> (8 * (idx & 3))) & 255u;
-      } else {
-        const int xs = D.flip ? D.n0 - 1 - xi : xi;
-        l = src_nn[((size_t)xs * D.n1 + yi) * D.n2 + zi];
-      }
-      lab4 |= l << (8 * q);
-    }
-    if (HAS_LIN) {
-      const bool ok = (x[q] > 0.f) && (y[q] > 0.f) && (z[q] > 0.f) && (x[q] <= hx) && (y[q] <= hy) && (z[q] <= hz);
-      float r = 0.f;
-      if (ok) {
-        const float fx = floorf(x[q]), fy = floorf(y[q]), fz = floorf(z[q]);
-        const int x0 = (int)fx, y0 = (int)fy, z0 = (int)fz;
-        const int dx = min(x0 + 1, D.n0 - 1) - x0, dy = min(y0 + 1, D.n1 - 1) - y0, dz = min(z0 + 1, D.n2 - 1) - z0;
-        const float bx = x[q] - fx, by = y[q] - fy, bz = z[q] - fz;
-        const float ax = 1.f - bx, ay = 1.f - by, az = 1.f - bz;
-        float c000, c100, c010, c110, c001, c101, c011, c111;
-        if (fits) {
-          const int b00 = ((x0 - X0) * ey + (y0 - Y0)) * pitch + (z0 - Z0);
-          const int sxl = dx * ey * pitch, syl = dy * pitch;
-          const __attribute__((address_space(3))) float* B = (const __attribute__((address_space(3))) float*)S.box;
-          c000 = B[b00];             c001 = B[b00 + dz];
-          c100 = B[b00 + sxl];       c101 = B[b00 + sxl + dz];
-          c010 = B[b00 + syl];       c011 = B[b00 + syl + dz];
-          c110 = B[b00 + sxl + syl]; c111 = B[b00 + sxl + syl + dz];
-        } else {
-          int xs0 = x0, xs1 = x0 + dx;
-          if (D.flip) { xs0 = D.n0 - 1 - xs0; xs1 = D.n0 - 1 - xs1; }
-          const float* r00 = src_lin + ((size_t)xs0 * D.n1 + y0) * D.n2 + z0;
-          const float* r10 = src_lin + ((size_t)xs1 * D.n1 + y0) * D.n2 + z0;
-          const float* r01 = src_lin + ((size_t)xs0 * D.n1 + y0 + dy) * D.n2 + z0;
-          const float* r11 = src_lin + ((size_t)xs1 * D.n1 + y0 + dy) * D.n2 + z0;
-          c000 = r00[0]; c001 = r00[dz]; c100 = r10[0]; c101 = r10[dz];
-          c010 = r01[0]; c011 = r01[dz]; c110 = r11[0]; c111 = r11[dz];
-        }
-        const float c00 = c000 * ax + c100 * bx;
-        const float c01 = c001 * ax + c101 * bx;
-        const float c10 = c010 * ax + c110 * bx;
-        const float c11 = c011 * ax + c111 * bx;
-        const float c0 = c00 * ay + c10 * by;
-        const float c1 = c01 * ay + c11 * by;
-        r = c0 * az + c1 * bz;
-      }
-      if (E.gamma > 0.f) {
-        if (FAST) r = 300.0f * __builtin_amdgcn_exp2f(E.gamma * (__builtin_amdgcn_logf(r) - 8.2288186904958804f));
-        else r = 300.0f * powf(r / 300.0f, E.gamma);
-      }
-      if (E.bias) r = r * (FAST ? __builtin_amdgcn_exp2f(bval[q] * 1.4426950408889634f) : expf(bval[q]));
-      v[q] = r;
-    }
-  }
-  const int k = k0 + 4 * k4;
-  if (live_ij && k < D.n2) {  // n2 % 4 == 0: the four voxels are all inside or all outside
-    const size_t o = ((size_t)i * D.n1 + j) * D.n2 + k;
-    if (HAS_LIN) *reinterpret_cast<float4*>(out_lin + o) = make_float4(v[0], v[1], v[2], v[3]);
-    if (HAS_NN) {
-      if (sizeof(LD) == 1) {
-        *reinterpret_cast<uint32_t*>(out_nn + o) = lab4;
-      } else {
-        *reinterpret_cast<float4*>(out_nn + o) = make_float4((float)(lab4 & 255u), (float)((lab4 >> 8) & 255u),
-                                                             (float)((lab4 >> 16) & 255u), (float)(lab4 >> 24));
-      }
-    }
-  }
-}
-
-
 template <typename LT>
 int launch_warp(const fsg_deform* d, const int32_t* mm6, const float* src_lin, float* out_lin, const LT* src_nn,
                 LT* out_nn, const fsg_epilogue* epi, void* stream) {
@@ -1380,8 +837,7 @@ int launch_warp(const fsg_deform* d, const int32_t* mm6, const float* src_lin, f
   if (rc) return rc;
   const int need = (D.field ? 3 * D.f2 : 0) + (E.bias ? E.b2 : 0);
   if (D.rows && D.row_stride < need) return FSG_E_BADARG;
-  if (g_warp_variant == 0 &&
-      !(g_tuning_flags & (FSG_TUNE_GENERIC_WARP | FSG_TUNE_NO_PATCH | FSG_TUNE_BUFFER_LOADS | FSG_TUNE_NO_LEAN))) {
+  if (!(g_tuning_flags & (FSG_TUNE_GENERIC_WARP | FSG_TUNE_NO_PATCH | FSG_TUNE_NO_LEAN))) {
     // default: the lean body (fsg_warp_lean.hip); FSG_E_ALIGN = configuration outside its domain
     rc = fsg_launch_warp_lean(D, E, mm6, src_lin, out_lin, src_nn, out_nn, (int)sizeof(LT), (int)sizeof(LT),
                               !(g_tuning_flags & FSG_TUNE_PRECISE_MATH), stream);
@@ -1392,41 +848,8 @@ int launch_warp(const fsg_deform* d, const int32_t* mm6, const float* src_lin, f
     const bool fast = !(g_tuning_flags & FSG_TUNE_PRECISE_MATH);
     const dim3 grid((unsigned)ntiles), block(1024);
     hipStream_t st = fsg_stream(stream);
-    const bool buf = (g_tuning_flags & FSG_TUNE_BUFFER_LOADS) != 0;
-    if (g_warp_variant > 0) {
-      // lockstep tile variants (fsg_warp_set_variant): 1 = 8x8 rows x 16 voxels, 2 = 4x8 rows x 32, 3 = 8x4 rows x 32, 4 = 4x16 rows x 16
-#define FSG_LAUNCH_TILE(L, N, F, KZ, WI)                                                                                \
-  do {                                                                                                                 \
-    constexpr int PI_ = WI, PJ_ = (16 / WI) * (64 / KZ);                                                               \
-    const dim3 g((unsigned)(((D.n0 + PI_ - 1) / PI_) * ((D.n1 + PJ_ - 1) / PJ_)));                                     \
-    hipLaunchKernelGGL((warp_tile_kernel<LT, L, N, F, KZ, WI>), g, block, 0, st, D, mm6, src_lin, out_lin, src_nn,     \
-                       out_nn, E);                                                                                     \
-  } while (0)
-#define FSG_LAUNCH_TILE_V(L, N, F)                      \
-  do {                                                  \
-    switch (g_warp_variant) {                           \
-      case 1: FSG_LAUNCH_TILE(L, N, F, 16, 8); break;   \
-      case 2: FSG_LAUNCH_TILE(L, N, F, 32, 4); break;   \
-      case 3: FSG_LAUNCH_TILE(L, N, F, 32, 8); break;   \
-      default: FSG_LAUNCH_TILE(L, N, F, 16, 4); break;  \
-    }                                                   \
-  } while (0)
-      if (src_lin && src_nn) { if (fast) FSG_LAUNCH_TILE_V(true, true, true); else FSG_LAUNCH_TILE_V(true, true, false); }
-      else if (src_lin)      { if (fast) FSG_LAUNCH_TILE_V(true, false, true); else FSG_LAUNCH_TILE_V(true, false, false); }
-      else                   { FSG_LAUNCH_TILE_V(false, true, true); }
-#undef FSG_LAUNCH_TILE_V
-#undef FSG_LAUNCH_TILE
-      FSG_RETURN_LAUNCH();
-    }
-#define FSG_LAUNCH_PATCH(L, N, F)                                                                                      \
-  do {                                                                                                                 \
-    if (buf)                                                                                                           \
-      hipLaunchKernelGGL((warp_patch_kernel<LT, L, N, F, true>), grid, block, 0, st, D, mm6, src_lin, out_lin, src_nn, \
-                         out_nn, E);                                                                                   \
-    else                                                                                                               \
-      hipLaunchKernelGGL((warp_patch_kernel<LT, L, N, F, false>), grid, block, 0, st, D, mm6, src_lin, out_lin,        \
-                         src_nn, out_nn, E);                                                                           \
-  } while (0)
+#define FSG_LAUNCH_PATCH(L, N, F) \
+  hipLaunchKernelGGL((warp_patch_kernel<LT, L, N, F>), grid, block, 0, st, D, mm6, src_lin, out_lin, src_nn, out_nn, E)
     if (src_lin && src_nn) { if (fast) FSG_LAUNCH_PATCH(true, true, true); else FSG_LAUNCH_PATCH(true, true, false); }
     else if (src_lin)      { if (fast) FSG_LAUNCH_PATCH(true, false, true); else FSG_LAUNCH_PATCH(true, false, false); }
     else                   { FSG_LAUNCH_PATCH(false, true, true); }
@@ -1454,44 +877,6 @@ int launch_warp(const fsg_deform* d, const int32_t* mm6, const float* src_lin, f
   }
   hipLaunchKernelGGL(warp_kernel<LT>, fsg_grid3(D.n0, D.n1, D.n2), fsg_block3(), 0, fsg_stream(stream), D, mm6,
                      src_lin, out_lin, src_nn, out_nn, E);
-  FSG_RETURN_LAUNCH();
-}
-
-
-// nearest-neighbour source as uint8 (label volumes), output uint8 or float32
-template <typename LD>
-int launch_warp_u8src(const fsg_deform* d, const int32_t* mm6, const float* src_lin, float* out_lin,
-                      const uint8_t* src_nn, LD* out_nn, const fsg_epilogue* epi, void* stream) {
-  FsgDeformK D;
-  int rc = fsg_fill_deform(d, D);
-  if (rc) return rc;
-  if (!mm6) return FSG_E_BADARG;
-  if ((src_lin == nullptr) != (out_lin == nullptr)) return FSG_E_BADARG;
-  if ((src_nn == nullptr) != (out_nn == nullptr)) return FSG_E_BADARG;
-  if (!src_lin && !src_nn) return FSG_E_BADARG;
-  EpiK E;
-  rc = fill_epilogue(epi, E);
-  if (rc) return rc;
-  if (g_warp_variant == 0 && sizeof(LD) == 4 &&
-      !(g_tuning_flags & (FSG_TUNE_GENERIC_WARP | FSG_TUNE_NO_PATCH | FSG_TUNE_BUFFER_LOADS | FSG_TUNE_NO_LEAN | FSG_TUNE_BRICK))) {
-    // uint8 labels in, float32 labels out: served by the lean kernel (the uint8 -> uint8 case reaches it through launch_warp)
-    rc = fsg_launch_warp_lean(D, E, mm6, src_lin, out_lin, src_nn, out_nn, 1, 4, !(g_tuning_flags & FSG_TUNE_PRECISE_MATH),
-                              stream);
-    if (rc != FSG_E_ALIGN) return rc;
-  }
-  const uintptr_t al16 = (uintptr_t)src_lin | (uintptr_t)out_lin | (sizeof(LD) == 4 ? (uintptr_t)out_nn : 0);
-  const uintptr_t al4 = (uintptr_t)src_nn | (sizeof(LD) == 1 ? (uintptr_t)out_nn : 0);
-  if ((D.n2 & 3) || (al16 & 15) || (al4 & 3) || D.n2 < 4 || !(g_tuning_flags & FSG_TUNE_BRICK)) return FSG_E_ALIGN;
-  const int nb = ((D.n0 + BRI - 1) / BRI) * ((D.n1 + BRJ - 1) / BRJ) * ((D.n2 + BRK - 1) / BRK);
-  const bool fast = !(g_tuning_flags & FSG_TUNE_PRECISE_MATH);
-  const dim3 grid((unsigned)nb), block(256);
-  hipStream_t st = fsg_stream(stream);
-#define FSG_LAUNCH_BRICK(L, N, F) \
-  hipLaunchKernelGGL((warp_brick_kernel<LD, L, N, F>), grid, block, 0, st, D, mm6, src_lin, out_lin, src_nn, out_nn, E)
-  if (src_lin && src_nn) { if (fast) FSG_LAUNCH_BRICK(true, true, true); else FSG_LAUNCH_BRICK(true, true, false); }
-  else if (src_lin)      { if (fast) FSG_LAUNCH_BRICK(true, false, true); else FSG_LAUNCH_BRICK(true, false, false); }
-  else                   { FSG_LAUNCH_BRICK(false, true, true); }
-#undef FSG_LAUNCH_BRICK
   FSG_RETURN_LAUNCH();
 }
 
@@ -1532,15 +917,13 @@ int fsg_set_tuning(int flags) {
 
 extern int g_lean_pace, g_lean_ablate;
 int fsg_warp_set_variant(int variant) {
-  const int prev = g_warp_variant;
-  g_lean_ablate = 0;
+  const int prev = g_lean_pace < 0 ? 0 : (g_lean_pace == 0 ? 5 : (g_lean_pace == 2 ? 6 : 7));
 #ifdef FSG_DIAG  // the ablation kernels (wrong results by construction) exist in a -DFSG_DIAG build only
-  if (variant == 8 || variant == 9) { g_warp_variant = 0; g_lean_pace = 1; g_lean_ablate = variant - 7; }
-#else
-  if (variant == 8 || variant == 9) return FSG_E_BADARG;
+  if (variant == 8 || variant == 9) { g_lean_pace = 1; g_lean_ablate = variant - 7; return prev; }
 #endif
-  if (variant >= 0 && variant <= 4) { g_warp_variant = variant; g_lean_pace = -1; }
-  if (variant >= 5 && variant <= 7) { g_warp_variant = 0; g_lean_pace = variant == 5 ? 0 : (variant == 6 ? 2 : 1); }
+  if (variant != 0 && (variant < 5 || variant > 7)) return FSG_E_BADARG;
+  g_lean_ablate = 0;
+  g_lean_pace = variant == 0 ? -1 : (variant == 5 ? 0 : (variant == 6 ? 2 : 1));
   return prev;
 }
 
@@ -1718,14 +1101,25 @@ int fsg_warp_f32(const fsg_deform* d, const int32_t* mm6, const float* src_lin, 
 
 int fsg_warp_f32_u8(const fsg_deform* d, const int32_t* mm6, const float* src_lin, float* out_lin,
                     const uint8_t* src_nn, uint8_t* out_nn, const fsg_epilogue* epi, void* stream) {
-  const int rc = launch_warp_u8src<uint8_t>(d, mm6, src_lin, out_lin, src_nn, out_nn, epi, stream);
-  if (rc != FSG_E_ALIGN) return rc;  // brick kernel not selected / not applicable: patch or row kernel
   return launch_warp<uint8_t>(d, mm6, src_lin, out_lin, src_nn, out_nn, epi, stream);
 }
 
 int fsg_warp_f32_u8_to_f32(const fsg_deform* d, const int32_t* mm6, const float* src_lin, float* out_lin,
                            const uint8_t* src_nn, float* out_nn, const fsg_epilogue* epi, void* stream) {
-  return launch_warp_u8src<float>(d, mm6, src_lin, out_lin, src_nn, out_nn, epi, stream);
+  FsgDeformK D;
+  int rc = fsg_fill_deform(d, D);
+  if (rc) return rc;
+  if (!mm6) return FSG_E_BADARG;
+  if ((src_lin == nullptr) != (out_lin == nullptr)) return FSG_E_BADARG;
+  if ((src_nn == nullptr) != (out_nn == nullptr)) return FSG_E_BADARG;
+  if (!src_lin && !src_nn) return FSG_E_BADARG;
+  EpiK E;
+  rc = fill_epilogue(epi, E);
+  if (rc) return rc;
+  if (g_tuning_flags & (FSG_TUNE_GENERIC_WARP | FSG_TUNE_NO_PATCH | FSG_TUNE_NO_LEAN)) return FSG_E_ALIGN;
+  // served by the lean kernel alone (the uint8 -> uint8 case reaches it through launch_warp)
+  return fsg_launch_warp_lean(D, E, mm6, src_lin, out_lin, src_nn, out_nn, 1, 4, !(g_tuning_flags & FSG_TUNE_PRECISE_MATH),
+                              stream);
 }
 
 int fsg_interp3d_f32(const float* src, int sx, int sy, int sz, const float* ii, const float* jj, const float* kk,

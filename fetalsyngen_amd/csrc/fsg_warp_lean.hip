@@ -19,7 +19,7 @@
 //   * the axis-0 flip is folded into a signed plane stride and a base offset (no per-voxel select);
 //   * index products on v_mul_i32_i24 / v_mad_i32_i24;
 //   * work shape: the 16 waves of a workgroup sweep 8 x 4 adjacent rows, 32 voxels of each per lockstep step
-//     (fsg_warp_set_variant 3 of the patch kernel family, the fastest of the shapes measured).
+//     (the fastest of the work shapes measured: profiles/r02_a_warp_patch_shapes.txt).
 // Domain (else FSG_E_ALIGN and the caller falls back): per-row coarse values precomputed (fsg_deform_rows_f32),
 // coarse grids of at most 32 entries along z, shape[2] <= 512, shape[1]*shape[2] < 2^22, fewer than 2^30 voxels.
 #include "fsg_common.h"

@@ -464,7 +464,7 @@ def warp(spec: DeformSpec, mm6, src_lin=None, src_nn=None, gamma=None, bias=None
         elif nn_out == F32:
             out_nn = torch.empty(src_nn.shape, dtype=F32, device=src_nn.device)
             rc = lib.fsg_warp_f32_u8_to_f32(*args(src_nn, out_nn))
-            if rc == _lib.E_ALIGN:  # outside the brick kernel's domain: float32 label volume, row kernel
+            if rc == _lib.E_ALIGN:  # outside the lean kernel's domain: float32 label volume through fsg_warp_f32
                 _lib.check(lib.fsg_warp_f32(*args(src_nn.to(F32), out_nn)), "fsg_warp_f32")
             else:
                 _lib.check(rc, "fsg_warp_f32_u8_to_f32")

@@ -74,7 +74,6 @@ const char* fsg_error_string(int code);
 #define FSG_TUNE_GENERIC_ZOOM 4  /* per-voxel 8-tap zoom instead of the row-wise LDS kernels */
 #define FSG_TUNE_NO_PREFETCH 8   /* row-wise zoom without the register-prefetch pipeline */
 #define FSG_TUNE_NO_PATCH 32     /* row kernel (4 waves, own rows) instead of the 16-wave lockstep patch kernel */
-#define FSG_TUNE_BUFFER_LOADS 64 /* opt in: patch kernel body on raw buffer loads (fewer instructions, slower in r01) */
 #define FSG_TUNE_ROW_ZOOM 256    /* every zoom through the row-per-wave kernels (r01 default for K9) */
 #define FSG_TUNE_TILE_ZOOM 512   /* every zoom through the tile kernel (default: only the noise epilogues) */
 #define FSG_TUNE_NO_BLUR_FUSE 1024 /* blur: y and z passes as two launches */
@@ -85,12 +84,12 @@ const char* fsg_error_string(int code);
 #define FSG_TUNE_NO_SEED_CODES 65536 /* A/B: the one-launch head reads the four label volumes even when the plan carries a code volume */
 #define FSG_TUNE_SA_FWD_DIRECT 131072 /* slice-acquisition forward (linear PSF, no volume mask): direct global gathers for every slice */
 #define FSG_TUNE_SA_FWD_PLATE 262144  /* ... the LDS plate kernel for every slice (default: chosen per slice by its orientation) */
-#define FSG_TUNE_WAVE_ZOOM 32768 /* opt in: zooms without a noise draw through the wave kernel (independent waves; slower in r03) */
 #define FSG_TUNE_NO_BLUR_RS 16384 /* fsg_sample_run: blur x3 + K7 as separate launches instead of the fused blur+resample pair */
-#define FSG_TUNE_BRICK 16        /* opt in: uint8-label warps through the LDS brick kernel (experimental, slower in r01) */
+/* Bits 16, 64 and 32768 are retired (kernel variants measured slower and removed): ignored by fsg_set_tuning, never reuse them. */
 int fsg_set_tuning(int flags);
-/* Work shape of the fused warp kernel (speed only, results identical): 0 = 4x4 rows x 64 voxels per lockstep step,
- * 1 = 8x8 rows x 16 voxels, 2 = 4x8 rows x 32, 3 = 8x4 rows x 32, 4 = 4x16 rows x 16.  Returns the previous value. */
+/* Lockstep pacing of the lean warp kernel (speed only, results identical): 0 = chosen per launch, 5 = no barrier,
+ * 6 = a barrier every second step, 7 = a barrier every step.  Returns the previous value, or FSG_E_BADARG (setting
+ * unchanged) for any other value. */
 int fsg_warp_set_variant(int variant);
 
 /* ---- RNG ------------------------------------------------------------------------------------ */
@@ -207,9 +206,8 @@ int fsg_warp_f32_u8(const fsg_deform* d_host, const int32_t* mm6, const float* s
 
 /* Label volume read as uint8, deformed labels written as float32 (exact for 0..255): the reference keeps
  * segmentations as float32 tensors, the device-resident copy is uint8.  Served by the lean warp kernel (per-row
- * coarse values prepared, coarse grids <= 32 entries along z, shape[2] <= 512) or, with FSG_TUNE_BRICK, by the LDS
- * brick kernel (shape[2] % 4 == 0, 16-byte aligned fp32 volumes); returns FSG_E_ALIGN otherwise and the caller
- * uses fsg_warp_f32 / fsg_warp_f32_u8. */
+ * coarse values prepared, coarse grids <= 32 entries along z, shape[2] <= 512) only; returns FSG_E_ALIGN otherwise
+ * and the caller uses fsg_warp_f32 / fsg_warp_f32_u8. */
 int fsg_warp_f32_u8_to_f32(const fsg_deform* d_host, const int32_t* mm6, const float* src_lin, float* out_lin,
                            const uint8_t* src_nn, float* out_nn, const fsg_epilogue* epi_host, void* stream);
 

@@ -356,10 +356,10 @@ def test_zoom_tile_kernel_equals_row_kernels(K):
         bt, _ = T.zoom_tables(new, 1 / np.asarray(fac))
         zt = K.DeviceTables(bt, DEV)
         res = {}
-        for flag in (256, 512, 8192, 32768, 0):  # FSG_TUNE_ROW_ZOOM, _TILE_ZOOM, _SLAB_ZOOM, _WAVE_ZOOM (r03, opt-in), defaults
+        for flag in (256, 512, 8192, 0):  # FSG_TUNE_ROW_ZOOM, _TILE_ZOOM, _SLAB_ZOOM, defaults
             prev = lib.fsg_set_tuning(flag)
             try:
-                for ty in ((16,) if flag in (256, 32768, 0) else (1, 5, 16, 32)):
+                for ty in ((16,) if flag in (256, 0) else (1, 5, 16, 32)):
                     lib.fsg_zoom_set_tuning(ty, 12288)
                     low = K.resample_noise(x, rt, noise_std=9.0, seed=11, stream_id=2)
                     z = K.randn(tuple(new), 5, 6, DEV)
@@ -385,7 +385,7 @@ def test_zoom_tile_kernel_equals_row_kernels(K):
 
 
 def test_uniform_division_in_k9b_is_the_ieee_quotient(K):
-    """K9b divides every voxel by the same maximum through a reciprocal + two FMAs (`unidiv`, fsg_zoom.hip) instead of the
+    """K9b divides every voxel by the same maximum through a reciprocal + two FMAs (`UniDiv`, fsg_zoom.hip) instead of the
     IEEE division expansion.  Exhaustive over the significand: a 2^23-voxel volume holding EVERY float32 significand of one
     binade goes through an identity zoom + normalise (mode 0: v / max) for divisors that include powers of two, all-ones
     significands (where the shortcut is not valid and the kernel must fall back), tiny and huge values; the result must be the
@@ -784,9 +784,9 @@ def test_gmm_from_label_parts_equals_gmm_of_the_sum(K):
 
 
 @pytest.mark.parametrize("case", ["typical", "extreme", "fine_grid", "no_field"])
-def test_brick_kernel_equals_row_kernel(K, case):
-    """LDS-brick warp (uint8 labels) vs the row kernel: bit-identical image and labels, with/without flip,
-    ragged brick counts, boxes that do not fit LDS (extreme) and coarse windows wider than 4 nodes."""
+def test_uint8_label_warps_equal_float32_label_warps(K, case):
+    """Warps of uint8 label volumes (uint8 or float32 labels out) vs the float32-label warps: bit-identical image and
+    labels, with/without flip, ragged shapes, extreme deformations and fine coarse grids."""
     from fetalsyngen_amd import _lib
     from fetalsyngen_amd import tables as T
     from fetalsyngen_amd.utils.generation import make_affine_matrix
@@ -809,20 +809,17 @@ def test_brick_kernel_equals_row_kernel(K, case):
             ft = K.DeviceTables(T.zoom_tables(fsh, np.array(shape) / np.array(fsh))[0], DEV)
         spec = K.DeformSpec(shape, A, c, c.astype(np.float32) + np.float32(0.3), flip, fs, ft, device=DEV)
         mm = K.coords_floormin(spec)
-        outs = {}
-        for flags in (16, 0):
-            prev = lib.fsg_set_tuning(flags)
-            try:
-                a, l8 = K.warp(spec, mm, src_lin=dev(img), src_nn=dev(lab), gamma=0.9, bias=dev(bias), bias_tabs=bt)
-                b, lf = K.warp(spec, mm, src_lin=dev(img), src_nn=dev(lab), nn_out=torch.float32)
-                _, l8o = K.warp(spec, mm, src_nn=dev(lab))
-                p, _ = K.warp(spec, mm, src_lin=dev(img))
-                outs[flags] = [host(v) for v in (a, l8, b, lf, l8o, p)]
-            finally:
-                lib.fsg_set_tuning(prev)
-        for u, v in zip(outs[16], outs[0]):  # brick kernel (16) vs default kernels
-            assert np.array_equal(u, v), (case, flip)
-        assert np.array_equal(outs[0][1], outs[0][3].astype(np.uint8)) and np.array_equal(outs[0][1], outs[0][4])
+        prev = lib.fsg_set_tuning(0)
+        try:
+            a, l8 = K.warp(spec, mm, src_lin=dev(img), src_nn=dev(lab), gamma=0.9, bias=dev(bias), bias_tabs=bt)
+            b, lf = K.warp(spec, mm, src_lin=dev(img), src_nn=dev(lab), nn_out=torch.float32)
+            _, l8o = K.warp(spec, mm, src_nn=dev(lab))
+            p, _ = K.warp(spec, mm, src_lin=dev(img))
+            outs = [host(v) for v in (a, l8, b, lf, l8o, p)]
+        finally:
+            lib.fsg_set_tuning(prev)
+        assert np.array_equal(outs[1], outs[3].astype(np.uint8)) and np.array_equal(outs[1], outs[4])
+        assert np.array_equal(outs[2], outs[5]), (case, flip)  # the label leg leaves the image as the image-only warp has it
         # and against the float32-label kernels: 16-wave patch kernel (default), row kernel (flag 32), and with
         # the precomputed row workspace
         f32 = {}
@@ -838,14 +835,15 @@ def test_brick_kernel_equals_row_kernel(K, case):
         a, lf32 = K.warp(spec, mm, src_lin=dev(img), src_nn=dev(lab.astype(np.float32)), gamma=0.9, bias=dev(bias),
                          bias_tabs=bt)
         for got in (f32[0], f32[32], (host(a), host(lf32))):
-            assert np.array_equal(got[0], outs[0][0]) and np.array_equal(got[1], outs[0][3]), (case, flip)
+            assert np.array_equal(got[0], outs[0]) and np.array_equal(got[1], outs[3]), (case, flip)
 
 
 # ---- the other entry modes of FetalSynthGen.sample ----------------------------------------------------
 @pytest.mark.parametrize("shape", [(50, 37, 70), (64, 64, 64), (33, 72, 130)])
 def test_warp_work_shapes_are_bit_identical(K, shape):
-    """fsg_warp_set_variant only changes which voxels a wave processes together: every variant must reproduce the
-    default kernel bit for bit (image with gamma + bias epilogue, f32 and u8 labels, both flips, ragged shapes)."""
+    """fsg_warp_set_variant only changes how the lean kernel's 16 waves are paced (the barrier guards no shared data):
+    every pacing must reproduce the default bit for bit (image with gamma + bias epilogue, f32 and u8 labels, both flips,
+    ragged shapes).  The retired work shapes 1-4 are refused and leave the setting as it was."""
     from fetalsyngen_amd import _lib
     from fetalsyngen_amd import tables as T
     from fetalsyngen_amd.utils.generation import make_affine_matrix
@@ -865,7 +863,11 @@ def test_warp_work_shapes_are_bit_identical(K, shape):
     res = {}
     prev = lib.fsg_warp_set_variant(0)
     try:
-        for variant in (0, 1, 2, 3, 4):
+        lib.fsg_warp_set_variant(6)
+        for v in (1, 2, 3, 4):
+            assert lib.fsg_warp_set_variant(v) == _lib.E_BADARG, v
+        assert lib.fsg_warp_set_variant(0) == 6
+        for variant in (0, 5, 6, 7):
             lib.fsg_warp_set_variant(variant)
             for flip in (False, True):
                 spec = K.DeformSpec(shape, A, c, c.astype(np.float32), flip, fs, K.DeviceTables(ft, DEV), device=DEV)
@@ -898,7 +900,7 @@ def test_warp_work_shapes_are_bit_identical(K, shape):
         base = res[(0, flip)]
         assert np.array_equal(base[1].astype(np.uint8), base[2]) and np.array_equal(base[1], base[5])
         assert np.array_equal(base[0], base[4])
-        for variant in (1, 2, 3, 4):
+        for variant in (5, 6, 7):
             for a, b in zip(res[(variant, flip)], base):
                 assert np.array_equal(a, b), (variant, flip)
         assert np.array_equal(res[("patch", flip)][0], base[0]) and np.array_equal(res[("patch", flip)][1], base[1])

@@ -18,7 +18,7 @@ ap.add_argument("--only", default="")
 ap.add_argument("--m", type=int, default=171, help="low-res size for the resample kernels")
 ap.add_argument("--rot", type=float, default=12.0, help="rotation (degrees) about each axis")
 ap.add_argument("--tune", type=int, default=0, help="fsg_set_tuning flags")
-ap.add_argument("--variant", type=int, default=0, help="fsg_warp_set_variant")
+ap.add_argument("--variant", type=int, default=0, help="fsg_warp_set_variant: lean warp pacing, 0 = per launch, 5/6/7 = forced (8/9: -DFSG_DIAG ablations)")
 ap.add_argument("--zoom-ty", type=int, default=0, help="fsg_zoom_set_tuning: output rows per workgroup (0 = default)")
 args = ap.parse_args()
 dev = "cuda:0"
