@@ -6,11 +6,7 @@
 // interpreter between launches costs as much as the kernels; semantics and results are those of calling the
 // entry points one by one (tests/test_hip_parity.py::test_native_pipeline_equals_stagewise).
 #include <hip/hip_runtime.h>
-#include <atomic>
 #include <cstddef>
-#include <map>
-#include <mutex>
-#include <utility>
 #include "../../include/fsg_hip.h"
 
 // look-ahead launches (fsg_deform.hip, fsg_zoom.hip): not part of the public header
@@ -19,63 +15,8 @@ extern "C" int fsg_internal_floormin_rest_ride(const fsg_deform* d, int32_t* mm3
 
 extern int g_tuning_flags;
 
-// ---- head of sample n+1 beside the tail of sample n (fsg_sample_plan::overlap) ---------------------------------------
-// Per launch stream: a side stream and two events.  `ev_free` is recorded on the launch stream at the point of a call after
-// which it no longer touches ws0 / ws_rows (after the blur, or after K7 when the blur's last pass lands in ws0); the next
-// call's upload + head wait for it on the side stream, the launch stream waits for `ev_head` before the margins and the warp.
-// The head is VALU-bound (Philox + Box-Muller), the resampling tail it runs beside is bound by LDS and latency.
-namespace {
-struct HeadOverlap {
-  hipStream_t side = nullptr;
-  hipEvent_t ev_free = nullptr, ev_head = nullptr;
-  bool has_free = false;
-  uint64_t seq = 0;
-  const float* ws0 = nullptr;
-};
-// g_ho_mu guards the map AND every field of its entries: fsg_sample_run holds it from the look-up to its last access of the
-// entry whenever the overlap state is involved (two host threads launching on one (device, stream) pair serialise there;
-// without the overlap the lock is taken once, briefly, to invalidate a stale entry).
-std::mutex g_ho_mu;
-std::map<std::pair<int, hipStream_t>, HeadOverlap> g_ho;
-std::atomic<bool> g_ho_used{false};  // no entry was ever created: the default path never takes the lock
-
-// Caller holds g_ho_mu.  `err` receives the HIP error of a failed creation (partially created objects are destroyed).
-HeadOverlap* head_overlap_state(hipStream_t st, bool create, hipError_t* err) {
-  int dev = 0;
-  hipError_t e = hipGetDevice(&dev);
-  if (e != hipSuccess) { if (err) *err = e; return nullptr; }
-  auto key = std::make_pair(dev, st);
-  auto it = g_ho.find(key);
-  if (it != g_ho.end()) return &it->second;
-  if (!create) return nullptr;
-  HeadOverlap h;
-  if ((e = hipStreamCreateWithFlags(&h.side, hipStreamNonBlocking)) != hipSuccess) { if (err) *err = e; return nullptr; }
-  if ((e = hipEventCreateWithFlags(&h.ev_free, hipEventDisableTiming)) != hipSuccess ||
-      (e = hipEventCreateWithFlags(&h.ev_head, hipEventDisableTiming)) != hipSuccess) {
-    if (h.ev_free) (void)hipEventDestroy(h.ev_free);
-    (void)hipStreamDestroy(h.side);
-    if (err) *err = e;
-    return nullptr;
-  }
-  return &g_ho.emplace(key, h).first->second;  // std::map: the address stays valid
-}
-}  // namespace
-
-// Releases the side streams and events of the head overlap (they otherwise live for the life of the process).  The caller
-// must have synchronised the streams it launched samples on.
-extern "C" int fsg_pipeline_teardown(void) {
-  std::lock_guard<std::mutex> lk(g_ho_mu);
-  int rc = 0;
-  for (auto& kv : g_ho) {
-    HeadOverlap& h = kv.second;
-    hipError_t e;
-    if (h.ev_free && (e = hipEventDestroy(h.ev_free)) != hipSuccess) rc = (int)e;
-    if (h.ev_head && (e = hipEventDestroy(h.ev_head)) != hipSuccess) rc = (int)e;
-    if (h.side && (e = hipStreamDestroy(h.side)) != hipSuccess) rc = (int)e;
-  }
-  g_ho.clear();
-  return rc;
-}
+// Kept for the ABI (include/fsg_hip.h): the library owns no streams or events, so there is nothing to release.
+extern "C" int fsg_pipeline_teardown(void) { return 0; }
 
 #define FSG_TRY(expr)        \
   do {                       \
@@ -116,36 +57,10 @@ extern "C" int fsg_sample_run(const fsg_sample_plan* p, void* stream) {
   const int need_h = 3 * dh.field_dims[2] + (has_bias ? p->epi.bias_dims[2] : 0);
   const bool fused_head = p->deform_active && p->mm8_preset && p->ws_rows && !(g_tuning_flags & FSG_TUNE_SPLIT_HEAD) &&
                           need_h > 0 && need_h <= p->row_stride;
-  // where the upload and the head go: the side stream when the caller asked for the overlap and the head is one launch
-  HeadOverlap* ho = nullptr;
-  std::unique_lock<std::mutex> ho_lock(g_ho_mu, std::defer_lock);
-  const bool want_overlap = p->overlap && fused_head && p->resample_active && p->arena_host;
-  if (want_overlap || g_ho_used.load(std::memory_order_acquire)) {
-    ho_lock.lock();
-    if (want_overlap) {
-      hipError_t herr = hipSuccess;
-      ho = head_overlap_state(st, true, &herr);
-      if (!ho) return herr != hipSuccess ? (int)herr : FSG_E_BADARG;
-      g_ho_used.store(true, std::memory_order_release);
-    } else {  // this call uses the workspace in launch-stream order only: a later overlapped call must not trust an old event
-      HeadOverlap* old = head_overlap_state(st, false, nullptr);
-      if (old) old->has_free = false;
-      ho_lock.unlock();
-    }
-  }
-  void* hstream = stream;
-  if (ho) {  // ho_lock is held until this call returns
-    if (!(ho->has_free && ho->ws0 == p->ws0 && ho->seq + 1 == p->ws_seq)) {
-      FSG_HIP(hipEventRecord(ho->ev_free, st));  // behind everything enqueued so far
-    }
-    FSG_HIP(hipStreamWaitEvent(ho->side, ho->ev_free, 0));
-    ho->has_free = false;
-    hstream = (void*)ho->side;
-  }
-  if (p->arena_host) {
+  if (p->arena_host) {  // the sample's parameter block, copied on the launch stream before its first kernel
     if (!p->arena_dev || (p->arena_bytes & 15)) return FSG_E_BADARG;
-    FSG_TRY(fsg_copy_bytes(p->arena_dev, p->arena_host, (size_t)p->arena_bytes, hstream));
-    if (!ho) FSG_TRY(mark(FSG_ST_UPLOAD));
+    FSG_TRY(fsg_copy_bytes(p->arena_dev, p->arena_host, (size_t)p->arena_bytes, stream));
+    FSG_TRY(mark(FSG_ST_UPLOAD));
   }
   int head_rc = 0;
   if (fused_head) {
@@ -156,17 +71,13 @@ extern "C" int fsg_sample_run(const fsg_sample_plan* p, void* stream) {
     if (p->label_codes && p->code_tuples && !p->gmm_noise && !(g_tuning_flags & FSG_TUNE_NO_SEED_CODES))  // 6 instead of 8 B/voxel
       head_rc = fsg_sample_head_codes_f32(p->label_codes, p->code_tuples, p->code_ntuples, p->code_stride, p->code_sel, n, p->mus,
                                           p->sigmas, p->ntab, p->gmm_seed, p->gmm_stream, p->ws0, &dh, &p->epi, p->ws_rows,
-                                          p->row_stride, p->mm8, hstream);
+                                          p->row_stride, p->mm8, stream);
     if (head_rc == FSG_E_ALIGN || head_rc == FSG_E_TOOBIG)  // no codes, or outside their domain: the four label volumes
       head_rc = fsg_sample_head_f32(p->label_parts[0], p->label_parts[1], p->label_parts[2], p->label_parts[3], n, p->mus,
                                     p->sigmas, p->ntab, p->gmm_noise, p->gmm_seed, p->gmm_stream, p->ws0, &dh, &p->epi,
-                                    p->ws_rows, p->row_stride, p->mm8, hstream);
+                                    p->ws_rows, p->row_stride, p->mm8, stream);
     if (head_rc == 0) head_done = true;
-    if (head_done && !ho) FSG_TRY(mark(FSG_ST_HEAD));
-  }
-  if (ho) {  // whatever happened on the side stream is ordered before the rest of the sample (and before any fallback)
-    FSG_HIP(hipEventRecord(ho->ev_head, ho->side));
-    FSG_HIP(hipStreamWaitEvent(st, ho->ev_head, 0));
+    if (head_done) FSG_TRY(mark(FSG_ST_HEAD));
   }
   if (head_rc != 0 && head_rc != FSG_E_TOOBIG && head_rc != FSG_E_ALIGN) return head_rc;
   // K1: GMM draw -> ws0; the same launch resets every min/max key of the sample (unless they arrived initialised):
@@ -241,14 +152,6 @@ extern "C" int fsg_sample_run(const fsg_sample_plan* p, void* stream) {
   if (p->resample_active) {
     if (!p->ws_low) return FSG_E_BADARG;
     const int m0 = p->low_shape[0], m1 = p->low_shape[1], m2 = p->low_shape[2];
-    auto mark_free = [&]() -> int {  // from here on this call touches neither ws0 nor ws_rows
-      if (!ho) return 0;
-      FSG_HIP(hipEventRecord(ho->ev_free, st));
-      ho->has_free = true;
-      ho->seq = p->ws_seq;
-      ho->ws0 = p->ws0;
-      return 0;
-    };
     // K6 + K7 + K8 as the fused pair (csrc/fsg_blur_rs.hip): blur and down-sampling of an axis in one operator, the blurred
     // full-resolution volume never exists.  Bracketed by the caller's HIP events like the unfused blur below.
     const bool fused_rs = fsg_blur_resample_supported(n0, n1, n2, m0, m1, m2, p->blur_ntaps[0], p->blur_ntaps[1], p->blur_ntaps[2]);
@@ -261,7 +164,6 @@ extern "C" int fsg_sample_run(const fsg_sample_plan* p, void* stream) {
                                              p->noise_seed, p->noise_stream, p->noise_std, p->ws_low, stream));
       FSG_TRY(mark(FSG_ST_BLUR_RS_YZ));
       if (p->ev_blur_end) FSG_HIP(hipEventRecord((hipEvent_t)p->ev_blur_end, st));
-      FSG_TRY(mark_free());
     } else {
     // K6: separable blur, x then y then z (optionally bracketed by the caller's HIP events: bench.py's live
     // measurement of the graded kernel on the launch stream)
@@ -288,12 +190,9 @@ extern "C" int fsg_sample_run(const fsg_sample_plan* p, void* stream) {
     }
     if (p->ev_blur_end) FSG_HIP(hipEventRecord((hipEvent_t)p->ev_blur_end, st));
     // K7+K8: resample + noise -> low
-    const bool k7_reads_ws0 = cur == p->ws0;
-    if (!k7_reads_ws0) FSG_TRY(mark_free());
     FSG_TRY(fsg_resample_noise_f32(cur, n0, n1, n2, p->rs_tab[0], p->rs_tab[1], p->rs_tab[2], p->ws_low, m0, m1, m2,
                                    p->noise_mode, p->noise, p->noise_seed, p->noise_stream, p->noise_std, stream));
     FSG_TRY(mark(FSG_ST_K7));
-    if (k7_reads_ws0) FSG_TRY(mark_free());
     }
     // K9 (+K10): min/max of the zoom-back, then zoom-back + normalise -> out
     if (p->mm_slots && p->mm_nslots >= 2 && p->mm_nslots <= 64) {  // keys sharded over slots: no contended address
@@ -416,7 +315,7 @@ extern "C" int fsg_sample_plan_pack(fsg_sample_plan* p, const int64_t* iv, int n
   q.arena_host = (const void*)(uintptr_t)iv[FSG_PLAN_I_ARENA_HOST];
   q.arena_dev = (void*)(uintptr_t)iv[FSG_PLAN_I_ARENA_DEV];
   q.arena_bytes = (uint64_t)iv[FSG_PLAN_I_ARENA_BYTES];
-  q.overlap = (int32_t)iv[FSG_PLAN_I_OVERLAP];
+  q.overlap = (int32_t)iv[FSG_PLAN_I_OVERLAP];  // retired fields: carried over, ignored by fsg_sample_run
   q.ws_seq = (uint64_t)iv[FSG_PLAN_I_WS_SEQ];
   q.seg_out_u8 = (uint8_t*)(uintptr_t)iv[FSG_PLAN_I_SEG_OUT_U8];
   q.trace_events = (void**)(uintptr_t)iv[FSG_PLAN_I_TRACE_EVENTS];

@@ -17,6 +17,7 @@ The optional SR-artifact stages (`blur_cortex`, `struct_noise`, `simulate_motion
 """
 from __future__ import annotations
 
+import weakref
 from typing import Iterable
 
 import numpy as np
@@ -41,20 +42,6 @@ MM_NSLOTS, MM_SLOT_STRIDE = 64, 16
 _MM_SLOTS_INIT = np.zeros((MM_NSLOTS, MM_SLOT_STRIDE), dtype=np.int32)
 _MM_SLOTS_INIT[:, 0], _MM_SLOTS_INIT[:, 1] = 0x7F800000, -2139095041
 _MM_SLOTS_INIT.setflags(write=False)
-
-
-import os as _os
-import weakref
-
-_NO_MM_SLOTS = _os.environ.get("FSG_NO_MM_SLOTS", "0") == "1"  # K9's keys as ONE pair (A/B runs)
-# "0" (default): parameter upload on the launch stream before the native call.  "1": upload inside the call.  "2": upload and
-# head of the sample on the library's side stream beside the previous sample's resampling tail (fsg_sample_plan::overlap).
-# Measured on MI355X (profiles/r02_g_head_overlap.txt): bit-identical results, but the two cross-queue dependencies per sample
-# cost more than the overlap returns (replay with the host out of the way: 255 us per sample in order, 263-283 us overlapped),
-# so the in-order form stays the default.
-_HEAD_OVERLAP = _os.environ.get("FSG_HEAD_OVERLAP", "0")
-_ARENA_BLOCK = 1 << 16  # device block of one sample's parameters (tables._StagingRing.SLOT)
-_SLOW_PLAN = _os.environ.get("FSG_SLOW_PLAN", "0") == "1"  # field-by-field ctypes plan instead of the flat arrays (cross-check)
 
 
 class _Ctx:
@@ -138,7 +125,7 @@ class FetalSynthGen:
         }
         self.device = device
         self.rng = rng  # None: module default (fetalsyngen_amd.rng.get_mode())
-        self.native_pipeline = True  # one fsg_sample_run call per sample when the inputs allow it
+        self.native_pipeline = True  # one native call per sample when the inputs allow it
         self.blur_events = None      # set to a list: (begin, end, [(axis, radius)], low-res shape) per sample, HIP events recorded
                                      # around the blur (+ down-sampling, when fused) launches inside the native call
         self.blur_events_every = 1   # ... of every k-th sample only (an event record is a barrier packet: ~5.5 us of bubble)
@@ -147,12 +134,12 @@ class FetalSynthGen:
         self._ws = {}
 
     # Everything below lives and dies with ONE process: raw host addresses (`_flat`: ivp / fvp / tbp are `ndarray.ctypes.data`
-    # integers), device tensors (`_ws`, `_twins`, `_arena_next`), HIP events and streams, caches keyed by `id()` of tensors of
+    # integers), device tensors (`_ws`, `_twins`), HIP events and streams, caches keyed by `id()` of tensors of
     # this process.  None of it is configuration, all of it is rebuilt on first use -- so a pickled generator (the reference's
     # DataLoader pattern: `num_workers=2, multiprocessing_context="spawn"`, fetalsyngen/test_dl.py:17-24, docs/datasets.md:4-6)
     # carries none of it into the worker.
-    _PROCESS_LOCAL = ("_ws", "_flat", "_twins", "_seen_parts", "_arena_next", "_rs_dt", "_batch_streams", "blur_events",
-                      "_blur_tick", "_keyed", "stage_traces", "_pre")
+    _PROCESS_LOCAL = ("_ws", "_flat", "_twins", "_rs_dt", "_batch_streams", "blur_events", "_blur_tick", "_keyed",
+                      "stage_traces", "_pre")
 
     def __getstate__(self):
         state = {k: v for k, v in self.__dict__.items() if k not in self._PROCESS_LOCAL}
@@ -225,75 +212,7 @@ class FetalSynthGen:
         if need_rows > ws["stride"]:
             ws["stride"] = (max(need_rows, 64) + 3) // 4 * 4
             ws["rows"] = torch.empty(shape[0] * shape[1] * ws["stride"], dtype=torch.float32, device=dev)
-        ws["seq"] = ws.get("seq", 0) + 1  # every use of the scratch set, whatever path makes it (fsg_sample_plan::ws_seq)
         return ws
-
-    def _fill_native_plan(self, p, c, scale01, ws, out, seg_out):
-        """Fill the fsg_sample_plan `p` of prepared sample `c` (see _prepare / _resolve).  `out` / `seg_out`: where the
-        image and the deformed labels go (seg_out is ignored when there is no deformation).  Returns False when the
-        configuration is outside the fused kernels' domain (blur radius beyond the plan's tap capacity)."""
-        import ctypes as C
-
-
-        dev = torch.device(self.device)
-        shape, seg, spec, rplan, nplan = c.shape, c.seg, c.spec, c.rplan, c.nplan
-        p.shape[:] = shape
-        for q, part in enumerate(c.label_parts):
-            p.label_parts[q] = part.data_ptr()
-        p.mus, p.sigmas, p.ntab = c.mus.data_ptr(), c.sigmas.data_ptr(), int(c.mus.numel())
-        f = c.gmm_plan.field
-        if f.host is not None:
-            z = f.device_tensor(dev)
-            c.keep.append(z)
-            p.gmm_noise = z.data_ptr()
-        else:
-            p.gmm_seed, p.gmm_stream = f.seed, f.stream_id
-        if spec is not None:
-            p.deform_active = 1
-            p.deform = spec.c
-            p.seg_in = seg.data_ptr()
-            # only for a caller-owned device tensor (stable identity): a converted copy would be a new cache entry per call
-            twin = self._label_twin(seg) if seg is c.segmentation else None
-            if twin is not None:
-                p.seg_in_u8 = twin.data_ptr()
-            if seg_out.dtype == torch.uint8:  # uint8 labels out: written by the warp from the uint8 source
-                if twin is None:
-                    return False
-                p.seg_out_u8 = seg_out.data_ptr()
-            else:
-                p.seg_out = seg_out.data_ptr()
-        p.epi = K._epilogue(c.gam, c.bias_dev, c.bias_tabs, shape)
-        c.keep.append(p.epi)
-        if rplan.active:
-            p.resample_active = 1
-            p.low_shape[:] = rplan.new_size
-            for a_, (t1, t2) in enumerate(zip(c.rs_tabs.ptrs, c.back_tabs.ptrs)):
-                p.rs_tab[a_], p.back_tab[a_] = t1.value, t2.value
-            for a_ in range(3):
-                if rplan.stds[a_] > 0:
-                    taps = T.gaussian_taps(float(rplan.stds[a_]))
-                    if len(taps) > 129:
-                        return False
-                    p.blur_ntaps[a_] = len(taps)
-                    C.memmove(p.blur_taps[a_], taps.ctypes.data, taps.nbytes)
-        if nplan.active:
-            nf = nplan.field
-            p.noise_std = nplan.std32
-            if nf.host is not None:
-                zn = nf.device_tensor(dev)
-                c.keep.append(zn)
-                p.noise_mode, p.noise = 1, zn.data_ptr()
-            else:
-                p.noise_mode, p.noise_seed, p.noise_stream = 2, nf.seed, nf.stream_id
-        p.scale01 = int(bool(scale01))
-        p.ws0, p.ws1, p.ws_low = ws["ws0"].data_ptr(), ws["ws1"].data_ptr(), ws["low"].data_ptr()
-        if ws["rows"] is not None:
-            p.ws_rows, p.row_stride = ws["rows"].data_ptr(), ws["stride"]
-        p.mm8, p.mm8_preset = c.arena.ptr(c.mm_off), 1
-        if c.slots_off is not None:
-            p.mm_slots, p.mm_nslots = c.arena.ptr(c.slots_off), MM_NSLOTS
-        p.out = out.data_ptr()
-        return True
 
     label_twin_budget_bytes = 1 << 30  # HBM the uint8 twins of caller-owned label volumes may take (64 at 256^3)
 
@@ -376,38 +295,62 @@ class FetalSynthGen:
 
     def _native_operands(self, c):
         """Shape / dtype / device checks of everything the C side only sees as pointers (a mismatched volume would make
-        the fused kernels gather outside a smaller buffer), and the float32 device segmentation."""
-        dev = torch.device(self.device)
-        seg = c.segmentation.to(dev)
-        if seg.dtype != torch.float32:
-            seg = seg.float()
-        seg = seg.contiguous()
-        shape = tuple(int(v) for v in c.shape)
-        if tuple(seg.shape) != shape:
-            raise ValueError(f"segmentation shape {tuple(seg.shape)} differs from the seed volumes' shape {shape}")
-        if not 1 <= len(c.label_parts) <= 4:
-            raise ValueError(f"{len(c.label_parts)} seed label volumes: the fused path takes 1..4")
-        for q, part in enumerate(c.label_parts):
-            off_dev = part.device.type != dev.type or (dev.index is not None and part.device.index != dev.index)
-            if tuple(part.shape) != shape or part.dtype != torch.uint8 or not part.is_contiguous() or off_dev:
-                raise ValueError(
-                    f"seed label volume {q}: expected a contiguous uint8 tensor of shape {shape} on {dev}, got "
-                    f"{part.dtype} {tuple(part.shape)} on {part.device} (contiguous={part.is_contiguous()})")
-        if c.mus.numel() != c.sigmas.numel() or not 1 <= c.mus.numel() <= 256:
-            raise ValueError(f"mus / sigmas tables of {c.mus.numel()} / {c.sigmas.numel()} entries (need equal, 1..256)")
-        c.shape, c.seg = shape, seg
-        c.keep.append(seg)
+        the fused kernels gather outside a smaller buffer); sets `c.seg`, the segmentation as a contiguous float32 device
+        tensor.  A caller's segmentation that already is one is used as it is, and it and the seed volumes are checked once
+        per tensor OBJECT (id + weak reference: a new tensor at a recycled address is a new object) together with the sample
+        shape -- per tensor, not per combination: the seed volumes of a subject combine in up to 6^4 ways.  Any other
+        segmentation (host, other dtype, not contiguous) is converted, and the copy is checked, on every call."""
+        shape = c.shape = tuple(int(v) for v in c.shape)
+        seg = c.segmentation
+        val = self._flat_buffers()["validated"]
+        known = torch.is_tensor(seg) and seg.is_cuda and seg.dtype == torch.float32 and seg.is_contiguous()
+        for t_ in (seg, *c.label_parts) if known else ():
+            hit = val.get(id(t_))
+            if hit is None or hit[0]() is not t_ or hit[1] != shape:
+                known = False
+                break
+        if not known:
+            dev = torch.device(self.device)
+            seg = seg.to(dev)
+            if seg.dtype != torch.float32:
+                seg = seg.float()
+            seg = seg.contiguous()
+            if tuple(seg.shape) != shape:
+                raise ValueError(f"segmentation shape {tuple(seg.shape)} differs from the seed volumes' shape {shape}")
+            if not 1 <= len(c.label_parts) <= 4:
+                raise ValueError(f"{len(c.label_parts)} seed label volumes: the fused path takes 1..4")
+            for q, part in enumerate(c.label_parts):
+                off_dev = part.device.type != dev.type or (dev.index is not None and part.device.index != dev.index)
+                if tuple(part.shape) != shape or part.dtype != torch.uint8 or not part.is_contiguous() or off_dev:
+                    raise ValueError(
+                        f"seed label volume {q}: expected a contiguous uint8 tensor of shape {shape} on {dev}, got "
+                        f"{part.dtype} {tuple(part.shape)} on {part.device} (contiguous={part.is_contiguous()})")
+            if seg is c.segmentation:
+                if len(val) > 4096:
+                    val.clear()
+                for t_ in (seg, *c.label_parts):
+                    val[id(t_)] = (weakref.ref(t_), shape)
+        c.seg = seg
+        if not 1 <= c.gm_off[2] <= 256:
+            raise ValueError(f"mus / sigmas tables of {c.gm_off[2]} entries (need 1..256)")
+
+    def _twin_of(self, c):
+        """The cached uint8 copy of the segmentation (_label_twin), only for a caller-owned device tensor (stable identity):
+        a converted copy would be a new cache entry per call."""
+        return self._label_twin(c.seg) if c.seg is c.segmentation else None
 
     def _rows_needed(self, c) -> int:
-        f2 = int(c.spec.c.field_dims[2]) if c.spec is not None else 0
-        b2 = int(c.bias_dev.shape[2]) if c.bias_dev is not None else 0
-        return 3 * f2 + b2 if c.spec is not None else 0
+        """Row workspace of the fused head: three components of the coarse deformation field and the bias field per row."""
+        if not c.dplan.active:
+            return 0
+        f2 = int(c.sb.pending[1][2]) if c.sb.pending is not None else 0
+        b2 = int(c.bplan.grid.shape[2]) if c.bplan.active else 0
+        return 3 * f2 + b2
 
-    # ---- fast form of _resolve + _native_operands + _fill_native_plan + fsg_sample_run ---------------------------------
-    # Same plan, built as two flat arrays and handed over with ONE native call (fsg_sample_pack_run): filling the ctypes
-    # struct field by field cost 41 us per sample, the spec / view objects 28 us, the operand checks 16 us
-    # (profiles/r02_c_host_phases.txt).  tests/test_hip_parity.py::test_fast_plan_equals_field_by_field_plan compares the two
-    # plans byte for byte.  FSG_SLOW_PLAN=1 forces the field-by-field path.
+    # ---- the per-sample plan -------------------------------------------------------------------------------------------
+    # fsg_sample_plan as two flat arrays (FSG_PLAN_I_* / FSG_PLAN_F_* in include/fsg_hip.h) handed over with ONE native call
+    # (fsg_sample_pack_run; fsg_sample_plan_pack for a batch): filling the ctypes struct field by field cost 41 us per sample,
+    # the spec / view objects 28 us (profiles/r02_c_host_phases.txt).
     _I = dict(SHAPE=0, LABEL_PARTS=3, MUS=7, SIGMAS=8, NTAB=9, GMM_NOISE=10, GMM_SEED=11, GMM_STREAM=12, DEFORM_ACTIVE=13,
               FLIP=14, FIELD_DIMS=15, FIELD=18, FIELD_TABS=19, SEG_IN=22, SEG_OUT=23, SEG_IN_U8=24, BIAS_DIMS=25, BIAS=28,
               BIAS_TABS=29, RESAMPLE_ACTIVE=32, LOW_SHAPE=33, RS_TABS=36, BACK_TABS=39, BLUR_NTAPS=42, NOISE_MODE=45, NOISE=46,
@@ -427,13 +370,15 @@ class FetalSynthGen:
                                    centre=np.asarray(centre, dtype=np.float32).tolist(), validated={})
         return fb
 
-    def _flat_plan(self, c, scale01, out, seg_out, ws, events=None):
-        """The two flat arrays of prepared sample `c` (uploaded arena, no _resolve needed).  Returns False when the
-        sample is outside the fused path's domain (blur radius beyond the tap capacity)."""
+    def _flat_plan(self, c, scale01, out, seg_out, ws, twin=None):
+        """The two flat arrays of prepared sample `c` (arena uploaded, _native_operands done, no _resolve needed) in the
+        generator's `_flat` buffers, which hold one plan at a time.  `seg_out`: where the deformed labels go, uint8 only
+        with `twin`, the uint8 copy of the segmentation.  Returns False when the sample is outside the fused path's domain
+        (blur radius beyond the tap capacity, uint8 labels without a twin)."""
         I = self._I
         fb = self._flat_buffers()
         iv, fv, tb = [0] * I["COUNT"], [0.0] * 17, fb["tb"]
-        arena, base = c.arena, c.arena.base
+        base = c.arena.base
         shape = c.shape
         iv[0:3] = shape
         for q, part in enumerate(c.label_parts):
@@ -459,7 +404,6 @@ class FetalSynthGen:
                 iv[I["FIELD_DIMS"]:I["FIELD_DIMS"] + 3] = fshape[:3]
                 iv[I["FIELD"]] = base + off
                 iv[I["FIELD_TABS"]:I["FIELD_TABS"] + 3] = c.sb.tabs.ptrs_i
-            twin = self._label_twin(c.seg) if c.seg is c.segmentation else None
             if twin is not None:
                 iv[I["SEG_IN_U8"]] = twin.data_ptr()
             iv[I["SEG_IN"]] = c.seg.data_ptr()
@@ -506,150 +450,49 @@ class FetalSynthGen:
         if c.slots_off is not None:
             iv[I["MM_SLOTS"]], iv[I["MM_NSLOTS"]] = base + c.slots_off, MM_NSLOTS
         iv[I["OUT"]] = out.data_ptr()
-        if events is not None:
-            iv[I["EV_BEGIN"]], iv[I["EV_END"]] = events
-        if self.stage_traces is not None:
-            tr = StageTrace()
-            tr.meta = {"shape": tuple(shape), "low_shape": tuple(rplan.new_size) if rplan.active else None,
-                       "blur_ntaps": [int(iv[I["BLUR_NTAPS"] + a_]) for a_ in range(3)]}
-            iv[I["TRACE_EVENTS"]], iv[I["TRACE_IDS"]], iv[I["TRACE_CAP"]] = tr.slots()
-            self.stage_traces.append(tr)
-        if arena.pending is not None:  # staged, not yet copied: the call uploads (Arena.stage)
-            iv[I["ARENA_HOST"]], iv[I["ARENA_DEV"]], iv[I["ARENA_BYTES"]] = arena.pending[2], base, arena.pending[3]
-            iv[I["OVERLAP"]], iv[I["WS_SEQ"]] = int(self._overlap_ok(c)), ws["seq"]
         fb["iv"][:] = iv
         fb["fv"][:] = fv
         return True
 
-    def _overlap_ok(self, c) -> bool:
-        """May the head of this sample run on the library's side stream, ordered only behind the previous sample's blur
-        (fsg_sample_plan::overlap)?  Only if everything the head reads besides the arena was handed to the device before this
-        sample's host phase: seed volumes this generator has already used (same tensor object, same in-place version),
-        tap tables built in an earlier epoch, device Philox noise (a host noise field is uploaded per sample)."""
-        if _HEAD_OVERLAP != "2" or not c.arena_early or c.gmm_plan is None or c.gmm_plan.field.host is not None:
-            return False
-        if not (c.dplan.active and c.rplan.active and c.sb.pending is not None):
-            return False
-        epoch = K._EPOCH[0]
-        if c.sb.tabs.born >= epoch or (c.bplan.active and c.bias_tabs.born >= epoch):
-            return False
-        seen, ok = self.__dict__.setdefault("_seen_parts", {}), True
-        for part in c.label_parts:
-            key = part.data_ptr()
-            hit = seen.get(key)
-            if hit is None or hit[0]() is not part or hit[1] != part._version:
-                if len(seen) > 1024:
-                    seen.clear()
-                seen[key] = (weakref.ref(part), part._version, epoch)  # first use (or rewritten in place): from the next sample on
-                ok = False
-            elif hit[2] >= epoch:
-                ok = False
-        return ok
-
-    def _fast_operands(self, c) -> bool:
-        """The operand checks of _native_operands, once per distinct (segmentation, seed volumes) set; False when the
-        segmentation needs a conversion (host tensor, other dtype): the field-by-field path handles that."""
-        seg = c.segmentation
+    def _run_native(self, c, scale01, labels_u8=False):
+        """Enqueue prepared sample `c` (arena uploaded) with one fsg_sample_pack_run call.  Returns (image, labels), or None
+        when the sample is outside the fused kernels' domain (the caller then launches stage by stage).  labels_u8: the
+        labels as a uint8 volume (written by the warp itself; without a deformation the cached uint8 copy of the input), or
+        as float32 while no uint8 copy is cached (the caller converts them)."""
+        self._native_operands(c)
         dev = torch.device(self.device)
-        if not (torch.is_tensor(seg) and seg.is_cuda and seg.dtype == torch.float32 and seg.is_contiguous()):
-            return False
-        fb = self._flat_buffers()
-        # Every tensor is checked once, as an object (id + weak reference: a new tensor at a recycled address is a new object)
-        # together with the sample shape it was checked against.  Per TENSOR, not per combination: the seed volumes of a subject
-        # combine in up to 6^4 ways, and a per-combination cache missed on most samples of a run.
-        val = fb["validated"]
-        shape = c.shape = tuple(int(v) for v in c.shape)
-        known = True
-        for t_ in (seg, *c.label_parts):
-            hit = val.get(id(t_))
-            if hit is None or hit[0]() is not t_ or hit[1] != shape:
-                known = False
-                break
-        if not known:
-            c.mus, c.sigmas = (c.arena.f32(c.gm_off[0], (c.gm_off[2],)), c.arena.f32(c.gm_off[1], (c.gm_off[2],)))
-            self._native_operands(c)  # raises on a mismatch
-            if c.seg is not seg:
-                return False
-            if len(val) > 4096:
-                val.clear()
-            for t_ in (seg, *c.label_parts):
-                val[id(t_)] = (weakref.ref(t_), shape)
-        c.seg = seg
-        if c.gm_off[2] > 256 or c.gm_off[2] < 1:
-            raise ValueError(f"mus / sigmas tables of {c.gm_off[2]} entries (need 1..256)")
-        return True
-
-    def _run_native_fast(self, c, scale01, labels_u8=False):
-        """Prepared sample -> (image, labels) through fsg_sample_pack_run, or None (caller falls back).  labels_u8: the labels
-        as a uint8 volume (written by the warp itself; without a deformation the cached uint8 copy of the input)."""
-
-        if not self._fast_operands(c):
-            return None
-        dev = torch.device(self.device)
-        f2 = int(c.sb.pending[1][2]) if (c.dplan.active and c.sb.pending is not None) else 0
-        b2 = int(c.bplan.grid.shape[2]) if c.bplan.active else 0
-        ws = self._workspace(c.shape, 3 * f2 + b2 if c.dplan.active else 0)
+        ws = self._workspace(c.shape, self._rows_needed(c))
         out = torch.empty(c.shape, dtype=torch.float32, device=dev)
-        if labels_u8:
-            if c.dplan.active:
-                seg_out = torch.empty(c.shape, dtype=torch.uint8, device=dev)
-            else:
-                seg_out = self._label_twin(c.seg) if c.seg is c.segmentation else None
-                if seg_out is None:
-                    return None
+        twin = self._twin_of(c) if (c.dplan.active or labels_u8) else None
+        if labels_u8 and twin is not None:
+            seg_out = torch.empty(c.shape, dtype=torch.uint8, device=dev) if c.dplan.active else twin
         else:
             seg_out = torch.empty_like(c.seg) if c.dplan.active else c.seg
-        events = None
-        lib = _lib.load()
+        if not self._flat_plan(c, scale01, out, seg_out, ws, twin):
+            return None
+        I, fb, lib = self._I, self._flat, _lib.load()
+        iv = fb["iv"]
         if self.blur_events is not None and c.rplan.active:
             self._blur_tick += 1
             if self._blur_tick % self.blur_events_every == 0:
                 events = (lib.fsg_event_create(), lib.fsg_event_create())
-        if not self._flat_plan(c, scale01, out, seg_out, ws, events):
-            return None
-        if events is not None:
-            fbiv = self._flat["iv"]
-            nt = [int(fbiv[self._I["BLUR_NTAPS"] + a_]) for a_ in range(3)]
-            self.blur_events.append((events[0], events[1], [(a_, nt[a_] // 2) for a_ in range(3) if nt[a_]],
-                                     tuple(int(v) for v in c.rplan.new_size)))
-        fb = self._flat
-        rc = lib.fsg_sample_pack_run(fb["ivp"], self._I["COUNT"], fb["fvp"], 17, fb["tbp"], K._stream(dev))
+                iv[I["EV_BEGIN"]], iv[I["EV_END"]] = events
+                nt = iv[I["BLUR_NTAPS"]:I["BLUR_NTAPS"] + 3].tolist()
+                self.blur_events.append((events[0], events[1], [(a_, nt[a_] // 2) for a_ in range(3) if nt[a_]],
+                                         tuple(int(v) for v in c.rplan.new_size)))
+        if self.stage_traces is not None:
+            tr = StageTrace()
+            tr.meta = {"shape": tuple(c.shape), "low_shape": tuple(c.rplan.new_size) if c.rplan.active else None,
+                       "blur_ntaps": iv[I["BLUR_NTAPS"]:I["BLUR_NTAPS"] + 3].tolist()}
+            iv[I["TRACE_EVENTS"]], iv[I["TRACE_IDS"]], iv[I["TRACE_CAP"]] = tr.slots()
+            self.stage_traces.append(tr)
+        rc = lib.fsg_sample_pack_run(fb["ivp"], I["COUNT"], fb["fvp"], 17, fb["tbp"], K._stream(dev))
         if rc in (_lib.E_ALIGN, _lib.E_TOOBIG):
-            if c.arena.pending is not None:
-                c.arena.flush(False)  # outside the fused domain: the parameters (keys re-initialised) for the fallback path
             return None
-        if c.arena.pending is not None:
-            c.arena.flush(rc == 0)
         _lib.check(rc, "fsg_sample_pack_run")
         f32_view = c.arena.f32
         c.mus, c.sigmas = f32_view(c.gm_off[0], (c.gm_off[2],)), f32_view(c.gm_off[1], (c.gm_off[2],))
         c.seed_intensities = {"mus": c.mus, "sigmas": c.sigmas}
-        return out, seg_out
-
-    def _run_native(self, c, scale01):
-        """Enqueue prepared sample `c` with one fsg_sample_run call.  Returns (image, labels), or None when the
-        configuration is outside the fused kernels' domain (the caller then launches stage by stage)."""
-        import ctypes as C
-
-
-        dev = torch.device(self.device)
-        self._native_operands(c)
-        ws = self._workspace(c.shape, self._rows_needed(c))
-        out = torch.empty(c.shape, dtype=torch.float32, device=dev)
-        seg_out = torch.empty_like(c.seg) if c.spec is not None else c.seg
-        p = _lib.SamplePlan()
-        if not self._fill_native_plan(p, c, scale01, ws, out, seg_out):
-            return None
-        if self.blur_events is not None and c.rplan.active:  # (begin, end, n_passes) appended per sample
-            lib = _lib.load()
-            e0, e1 = lib.fsg_event_create(), lib.fsg_event_create()
-            p.ev_blur_begin, p.ev_blur_end = e0, e1
-            self.blur_events.append((e0, e1, [(a_, int(p.blur_ntaps[a_]) // 2) for a_ in range(3) if p.blur_ntaps[a_]],
-                                     tuple(int(v) for v in p.low_shape)))
-        rc = _lib.load().fsg_sample_run(C.byref(p), K._stream(dev))
-        if rc in (_lib.E_ALIGN, _lib.E_TOOBIG):
-            return None
-        _lib.check(rc, "fsg_sample_run")
         return out, seg_out
 
     @staticmethod
@@ -749,7 +592,7 @@ class FetalSynthGen:
         """Every host draw of one seeds-based sample, nothing enqueued (bench.py --dry-plan, host profiling).
         fast=None: the bulk-draw form when there are no genparams (what `_prepare` uses); False: the per-stage plan()s."""
         with _rng.use(self.rng):
-            if (fast is None and not genparams and not _SLOW_PLAN) or fast:
+            if (fast is None and not genparams) or fast:
                 return self._draw_all_fast(tuple(shape))
             m2s = self.intensity_generator.draw_subclusters(genparams.get("selected_seeds", {}))
             gmm_plan = self.intensity_generator.plan_intensities(tuple(shape), genparams.get("seed_intensities", {}))
@@ -857,11 +700,11 @@ class FetalSynthGen:
             nplan.field = _rng.normal_field(tuple(rplan.new_size if rplan.active else shape), stream_id=2)
         return m2s, gmm_plan, dplan, g, bplan, rplan, nplan
 
-    # A sample goes through three host phases so that B samples can share one parameter upload and one native call:
+    # A sample goes through these host phases so that B samples can share one parameter upload and one native call:
     #   _prepare : every random draw, in the reference's order, and the small arrays added to the arena   (no device work)
     #   arena.upload
-    #   _resolve : device views of the uploaded arrays
-    # then either one fsg_sample_run / fsg_sample_run_batch call, or the stage-by-stage launches (_run_stagewise).
+    # then either its plan (_flat_plan) and one fsg_sample_pack_run / fsg_sample_run_batch call, or _resolve (device views of
+    # the uploaded arrays) and the stage-by-stage launches (_run_stagewise).
     def _prepare(self, image, segmentation, seeds, genparams, arena, segmentation_u8=None):
         if genparams:
             genparams = self._validated_genparams(genparams)
@@ -873,7 +716,7 @@ class FetalSynthGen:
         drawn = False
         if seeds is not None:
             gs = genparams.get("selected_seeds", {})
-            if hasattr(seeds, "parts") and ig.meta_labels <= 4 and not genparams and not _SLOW_PLAN:
+            if hasattr(seeds, "parts") and ig.meta_labels <= 4 and not genparams:
                 # the common case (device-resident SeedBank, nothing fixed by the caller): every draw of the sample in bulk
                 shape = tuple(seeds.shape)
                 m2s, c.gmm_plan, c.dplan, c.g, c.bplan, c.rplan, c.nplan = self._draw_all_fast(shape)
@@ -917,7 +760,7 @@ class FetalSynthGen:
             bt, new = T.zoom_tables_between(tuple(rplan.new_size), shape, True)
             c.back_tabs = K.device_tables_for(bt, dev)
         c.mm_off = arena.add(_MM8_INIT)  # the sample's min/max keys arrive initialised with its parameters
-        c.slots_off = arena.add(_MM_SLOTS_INIT) if rplan.active and not _NO_MM_SLOTS else None
+        c.slots_off = arena.add(_MM_SLOTS_INIT) if rplan.active else None
         c.gm_off = None
         if c.gmm_plan is not None:
             c.gm_off = (arena.add(c.gmm_plan.mus.numpy()), arena.add(c.gmm_plan.sigmas.numpy()), c.gmm_plan.mus.numel())
@@ -1082,41 +925,14 @@ class FetalSynthGen:
 
     def _pipeline_f(self, image, segmentation, seeds, genparams, scale01: bool, segmentation_u8=None, labels_u8: bool = False):
         with _rng.use(self.rng):
-            K._EPOCH[0] += 1
             arena = T.Arena()
-            # The device block of THIS sample's parameters was allocated during the previous sample's host phase, i.e. before
-            # that sample's kernels were enqueued: whatever owned the block before was last used ahead of them, so the upload
-            # may be ordered behind the previous sample's blur alone (fsg_sample_plan::overlap).  The next sample's block
-            # is allocated here, before this sample enqueues anything.
-            dev = torch.device(self.device)
-            nxt = self.__dict__.setdefault("_arena_next", {})
-            akey = (dev.index, K._stream(dev).value)
-            block = nxt.pop(akey, None) if _HEAD_OVERLAP != "0" else None
-            early = block is not None
-            if _HEAD_OVERLAP != "0":
-                if block is None:
-                    block = torch.empty(_ARENA_BLOCK, dtype=torch.uint8, device=dev)
-                if len(nxt) > 8:
-                    nxt.clear()
-                nxt[akey] = torch.empty(_ARENA_BLOCK, dtype=torch.uint8, device=dev)
             c = self._prepare(image, segmentation, seeds, genparams, arena, segmentation_u8)
-            c.arena_early = early
-            fast = self._native_ok(c, labels_u8) and not _SLOW_PLAN
-            if not (fast and block is not None and arena.stage(self.device, block)):
-                arena.upload(self.device)
-            if fast:
-                try:
-                    native = self._run_native_fast(c, scale01, labels_u8)
-                finally:
-                    if arena.pending is not None:  # the native call was not reached: upload on the launch stream now
-                        arena.flush(False)
+            arena.upload(self.device)
+            if self._native_ok(c, labels_u8):
+                native = self._run_native(c, scale01, labels_u8)
                 if native is not None:
                     return native[0], native[1], None, self._synth_params(c, {})
             self._resolve(c)
-            if self._native_ok(c, labels_u8):
-                native = self._run_native(c, scale01)
-                if native is not None:
-                    return native[0], native[1], None, self._synth_params(c, {})
             return self._run_stagewise(c, scale01)
 
     def sample_batch(self, items, genparams_list=None, scale01: bool = False, streams: int = 1, lazy_items: int | None = None,
@@ -1176,11 +992,15 @@ class FetalSynthGen:
                 out_all = torch.empty((B, *shape), dtype=torch.float32, device=dev)
                 seg_all = torch.empty((B, *shape), dtype=torch.uint8 if labels_u8 else torch.float32, device=dev)
                 plans = (_lib.SamplePlan * B)()
-                ok = True
+                lib, fb, ok = _lib.load(), self._flat, True
                 for b, c in enumerate(ctxs):
-                    if c.spec is None:
+                    if not c.dplan.active:
                         seg_all[b].copy_(c.seg)  # no deformation: labels pass through (same stream as the upload)
-                    ok = ok and self._fill_native_plan(plans[b], c, scale01, wss[b % nstreams], out_all[b], seg_all[b])
+                    ok = ok and self._flat_plan(c, scale01, out_all[b], seg_all[b], wss[b % nstreams],
+                                                self._twin_of(c) if c.dplan.active else None)
+                    if ok:  # _flat holds one plan: pack it before the next one is built
+                        _lib.check(lib.fsg_sample_plan_pack(C.byref(plans[b]), fb["ivp"], self._I["COUNT"], fb["fvp"], 17,
+                                                            fb["tbp"]), "fsg_sample_plan_pack")
                 if ok:
                     handles = (C.c_void_p * nstreams)()
                     if nstreams > 1:
@@ -1191,7 +1011,7 @@ class FetalSynthGen:
                             handles[q] = side[q].cuda_stream
                     else:
                         handles[0] = K._stream(dev).value
-                    rc = _lib.load().fsg_sample_run_batch(plans, B, handles, nstreams)
+                    rc = lib.fsg_sample_run_batch(plans, B, handles, nstreams)
                     if nstreams > 1:
                         for q in range(nstreams):
                             join = torch.cuda.Event()

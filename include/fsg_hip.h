@@ -464,13 +464,8 @@ typedef struct fsg_sample_plan {
   const void* arena_host;
   void* arena_dev;
   uint64_t arena_bytes;
-  /* overlap != 0: the upload and the head of the sample (K1 + per-row coarse values + face minima) run on a side stream
-   * owned by the library, ordered behind the point of the PREVIOUS call on `stream` after which ws0 / ws_rows are no longer
-   * touched (its blur), so that they execute beside the previous sample's resampling tail; `stream` waits for them before
-   * the warp.  ws_seq identifies consecutive uses of the workspace: the previous call's ordering point is honoured only if
-   * it carried ws_seq - 1 and the same ws0, otherwise the side stream is ordered behind everything enqueued on `stream`
-   * so far.  Requires arena_dev to be private to this call and not reused by the next one (a ring of >= 2 blocks).
-   * Results are those of overlap == 0. */
+  /* overlap / ws_seq: retired (a side stream for the upload and the head of the sample, measured slower and removed).
+   * Ignored: results are those of overlap == 0, and the layout stays.  Never reuse them. */
   int32_t overlap;
   uint64_t ws_seq;
   /* optional: the deformed labels as uint8 (needs seg_in_u8; seg_out may then be NULL): the device-resident streaming hand-over
@@ -654,9 +649,7 @@ int fsg_keyed_sample_run(void* ctx, const int64_t* iv, int niv, fsg_keyed_draws*
 /* The draw kernel alone (tests): fills the parameter block of `draws` at block_dev. */
 int fsg_keyed_fill_block(void* ctx, const fsg_keyed_draws* draws, void* block_dev, void* stream);
 
-/* Releases the library-owned side streams / events of the opt-in head overlap (fsg_sample_plan::overlap); they otherwise
- * live for the life of the process.  Synchronise the launch streams first.  No reference counterpart (the reference owns
- * no streams). */
+/* Retired with fsg_sample_plan::overlap: the library owns no streams or events any more.  Kept for the ABI; returns 0. */
 int fsg_pipeline_teardown(void);
 /* float32 -> float16 (round to nearest even) copy of a volume: the optional half-precision image of the output side. */
 int fsg_cast_f32_to_f16(const float* x, size_t n, void* out_f16, void* stream);

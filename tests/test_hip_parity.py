@@ -1269,69 +1269,59 @@ def test_uint8_label_output_equals_the_float_labels(K, prob):
             assert torch.equal(out[b], want[b][0]) and torch.equal(lab[b].float(), want[b][1])
 
 
-@pytest.mark.parametrize("shape", [(64, 56, 72), (256, 256, 256)])
-def test_head_overlap_reproduces_the_in_order_stream(K, shape):
-    """fsg_sample_plan::overlap: the parameter upload and the head of sample n+1 run on the library's side stream beside the
-    resampling tail of sample n.  The results must be those of the plain in-order launch (FSG_HEAD_OVERLAP=0: upload on the
-    launch stream before the call) bit for bit, for a sequence that keeps invalidating the ordering point: seed banks the
-    generator has not used yet, a bank rewritten in place, a `sample_batch` in between, a second launch stream, and user
-    work on the outputs enqueued between the calls (256^3: kernels long enough for a missing dependency to be hit)."""
+def test_plan_that_uploads_its_own_parameters_equals_the_uploaded_arena(K):
+    """fsg_sample_plan::arena_host / arena_dev / arena_bytes: the call copies the sample's parameter block from pinned host
+    memory on the launch stream before its first kernel.  The result must be the same plan's with the arena uploaded
+    beforehand (what `_pipeline` does) bit for bit, with the device block cleared so that only the call's copy can fill it;
+    the retired `overlap` / `ws_seq` fields are ignored."""
+    from fetalsyngen_amd import _lib
+    from fetalsyngen_amd import rng as _rng
+    from fetalsyngen_amd import tables as T
     from fetalsyngen_amd.data.datasets import SeedBank
-    from fetalsyngen_amd.generator import model as M
     from fetalsyngen_amd.phantom import make_seed_volumes
 
-    nsub = 3
-    subjects = []
-    for v in range(nsub):
-        seg, seeds = make_seed_volumes(shape, v)
-        subjects.append((dev(seg), SeedBank(seeds, DEV)))
-    small = shape[0] < 128
-    gen = make_generator(shape, DEV, rng="device", prob=1.0, nonlin_scale=(0.08, 0.2) if small else (0.03, 0.06),
-                         bf_scale=(0.03, 0.12) if small else (0.004, 0.02))
-    other = torch.cuda.Stream()
+    shape = (64, 56, 72)
+    seg, seeds = make_seed_volumes(shape, 1)
+    segd, bank = dev(seg), SeedBank(seeds, DEV)
+    gen = make_generator(shape, DEV, rng="device", prob=1.0, nonlin_scale=(0.08, 0.2), bf_scale=(0.03, 0.12))
+    lib = _lib.load()
+    I = gen._I
 
-    def run(mode):
-        prev = M._HEAD_OVERLAP
-        M._HEAD_OVERLAP = mode
-        try:
-            sums = []
-            keep = None
-            for i in range(14):
-                np.random.seed(100 + i)
-                torch.manual_seed(100 + i)
-                seg, bank = subjects[i % nsub]
-                if i == 6:  # a bank the generator has never seen, uploaded right before the call
-                    seg2, seeds2 = make_seed_volumes(shape, 7)
-                    seg, bank = dev(seg2), SeedBank(seeds2, DEV)
-                if i == 8:  # rewritten in place (same storage, new _version)
-                    for d in bank.vol.values():
-                        for t in d.values():
-                            t.copy_(t.flip(0).contiguous())
-                if i == 9:
-                    out, lab, _, _ = gen.sample_batch([(None, seg, bank)], streams=1)
-                    out, lab = out[0], lab[0]
-                elif i == 11:
-                    with torch.cuda.stream(other):
-                        other.wait_stream(torch.cuda.current_stream())
-                        out, lab, _, _ = gen.sample(None, seg, bank)
-                    torch.cuda.current_stream().wait_stream(other)
-                else:
-                    out, lab, _, _ = gen.sample(None, seg, bank)
-                keep = (out * 2.0).sum()  # user work on the launch stream between the calls; its block is freed next turn
-                sums.append((out.double().sum().item(), lab.double().sum().item(), out[3, 5, 7].item(), keep.item()))
-                if i == 8:
-                    for d in bank.vol.values():
-                        for t in d.values():
-                            t.copy_(t.flip(0).contiguous())
-            torch.cuda.synchronize()
-            return sums
-        finally:
-            M._HEAD_OVERLAP = prev
+    def run(seed, upload):
+        np.random.seed(seed)
+        torch.manual_seed(seed)
+        with _rng.use(gen.rng):
+            arena = T.Arena()
+            c = gen._prepare(None, segd, bank, {}, arena)
+            arena.upload(DEV)
+            gen._native_operands(c)
+            ws = gen._workspace(c.shape, gen._rows_needed(c))
+            out = torch.empty(c.shape, dtype=torch.float32, device=DEV)
+            seg_out = torch.empty_like(c.seg) if c.dplan.active else c.seg
+            assert gen._flat_plan(c, True, out, seg_out, ws, gen._twin_of(c) if c.dplan.active else None)
+            iv, host = gen._flat["iv"], None
+            if upload is not None:
+                host = torch.empty(arena.dev.numel(), dtype=torch.uint8, pin_memory=True)
+                host.copy_(arena.dev)
+                arena.dev.zero_()
+                iv[I["ARENA_HOST"]], iv[I["ARENA_DEV"]], iv[I["ARENA_BYTES"]] = host.data_ptr(), arena.dev.data_ptr(), host.numel()
+                iv[I["OVERLAP"]], iv[I["WS_SEQ"]] = upload, 5 * upload
+            fb = gen._flat
+            rc = lib.fsg_sample_pack_run(fb["ivp"], I["COUNT"], fb["fvp"], 17, fb["tbp"], K._stream(torch.device(DEV)))
+            _lib.check(rc, "fsg_sample_pack_run")
+            torch.cuda.synchronize()  # `host` must outlive the copy
+            return out.clone(), seg_out.clone(), c
 
-    want = run("0")
-    got = run("2")
-    assert got == want
-    assert run("1") == want  # upload inside the call, launch stream only
+    for seed in range(3):
+        want_out, want_lab, c = run(seed, None)
+        assert c.dplan.active and c.rplan.active and c.bplan.active
+        np.random.seed(seed)
+        torch.manual_seed(seed)
+        o, l, _, _ = gen._pipeline(None, segd, bank, {}, scale01=True)
+        assert torch.equal(o, want_out) and torch.equal(l, want_lab)  # the plan is the one `_pipeline` runs
+        for upload in (0, 1):
+            got_out, got_lab, _ = run(seed, upload)
+            assert torch.equal(got_out, want_out) and torch.equal(got_lab, want_lab), (seed, upload)
 
 
 @pytest.mark.parametrize("prob", [1.0, 0.6])
@@ -1423,65 +1413,44 @@ def test_prefetching_stream_batched_and_half_precision(K, tmp_path):
 
 
 @pytest.mark.parametrize("prob", [1.0, 0.5])
-def test_fast_plan_equals_field_by_field_plan(K, prob):
-    """The per-sample plan built as two flat arrays + fsg_sample_plan_pack (what `_pipeline` uses) against the plan filled
-    field by field through ctypes: byte-identical structs for random samples (gates on and off, reference and device RNG),
-    and identical outputs from the two paths."""
-    import ctypes as C
-
-    from fetalsyngen_amd import _lib
-    from fetalsyngen_amd import rng as _rng
-    from fetalsyngen_amd import tables as T
+@pytest.mark.parametrize("case", ["host_f32", "host_f64", "device_strided", "u8_without_twin"])
+def test_converted_inputs_equal_the_primary_path(K, case, prob):
+    """One plan builder serves every input the fused path accepts: a segmentation on the host (float32 or float64) or not
+    contiguous is converted to a float32 device copy, and uint8 labels asked for while no uint8 copy of the segmentation is
+    cached come out of the plan as float32 and are converted afterwards.  Images and labels must equal, bit for bit, the
+    same samples made the primary way (a contiguous float32 device segmentation; for uint8 labels the float32 labels
+    converted), with gates on and off, in both RNG modes."""
     from fetalsyngen_amd.data.datasets import SeedBank
-    from fetalsyngen_amd.generator import model as M
     from fetalsyngen_amd.phantom import make_seed_volumes
 
     shape = (40, 48, 56)
     seg, seeds = make_seed_volumes(shape, 2)
     bank, segd = SeedBank(seeds, DEV), dev(seg)
-    lib = _lib.load()
     for mode in ("device", "reference"):
         gen = make_generator(shape, DEV, rng=mode, prob=prob, nonlin_scale=(0.08, 0.2), bf_scale=(0.03, 0.12))
-        gen.register_label_twin(segd, segd.to(torch.uint8))  # both plans then see the same uint8 label source
-        for seed in range(6):
+        alt = make_generator(shape, DEV, rng=mode, prob=prob, nonlin_scale=(0.08, 0.2), bf_scale=(0.03, 0.12))
+        for seed in range(4):
             np.random.seed(seed)
             torch.manual_seed(seed)
-            with _rng.use(gen.rng):
-                arena = T.Arena()
-                c = gen._prepare(None, segd, bank, {}, arena)
-                arena.upload(DEV)
-                gen._resolve(c)
-                gen._native_operands(c)
-                ws = gen._workspace(c.shape, gen._rows_needed(c))
-                out = torch.empty(c.shape, dtype=torch.float32, device=DEV)
-                seg_out = torch.empty_like(c.seg)
-                slow = _lib.SamplePlan()
-                assert gen._fill_native_plan(slow, c, True, ws, out, seg_out)
-                assert gen._fast_operands(c) and gen._flat_plan(c, True, out, seg_out if c.dplan.active else c.seg, ws)
-                fb = gen._flat
-                fast = _lib.SamplePlan()
-                _lib.check(lib.fsg_sample_plan_pack(C.byref(fast), fb["ivp"], gen._I["COUNT"], fb["fvp"], 17, fb["tbp"]), "pack")
-                if not c.dplan.active:  # the field-by-field plan leaves seg pointers unset without a deformation; so does pack
-                    assert fast.seg_in is None and fast.seg_out is None
-                if mode == "reference":  # host-tape noise is uploaded per plan: fresh device tensors, so the pointers differ
-                    for pl in (slow, fast):
-                        assert pl.gmm_noise and (pl.noise or not c.nplan.active)
-                        pl.gmm_noise, pl.noise = None, None
-                a, b = bytes(slow), bytes(fast)
-                assert a == b, [i for i in range(len(a)) if a[i] != b[i]][:16]
-    # and end to end: both paths give the same sample
-    gen = make_generator(shape, DEV, rng="device", prob=prob, nonlin_scale=(0.08, 0.2), bf_scale=(0.03, 0.12))
-    res = {}
-    for slow_plan in (False, True):
-        M._SLOW_PLAN = slow_plan
-        try:
-            np.random.seed(3)
-            torch.manual_seed(3)
-            res[slow_plan] = [gen._pipeline(None, segd, bank, {}, scale01=True)[:2] for _ in range(4)]
-        finally:
-            M._SLOW_PLAN = False
-    for (o1, l1), (o2, l2) in zip(res[False], res[True]):
-        assert torch.equal(o1, o2) and torch.equal(l1, l2)
+            want_out, want_lab, _, want_p = gen._pipeline(None, segd, bank, {}, scale01=True)
+            labels_u8 = case == "u8_without_twin"
+            if case == "host_f32":
+                s_ = torch.from_numpy(seg)
+            elif case == "host_f64":
+                s_ = torch.from_numpy(seg.astype(np.float64))
+            elif case == "device_strided":
+                s_ = segd.permute(2, 1, 0).contiguous().permute(2, 1, 0)
+                assert not s_.is_contiguous()
+            else:
+                s_ = segd.clone()  # a tensor the generator has never seen: no uint8 twin yet
+            np.random.seed(seed)
+            torch.manual_seed(seed)
+            out, lab, _, p = alt._pipeline(None, s_, bank, {}, scale01=True, labels_u8=labels_u8)
+            assert lab.is_cuda and lab.dtype == (torch.uint8 if labels_u8 else torch.float32)
+            assert torch.equal(out, want_out), (mode, seed)
+            assert torch.equal(lab, want_lab.to(torch.uint8) if labels_u8 else want_lab), (mode, seed)
+            assert p["resample_params"] == want_p["resample_params"]
+            assert torch.equal(p["seed_intensities"]["mus"], want_p["seed_intensities"]["mus"])
 
 
 def test_workspace_eviction_across_streams(K):

@@ -41,7 +41,7 @@ def _assert_clean(obj, forbidden_ints=()):
             assert leaf not in forbidden_ints, f"{path}: an address of the parent process survived pickling"
 
 
-def test_generator_pickle_drops_every_process_local_thing():
+def test_generator_pickle_drops_its_process_local_state():
     shape = (16, 16, 16)
     gen = make_generator(shape, "cuda:0", rng="device")
     fb = gen._flat_buffers()
@@ -49,14 +49,12 @@ def test_generator_pickle_drops_every_process_local_thing():
     # what a generator that has produced samples carries (device tensors stood in for by CPU tensors: no GPU here)
     gen._ws[(shape, 0, 0)] = {"ws0": torch.zeros(8), "ws1": torch.zeros(8), "low": torch.zeros(8), "rows": None, "stride": 0}
     gen.__dict__["_twins"] = {"by_id": {1: [None, 0, torch.zeros(8, dtype=torch.uint8), 2]}, "bytes": 8}
-    gen.__dict__["_seen_parts"] = {123: (None, 0, 0)}
-    gen.__dict__["_arena_next"] = {(0, 0): torch.zeros(8, dtype=torch.uint8)}
     gen.__dict__["_rs_dt"] = {((8, 8, 8), shape): object()}
     gen.blur_events = [(1, 2, [])]
     fb["validated"][42] = (None, shape)
 
     clone = pickle.loads(pickle.dumps(gen))
-    for name in ("_flat", "_twins", "_seen_parts", "_arena_next", "_rs_dt", "_batch_streams", "_keyed"):
+    for name in ("_flat", "_twins", "_rs_dt", "_batch_streams", "_keyed"):
         assert name not in clone.__dict__, name
     assert clone._ws == {} and clone.blur_events is None
     _assert_clean(clone, parent_addresses)

@@ -38,11 +38,13 @@ for i in range(a.n):
         arena = T.Arena()
         c = gen._prepare(None, segd, bank, {}, arena); t = tick("_prepare(total incl. draws)", t)
         arena.upload(dev); t = tick("arena.upload", t)
-        gen._resolve(c); t = tick("_resolve", t)
         gen._native_operands(c); ws = gen._workspace(c.shape, gen._rows_needed(c)); t = tick("operands+workspace", t)
         out = torch.empty(c.shape, dtype=torch.float32, device=dev); so = torch.empty_like(c.seg); t = tick("torch.empty x2", t)
-        p = _lib.SamplePlan(); ok = gen._fill_native_plan(p, c, True, ws, out, so); t = tick("fill_native_plan", t)
-        rc = lib.fsg_sample_run(C.byref(p), K._stream(torch.device(dev))); t = tick("fsg_sample_run (C: launches)", t)
+        ok = gen._flat_plan(c, True, out, so, ws, gen._twin_of(c) if c.dplan.active else None); t = tick("flat_plan", t)
+        fb = gen._flat
+        rc = lib.fsg_sample_pack_run(fb["ivp"], gen._I["COUNT"], fb["fvp"], 17, fb["tbp"], K._stream(torch.device(dev)))
+        t = tick("fsg_sample_pack_run (C: pack + launches)", t)
+        c.seed_intensities = {"mus": arena.f32(c.gm_off[0], (c.gm_off[2],)), "sigmas": arena.f32(c.gm_off[1], (c.gm_off[2],))}
         prm = gen._synth_params(c, {}); t = tick("synth_params", t)
 tot = time.perf_counter() - t_all
 torch.cuda.synchronize()
