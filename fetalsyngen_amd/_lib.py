@@ -243,10 +243,15 @@ SIGNATURES = {
     "fsg_event_destroy": [P],
     "fsg_event_record": [P, P],
     "fsg_event_elapsed_ms": [P, P, C.POINTER(C.c_float)],
+    "fsg_seed_meta_pack": [P, P, P, SZ, P, I, P, P, P, P, P, P],
+    "fsg_em1d_tile": [],
+    "fsg_em1d_fit": [P, SZ, I, P, P, P, P, P, P, SZ, P],
+    "fsg_seed_assign": [P, SZ, P, I, P, I, P, P, P, SZ, P],
 }
 SPECIAL_RESTYPE = {"fsg_error_string": (C.c_char_p, [I]), "fsg_key_to_float": (F, [C.c_int32]),
                    "fsg_event_create": (C.c_void_p, []), "fsg_sample_plan_layout": (C.c_int64, [I]),
-                   "fsg_keyed_block_bytes": (C.c_int64, [P]), "fsg_seed_codes_work_bytes": (C.c_size_t, [])}
+                   "fsg_keyed_block_bytes": (C.c_int64, [P]), "fsg_seed_codes_work_bytes": (C.c_size_t, []),
+                   "fsg_seed_meta_work_bytes": (C.c_size_t, [SZ]), "fsg_em1d_work_bytes": (C.c_size_t, [I, C.c_int64])}
 
 _lib = None
 

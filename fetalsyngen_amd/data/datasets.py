@@ -35,7 +35,7 @@ class SeedBank:
         self.device = device
         self._host = None
         self._vol = {
-            n: {m: torch.as_tensor(np.asarray(v)).to(torch.uint8).to(device) for m, v in d.items()}
+            n: {m: (v if torch.is_tensor(v) else torch.as_tensor(np.asarray(v))).to(torch.uint8).to(device) for m, v in d.items()}
             for n, d in volumes.items()
         }
         self._cache = {}
@@ -208,6 +208,8 @@ class FetalDataset:
 
 
 class FetalSynthDataset(FetalDataset):
+    seeds_from_images = None  # subclasses that build themselves without this constructor read seeds from what they were given
+
     def __init__(
         self,
         bids_path: str,
@@ -220,13 +222,22 @@ class FetalSynthDataset(FetalDataset):
         return_device: bool = False,
         cache_bytes: int | None = None,
         base_seed: int | None = None,
+        seeds_from_images: int | None = None,
     ):
         """`cache_bytes`: HBM budget of the decoded-label cache (`LabelCache`; None = half of the free HBM).
         `base_seed`: None keeps the reference's behaviour (`__getitem__` draws from the global generators as they stand);
         an integer makes `__getitem__(idx)` re-seed numpy's and torch's CPU generators with the key
         `(base_seed, epoch * len(self) + idx)` first (`sharding.seed_for_sample`), so a sample depends on its index only --
-        not on which DataLoader worker produced it, nor on how many workers there are (`set_epoch` moves to fresh keys)."""
+        not on which DataLoader worker produced it, nor on how many workers there are (`set_epoch` moves to fresh keys).
+        `seeds_from_images`: None keeps the reference's behaviour (seeds come from the files under `seed_path`).  An integer,
+        with `seed_path=None`: a subject's seed volumes for 1..`seeds_from_images` subclasses are generated on the device from
+        its T2w + dseg on first use (`seedgen.generate_seeds`, key `seedgen.subject_key(base_seed, idx)`) and cached like
+        file-loaded ones."""
+        if seed_path is not None and seeds_from_images is not None:
+            raise ValueError("seed_path and seeds_from_images exclude each other: seeds are read from files or generated, not both")
         super().__init__(bids_path, sub_list)
+        self.seeds_from_images = None if seeds_from_images is None else int(seeds_from_images)
+        self.seeds_annotation = "feta"
         self.seed_path = Path(seed_path) if isinstance(seed_path, str) else None
         self.load_image = load_image
         self.generator = generator
@@ -273,6 +284,13 @@ class FetalSynthDataset(FetalDataset):
                 nbytes += bank.nbytes
             host = self.loader(self.segm_paths[idx]).float()
             dev = host.to(self.generator.device)
+            if self.seeds_from_images is not None and not self.image_as_intensity:
+                from .. import seedgen
+
+                image = self.loader(self.img_paths[idx]).float().to(self.generator.device)
+                bank = SeedBank(seedgen.generate_seeds(image, dev, self.seeds_from_images, self.seeds_annotation,
+                                                       key=seedgen.subject_key(self.base_seed, idx)), self.generator.device)
+                nbytes += bank.nbytes
             # uint8 twin for the label gather when the segmentation is integer valued in 0..255 (always the
             # case for dseg files); results are identical, the kernel reads 1 byte instead of 4 per voxel
             ok = bool(torch.equal(host, host.round()) and host.min() >= 0 and host.max() <= 255)
@@ -285,7 +303,7 @@ class FetalSynthDataset(FetalDataset):
         return self._labels.get(idx, build)
 
     def _seeds_for(self, name, idx=None):
-        if not self.cache_on_device:
+        if not self.cache_on_device and self.seeds_from_images is None:
             return self.seed_paths[name]
         if idx is None:
             idx = [self._sub_ses_idx(k) for k in range(len(self.sub_ses))].index(name)
@@ -307,7 +325,7 @@ class FetalSynthDataset(FetalDataset):
         segm = self._segmentation(idx)
         name = self._sub_ses_idx(idx)
         seeds = None
-        if self.seed_path is not None and not self.image_as_intensity:
+        if (self.seed_path is not None or self.seeds_from_images is not None) and not self.image_as_intensity:
             seeds = self._seeds_for(name, idx)
         generation_params = {
             "idx": idx,
@@ -340,7 +358,8 @@ class FetalSynthDataset(FetalDataset):
         {"image": (B,1,H,W,D) float32 in [0,1], "label": (B,1,H,W,D) int64, "name": [B]} on the CPU, or on the device with
         uint8 labels when `return_device` -- and the list of B generation_params.  Same draws, same values as B
         consecutive `sample` calls."""
-        if self.load_image or self.image_as_intensity or self.seed_path is None or not self.cache_on_device:
+        if (self.load_image or self.image_as_intensity or (self.seed_path is None and self.seeds_from_images is None)
+                or not self.cache_on_device):
             raise ValueError("sample_batch serves the seeds-based path with device-cached label volumes "
                              "(load_image=False, image_as_intensity=False, cache_on_device=True)")
         indices = [int(i) for i in indices]

@@ -81,6 +81,42 @@ def read_nifti(path):
     return np.ascontiguousarray(arr), affine, pixdim[1:4]
 
 
+def write_nifti(path, arr, affine) -> None:
+    """Write a 3-D array indexed (x, y, z) as a little-endian single-file NIfTI-1 volume (gzip when the name ends in .gz):
+    the array's own dtype (one of those `read_nifti` reads), `affine` as the sform (sform_code 2, "aligned"; no qform),
+    pixdim = the affine's column norms, no intensity scaling.  The counterpart of `read_nifti`, used to store generated seed
+    volumes the way the reference's seed files are stored (int8)."""
+    arr = np.asarray(arr)
+    codes = {np.dtype(v): k for k, v in _DTYPES.items()}
+    if arr.dtype not in codes:
+        raise ValueError(f"unsupported dtype {arr.dtype} for a NIfTI-1 volume")
+    if arr.ndim != 3:
+        raise ValueError(f"expected a 3-D volume, got shape {arr.shape}")
+    affine = np.asarray(affine, dtype=np.float64)
+    if affine.shape != (4, 4):
+        raise ValueError("affine must be 4x4")
+    zooms = np.sqrt((affine[:3, :3] ** 2).sum(axis=0))
+    hdr = bytearray(348)
+    struct.pack_into("<i", hdr, 0, 348)
+    struct.pack_into("<8h", hdr, 40, 3, arr.shape[0], arr.shape[1], arr.shape[2], 1, 1, 1, 1)
+    struct.pack_into("<2h", hdr, 70, codes[arr.dtype], arr.dtype.itemsize * 8)
+    struct.pack_into("<8f", hdr, 76, 1.0, float(zooms[0]), float(zooms[1]), float(zooms[2]), 0.0, 0.0, 0.0, 0.0)
+    struct.pack_into("<f", hdr, 108, 352.0)
+    struct.pack_into("<2f", hdr, 112, 1.0, 0.0)
+    hdr[123] = 2  # xyzt_units: millimetres
+    struct.pack_into("<2h", hdr, 252, 0, 2)
+    struct.pack_into("<12f", hdr, 280, *[float(v) for v in affine[:3, :].reshape(-1)])
+    hdr[344:348] = b"n+1\0"
+    payload = bytes(hdr) + b"\0\0\0\0" + np.asarray(arr, dtype=arr.dtype.newbyteorder("<")).tobytes(order="F")
+    path = str(path)
+    if path.endswith(".gz"):
+        with open(path, "wb") as raw, gzip.GzipFile(filename="", fileobj=raw, mode="wb", compresslevel=6, mtime=0) as fh:
+            fh.write(payload)  # no name, no timestamp in the gzip header: the same volume gives the same file
+    else:
+        with open(path, "wb") as fh:
+            fh.write(payload)
+
+
 def io_orientation(affine: np.ndarray) -> np.ndarray:
     """(3,2) array: for every voxel axis the world axis (0=R,1=A,2=S) it is closest to and the direction (+1/-1).
 

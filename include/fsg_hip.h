@@ -660,6 +660,43 @@ int fsg_event_record(void* event, void* stream);
 int fsg_event_destroy(void* event);
 int fsg_event_elapsed_ms(void* begin, void* end, float* ms);
 
+/* ---------------------------------------------------------------------------------------------------------------------
+ * Seed generation (fsg_seedgen.hip): what scripts/generate_seeds.py of the reference does offline with sklearn.
+ *
+ * Meta-label fusion + stable compaction.  Exactly one of seg_u8 / seg_f32 is given.  NaN in image or label counts as 0;
+ * a label equal to clear_label (-1 = none) is set to 0 first; meta = table256[label] (values 0..4); label 0 with a non-zero
+ * image value -> 4.  Outputs: the uint8 meta volume, counts4[m-1] = voxels of meta-label m, and packed_x / packed_idx
+ * (n entries each): the intensities and voxel indices of meta-label 1, then 2, 3, 4, each in voxel order -- the order
+ * is a function of the inputs alone.  work: fsg_seed_meta_work_bytes(n) bytes.  Three launches, no host sync. */
+size_t fsg_seed_meta_work_bytes(size_t n);
+int fsg_seed_meta_pack(const uint8_t* seg_u8, const float* seg_f32, const float* image, size_t n, const uint8_t* table256,
+                       int clear_label, uint8_t* meta, uint32_t* counts4, float* packed_x, int32_t* packed_idx, void* work,
+                       void* stream);
+
+/* Batched 1-D Gaussian-mixture EM.  jobs_host: HOST table, 8 int64 per job:
+ *   [0] offset of the job's samples in x   [1] n samples   [2] k components (1..16)
+ *   [3] first workgroup of the job   [4] its workgroup count = ceil(n / tile)   (consecutive over the table; tile from the
+ *       call below)   [5] max_iter (>= 1)   [6] 0 = params holds initial weights/means/variances, 1 = params holds initial
+ *       means only (one-hot responsibilities of the nearest mean, then an M-step), 2 = no fit (params are final: assignment only)   [7] 0
+ * tol_host: HOST, one double per job (>= 0; 0 = run max_iter iterations).  params: DEVICE double [njobs][3][16] (weights,
+ * means, variances; in: initial, out: fitted).  lower_bound: DEVICE double [njobs].  status: DEVICE int32 [njobs][4] =
+ * n_iter, converged, done, 0.  work: DEVICE, 16-byte aligned, at least the work-bytes call says for (njobs, total workgroups).
+ * The two host tables are copied to the device on `stream` (they must stay valid until the stream has passed the copies); then
+ * two launches per iteration up to the largest max_iter, no host synchronisation, workgroups of finished jobs return at once.
+ * Sums are float64 and reduced in a fixed order: results are bitwise reproducible and independent of the job order.
+ * FSG_E_BADARG: null pointer, k < 1 or k > 16, n == 0 with k > 1, max_iter < 1, a job outside x, inconsistent workgroup ranges. */
+int fsg_em1d_tile(void);
+size_t fsg_em1d_work_bytes(int njobs, int64_t nblocks);
+int fsg_em1d_fit(const float* x, size_t nx, int njobs, const int64_t* jobs_host, const double* tol_host, double* params,
+                 double* lower_bound, int32_t* status, void* work, size_t work_bytes, void* stream);
+
+/* Assignment + scatter for nwin jobs of the table the fit ran on (same work buffer).  wins_host: HOST, 4 int64 per entry: job
+ * index, DEVICE pointer of a zero-filled uint8 volume, base value, first workgroup (consecutive, job's workgroup count each).
+ * out[packed_idx[i]] = base + rank of the component with the largest weighted log-density (ties -> lowest component), where
+ * rank orders the components by ascending mean. */
+int fsg_seed_assign(const float* x, size_t nx, const int32_t* packed_idx, int njobs, const int64_t* jobs_host, int nwin,
+                    const int64_t* wins_host, const double* params, void* work, size_t work_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
