@@ -1,19 +1,39 @@
-"""ctypes binding of libfsg_hip.so (C ABI in include/fsg_hip.h).
+"""ctypes binding of libfsg_hip.so, derived from include/fsg_hip.h when this module is imported.
+
+The header is the one statement of the C ABI: its constants, struct layouts and prototypes are read from it here (`parse`),
+so a field, a slot or an entry point added there needs no edit in this file.  The parser covers what that header uses and
+refuses, with the line, anything else.
+
+    constants   header name without FSG_: ABI_VERSION, E_ALIGN, MM_SLOT_STRIDE, ...; the families in GROUPS as namespaces:
+                PLAN_I.MUS, KEYED_I.NEXT_KEY, TUNE.NO_SEED_CODES, ...  A name the header lacks raises AttributeError.
+    structs     fsg_sample_plan -> SamplePlan, ...; every pointer field is c_void_p.
+    prototypes  set on the library by load(); a pointer to one of the header's structs is POINTER(that struct), any other
+                pointer c_void_p (which takes byref(), ctypes arrays and pointers, integers and None).
 
 There is NO fallback: if the library is missing or does not load, every entry point raises.
 """
 from __future__ import annotations
 
+import ast
 import ctypes as C
-from pathlib import Path
-
 import os
+import re
+from pathlib import Path
+from types import SimpleNamespace
 
 PKG = Path(__file__).resolve().parent
 LIB_PATH = Path(os.environ.get("FSG_LIB", PKG / "libfsg_hip.so"))  # FSG_LIB: A/B another build of the same ABI
+HEADER_PATH = PKG.parent / "include" / "fsg_hip.h"
 
-E_BADARG, E_TOOBIG, E_ALIGN = -1, -2, -3
-ABI_VERSION = 3  # include/fsg_hip.h: FSG_ABI_VERSION
+GROUPS = ("PLAN_I", "PLAN_F", "KEYED_I", "KEYED_FLAG", "TUNE", "ST", "KT", "SA", "SIZEOF")
+# fsg_tap only ever crosses the boundary as the address of a DEVICE table (tensor.data_ptr()), which POINTER(Tap) would refuse
+DEVICE_STRUCTS = ("fsg_tap",)
+
+_SCALARS = {"int": C.c_int, "int32_t": C.c_int32, "uint32_t": C.c_uint32, "int64_t": C.c_int64, "uint64_t": C.c_uint64,
+            "uint8_t": C.c_uint8, "uint16_t": C.c_uint16, "float": C.c_float, "double": C.c_double, "size_t": C.c_size_t,
+            "char": C.c_char, "long long": C.c_longlong, "unsigned long long": C.c_ulonglong}
+# what carries nothing of the ABI: include guard, includes, the extern "C" bracket, forward declarations
+_IGNORED = re.compile(r'#\s*(ifndef|ifdef|endif|include)\b.*|#\s*define\s+FSG_HIP_H|extern\s+"C"\s*\{|\}|struct\s+\w+\s*;')
 
 
 class FsgError(RuntimeError):
@@ -22,236 +42,164 @@ class FsgError(RuntimeError):
         self.code = code
 
 
-class Tap(C.Structure):
-    _fields_ = [("lo", C.c_int32), ("hi", C.c_int32), ("w_lo", C.c_float), ("w_hi", C.c_float)]
+class HeaderError(RuntimeError):
+    def __init__(self, line: int, msg: str):
+        super().__init__(f"fsg_hip.h line {line}: {msg}")
 
 
-class Deform(C.Structure):
-    _fields_ = [
-        ("shape", C.c_int32 * 3),
-        ("A", C.c_float * 9),
-        ("centre", C.c_float * 3),
-        ("c2", C.c_float * 3),
-        ("flip", C.c_int32),
-        ("field_dims", C.c_int32 * 3),
-        ("field", C.c_void_p),
-        ("tx", C.c_void_p),
-        ("ty", C.c_void_p),
-        ("tz", C.c_void_p),
-        ("rows", C.c_void_p),
-        ("row_stride", C.c_int32),
-    ]
+def _statements(text):
+    """(line, statement) for every preprocessor line and every `;`-terminated statement (braces balanced), comments removed."""
+    text = re.sub(r"/\*.*?\*/", lambda m: "\n" * m.group().count("\n"), text, flags=re.S)
+    bracket = re.compile(r'#[^\n]*|extern\s+"C"\s*\{|\}')
+    punct = re.compile(r"[;{}]")
+    pos, n = 0, len(text)
+    while True:
+        while pos < n and text[pos].isspace():
+            pos += 1
+        if pos == n:
+            return
+        line = text.count("\n", 0, pos) + 1
+        m = bracket.match(text, pos)
+        if m:
+            end = m.end()
+        else:
+            depth = 0
+            for m in punct.finditer(text, pos):
+                if m.group() == ";" and not depth:
+                    break
+                depth += (m.group() == "{") - (m.group() == "}")
+            else:
+                raise HeaderError(line, f"statement without an end: {text[pos:pos + 40]!r}")
+            end = m.end()
+        yield line, text[pos:end]
+        pos = end
 
 
-class Epilogue(C.Structure):
-    _fields_ = [
-        ("gamma", C.c_float),
-        ("bias_dims", C.c_int32 * 3),
-        ("bias", C.c_void_p),
-        ("bx", C.c_void_p),
-        ("by", C.c_void_p),
-        ("bz", C.c_void_p),
-    ]
+def _split(text, sep, line):
+    """(line, piece) for the pieces of `text` between `sep`; `line` is that of the first character of `text`."""
+    pos = 0
+    for piece in text.split(sep):
+        lead = len(piece) - len(piece.lstrip())
+        yield line + text.count("\n", 0, pos + lead), piece.strip()
+        pos += len(piece) + len(sep)
 
 
-class SamplePlan(C.Structure):
-    _fields_ = [
-        ("shape", C.c_int32 * 3),
-        ("label_parts", C.c_void_p * 4),
-        ("mus", C.c_void_p),
-        ("sigmas", C.c_void_p),
-        ("ntab", C.c_int32),
-        ("gmm_noise", C.c_void_p),
-        ("gmm_seed", C.c_uint64),
-        ("gmm_stream", C.c_uint64),
-        ("deform_active", C.c_int32),
-        ("deform", Deform),
-        ("seg_in", C.c_void_p),
-        ("seg_out", C.c_void_p),
-        ("epi", Epilogue),
-        ("resample_active", C.c_int32),
-        ("low_shape", C.c_int32 * 3),
-        ("rs_tab", C.c_void_p * 3),
-        ("back_tab", C.c_void_p * 3),
-        ("blur_ntaps", C.c_int32 * 3),
-        ("blur_taps", (C.c_float * 129) * 3),
-        ("noise_mode", C.c_int32),
-        ("noise", C.c_void_p),
-        ("noise_seed", C.c_uint64),
-        ("noise_stream", C.c_uint64),
-        ("noise_std", C.c_float),
-        ("scale01", C.c_int32),
-        ("ws0", C.c_void_p),
-        ("ws1", C.c_void_p),
-        ("ws_low", C.c_void_p),
-        ("ws_rows", C.c_void_p),
-        ("row_stride", C.c_int32),
-        ("mm8", C.c_void_p),
-        ("mm8_preset", C.c_int32),
-        ("out", C.c_void_p),
-        ("ev_blur_begin", C.c_void_p),
-        ("ev_blur_end", C.c_void_p),
-        ("mm_slots", C.c_void_p),
-        ("mm_nslots", C.c_int32),
-        ("seg_in_u8", C.c_void_p),
-        ("arena_host", C.c_void_p),
-        ("arena_dev", C.c_void_p),
-        ("arena_bytes", C.c_uint64),
-        ("overlap", C.c_int32),
-        ("ws_seq", C.c_uint64),
-        ("seg_out_u8", C.c_void_p),
-        ("trace_events", C.c_void_p),
-        ("trace_ids", C.c_void_p),
-        ("trace_cap", C.c_int32),
-        ("trace_start", C.c_int32),
-        ("trace_first_id", C.c_int32),
-        ("label_codes", C.c_void_p),
-        ("code_tuples", C.c_void_p),
-        ("code_ntuples", C.c_int32),
-        ("code_stride", C.c_int32),
-        ("code_sel", C.c_int32 * 4),
-        ("ride_draw", C.c_void_p),
-        ("ride_draw_blocks", C.c_uint32),
-        ("rode", C.c_void_p),
-    ]
+def _int(expr, line):
+    """Value of an integer literal or a sum / difference / product of them: `3`, `(-1)`, `16 + 70`."""
+    def ev(node):
+        if isinstance(node, ast.Constant) and type(node.value) is int:
+            return node.value
+        if isinstance(node, ast.UnaryOp) and isinstance(node.op, ast.USub):
+            return -ev(node.operand)
+        if isinstance(node, ast.BinOp) and isinstance(node.op, (ast.Add, ast.Sub, ast.Mult)):
+            a, b = ev(node.left), ev(node.right)
+            return a + b if isinstance(node.op, ast.Add) else a - b if isinstance(node.op, ast.Sub) else a * b
+        raise ValueError
+    try:
+        return ev(ast.parse(expr.strip(), mode="eval").body)
+    except (ValueError, SyntaxError):
+        raise HeaderError(line, f"not an integer constant: {expr.strip()!r}") from None
 
 
-class KeyedConfig(C.Structure):
-    _fields_ = [
-        ("shape", C.c_int32 * 3), ("size", C.c_int32 * 3), ("resolution", C.c_double * 3),
-        ("min_subclusters", C.c_int32), ("max_subclusters", C.c_int32), ("meta_labels", C.c_int32),
-        ("nlabels", C.c_int32), ("n_seed_labels", C.c_int32), ("tie_classes", C.c_int32),
-        ("seed_labels", C.c_uint8 * 256), ("generation_classes", C.c_uint8 * 256),
-        ("deform_prob", C.c_double), ("flip_prb", C.c_double), ("max_rotation", C.c_double), ("max_shear", C.c_double),
-        ("max_scaling", C.c_double), ("nonlinear", C.c_int32),
-        ("nonlin_scale_min", C.c_double), ("nonlin_scale_max", C.c_double), ("nonlin_std_max", C.c_double),
-        ("gamma_prob", C.c_double), ("gamma_std", C.c_double),
-        ("bias_prob", C.c_double), ("bf_scale_min", C.c_double), ("bf_scale_max", C.c_double), ("bf_std_min", C.c_double),
-        ("bf_std_max", C.c_double),
-        ("resample_prob", C.c_double), ("min_resolution", C.c_double), ("max_resolution", C.c_double),
-        ("noise_prob", C.c_double), ("noise_std_min", C.c_double), ("noise_std_max", C.c_double),
-    ]
+def _declarator(text, line, structs, base=None):
+    """'const float* const* grads' -> ('float', c_float, 2, 'grads', []); 'float blur_taps[3][129]' -> (.., 0, 'blur_taps', [3, 129]).
+    base: the type name when `text` is a later declarator of a member (`uint64_t gmm_seed, gmm_stream`)."""
+    m = re.fullmatch(r"([\w\s*]*?)(\w+)\s*((?:\[\d+\])*)", text)
+    if not m:
+        raise HeaderError(line, f"not a declarator: {text!r}")
+    toks = [t for t in m.group(1).replace("*", " * ").split() if t not in ("const", "struct")]
+    base = " ".join(t for t in toks if t != "*") or base
+    stars = toks.count("*")
+    ctype = _SCALARS.get(base) or structs.get(base)
+    if ctype is None and not (base == "void" and stars):
+        raise HeaderError(line, f"unknown type {base!r} in {text!r}")
+    return base, ctype, stars, m.group(2), [int(d) for d in re.findall(r"\d+", m.group(3))]
 
 
-class KeyedDraws(C.Structure):
-    _fields_ = [
-        ("key", C.c_uint64), ("subclusters", C.c_int32 * 4), ("ntab", C.c_int32),
-        ("deform_active", C.c_int32), ("flip", C.c_int32),
-        ("rotations", C.c_double * 3), ("shears", C.c_double * 3), ("scalings", C.c_double * 3),
-        ("A", C.c_float * 9), ("c2", C.c_double * 3),
-        ("nonlinear", C.c_int32), ("nonlin_scale", C.c_double), ("nonlin_std", C.c_double), ("field_dims", C.c_int32 * 3),
-        ("gamma_active", C.c_int32), ("gamma", C.c_double),
-        ("bias_active", C.c_int32), ("bf_scale", C.c_double), ("bf_std", C.c_double), ("bias_dims", C.c_int32 * 3),
-        ("resample_active", C.c_int32), ("spacing", C.c_double), ("u_std", C.c_double), ("stds", C.c_double * 3),
-        ("low_shape", C.c_int32 * 3), ("blur_ntaps", C.c_int32 * 3),
-        ("noise_active", C.c_int32), ("noise_std", C.c_double), ("noise_std32", C.c_float),
-        ("off_mm8", C.c_int32), ("off_slots", C.c_int32), ("off_mus", C.c_int32), ("off_sigmas", C.c_int32),
-        ("off_bias", C.c_int32), ("off_field", C.c_int32), ("block_bytes", C.c_int32),
-        ("rode", C.c_int32),
-    ]
+def _fields(body, line, structs):
+    *members, rest = _split(body, ";", line)
+    if rest[1]:
+        raise HeaderError(rest[0], f"struct member without ';': {rest[1]!r}")
+    out = []
+    for mline, member in members:
+        base = None
+        for decl in member.split(","):
+            base, ctype, stars, name, dims = _declarator(decl.strip(), mline, structs, base)
+            ctype = C.c_void_p if stars else ctype
+            for d in reversed(dims):
+                ctype = ctype * d
+            out.append((name, ctype))
+    return out
 
 
-E_NOTABLE = -4
-KT_RESAMPLE, KT_BACK, KT_FIELD, KT_BIAS = 0, 1, 2, 3
-KEYED_I = dict(KEY=0, OUT=1, SEG_OUT=2, SEG_OUT_U8=3, SEG_IN=4, SEG_IN_U8=5, BLOCK=6, WS0=7, WS1=8, WS_LOW=9, WS_ROWS=10,
-               ROW_STRIDE=11, SCALE01=12, TRACE_EVENTS=13, TRACE_IDS=14, TRACE_CAP=15, BANK=16, EV_BLUR_BEGIN=80,
-               EV_BLUR_END=81, CODES=82, CODE_TUPLES=83, CODE_NTUPLES=84, CODE_STRIDE=85, FLAGS=86, NEXT_KEY=87, NEXT_BLOCK=88, COUNT=89)
+def _prototype(stmt, line, structs):
+    m = re.fullmatch(r"([\w\s*]+?)(\w+)\s*\((.*)\)\s*;", stmt, re.S)
+    if not m:
+        raise HeaderError(line, f"not recognised: {' '.join(stmt.split())[:60]!r}")
+    _, res, stars, name, _ = _declarator(m.group(1) + m.group(2), line, structs)
+    if stars:
+        res = C.c_char_p if res is C.c_char else C.c_void_p
+    args = []
+    params = m.group(3)
+    for pline, p in [] if params.strip() == "void" else _split(params, ",", line + stmt.count("\n", 0, m.start(3))):
+        base, ctype, stars, _, dims = _declarator(p, pline, structs)
+        if stars or dims:
+            by_struct = stars == 1 and not dims and base in structs and base not in DEVICE_STRUCTS
+            ctype = C.POINTER(ctype) if by_struct else C.c_void_p
+        args.append(ctype)
+    return name, (res, args)
 
-STAGE_NAMES = ("begin", "upload", "draw", "head", "floormin", "warp", "blur_x", "blur_y", "blur_z", "blur_yz", "k7", "k9a", "k9b",
-               "gmm", "rows", "pointwise", "blur_rs_x", "blur_rs_yz")  # include/fsg_hip.h: FSG_ST_*
+
+def parse(text):
+    """constants {name without FSG_: int}, structs {C name: ctypes.Structure, in header order}, prototypes {name: (restype,
+    argtypes)}.  HeaderError for anything that is not a constant, an enum, a struct or a prototype as fsg_hip.h writes them."""
+    consts, structs, protos = {}, {}, []
+    for line, stmt in _statements(text):
+        if _IGNORED.fullmatch(stmt):
+            continue
+        m = re.fullmatch(r"#\s*define\s+FSG_(\w+)\s+(.*)", stmt)
+        if m:
+            consts[m.group(1)] = _int(m.group(2), line)
+            continue
+        m = re.fullmatch(r"enum\s*\{(.*)\}\s*;", stmt, re.S)
+        if m:
+            for eline, item in _split(m.group(1), ",", line + stmt.count("\n", 0, m.start(1))):
+                em = re.fullmatch(r"FSG_(\w+)\s*=(.*)", item, re.S)
+                if not em:
+                    raise HeaderError(eline, f"not FSG_NAME = value: {item!r}")
+                consts[em.group(1)] = _int(em.group(2), eline)
+            continue
+        m = re.fullmatch(r"typedef\s+struct\s+(fsg_\w+)\s*\{(.*)\}\s*(\w+)\s*;", stmt, re.S)
+        if m and m.group(1) == m.group(3):
+            fields = _fields(m.group(2), line + stmt.count("\n", 0, m.start(2)), structs)
+            name = "".join(w.capitalize() for w in m.group(1).split("_")[1:])  # fsg_sample_plan -> SamplePlan
+            structs[m.group(1)] = type(name, (C.Structure,), {"_fields_": fields})
+            continue
+        if stmt.startswith(("#", "typedef", "enum", "struct")):
+            raise HeaderError(line, f"not recognised: {' '.join(stmt.split())[:60]!r}")
+        protos.append((line, stmt))  # resolved below: a prototype may name a struct that is defined after it
+    return consts, structs, dict(_prototype(stmt, line, structs) for line, stmt in protos)
 
 
-P, I, F, SZ, U64 = C.c_void_p, C.c_int, C.c_float, C.c_size_t, C.c_uint64
+def _bind(consts):
+    """Module-level names and the GROUPS namespaces from the header's constants (longest group prefix wins)."""
+    flat, groups = {}, {g: {} for g in GROUPS}
+    for name, v in consts.items():
+        g = max((g for g in GROUPS if name.startswith(g + "_")), key=len, default=None)
+        if g is None:
+            flat[name] = v
+        else:
+            groups[g][name[len(g) + 1:]] = v
+    flat.update({g: SimpleNamespace(**members) for g, members in groups.items()})
+    return flat
 
-# name -> argtypes; every function returns int except where noted.  Must list EVERY symbol the
-# header declares (tests/test_abi.py cross-checks against include/fsg_hip.h).
-SIGNATURES = {
-    "fsg_abi_version": [],
-    "fsg_set_tuning": [I],
-    "fsg_warp_set_variant": [I],
-    "fsg_randn_f32": [P, SZ, U64, U64, P],
-    "fsg_gmm_sample_u8": [P, SZ, P, P, I, P, U64, U64, P, P],
-    "fsg_gmm_sample_i64": [P, SZ, P, P, I, P, U64, U64, P, P],
-    "fsg_gmm_sample_u8x4": [P, P, P, P, SZ, P, P, I, P, U64, U64, P, P],
-    "fsg_gmm_sample_u8x4_mm": [P, P, P, P, SZ, P, P, I, P, U64, U64, P, P, I, I, P],
-    "fsg_label_stats_u8": [P, P, SZ, I, P, P, P, P],
-    "fsg_zoom3d_f32": [P, I, I, I, I, P, P, P, P, I, I, I, P],
-    "fsg_resample_noise_f32": [P, I, I, I, P, P, P, P, I, I, I, I, P, U64, U64, F, P],
-    "fsg_zoom3d_minmax_f32": [P, I, I, I, P, P, P, I, I, I, P, P],
-    "fsg_zoom3d_normalise_f32": [P, I, I, I, P, P, P, P, I, I, I, P, I, P],
-    "fsg_minmax_init": [P, I, I, P],
-    "fsg_zoom3d_minmax_sharded_f32": [P, I, I, I, P, P, P, I, I, I, P, I, P],
-    "fsg_zoom3d_normalise_sharded_f32": [P, I, I, I, P, P, P, P, I, I, I, P, I, I, P],
-    "fsg_deform_rows_f32": [C.POINTER(Deform), C.POINTER(Epilogue), P, I, P],
-    "fsg_coords_minmax_f32": [C.POINTER(Deform), P, P],
-    "fsg_coords_floormin_f32": [C.POINTER(Deform), P, P],
-    "fsg_coords_f32": [C.POINTER(Deform), P, P, P, P, P],
-    "fsg_warp_f32": [C.POINTER(Deform), P, P, P, P, P, C.POINTER(Epilogue), P],
-    "fsg_warp_f32_u8": [C.POINTER(Deform), P, P, P, P, P, C.POINTER(Epilogue), P],
-    "fsg_warp_f32_u8_to_f32": [C.POINTER(Deform), P, P, P, P, P, C.POINTER(Epilogue), P],
-    "fsg_interp3d_f32": [P, I, I, I, P, P, P, SZ, I, F, P, P],
-    "fsg_gamma_f32": [P, SZ, F, P, P],
-    "fsg_bias_mul_f32": [P, I, I, I, P, I, I, I, P, P, P, P, P],
-    "fsg_blur_axis_f32": [P, P, I, I, I, I, P, I, P],
-    "fsg_blur_axis_taps_host_f32": [P, P, I, I, I, I, C.POINTER(C.c_float), I, P],
-    "fsg_blur_yz_taps_host_f32": [P, P, I, I, I, C.POINTER(C.c_float), I, C.POINTER(C.c_float), I, P],
-    "fsg_add_noise_f32": [P, SZ, P, U64, U64, F, P, P],
-    "fsg_reduce_minmax_f32": [P, SZ, P, P],
-    "fsg_scale_f32": [P, SZ, P, I, P, P],
-    "fsg_slice_acq_forward_f32": [P, P, P, P, I, I, I, P, P, P, I, I, I, I, I, I, F, I, P],
-    "fsg_slice_acq_adjoint_f32": [P, P, I, I, I, P, P, P, P, P, P, I, I, I, I, I, I, F, I, P],
-    "fsg_equalize_f32": [P, P, P, F, SZ, P],
-    "fsg_slice_acq_set_tuning": [I, I, I],
-    "fsg_mog3d_f32": [P, P, I, I, I, I, P, P, P],
-    "fsg_perlin_fractal_f32": [P, P, P, P, I, I, I, I, P, P, P],
-    "fsg_blend_f32": [P, P, P, SZ, I, P, F, P, I, P, P, F, P, P, P],
-    "fsg_slice_noise_f32": [P, SZ, F, F, P, P, U64, U64, P],
-    "fsg_slice_void_f32": [P, I, I, P, P, I, P, P, P],
-    "fsg_slice_sums_f32": [P, I, SZ, P, P],
-    "fsg_nonzero_count_f32": [P, SZ, I, F, P, P],
-    "fsg_nonzero_count_u8": [P, SZ, I, F, P, P],
-    "fsg_nonzero_select_f32": [P, SZ, I, F, P, P, I, P, P],
-    "fsg_nonzero_select_u8": [P, SZ, I, F, P, P, I, P, P],
-    "fsg_compact_f32": [P, P, SZ, I, F, P, P, P],
-    "fsg_ewise_f32": [P, P, SZ, I, F, P, P],
-    "fsg_dist_pass_f32": [P, P, I, I, I, I, I, I, I, P],
-    "fsg_boundary_mask_f32": [P, P, P, P, P, I, SZ, P, P, P],
-    "fsg_bernoulli_keep_f32": [P, SZ, F, U64, U64, P, P],
-    "fsg_scatter_const_f32": [P, SZ, P, I, F, P],
-    "fsg_copy_bytes": [P, P, SZ, P],
-    "fsg_zoom_set_tuning": [I, I],
-    "fsg_sample_head_f32": [P, P, P, P, SZ, P, P, I, P, U64, U64, P, C.POINTER(Deform), C.POINTER(Epilogue), P, I, P, P],
-    "fsg_seed_codes_build": [P, I, SZ, I, P, P, I, P, SZ, P, P],
-    "fsg_sample_head_codes_f32": [P, P, I, I, C.POINTER(C.c_int32), SZ, P, P, I, U64, U64, P, C.POINTER(Deform), C.POINTER(Epilogue), P, I, P, P],
-    "fsg_coords_floormin_rest_f32": [C.POINTER(Deform), P, P],
-    "fsg_sample_run": [C.POINTER(SamplePlan), P],
-    "fsg_sample_plan_pack": [C.POINTER(SamplePlan), P, I, P, I, P],
-    "fsg_sample_pack_run": [P, I, P, I, P, P],
-    "fsg_sample_run_batch": [C.POINTER(SamplePlan), I, C.POINTER(C.c_void_p), I],
-    "fsg_cast_f32_to_f16": [P, SZ, P, P],
-    "fsg_pipeline_teardown": [],
-    "fsg_blur_resample_supported": [I, I, I, I, I, I, I, I, I],
-    "fsg_blur_resample_x_f32": [P, I, I, I, P, I, C.POINTER(C.c_float), I, P, P],
-    "fsg_blur_resample_yz_noise_f32": [P, I, I, I, P, P, I, I, C.POINTER(C.c_float), I, C.POINTER(C.c_float), I, I, P, U64, U64,
-                                       F, P, P],
-    "fsg_keyed_create": [C.POINTER(KeyedConfig), C.POINTER(C.c_void_p)],
-    "fsg_keyed_destroy": [P],
-    "fsg_keyed_set_table": [P, I, I, I, P],
-    "fsg_keyed_draw": [P, U64, C.POINTER(KeyedDraws)],
-    "fsg_keyed_sample_run": [P, P, I, P, P],
-    "fsg_keyed_fill_block": [P, C.POINTER(KeyedDraws), P, P],
-    "fsg_event_destroy": [P],
-    "fsg_event_record": [P, P],
-    "fsg_event_elapsed_ms": [P, P, C.POINTER(C.c_float)],
-    "fsg_seed_meta_pack": [P, P, P, SZ, P, I, P, P, P, P, P, P],
-    "fsg_em1d_tile": [],
-    "fsg_em1d_fit": [P, SZ, I, P, P, P, P, P, P, SZ, P],
-    "fsg_seed_assign": [P, SZ, P, I, P, I, P, P, P, SZ, P],
-}
-SPECIAL_RESTYPE = {"fsg_error_string": (C.c_char_p, [I]), "fsg_key_to_float": (F, [C.c_int32]),
-                   "fsg_event_create": (C.c_void_p, []), "fsg_sample_plan_layout": (C.c_int64, [I]),
-                   "fsg_keyed_block_bytes": (C.c_int64, [P]), "fsg_seed_codes_work_bytes": (C.c_size_t, []),
-                   "fsg_seed_meta_work_bytes": (C.c_size_t, [SZ]), "fsg_em1d_work_bytes": (C.c_size_t, [I, C.c_int64])}
+
+if not HEADER_PATH.exists():
+    raise RuntimeError(f"{HEADER_PATH} is missing: the binding of libfsg_hip.so is derived from it")
+CONSTANTS, STRUCTS, PROTOTYPES = parse(HEADER_PATH.read_text())
+globals().update(_bind(CONSTANTS))
+globals().update({cls.__name__: cls for cls in STRUCTS.values()})
+STAGE_NAMES = tuple(n.lower() for n, _v in sorted(vars(ST).items(), key=lambda kv: kv[1]) if n != "COUNT")  # noqa: F821
 
 _lib = None
 
@@ -267,20 +215,17 @@ def load():
             "(hipcc --offload-arch=gfx950). fetalsyngen_amd has no CPU or PyTorch fallback."
         )
     lib = C.CDLL(str(LIB_PATH))
-    for name, args in SIGNATURES.items():
-        fn = getattr(lib, name)
-        fn.argtypes = args
-        fn.restype = C.c_int
-    for name, (res, args) in SPECIAL_RESTYPE.items():
+    for name, (res, args) in PROTOTYPES.items():
         fn = getattr(lib, name)
         fn.argtypes = args
         fn.restype = res
-    if lib.fsg_abi_version() != ABI_VERSION:
-        raise RuntimeError(f"libfsg_hip.so ABI version {lib.fsg_abi_version()}, this binding expects {ABI_VERSION}")
+    if lib.fsg_abi_version() != ABI_VERSION:  # noqa: F821
+        raise RuntimeError(f"libfsg_hip.so ABI version {lib.fsg_abi_version()}, this binding expects {ABI_VERSION}")  # noqa: F821
     # the structs cross the boundary by pointer: a mirror that disagrees on their size would have the library read past its end
-    if lib.fsg_sample_plan_layout(0) != C.sizeof(SamplePlan):
-        raise RuntimeError(f"fsg_sample_plan is {lib.fsg_sample_plan_layout(0)} bytes in libfsg_hip.so, "
-                           f"{C.sizeof(SamplePlan)} in the ctypes mirror")
+    for cname, cls in STRUCTS.items():
+        size = lib.fsg_sample_plan_layout(getattr(SIZEOF, cname[4:].upper()))  # noqa: F821
+        if size != C.sizeof(cls):
+            raise RuntimeError(f"{cname} is {size} bytes in libfsg_hip.so, {C.sizeof(cls)} in the ctypes mirror")
     _lib = lib
     return lib
 

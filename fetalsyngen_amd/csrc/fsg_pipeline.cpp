@@ -235,7 +235,12 @@ extern "C" int fsg_sample_run(const fsg_sample_plan* p, void* stream) {
 
 extern "C" int64_t fsg_sample_plan_layout(int which) {
   switch (which) {
-    case 0: return (int64_t)sizeof(fsg_sample_plan);
+    case FSG_SIZEOF_SAMPLE_PLAN: return (int64_t)sizeof(fsg_sample_plan);
+    case FSG_SIZEOF_TAP: return (int64_t)sizeof(fsg_tap);
+    case FSG_SIZEOF_DEFORM: return (int64_t)sizeof(fsg_deform);
+    case FSG_SIZEOF_EPILOGUE: return (int64_t)sizeof(fsg_epilogue);
+    case FSG_SIZEOF_KEYED_CONFIG: return (int64_t)sizeof(fsg_keyed_config);
+    case FSG_SIZEOF_KEYED_DRAWS: return (int64_t)sizeof(fsg_keyed_draws);
     case 1: return (int64_t)offsetof(fsg_sample_plan, blur_taps);
     case 2: return (int64_t)offsetof(fsg_sample_plan, out);
     case 3: return (int64_t)offsetof(fsg_sample_plan, seg_in_u8);

@@ -36,12 +36,20 @@ from .intensity.rand_gmm import GMMPlan, ImageFromSeeds
 # [+inf x4 | -inf x4] as the order-preserving int32 keys of fsg_minmax_init (csrc/fsg_common.h: fsg_f2key)
 _MM8_INIT = np.array([0x7F800000] * 4 + [-2139095041] * 4, dtype=np.int32)
 _MM8_INIT.setflags(write=False)
-# K9's min / max keys sharded over 64 slots of 16 ints (include/fsg_hip.h: FSG_MM_SLOT_STRIDE), each {key(+inf), key(-inf), 0...}:
+# K9's min / max keys sharded over 64 slots, each {key(+inf), key(-inf), 0...}:
 # the min/max pass ends every workgroup with two atomics nobody waits for (csrc/fsg_zoom.hip: zoom_mm_update)
-MM_NSLOTS, MM_SLOT_STRIDE = 64, 16
-_MM_SLOTS_INIT = np.zeros((MM_NSLOTS, MM_SLOT_STRIDE), dtype=np.int32)
+MM_NSLOTS = 64
+_MM_SLOTS_INIT = np.zeros((MM_NSLOTS, _lib.MM_SLOT_STRIDE), dtype=np.int32)
 _MM_SLOTS_INIT[:, 0], _MM_SLOTS_INIT[:, 1] = 0x7F800000, -2139095041
 _MM_SLOTS_INIT.setflags(write=False)
+# slots of fsg_keyed_sample_run's argument array as plain module names: _pipeline_keyed fills them once per sample
+_KI, _KF = _lib.KEYED_I, _lib.KEYED_FLAG
+_K_KEY, _K_OUT, _K_SEG_OUT, _K_SEG_OUT_U8, _K_SEG_IN, _K_SEG_IN_U8 = _KI.KEY, _KI.OUT, _KI.SEG_OUT, _KI.SEG_OUT_U8, _KI.SEG_IN, _KI.SEG_IN_U8
+_K_BLOCK, _K_WS0, _K_WS1, _K_WS_LOW, _K_WS_ROWS, _K_ROW_STRIDE = _KI.BLOCK, _KI.WS0, _KI.WS1, _KI.WS_LOW, _KI.WS_ROWS, _KI.ROW_STRIDE
+_K_SCALE01, _K_TRACE_EVENTS, _K_TRACE_IDS, _K_TRACE_CAP, _K_BANK = _KI.SCALE01, _KI.TRACE_EVENTS, _KI.TRACE_IDS, _KI.TRACE_CAP, _KI.BANK
+_K_EV_BLUR_BEGIN, _K_EV_BLUR_END, _K_CODES, _K_CODE_TUPLES = _KI.EV_BLUR_BEGIN, _KI.EV_BLUR_END, _KI.CODES, _KI.CODE_TUPLES
+_K_CODE_NTUPLES, _K_CODE_STRIDE, _K_FLAGS, _K_NEXT_KEY, _K_NEXT_BLOCK = _KI.CODE_NTUPLES, _KI.CODE_STRIDE, _KI.FLAGS, _KI.NEXT_KEY, _KI.NEXT_BLOCK
+_KF_BLOCK_FILLED, _KF_NEXT_NAMED = _KF.BLOCK_FILLED, _KF.NEXT_NAMED
 
 
 class _Ctx:
@@ -243,8 +251,8 @@ class FetalSynthGen:
         entry points themselves) -- call this after such a write."""
         self.__dict__.pop("_twins", None)
         for kc in (self.__dict__.get("_keyed") or {}).values():  # keyed mode: the subjects' pointer blocks and code volumes
-            for hit in kc._subjects.values():
-                bank = hit[0]()
+            for ent in kc._subjects.values():
+                bank = ent.bank_ref()
                 if bank is not None:
                     bank.__dict__.pop("_seed_codes", None)
             kc._subjects.clear()
@@ -351,20 +359,12 @@ class FetalSynthGen:
     # fsg_sample_plan as two flat arrays (FSG_PLAN_I_* / FSG_PLAN_F_* in include/fsg_hip.h) handed over with ONE native call
     # (fsg_sample_pack_run; fsg_sample_plan_pack for a batch): filling the ctypes struct field by field cost 41 us per sample,
     # the spec / view objects 28 us (profiles/r02_c_host_phases.txt).
-    _I = dict(SHAPE=0, LABEL_PARTS=3, MUS=7, SIGMAS=8, NTAB=9, GMM_NOISE=10, GMM_SEED=11, GMM_STREAM=12, DEFORM_ACTIVE=13,
-              FLIP=14, FIELD_DIMS=15, FIELD=18, FIELD_TABS=19, SEG_IN=22, SEG_OUT=23, SEG_IN_U8=24, BIAS_DIMS=25, BIAS=28,
-              BIAS_TABS=29, RESAMPLE_ACTIVE=32, LOW_SHAPE=33, RS_TABS=36, BACK_TABS=39, BLUR_NTAPS=42, NOISE_MODE=45, NOISE=46,
-              NOISE_SEED=47, NOISE_STREAM=48, SCALE01=49, WS0=50, WS1=51, WS_LOW=52, WS_ROWS=53, ROW_STRIDE=54, MM8=55,
-              MM8_PRESET=56, OUT=57, EV_BEGIN=58, EV_END=59, MM_SLOTS=60, MM_NSLOTS=61, ARENA_HOST=62, ARENA_DEV=63,
-              ARENA_BYTES=64, OVERLAP=65, WS_SEQ=66, SEG_OUT_U8=67, TRACE_EVENTS=68, TRACE_IDS=69, TRACE_CAP=70, COUNT=71)
-    _TAPS_STRIDE = 132
-
     def _flat_buffers(self):
         fb = self.__dict__.get("_flat")
         if fb is None:
-            iv = np.zeros(self._I["COUNT"], dtype=np.int64)
-            fv = np.zeros(17, dtype=np.float64)
-            tb = np.zeros((3, self._TAPS_STRIDE), dtype=np.float32)
+            iv = np.zeros(_lib.PLAN_I.COUNT, dtype=np.int64)
+            fv = np.zeros(_lib.PLAN_F.COUNT, dtype=np.float64)
+            tb = np.zeros((3, _lib.PLAN_TAPS_STRIDE), dtype=np.float32)
             centre = (np.array(self.spatial_deform.size) - 1) / 2
             fb = self._flat = dict(iv=iv, fv=fv, tb=tb, ivp=iv.ctypes.data, fvp=fv.ctypes.data, tbp=tb.ctypes.data,
                                    centre=np.asarray(centre, dtype=np.float32).tolist(), validated={})
@@ -375,81 +375,81 @@ class FetalSynthGen:
         generator's `_flat` buffers, which hold one plan at a time.  `seg_out`: where the deformed labels go, uint8 only
         with `twin`, the uint8 copy of the segmentation.  Returns False when the sample is outside the fused path's domain
         (blur radius beyond the tap capacity, uint8 labels without a twin)."""
-        I = self._I
+        I, F = _lib.PLAN_I, _lib.PLAN_F
         fb = self._flat_buffers()
-        iv, fv, tb = [0] * I["COUNT"], [0.0] * 17, fb["tb"]
+        iv, fv, tb = [0] * I.COUNT, [0.0] * F.COUNT, fb["tb"]
         base = c.arena.base
         shape = c.shape
-        iv[0:3] = shape
+        iv[I.SHAPE:I.SHAPE + 3] = shape
         for q, part in enumerate(c.label_parts):
-            iv[I["LABEL_PARTS"] + q] = part.data_ptr()
-        iv[I["MUS"]], iv[I["SIGMAS"]], iv[I["NTAB"]] = base + c.gm_off[0], base + c.gm_off[1], c.gm_off[2]
+            iv[I.LABEL_PARTS + q] = part.data_ptr()
+        iv[I.MUS], iv[I.SIGMAS], iv[I.NTAB] = base + c.gm_off[0], base + c.gm_off[1], c.gm_off[2]
         f = c.gmm_plan.field
         if f.host is not None:
             z = f.device_tensor(torch.device(self.device))
             c.keep.append(z)
-            iv[I["GMM_NOISE"]] = z.data_ptr()
+            iv[I.GMM_NOISE] = z.data_ptr()
         else:
-            iv[I["GMM_SEED"]], iv[I["GMM_STREAM"]] = f.seed, f.stream_id
+            iv[I.GMM_SEED], iv[I.GMM_STREAM] = f.seed, f.stream_id
         dplan = c.dplan
         if dplan.active:
-            iv[I["DEFORM_ACTIVE"]] = 1
-            iv[I["FLIP"]] = int(bool(dplan.flip))
+            iv[I.DEFORM_ACTIVE] = 1
+            iv[I.FLIP] = int(bool(dplan.flip))
             a_np, c2_np = dplan.A_np, dplan.c2_np  # left by _draw_all_fast (no torch round trip)
-            fv[0:9] = a_np.ravel().tolist() if a_np is not None else dplan.A.reshape(-1).tolist()
-            fv[9:12] = fb["centre"]
-            fv[12:15] = c2_np.astype(np.float32).tolist() if c2_np is not None else dplan.c2.to(torch.float32).tolist()
+            fv[F.A:F.A + 9] = a_np.ravel().tolist() if a_np is not None else dplan.A.reshape(-1).tolist()
+            fv[F.CENTRE:F.CENTRE + 3] = fb["centre"]
+            fv[F.C2:F.C2 + 3] = c2_np.astype(np.float32).tolist() if c2_np is not None else dplan.c2.to(torch.float32).tolist()
             if c.sb.pending is not None:
                 off, fshape = c.sb.pending
-                iv[I["FIELD_DIMS"]:I["FIELD_DIMS"] + 3] = fshape[:3]
-                iv[I["FIELD"]] = base + off
-                iv[I["FIELD_TABS"]:I["FIELD_TABS"] + 3] = c.sb.tabs.ptrs_i
+                iv[I.FIELD_DIMS:I.FIELD_DIMS + 3] = fshape[:3]
+                iv[I.FIELD] = base + off
+                iv[I.FIELD_TABS:I.FIELD_TABS + 3] = c.sb.tabs.ptrs_i
             if twin is not None:
-                iv[I["SEG_IN_U8"]] = twin.data_ptr()
-            iv[I["SEG_IN"]] = c.seg.data_ptr()
+                iv[I.SEG_IN_U8] = twin.data_ptr()
+            iv[I.SEG_IN] = c.seg.data_ptr()
             if seg_out.dtype == torch.uint8:  # uint8 labels out (device-resident hand-over): needs the uint8 source
                 if twin is None:
                     return False
-                iv[I["SEG_OUT_U8"]] = seg_out.data_ptr()
+                iv[I.SEG_OUT_U8] = seg_out.data_ptr()
             else:
-                iv[I["SEG_OUT"]] = seg_out.data_ptr()
+                iv[I.SEG_OUT] = seg_out.data_ptr()
         if c.g is not None:
-            fv[15] = float(np.float32(float(c.g)))
+            fv[F.GAMMA] = float(np.float32(float(c.g)))
         if c.bplan.active:
-            iv[I["BIAS_DIMS"]:I["BIAS_DIMS"] + 3] = c.bplan.grid.shape
-            iv[I["BIAS"]] = base + c.bias_off
-            iv[I["BIAS_TABS"]:I["BIAS_TABS"] + 3] = c.bias_tabs.ptrs_i
+            iv[I.BIAS_DIMS:I.BIAS_DIMS + 3] = c.bplan.grid.shape
+            iv[I.BIAS] = base + c.bias_off
+            iv[I.BIAS_TABS:I.BIAS_TABS + 3] = c.bias_tabs.ptrs_i
         rplan, nplan = c.rplan, c.nplan
         if rplan.active:
-            iv[I["RESAMPLE_ACTIVE"]] = 1
-            iv[I["LOW_SHAPE"]:I["LOW_SHAPE"] + 3] = rplan.new_size
-            iv[I["RS_TABS"]:I["RS_TABS"] + 3] = c.rs_tabs.ptrs_i
-            iv[I["BACK_TABS"]:I["BACK_TABS"] + 3] = c.back_tabs.ptrs_i
+            iv[I.RESAMPLE_ACTIVE] = 1
+            iv[I.LOW_SHAPE:I.LOW_SHAPE + 3] = rplan.new_size
+            iv[I.RS_TABS:I.RS_TABS + 3] = c.rs_tabs.ptrs_i
+            iv[I.BACK_TABS:I.BACK_TABS + 3] = c.back_tabs.ptrs_i
             for a_ in range(3):
                 if rplan.stds[a_] > 0:
                     taps = T.gaussian_taps(float(rplan.stds[a_]))
                     n = len(taps)
                     if n > 129:
                         return False
-                    iv[I["BLUR_NTAPS"] + a_] = n
+                    iv[I.BLUR_NTAPS + a_] = n
                     tb[a_, :n] = taps
         if nplan.active:
             nf = nplan.field
-            fv[16] = nplan.std32
+            fv[F.NOISE_STD] = nplan.std32
             if nf.host is not None:
                 zn = nf.device_tensor(torch.device(self.device))
                 c.keep.append(zn)
-                iv[I["NOISE_MODE"]], iv[I["NOISE"]] = 1, zn.data_ptr()
+                iv[I.NOISE_MODE], iv[I.NOISE] = 1, zn.data_ptr()
             else:
-                iv[I["NOISE_MODE"]], iv[I["NOISE_SEED"]], iv[I["NOISE_STREAM"]] = 2, nf.seed, nf.stream_id
-        iv[I["SCALE01"]] = int(bool(scale01))
-        iv[I["WS0"]], iv[I["WS1"]], iv[I["WS_LOW"]] = ws["ws0"].data_ptr(), ws["ws1"].data_ptr(), ws["low"].data_ptr()
+                iv[I.NOISE_MODE], iv[I.NOISE_SEED], iv[I.NOISE_STREAM] = 2, nf.seed, nf.stream_id
+        iv[I.SCALE01] = int(bool(scale01))
+        iv[I.WS0], iv[I.WS1], iv[I.WS_LOW] = ws["ws0"].data_ptr(), ws["ws1"].data_ptr(), ws["low"].data_ptr()
         if ws["rows"] is not None:
-            iv[I["WS_ROWS"]], iv[I["ROW_STRIDE"]] = ws["rows"].data_ptr(), ws["stride"]
-        iv[I["MM8"]], iv[I["MM8_PRESET"]] = base + c.mm_off, 1
+            iv[I.WS_ROWS], iv[I.ROW_STRIDE] = ws["rows"].data_ptr(), ws["stride"]
+        iv[I.MM8], iv[I.MM8_PRESET] = base + c.mm_off, 1
         if c.slots_off is not None:
-            iv[I["MM_SLOTS"]], iv[I["MM_NSLOTS"]] = base + c.slots_off, MM_NSLOTS
-        iv[I["OUT"]] = out.data_ptr()
+            iv[I.MM_SLOTS], iv[I.MM_NSLOTS] = base + c.slots_off, MM_NSLOTS
+        iv[I.OUT] = out.data_ptr()
         fb["iv"][:] = iv
         fb["fv"][:] = fv
         return True
@@ -470,23 +470,23 @@ class FetalSynthGen:
             seg_out = torch.empty_like(c.seg) if c.dplan.active else c.seg
         if not self._flat_plan(c, scale01, out, seg_out, ws, twin):
             return None
-        I, fb, lib = self._I, self._flat, _lib.load()
+        I, fb, lib = _lib.PLAN_I, self._flat, _lib.load()
         iv = fb["iv"]
         if self.blur_events is not None and c.rplan.active:
             self._blur_tick += 1
             if self._blur_tick % self.blur_events_every == 0:
                 events = (lib.fsg_event_create(), lib.fsg_event_create())
-                iv[I["EV_BEGIN"]], iv[I["EV_END"]] = events
-                nt = iv[I["BLUR_NTAPS"]:I["BLUR_NTAPS"] + 3].tolist()
+                iv[I.EV_BEGIN], iv[I.EV_END] = events
+                nt = iv[I.BLUR_NTAPS:I.BLUR_NTAPS + 3].tolist()
                 self.blur_events.append((events[0], events[1], [(a_, nt[a_] // 2) for a_ in range(3) if nt[a_]],
                                          tuple(int(v) for v in c.rplan.new_size)))
         if self.stage_traces is not None:
             tr = StageTrace()
             tr.meta = {"shape": tuple(c.shape), "low_shape": tuple(c.rplan.new_size) if c.rplan.active else None,
-                       "blur_ntaps": iv[I["BLUR_NTAPS"]:I["BLUR_NTAPS"] + 3].tolist()}
-            iv[I["TRACE_EVENTS"]], iv[I["TRACE_IDS"]], iv[I["TRACE_CAP"]] = tr.slots()
+                       "blur_ntaps": iv[I.BLUR_NTAPS:I.BLUR_NTAPS + 3].tolist()}
+            iv[I.TRACE_EVENTS], iv[I.TRACE_IDS], iv[I.TRACE_CAP] = tr.slots()
             self.stage_traces.append(tr)
-        rc = lib.fsg_sample_pack_run(fb["ivp"], I["COUNT"], fb["fvp"], 17, fb["tbp"], K._stream(dev))
+        rc = lib.fsg_sample_pack_run(fb["ivp"], I.COUNT, fb["fvp"], _lib.PLAN_F.COUNT, fb["tbp"], K._stream(dev))
         if rc in (_lib.E_ALIGN, _lib.E_TOOBIG):
             return None
         _lib.check(rc, "fsg_sample_pack_run")
@@ -832,43 +832,45 @@ class FetalSynthGen:
         stream_id = K._stream(dev).value
         pre = self.__dict__.setdefault("_pre", {}).pop(stream_id, None)  # one carried block per launch stream
         if pre is not None and pre[0] == key and pre[1] is kc:
-            block, flags = pre[2], 1
+            block, flags = pre[2], _KF_BLOCK_FILLED
         if block is None:
             block = torch.empty(kc.block_bytes, dtype=torch.uint8, device=dev)
         nblock = None
         if next_key is not None:
             next_key &= 0xFFFFFFFFFFFFFFFF
             nblock = torch.empty(kc.block_bytes, dtype=torch.uint8, device=dev)
-            flags |= 4
+            flags |= _KF_NEXT_NAMED
         iv = kc.iv
-        iv[0] = key if key < (1 << 63) else key - (1 << 64)
-        iv[1] = out.data_ptr()
+        iv[_K_KEY] = key if key < (1 << 63) else key - (1 << 64)
+        iv[_K_OUT] = out.data_ptr()
         if labels_u8:
-            iv[2], iv[3] = 0, seg_out.data_ptr()
+            iv[_K_SEG_OUT], iv[_K_SEG_OUT_U8] = 0, seg_out.data_ptr()
         else:
-            iv[2], iv[3] = seg_out.data_ptr(), 0
-        iv[4], iv[5], iv[6] = ent[2], ent[1], block.data_ptr()
-        iv[7], iv[8], iv[9] = ws["ws0"].data_ptr(), ws["ws1"].data_ptr(), ws["low"].data_ptr()
-        iv[10], iv[11], iv[12] = (ws["rows"].data_ptr() if ws["rows"] is not None else 0), ws["stride"], int(bool(scale01))
+            iv[_K_SEG_OUT], iv[_K_SEG_OUT_U8] = seg_out.data_ptr(), 0
+        iv[_K_SEG_IN], iv[_K_SEG_IN_U8], iv[_K_BLOCK] = ent.seg_ptr, ent.twin_ptr, block.data_ptr()
+        iv[_K_WS0], iv[_K_WS1], iv[_K_WS_LOW] = ws["ws0"].data_ptr(), ws["ws1"].data_ptr(), ws["low"].data_ptr()
+        iv[_K_WS_ROWS], iv[_K_ROW_STRIDE] = (ws["rows"].data_ptr() if ws["rows"] is not None else 0), ws["stride"]
+        iv[_K_SCALE01] = int(bool(scale01))
         tr = None
         if self.stage_traces is not None:
             tr = StageTrace()
-            iv[13], iv[14], iv[15] = tr.slots()
+            iv[_K_TRACE_EVENTS], iv[_K_TRACE_IDS], iv[_K_TRACE_CAP] = tr.slots()
         else:
-            iv[13] = iv[14] = iv[15] = 0
-        iv[16:80] = ent[0]
+            iv[_K_TRACE_EVENTS] = iv[_K_TRACE_IDS] = iv[_K_TRACE_CAP] = 0
+        iv[_K_BANK:_K_BANK + keyed.BANK_SLOTS] = ent.bank_ptrs
         events = None
         if self.blur_events is not None:
             self._blur_tick += 1
             if self._blur_tick % self.blur_events_every == 0:
                 events = (kc.lib.fsg_event_create(), kc.lib.fsg_event_create())
-        iv[80], iv[81] = events if events is not None else (0, 0)
-        iv[82:86] = ent[3:7]  # the subject's code volume (0: four label volumes)
-        iv[86] = flags
+        iv[_K_EV_BLUR_BEGIN], iv[_K_EV_BLUR_END] = events if events is not None else (0, 0)
+        # the subject's code volume (0: four label volumes)
+        iv[_K_CODES], iv[_K_CODE_TUPLES], iv[_K_CODE_NTUPLES], iv[_K_CODE_STRIDE] = ent.codes, ent.code_tuples, ent.code_ntuples, ent.code_stride
+        iv[_K_FLAGS] = flags
         if nblock is not None:
-            iv[87], iv[88] = (next_key if next_key < (1 << 63) else next_key - (1 << 64)), nblock.data_ptr()
+            iv[_K_NEXT_KEY], iv[_K_NEXT_BLOCK] = (next_key if next_key < (1 << 63) else next_key - (1 << 64)), nblock.data_ptr()
         else:
-            iv[87] = iv[88] = 0
+            iv[_K_NEXT_KEY] = iv[_K_NEXT_BLOCK] = 0
         d = _lib.KeyedDraws()
         import ctypes as C
 
@@ -889,7 +891,7 @@ class FetalSynthGen:
             self._pre[stream_id] = (next_key, kc, nblock)
         if tr is not None:
             tr.meta = {"shape": shape, "low_shape": tuple(d.low_shape) if d.resample_active else None,
-                       "blur_ntaps": list(d.blur_ntaps), "label_bytes": 2 if ent[3] else 4, "draw_carried": flags & 1}
+                       "blur_ntaps": list(d.blur_ntaps), "label_bytes": 2 if ent.codes else 4, "draw_carried": flags & _KF_BLOCK_FILLED}
             self.stage_traces.append(tr)
         if not d.deform_active:  # no warp ran: the labels pass through
             if given:
@@ -999,7 +1001,7 @@ class FetalSynthGen:
                     ok = ok and self._flat_plan(c, scale01, out_all[b], seg_all[b], wss[b % nstreams],
                                                 self._twin_of(c) if c.dplan.active else None)
                     if ok:  # _flat holds one plan: pack it before the next one is built
-                        _lib.check(lib.fsg_sample_plan_pack(C.byref(plans[b]), fb["ivp"], self._I["COUNT"], fb["fvp"], 17,
+                        _lib.check(lib.fsg_sample_plan_pack(C.byref(plans[b]), fb["ivp"], _lib.PLAN_I.COUNT, fb["fvp"], _lib.PLAN_F.COUNT,
                                                             fb["tbp"]), "fsg_sample_plan_pack")
                 if ok:
                     handles = (C.c_void_p * nstreams)()

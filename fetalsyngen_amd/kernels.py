@@ -308,7 +308,7 @@ def zoom_minmax(src, tabs: DeviceTables, mm=None) -> torch.Tensor:
     return mm
 
 
-MM_SLOT_STRIDE = 16  # include/fsg_hip.h: FSG_MM_SLOT_STRIDE
+MM_SLOT_STRIDE = _lib.MM_SLOT_STRIDE
 
 
 def zoom_minmax_sharded(src, tabs: DeviceTables, nslots: int = 32) -> torch.Tensor:
@@ -607,7 +607,7 @@ def scale(x, mm, mode: int) -> torch.Tensor:
 
 
 # ---- SR-artifact slice-stack simulation (fsg_slice_acq.hip) -------------------------------------------
-SA_MODES = {"linear": 0, "nearest_psf": 1, "torch": 2}
+SA_MODES = {"linear": _lib.SA.LINEAR, "nearest_psf": _lib.SA.NEAREST_PSF, "torch": _lib.SA.TORCH}
 
 
 def _sa_mode(semantics: str, interp_psf: bool) -> int:
@@ -810,7 +810,7 @@ def slice_sums(slices) -> torch.Tensor:
     return out
 
 
-NZ_BUCKET = 4096
+NZ_BUCKET = _lib.NZ_BUCKET
 _NZ_MODES = {">": 0, "==": 1, "!=": 2}
 
 

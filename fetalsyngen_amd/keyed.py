@@ -62,6 +62,22 @@ def config_dict(cfg: _lib.KeyedConfig) -> dict:
     return out
 
 
+BANK_SLOTS = 64  # seed volumes the BANK slots of fsg_keyed_sample_run's argument array hold: 4 meta labels x 16 sub-cluster counts
+
+
+class Subject:
+    """Addresses of one subject's volumes as fsg_keyed_sample_run takes them (the C side only sees addresses), and the
+    objects they were taken from: weak references, and the segmentation's in-place version."""
+
+    __slots__ = ("bank_ref", "seg_ref", "seg_version", "bank_ptrs", "twin_ptr", "seg_ptr", "codes", "code_tuples", "code_ntuples",
+                 "code_stride")
+
+    def __init__(self, bank, seg, bank_ptrs, twin_ptr):
+        self.bank_ref, self.seg_ref, self.seg_version = weakref.ref(bank), weakref.ref(seg), seg._version
+        self.bank_ptrs, self.twin_ptr, self.seg_ptr = bank_ptrs, twin_ptr, seg.data_ptr()  # twin_ptr 0: no uint8 twin yet
+        self.codes = self.code_tuples = self.code_ntuples = self.code_stride = 0  # 0: no code volume (KeyedContext._codes)
+
+
 class KeyedContext:
     """One `fsg_keyed_ctx` (host-only object) for a (generator configuration, volume shape) pair."""
 
@@ -74,7 +90,7 @@ class KeyedContext:
         _lib.check(self.lib.fsg_keyed_create(C.byref(self.cfg), C.byref(h)), "fsg_keyed_create")
         self.handle = h
         self.block_bytes = int(self.lib.fsg_keyed_block_bytes(h))
-        self.iv = np.zeros(_lib.KEYED_I["COUNT"], dtype=np.int64)
+        self.iv = np.zeros(_lib.KEYED_I.COUNT, dtype=np.int64)
         self.ivp = self.iv.ctypes.data
         self._subjects = {}
         self.use_codes = True  # the subject's seed volumes as one uint16 code volume (seedcodes.py, built on first use)
@@ -113,33 +129,32 @@ class KeyedContext:
             lo = int(size * c.resolution[a] / max(c.max_resolution, c.resolution[a]))
             hi = int(size * c.resolution[a] / c.min_resolution)
             for m in range(max(lo - 1, 1), min(max(hi, lo) + 1, 4 * size) + 1):
-                self._register(_lib.KT_RESAMPLE, a, m, T._resample_axis_table(m, size))
+                self._register(_lib.KT.RESAMPLE, a, m, T._resample_axis_table(m, size))
                 f = np.float64(m) / np.float64(size)
-                self._register(_lib.KT_BACK, a, m, T.zoom_table(m, float(1 / f), int(np.round(m * (1 / f)))))
+                self._register(_lib.KT.BACK, a, m, T.zoom_table(m, float(1 / f), int(np.round(m * (1 / f)))))
             if c.nonlinear:
                 for s_ in range(max(int(np.floor(c.nonlin_scale_min * size)) - 1, 1), int(np.ceil(c.nonlin_scale_max * size)) + 2):
-                    self._register(_lib.KT_FIELD, a, s_, T.zoom_table(s_, float(np.float64(size) / np.float64(s_)), size))
+                    self._register(_lib.KT.FIELD, a, s_, T.zoom_table(s_, float(np.float64(size) / np.float64(s_)), size))
             for s_ in range(max(int(np.floor(c.bf_scale_min * size)) - 1, 1), int(np.ceil(c.bf_scale_max * size)) + 2):
-                self._register(_lib.KT_BIAS, a, s_, T.zoom_table(s_, float(np.float64(size) / np.float64(s_)), size))
+                self._register(_lib.KT.BIAS, a, s_, T.zoom_table(s_, float(np.float64(size) / np.float64(s_)), size))
         self._tables_ready = True
 
     # ---- per-subject pointer block --------------------------------------------------------------------------------------
     def subject(self, bank, seg, twin):
-        """int64 pointers of one subject's label volumes (bank slots, float32 segmentation, its uint8 twin), validated once
-        per (bank, segmentation) object pair -- the C side only sees addresses."""
+        """The `Subject` of (bank slots, float32 segmentation, its uint8 twin), validated once per (bank, segmentation) object
+        pair -- the C side only sees addresses."""
         key = (id(bank), id(seg))
-        hit = self._subjects.get(key)
-        if hit is not None and hit[0]() is bank and hit[1]() is seg and hit[2] == seg._version:
-            ent = hit[3]
-            if twin is not None and ent[1] == 0:
-                ent[1] = twin.data_ptr()
+        ent = self._subjects.get(key)
+        if ent is not None and ent.bank_ref() is bank and ent.seg_ref() is seg and ent.seg_version == seg._version:
+            if twin is not None and ent.twin_ptr == 0:
+                ent.twin_ptr = twin.data_ptr()
             self._codes(bank, ent)  # (built once per bank object; a rewrite of a seed volume through torch rebuilds it)
             return ent
         c, shape = self.cfg, self.shape
         dev = torch.device(self.device)
         if tuple(seg.shape) != shape or seg.dtype != torch.float32 or not seg.is_cuda or not seg.is_contiguous():
             raise ValueError(f"segmentation: expected a contiguous float32 tensor of shape {shape} on {dev}")
-        ptrs = np.zeros(64, dtype=np.int64)
+        ptrs = np.zeros(BANK_SLOTS, dtype=np.int64)
         vol = bank.vol
         for n in range(c.min_subclusters, c.max_subclusters + 1):
             for m in range(1, c.meta_labels + 1):
@@ -149,19 +164,19 @@ class KeyedContext:
                     raise ValueError(f"seed volume ({n}, {m}): expected a contiguous uint8 tensor of shape {shape} on {dev}, "
                                      f"got {part.dtype} {tuple(part.shape)} on {part.device}")
                 ptrs[4 * (n - c.min_subclusters) + (m - 1)] = part.data_ptr()
-        ent = [ptrs, 0 if twin is None else twin.data_ptr(), seg.data_ptr(), 0, 0, 0, 0]  # .. codes, tuples, ntuples, stride
+        ent = Subject(bank, seg, ptrs, 0 if twin is None else twin.data_ptr())
         self._codes(bank, ent)  # ~1 ms once per bank object (one pass over its volumes), little next to loading the subject
         if len(self._subjects) > 4096:
             self._subjects.clear()
-        self._subjects[key] = (weakref.ref(bank), weakref.ref(seg), seg._version, ent)
+        self._subjects[key] = ent
         return ent
 
     def _codes(self, bank, ent):
-        """ent[3:7] = the subject's code volume (seedcodes.build), kept ON the bank object so that it lives and dies with it.
+        """The code fields of `ent` = the subject's code volume (seedcodes.build), kept ON the bank object so that it lives and dies with it.
         A seed volume rewritten through torch bumps its `_version`: the codes are rebuilt; a rewrite through a raw pointer needs
         `FetalSynthGen.invalidate_label_twins()` (which drops them)."""
         if not self.use_codes:
-            ent[3:7] = [0, 0, 0, 0]
+            ent.codes = ent.code_tuples = ent.code_ntuples = ent.code_stride = 0
             return
         c = self.cfg
         vol = bank.vol
@@ -186,9 +201,10 @@ class KeyedContext:
             bank._seed_codes = have
         built = have[2]
         if built is None:
-            ent[3:7] = [0, 0, 0, 0]
+            ent.codes = ent.code_tuples = ent.code_ntuples = ent.code_stride = 0
         else:
-            ent[3:7] = [built[0].data_ptr(), built[1].data_ptr(), int(built[1].shape[0]), int(have[3])]
+            ent.codes, ent.code_tuples = built[0].data_ptr(), built[1].data_ptr()
+            ent.code_ntuples, ent.code_stride = int(built[1].shape[0]), int(have[3])
 
     def draws(self, key: int) -> _lib.KeyedDraws:
         d = _lib.KeyedDraws()

@@ -10,7 +10,9 @@ from __future__ import annotations
 
 import torch
 
-CODES_MAX = 2048  # FSG_CODES_MAX
+from . import _lib
+
+CODES_MAX = _lib.CODES_MAX
 
 
 def build_device(parts, stride: int):
@@ -19,7 +21,6 @@ def build_device(parts, stride: int):
     of distinct columns decides whether the codes are usable)."""
     import ctypes as C
 
-    from . import _lib
     from . import kernels as K
 
     if not parts or stride <= len(parts) or stride > 256 or len(parts) > 64:

@@ -501,8 +501,15 @@ enum {
   FSG_ST_ROWS = 14, FSG_ST_POINTWISE = 15, FSG_ST_BLUR_RS_X = 16, FSG_ST_BLUR_RS_YZ = 17, FSG_ST_COUNT = 18
 };
 int fsg_sample_run(const fsg_sample_plan* plan_host, void* stream);
-/* Layout check for FFI mirrors of the struct: which = 0 -> sizeof(fsg_sample_plan); 1 / 2 / 3 / 4 -> offsetof blur_taps / out /
- * seg_in_u8 / ws_seq; anything else -> -1.  Callable without a GPU. */
+/* Layout check for FFI mirrors of the structs: which = FSG_SIZEOF_x -> sizeof(fsg_x) (0: fsg_sample_plan, 6 .. 10: fsg_tap,
+ * fsg_deform, fsg_epilogue, fsg_keyed_config, fsg_keyed_draws); 1 / 2 / 3 / 4 / 5 -> offsetof blur_taps / out / seg_in_u8 /
+ * ws_seq / code_sel in fsg_sample_plan; anything else -> -1.  Callable without a GPU. */
+#define FSG_SIZEOF_SAMPLE_PLAN 0
+#define FSG_SIZEOF_TAP 6
+#define FSG_SIZEOF_DEFORM 7
+#define FSG_SIZEOF_EPILOGUE 8
+#define FSG_SIZEOF_KEYED_CONFIG 9
+#define FSG_SIZEOF_KEYED_DRAWS 10
 int64_t fsg_sample_plan_layout(int which);
 /* B samples with one call: plan b runs on streams[b % nstreams] (hipStream_t handles).  The caller orders those streams
  * behind the upload of every plan's parameters and waits for them afterwards; per sample the work is exactly
@@ -637,14 +644,16 @@ enum {
   /* optional code volume of the subject (0 = none): uint16 codes, uint8 tuples [ntuples][stride] whose byte
    * 4 * (n_sub - min_subclusters) + (mlabel - 1) is the value of seed volume (n_sub, mlabel) and whose byte stride - 1 is 0 */
   FSG_KEYED_I_CODES = 16 + 66, FSG_KEYED_I_CODE_TUPLES = 16 + 67, FSG_KEYED_I_CODE_NTUPLES = 16 + 68, FSG_KEYED_I_CODE_STRIDE = 16 + 69,
-  /* look-ahead (optional).  FLAGS bit 0: the block of THIS sample is already filled (the previous call carried its draw job);
-   * bit 2: NEXT_KEY / NEXT_BLOCK name the sample the caller will run next on this stream -- its draw job then rides in this
-   * sample's floor(min) launch (fsg_keyed_draws::rode says whether it did: not when the deformation gate is off).  A caller that
-   * then runs something else simply does not set bit 0.  (r03: the next sample's GMM draw beside the zoom-back launches was built
+  /* look-ahead (optional).  FLAGS bit 0 (FSG_KEYED_FLAG_BLOCK_FILLED): the block of THIS sample is already filled (the previous
+   * call carried its draw job); bit 2 (FSG_KEYED_FLAG_NEXT_NAMED): NEXT_KEY / NEXT_BLOCK name the sample the caller will run next
+   * on this stream -- its draw job then rides in this sample's floor(min) launch (fsg_keyed_draws::rode says whether it did: not
+   * when the deformation gate is off).  A caller that then runs something else simply does not set bit 0.  (r03: the next sample's GMM draw beside the zoom-back launches was built
    * and measured too -- 224 -> 230-244 us per step, the two jobs slow each other down -- and removed.) */
   FSG_KEYED_I_FLAGS = 16 + 70, FSG_KEYED_I_NEXT_KEY = 16 + 71, FSG_KEYED_I_NEXT_BLOCK = 16 + 72,
   FSG_KEYED_I_COUNT = 16 + 73
 };
+#define FSG_KEYED_FLAG_BLOCK_FILLED 1
+#define FSG_KEYED_FLAG_NEXT_NAMED 4
 int fsg_keyed_sample_run(void* ctx, const int64_t* iv, int niv, fsg_keyed_draws* draws_out, void* stream);
 /* The draw kernel alone (tests): fills the parameter block of `draws` at block_dev. */
 int fsg_keyed_fill_block(void* ctx, const fsg_keyed_draws* draws, void* block_dev, void* stream);

@@ -1,7 +1,9 @@
-"""CPU: the C-ABI library loads and exports every symbol include/fsg_hip.h declares; argument
-validation happens before any launch (no GPU needed for these calls)."""
+"""CPU: the C-ABI library loads and exports every symbol include/fsg_hip.h declares; the binding that fetalsyngen_amd/_lib.py
+derives from that header is the compiler's reading of it; argument validation happens before any launch (no GPU needed for
+these calls)."""
 import ctypes
 import re
+import subprocess
 from pathlib import Path
 
 import pytest
@@ -23,8 +25,8 @@ def test_library_exports_every_declared_symbol():
     assert len(syms) >= 20
     for s in syms:
         assert hasattr(lib, s), f"{s} declared in include/fsg_hip.h but not exported"
-    bound = set(_lib.SIGNATURES) | set(_lib.SPECIAL_RESTYPE)
-    assert set(syms) == bound, f"ctypes table and header disagree: {set(syms) ^ bound}"
+    bound = set(_lib.PROTOTYPES)  # header_symbols() is a scan of its own: a prototype the parser drops or invents shows here
+    assert set(syms) == bound, f"parsed prototypes and header disagree: {set(syms) ^ bound}"
 
 
 def test_version_and_error_strings():
@@ -94,4 +96,116 @@ def test_sample_plan_mirror_has_the_c_layout():
     assert lib.fsg_sample_plan_layout(3) == P.seg_in_u8.offset
     assert lib.fsg_sample_plan_layout(4) == P.ws_seq.offset
     assert lib.fsg_sample_plan_layout(5) == P.code_sel.offset
+    assert lib.fsg_sample_plan_layout(6) == C.sizeof(_lib.Tap)
+    assert lib.fsg_sample_plan_layout(7) == C.sizeof(_lib.Deform)
+    assert lib.fsg_sample_plan_layout(8) == C.sizeof(_lib.Epilogue)
+    assert lib.fsg_sample_plan_layout(9) == C.sizeof(_lib.KeyedConfig)
+    assert lib.fsg_sample_plan_layout(10) == C.sizeof(_lib.KeyedDraws)
+    assert lib.fsg_sample_plan_layout(11) == -1
     assert lib.fsg_sample_plan_layout(99) == -1
+
+
+def _header_without_comments():
+    return re.sub(r"/\*.*?\*/", "", (REPO / "include" / "fsg_hip.h").read_text(), flags=re.S)
+
+
+def test_parsed_header_is_what_the_compiler_sees(tmp_path):
+    """The parser against the compiler: a host program that includes the header prints sizeof of every struct, offsetof and
+    sizeof of every field and the value of every constant the parser found; each must equal the ctypes mirror.  The number
+    of fields per struct is held against a count of declarators made here, so a member the parser loses is seen as well."""
+    from fetalsyngen_amd import _build
+
+    try:
+        cc = _build.hipcc()
+    except RuntimeError:
+        pytest.skip("no compiler")
+    lines = ["#include <cstdio>", "#include <cstddef>", f'#include "{REPO / "include" / "fsg_hip.h"}"', "int main() {"]
+    want = {}
+    for cname, cls in _lib.STRUCTS.items():
+        lines.append(f'  printf("sizeof {cname} %zu\\n", sizeof({cname}));')
+        want[f"sizeof {cname}"] = ctypes.sizeof(cls)
+        for fname, ftype in cls._fields_:
+            lines.append(f'  printf("field {cname}.{fname} %zu %zu\\n", offsetof({cname}, {fname}), sizeof((({cname}*)0)->{fname}));')
+            want[f"field {cname}.{fname}"] = (getattr(cls, fname).offset, ctypes.sizeof(ftype))
+    for name, value in _lib.CONSTANTS.items():
+        lines.append(f'  printf("const {name} %lld\\n", (long long)(FSG_{name}));')
+        want[f"const {name}"] = value
+    lines += ["  return 0;", "}"]
+    src, exe = tmp_path / "layout.cpp", tmp_path / "layout"
+    src.write_text("\n".join(lines) + "\n")
+    subprocess.run([cc, "-x", "c++", "-std=c++17", str(src), "-o", str(exe)], check=True)
+    got = {}
+    for row in subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout.splitlines():
+        kind, name, *nums = row.split()
+        got[f"{kind} {name}"] = int(nums[0]) if len(nums) == 1 else tuple(int(v) for v in nums)
+    assert got == want, {k: (got.get(k), want.get(k)) for k in set(got) | set(want) if got.get(k) != want.get(k)}
+
+    text = _header_without_comments()
+    bodies = dict(re.findall(r"typedef\s+struct\s+(\w+)\s*\{(.*?)\}\s*\w+\s*;", text, flags=re.S))
+    assert list(bodies) == list(_lib.STRUCTS)
+    for cname, body in bodies.items():  # one declarator per ';' plus one per ',' (no member of the header has a ',' elsewhere)
+        assert body.count(";") + body.count(",") == len(_lib.STRUCTS[cname]._fields_), cname
+    assert len(_lib.CONSTANTS) == len(set(re.findall(r"\bFSG_[A-Z0-9_]+(?=\s*=|\s+[-(\d])", text)))
+    assert len(_lib.CONSTANTS) >= 140 and sum(len(c._fields_) for c in _lib.STRUCTS.values()) >= 149
+
+
+def test_binding_names():
+    """Constants are reachable by header name only, grouped by family; every pointer field is c_void_p; prototypes take
+    what the call sites pass (struct pointers by reference, every other pointer as address, array or byref)."""
+    assert _lib.PLAN_I.COUNT == len(_lib.SamplePlan._fields_) + 14 == 71  # iv slots: the header's own count
+    assert (_lib.E_BADARG, _lib.E_TOOBIG, _lib.E_ALIGN, _lib.E_NOTABLE) == (-1, -2, -3, -4)
+    assert _lib.KEYED_I.NEXT_BLOCK == 88 and _lib.KEYED_FLAG.BLOCK_FILLED == 1 and _lib.KEYED_FLAG.NEXT_NAMED == 4
+    assert _lib.STAGE_NAMES[:3] == ("begin", "upload", "draw") and len(_lib.STAGE_NAMES) == _lib.ST.COUNT
+    for missing in ("NOPE", "count"):
+        with pytest.raises(AttributeError):
+            getattr(_lib.PLAN_I, missing)
+    with pytest.raises(AttributeError):
+        _lib.TUNE_NO_SUCH_FLAG
+    assert _lib.SamplePlan.deform.size == ctypes.sizeof(_lib.Deform) and _lib.SamplePlan.epi.size == ctypes.sizeof(_lib.Epilogue)
+    assert ctypes.sizeof(_lib.SamplePlan().blur_taps) == 3 * 129 * 4 and len(_lib.SamplePlan().blur_taps[2]) == 129
+    assert ctypes.sizeof(_lib.SamplePlan().label_parts) == 4 * ctypes.sizeof(ctypes.c_void_p)
+    for cls in _lib.STRUCTS.values():
+        for fname, ftype in cls._fields_:
+            assert not issubclass(ftype, ctypes._Pointer), (cls, fname)
+    res, args = _lib.PROTOTYPES["fsg_sample_head_codes_f32"]
+    assert res is ctypes.c_int and args[4] is ctypes.c_void_p and args[12] is ctypes.POINTER(_lib.Deform)  # sel[4], d
+    assert _lib.PROTOTYPES["fsg_deform_rows_f32"][1][1] is ctypes.POINTER(_lib.Epilogue)  # declared before the struct is defined
+    assert _lib.PROTOTYPES["fsg_zoom3d_f32"][1][5] is ctypes.c_void_p  # fsg_tap tables are device addresses
+    assert _lib.PROTOTYPES["fsg_error_string"] == (ctypes.c_char_p, [ctypes.c_int])
+    assert _lib.PROTOTYPES["fsg_event_create"] == (ctypes.c_void_p, [])
+    assert _lib.PROTOTYPES["fsg_em1d_work_bytes"] == (ctypes.c_size_t, [ctypes.c_int, ctypes.c_int64])
+    assert _lib.PROTOTYPES["fsg_key_to_float"] == (ctypes.c_float, [ctypes.c_int32])
+    lib = _lib.load()
+    taps, ms = (ctypes.c_float * 3)(0.25, 0.5, 0.25), ctypes.c_float()
+    null = ctypes.c_void_p(0)
+    assert lib.fsg_blur_axis_taps_host_f32(null, null, 4, 4, 4, 0, taps, 3, null) == _lib.E_BADARG  # a ctypes array
+    assert lib.fsg_blur_axis_taps_host_f32(None, 0, 4, 4, 4, 0, ctypes.cast(taps, ctypes.POINTER(ctypes.c_float)), 3, None) == _lib.E_BADARG
+    assert lib.fsg_event_elapsed_ms(null, null, ctypes.byref(ms)) != 0  # byref of a scalar where the header says float*
+
+
+@pytest.mark.parametrize("snippet, line, what", [
+    ("#define FSG_A 1\ntypedef struct fsg_x {\n  int32_t a;\n  wchar_t b;\n} fsg_x;\n", 4, "unknown type 'wchar_t'"),
+    ("#define FSG_A 1\n\ntypedef struct fsg_x {\n  int32_t a;\n", 3, "without an end"),
+    ("enum {\n  FSG_A = 1,\n  FSG_B = 1.5\n};\n", 3, "not an integer constant"),
+    ("enum { FSG_A = 1, FSG_B };\n", 1, "not FSG_NAME = value"),
+    ("#define FSG_A sizeof(int)\n", 1, "not an integer constant"),
+    ("int fsg_f(int a);\nint fsg_g(int a,\n          FILE* f);\n", 3, "unknown type 'FILE'"),
+    ("union fsg_u { int a; float b; };\n", 1, "not recognised"),
+    ("typedef int fsg_int;\n", 1, "not recognised"),
+    ("#pragma once\n", 1, "not recognised"),
+])
+def test_parser_refuses_what_it_does_not_know(snippet, line, what):
+    with pytest.raises(_lib.HeaderError, match=f"line {line}: .*{re.escape(what)}"):
+        _lib.parse(snippet)
+
+
+def test_no_restated_header_numbers():
+    """Keeps the clean-up done: tuning flags and flat-array slots are spelled by their header names."""
+    lit = re.compile(r"fsg_set_tuning\(\s*(?!0\s*\))\d")
+    for folder in ("fetalsyngen_amd", "tests", "tools"):
+        for path in sorted((REPO / folder).rglob("*.py")):
+            assert not lit.search(path.read_text()), f"{path}: fsg_set_tuning with a bare number"
+    slot = re.compile(r"\b[if]v\[\d")
+    for rel in ("fetalsyngen_amd/generator/model.py", "fetalsyngen_amd/keyed.py", "tools/host_phases.py"):
+        hits = [ln for ln in (REPO / rel).read_text().splitlines() if slot.search(ln)]
+        assert not hits, f"{rel}: {hits[:3]}"

@@ -356,7 +356,7 @@ def test_zoom_tile_kernel_equals_row_kernels(K):
         bt, _ = T.zoom_tables(new, 1 / np.asarray(fac))
         zt = K.DeviceTables(bt, DEV)
         res = {}
-        for flag in (256, 512, 8192, 0):  # FSG_TUNE_ROW_ZOOM, _TILE_ZOOM, _SLAB_ZOOM, defaults
+        for flag in (_lib.TUNE.ROW_ZOOM, _lib.TUNE.TILE_ZOOM, _lib.TUNE.SLAB_ZOOM, 0):  # .., defaults
             prev = lib.fsg_set_tuning(flag)
             try:
                 for ty in ((16,) if flag in (256, 0) else (1, 5, 16, 32)):
@@ -691,7 +691,7 @@ def test_rowwise_kernels_equal_per_voxel_kernels(K, golden):
     bias = (rs.randn(3, 2, 4) * 0.3).astype(np.float32)
     bt, _ = T.zoom_tables(bias.shape, np.array(shape) / np.array(bias.shape))
     res = {}
-    for flags in (0, 1, 2, 3):
+    for flags in (0, _lib.TUNE.GENERIC_WARP, _lib.TUNE.PRECISE_MATH, _lib.TUNE.GENERIC_WARP | _lib.TUNE.PRECISE_MATH):
         prev = lib.fsg_set_tuning(flags)
         try:
             for flip in (False, True):
@@ -725,7 +725,7 @@ def test_rowwise_kernels_equal_per_voxel_kernels(K, golden):
     src = (rs.rand(37, 29, 41) * 255).astype(np.float32)
     tabs, _ = T.zoom_tables(src.shape, np.array((64, 80, 96)) / np.array(src.shape))
     outs = []
-    for flags in (0, 4, 8):
+    for flags in (0, _lib.TUNE.GENERIC_ZOOM, _lib.TUNE.NO_PREFETCH):
         prev = lib.fsg_set_tuning(flags)
         try:
             dt = K.DeviceTables(tabs, DEV)
@@ -820,10 +820,10 @@ def test_uint8_label_warps_equal_float32_label_warps(K, case):
             lib.fsg_set_tuning(prev)
         assert np.array_equal(outs[1], outs[3].astype(np.uint8)) and np.array_equal(outs[1], outs[4])
         assert np.array_equal(outs[2], outs[5]), (case, flip)  # the label leg leaves the image as the image-only warp has it
-        # and against the float32-label kernels: 16-wave patch kernel (default), row kernel (flag 32), and with
+        # and against the float32-label kernels: 16-wave patch kernel (default), row kernel (NO_PATCH), and with
         # the precomputed row workspace
         f32 = {}
-        for flags in (0, 32):
+        for flags in (0, _lib.TUNE.NO_PATCH):
             prev = lib.fsg_set_tuning(flags)
             try:
                 a, lf32 = K.warp(spec, mm, src_lin=dev(img), src_nn=dev(lab.astype(np.float32)), gamma=0.9,
@@ -882,7 +882,8 @@ def test_warp_work_shapes_are_bit_identical(K, shape):
                 res[(variant, flip)] = (host(out), host(seg), host(seg8), host(plain), host(out2), host(seg8f))
         # variant 0 = the lean body (fsg_warp_lean.hip); the same with the r01 patch body and precise math
         lib.fsg_warp_set_variant(0)
-        for key, flags in (("patch", 4096), ("lean_precise", 2), ("patch_precise", 4096 | 2)):
+        for key, flags in (("patch", _lib.TUNE.NO_LEAN), ("lean_precise", _lib.TUNE.PRECISE_MATH),
+                           ("patch_precise", _lib.TUNE.NO_LEAN | _lib.TUNE.PRECISE_MATH)):
             pf = lib.fsg_set_tuning(flags)
             try:
                 for flip in (False, True):
@@ -1091,7 +1092,7 @@ def test_fused_sample_head_equals_split_launches(K):
             gen = make_generator(shape, DEV, rng=rng_mode, prob=0.7, nonlin_scale=(0.1, 0.25), bf_scale=(0.05, 0.15))
             for seed in range(5):
                 res = []
-                for flag in (0, 2048):
+                for flag in (0, _lib.TUNE.SPLIT_HEAD):
                     prev = lib.fsg_set_tuning(flag)
                     try:
                         np.random.seed(seed)
@@ -1285,7 +1286,7 @@ def test_plan_that_uploads_its_own_parameters_equals_the_uploaded_arena(K):
     segd, bank = dev(seg), SeedBank(seeds, DEV)
     gen = make_generator(shape, DEV, rng="device", prob=1.0, nonlin_scale=(0.08, 0.2), bf_scale=(0.03, 0.12))
     lib = _lib.load()
-    I = gen._I
+    I = _lib.PLAN_I
 
     def run(seed, upload):
         np.random.seed(seed)
@@ -1304,10 +1305,10 @@ def test_plan_that_uploads_its_own_parameters_equals_the_uploaded_arena(K):
                 host = torch.empty(arena.dev.numel(), dtype=torch.uint8, pin_memory=True)
                 host.copy_(arena.dev)
                 arena.dev.zero_()
-                iv[I["ARENA_HOST"]], iv[I["ARENA_DEV"]], iv[I["ARENA_BYTES"]] = host.data_ptr(), arena.dev.data_ptr(), host.numel()
-                iv[I["OVERLAP"]], iv[I["WS_SEQ"]] = upload, 5 * upload
+                iv[I.ARENA_HOST], iv[I.ARENA_DEV], iv[I.ARENA_BYTES] = host.data_ptr(), arena.dev.data_ptr(), host.numel()
+                iv[I.OVERLAP], iv[I.WS_SEQ] = upload, 5 * upload
             fb = gen._flat
-            rc = lib.fsg_sample_pack_run(fb["ivp"], I["COUNT"], fb["fvp"], 17, fb["tbp"], K._stream(torch.device(DEV)))
+            rc = lib.fsg_sample_pack_run(fb["ivp"], I.COUNT, fb["fvp"], _lib.PLAN_F.COUNT, fb["tbp"], K._stream(torch.device(DEV)))
             _lib.check(rc, "fsg_sample_pack_run")
             torch.cuda.synchronize()  # `host` must outlive the copy
             return out.clone(), seg_out.clone(), c

@@ -146,7 +146,7 @@ def test_hip_forward_known_answers(tx, precise):
     from fetalsyngen_amd import kernels as K
 
     vol, psf, _ = _case()
-    prev = _lib.load().fsg_set_tuning(2 if precise else 0)  # FSG_TUNE_PRECISE_MATH: the .cu's operation order
+    prev = _lib.load().fsg_set_tuning(_lib.TUNE.PRECISE_MATH if precise else 0)  # the .cu's operation order
     try:
         for interp_psf, expected in ((False, _expected_forward_linear), (True, _expected_forward_nn)):
             s, w = K.slice_acq_forward(_dev(_transform(tx)), _dev(vol), None, None, _dev(psf), SS, 1.0, need_weight=True,
@@ -166,7 +166,7 @@ def test_hip_adjoint_known_answer(direct):
 
     _, psf, slices = _case()
     ev, ew = _expected_adjoint_linear(psf, slices)
-    prev = _lib.load().fsg_set_tuning(128 if direct else 0)  # FSG_TUNE_SA_DIRECT: direct atomics instead of the LDS pre-sum
+    prev = _lib.load().fsg_set_tuning(_lib.TUNE.SA_DIRECT if direct else 0)  # direct atomics instead of the LDS pre-sum
     try:
         v, w = K.slice_acq_adjoint(_dev(_transform()), _dev(psf), _dev(slices), None, None, VS, 1.0, equalize=False,
                                    return_weight=True)

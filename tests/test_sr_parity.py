@@ -80,7 +80,7 @@ def test_cuda_semantics_vs_oracle(K, golden, interp_psf, mk, pk):
     np.testing.assert_allclose(host(w), ew, rtol=0, atol=5e-6)
     np.testing.assert_allclose(host(s), es, rtol=1e-5, atol=1e-4)
     from fetalsyngen_amd import _lib
-    prev = _lib.load().fsg_set_tuning(2)
+    prev = _lib.load().fsg_set_tuning(_lib.TUNE.PRECISE_MATH)
     try:
         sp, wp = K.slice_acq_forward(dev(tr), dev(g["vol"]), dev(vm), dev(sm), dev(psf), SS, RES, need_weight=True,
                                      interp_psf=interp_psf)
@@ -173,7 +173,7 @@ def test_adjoint_lds_presum_matches_direct_atomics(K, tuning):
     sm = torch.rand((n, ss, ss), device=DEV) > 0.1
     vm = torch.rand(vs, device=DEV) > 0.1
     for masks in ((None, None), (sm, vm)):
-        prev = lib.fsg_set_tuning(128)  # FSG_TUNE_SA_DIRECT
+        prev = lib.fsg_set_tuning(_lib.TUNE.SA_DIRECT)
         try:
             ref, refw = K.slice_acq_adjoint(dev(tr), psf, s, masks[0], masks[1], vs, 1.4, interp_psf=True, return_weight=True)
         finally:
@@ -207,7 +207,7 @@ def test_forward_plate_kernel_equals_direct_gathers_for_any_orientation(K):
             tr = random_init_stack_transforms(12, 5.0, False, 6.0).matrix().to(DEV)
             sm = (torch.rand((12, *ss), device=DEV) > 0.2) if rep == 3 else None
             got = {}
-            for name, flag in (("direct", 131072), ("plate", 262144), ("auto", 0)):
+            for name, flag in (("direct", _lib.TUNE.SA_FWD_DIRECT), ("plate", _lib.TUNE.SA_FWD_PLATE), ("auto", 0)):
                 lib.fsg_set_tuning(flag)
                 try:
                     got[name] = K.slice_acq_forward(tr, vol, None, sm, psf, ss, rs, need_weight=True)

@@ -64,7 +64,7 @@ def main():
     from fetalsyngen_amd import _lib
     lib = _lib.load()
     adj = lambda t=tr: K.slice_acq_adjoint(t, psf, s, None, None, vs, rs, interp_psf=True, equalize=True)  # noqa: E731
-    prev = lib.fsg_set_tuning(128)
+    prev = lib.fsg_set_tuning(_lib.TUNE.SA_DIRECT)
     out["adjoint_direct_ms"] = round(timed(adj, a.reps), 3)
     lib.fsg_set_tuning(prev)
     sweep = {}
@@ -73,7 +73,7 @@ def main():
         np.random.seed(1)
         t2 = random_stack(a.slices, gap=a.size * res / a.slices / res, max_angle=ang).to(dev)
         row = {}
-        prev = lib.fsg_set_tuning(128)
+        prev = lib.fsg_set_tuning(_lib.TUNE.SA_DIRECT)
         row["direct"] = round(timed(lambda: adj(t2), a.reps), 2)
         lib.fsg_set_tuning(prev)
         for cap, zc, t16 in cfgs:

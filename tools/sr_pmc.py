@@ -24,7 +24,7 @@ vol = torch.rand(vs, device=dev)
 rs = res_s / res
 s = K.slice_acq_forward(tr, vol, None, None, psf, (ss, ss), rs)
 lib = _lib.load()
-prev = lib.fsg_set_tuning(128)
+prev = lib.fsg_set_tuning(_lib.TUNE.SA_DIRECT)
 K.slice_acq_adjoint(tr, psf, s, None, None, vs, rs, interp_psf=True, equalize=True)
 lib.fsg_set_tuning(prev)
 K.slice_acq_adjoint(tr, psf, s, None, None, vs, rs, interp_psf=True, equalize=True)

@@ -53,7 +53,7 @@ def main():
                 # the same call through each forward kernel alone, with the orientation figures the per-slice choice uses
                 from fetalsyngen_amd import _lib as _L
                 row = {"slices": int(tr.shape[0]), "psf": list(psf.shape), "ss": list(args[4]), "res": round(float(args[5]), 3)}
-                for tag, flag in (("direct", 131072), ("plate", 262144), ("default", 0)):
+                for tag, flag in (("direct", _L.TUNE.SA_FWD_DIRECT), ("plate", _L.TUNE.SA_FWD_PLATE), ("default", 0)):
                     _L.load().fsg_set_tuning(flag)
                     fn(tr, *args, **kw)
                     torch.cuda.synchronize()
