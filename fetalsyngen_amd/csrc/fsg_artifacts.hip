@@ -421,7 +421,8 @@ int fsg_perlin_fractal_f32(const float* const* grads, const float* const* lins, 
 int fsg_blend_f32(const float* a, const float* b, const float* w, size_t n, int w_mode, const int32_t* w_mm, float increase,
                   const float* seg, int b_mode, const int32_t* b_mm, const int32_t* a_mm, float std, float* out,
                   float* w_out, void* stream) {
-  if (!w || n == 0 || (!out && !w_out) || w_mode < 0 || w_mode > 1 || b_mode < 0 || b_mode > 1) return FSG_E_BADARG;
+  if (n == 0) return 0;  // nothing to do: no launch, pointers may be null
+  if (!w || (!out && !w_out) || w_mode < 0 || w_mode > 1 || b_mode < 0 || b_mode > 1) return FSG_E_BADARG;
   if (out && (!a || !b)) return FSG_E_BADARG;
   if (w_mode == 1 && !w_mm) return FSG_E_BADARG;
   if (b_mode == 1 && (!b_mm || !a_mm)) return FSG_E_BADARG;
@@ -434,7 +435,8 @@ int fsg_blend_f32(const float* a, const float* b, const float* w, size_t n, int 
 
 int fsg_slice_noise_f32(float* slices, size_t n, float threshold, float sigma, const float* noise1, const float* noise2,
                         uint64_t seed, uint64_t stream_id, void* stream) {
-  if (!slices || n == 0 || ((noise1 == nullptr) != (noise2 == nullptr))) return FSG_E_BADARG;
+  if (n == 0) return 0;  // nothing to do: no launch, pointers may be null
+  if (!slices || ((noise1 == nullptr) != (noise2 == nullptr))) return FSG_E_BADARG;
   size_t blocks = (n + 255) / 256;
   if (blocks > 16384) blocks = 16384;
   hipLaunchKernelGGL(slice_noise_kernel, dim3((unsigned)blocks), dim3(256), 0, fsg_stream(stream), slices, n, threshold, sigma,
@@ -460,27 +462,31 @@ int fsg_slice_sums_f32(const float* slices, int n, size_t hw, float* sums, void*
 }
 
 int fsg_nonzero_count_f32(const float* v, size_t n, int mode, float value, int32_t* counts, void* stream) {
-  if (!v || !counts || n == 0 || mode < 0 || mode > 2) return FSG_E_BADARG;
+  if (n == 0) return 0;  // nothing to do: no launch, pointers may be null
+  if (!v || !counts || mode < 0 || mode > 2) return FSG_E_BADARG;
   hipLaunchKernelGGL(nonzero_count_kernel<float>, dim3((unsigned)((n + NZ_BLOCK - 1) / NZ_BLOCK)), dim3(256), 0,
                      fsg_stream(stream), v, n, mode, value, counts);
   FSG_RETURN_LAUNCH();
 }
 int fsg_nonzero_count_u8(const uint8_t* v, size_t n, int mode, float value, int32_t* counts, void* stream) {
-  if (!v || !counts || n == 0 || mode < 0 || mode > 2) return FSG_E_BADARG;
+  if (n == 0) return 0;  // nothing to do: no launch, pointers may be null
+  if (!v || !counts || mode < 0 || mode > 2) return FSG_E_BADARG;
   hipLaunchKernelGGL(nonzero_count_kernel<uint8_t>, dim3((unsigned)((n + NZ_BLOCK - 1) / NZ_BLOCK)), dim3(256), 0,
                      fsg_stream(stream), v, n, mode, value, counts);
   FSG_RETURN_LAUNCH();
 }
 int fsg_nonzero_select_f32(const float* v, size_t n, int mode, float value, const int32_t* bucket, const int32_t* rank,
                            int nreq, long long* out, void* stream) {
-  if (!v || !bucket || !rank || !out || n == 0 || nreq <= 0 || mode < 0 || mode > 2) return FSG_E_BADARG;
+  if (n == 0) return 0;  // nothing to do: no launch, pointers may be null
+  if (!v || !bucket || !rank || !out || nreq <= 0 || mode < 0 || mode > 2) return FSG_E_BADARG;
   hipLaunchKernelGGL(nonzero_select_kernel<float>, dim3((unsigned)nreq), dim3(64), 0, fsg_stream(stream), v, n, mode, value,
                      bucket, rank, out);
   FSG_RETURN_LAUNCH();
 }
 int fsg_nonzero_select_u8(const uint8_t* v, size_t n, int mode, float value, const int32_t* bucket, const int32_t* rank,
                           int nreq, long long* out, void* stream) {
-  if (!v || !bucket || !rank || !out || n == 0 || nreq <= 0 || mode < 0 || mode > 2) return FSG_E_BADARG;
+  if (n == 0) return 0;  // nothing to do: no launch, pointers may be null
+  if (!v || !bucket || !rank || !out || nreq <= 0 || mode < 0 || mode > 2) return FSG_E_BADARG;
   hipLaunchKernelGGL(nonzero_select_kernel<uint8_t>, dim3((unsigned)nreq), dim3(64), 0, fsg_stream(stream), v, n, mode, value,
                      bucket, rank, out);
   FSG_RETURN_LAUNCH();
@@ -488,14 +494,16 @@ int fsg_nonzero_select_u8(const uint8_t* v, size_t n, int mode, float value, con
 
 int fsg_compact_f32(const float* values, const float* pred, size_t n, int mode, float value, const long long* offsets,
                     float* out, void* stream) {
-  if (!values || !pred || !offsets || !out || n == 0 || mode < 0 || mode > 2) return FSG_E_BADARG;
+  if (n == 0) return 0;  // nothing to do: no launch, pointers may be null
+  if (!values || !pred || !offsets || !out || mode < 0 || mode > 2) return FSG_E_BADARG;
   hipLaunchKernelGGL(compact_kernel, dim3((unsigned)((n + NZ_BLOCK - 1) / NZ_BLOCK)), dim3(64), 0, fsg_stream(stream), values,
                      pred, n, mode, value, offsets, out);
   FSG_RETURN_LAUNCH();
 }
 
 int fsg_ewise_f32(const float* a, const float* b, size_t n, int op, float value, float* out, void* stream) {
-  if (!a || !out || n == 0 || op < 0 || op > 7) return FSG_E_BADARG;
+  if (n == 0) return 0;  // nothing to do: no launch, pointers may be null
+  if (!a || !out || op < 0 || op > 7) return FSG_E_BADARG;
   if ((op == 0 || (op >= 3 && op <= 6)) && !b) return FSG_E_BADARG;
   size_t blocks = (n + 255) / 256;
   if (blocks > 16384) blocks = 16384;
@@ -517,7 +525,8 @@ int fsg_dist_pass_f32(const float* src, float* dst, int n0, int n1, int n2, int 
 
 int fsg_boundary_mask_f32(const float* image, const float* mask, const float* mask_modif, const float* mog, const float* dist,
                           int n_dilate, size_t n, float* out, float* mask_out, void* stream) {
-  if (!mask || !mask_modif || !mog || !dist || n == 0 || n_dilate <= 0 || (!out && !mask_out) || (out && !image))
+  if (n == 0) return 0;  // nothing to do: no launch, pointers may be null
+  if (!mask || !mask_modif || !mog || !dist || n_dilate <= 0 || (!out && !mask_out) || (out && !image))
     return FSG_E_BADARG;
   size_t blocks = (n + 255) / 256;
   if (blocks > 16384) blocks = 16384;
@@ -527,7 +536,8 @@ int fsg_boundary_mask_f32(const float* image, const float* mask, const float* ma
 }
 
 int fsg_bernoulli_keep_f32(const float* a, size_t n, float p, uint64_t seed, uint64_t stream_id, float* out, void* stream) {
-  if (!a || !out || n == 0) return FSG_E_BADARG;
+  if (n == 0) return 0;  // nothing to do: no launch, pointers may be null
+  if (!a || !out) return FSG_E_BADARG;
   size_t blocks = (n + 255) / 256;
   if (blocks > 16384) blocks = 16384;
   hipLaunchKernelGGL(bernoulli_kernel, dim3((unsigned)blocks), dim3(256), 0, fsg_stream(stream), a, n, p, seed, stream_id, out);
@@ -535,7 +545,8 @@ int fsg_bernoulli_keep_f32(const float* a, size_t n, float p, uint64_t seed, uin
 }
 
 int fsg_scatter_const_f32(float* out, size_t n, const long long* idx, int k, float value, void* stream) {
-  if (!out || !idx || k <= 0 || n == 0) return FSG_E_BADARG;
+  if (n == 0) return 0;  // nothing to do: no launch, pointers may be null
+  if (!out || !idx || k <= 0) return FSG_E_BADARG;
   hipLaunchKernelGGL(scatter_const_kernel, dim3((unsigned)((k + 255) / 256)), dim3(256), 0, fsg_stream(stream), out, n, idx, k,
                      value);
   FSG_RETURN_LAUNCH();

@@ -83,7 +83,7 @@ __global__ __launch_bounds__(256) void cast_f16_kernel(const float* __restrict__
 extern "C" {
 
 int fsg_cast_f32_to_f16(const float* x, size_t n, void* out_f16, void* stream) {
-  if (n == 0) return 0;
+  if (n == 0) return 0;  // nothing to do: no launch, pointers may be null
   if (!x || !out_f16) return FSG_E_BADARG;
   size_t blocks = (n / 8 + 255) / 256;
   if (blocks > 4096) blocks = 4096;
@@ -102,7 +102,8 @@ int fsg_copy_bytes(void* dst, const void* src, size_t nbytes, void* stream) {
 }
 
 int fsg_reduce_minmax_f32(const float* x, size_t n, int32_t* mm, void* stream) {
-  if (!x || !mm || n == 0) return FSG_E_BADARG;
+  if (n == 0) return 0;  // nothing to do: no launch, pointers may be null
+  if (!x || !mm) return FSG_E_BADARG;
   size_t blocks = (n / 4 + 255) / 256;
   if (blocks < 1) blocks = 1;
   if (blocks > 2048) blocks = 2048;
@@ -111,7 +112,8 @@ int fsg_reduce_minmax_f32(const float* x, size_t n, int32_t* mm, void* stream) {
 }
 
 int fsg_scale_f32(const float* x, size_t n, const int32_t* mm, int mode, float* out, void* stream) {
-  if (!x || !mm || !out || n == 0 || mode < 0 || mode > 2) return FSG_E_BADARG;
+  if (n == 0) return 0;  // nothing to do: no launch, pointers may be null
+  if (!x || !mm || !out || mode < 0 || mode > 2) return FSG_E_BADARG;
   size_t blocks = (n + 255) / 256;
   if (blocks > 8192) blocks = 8192;
   hipLaunchKernelGGL(scale_kernel, dim3((unsigned)blocks), dim3(256), 0, fsg_stream(stream), x, n, mm, mode, out);

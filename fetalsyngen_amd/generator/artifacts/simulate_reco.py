@@ -168,7 +168,7 @@ class Scanner:
             par = torch.stack([yc, xc, c.view(-1), s.view(-1), A.view(-1), sx.view(-1), sy.view(-1)], 1).float()
             ids = torch.nonzero(idx).view(-1).to(torch.int32)
             dev = slices.device
-            K.slice_void_(slices.view(n, h, w), K._upload(ids, dev), K._upload(par.contiguous(), dev),
+            K.slice_void_(slices.view(n, h, w), ids, K._upload(par.contiguous(), dev),
                           K._upload(y, dev), K._upload(x, dev))
         return slices
 

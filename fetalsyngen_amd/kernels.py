@@ -789,13 +789,22 @@ def slice_noise_(slices, threshold, sigma, noise1=None, noise2=None, seed=0, str
 
 
 def slice_void_(slices, slice_ids, params, ylin, xlin):
-    """slices (n,h,w) modified in place on rows slice_ids (int32 device); params (nvoid,7) device fp32."""
-    _need_gpu(slices, slice_ids, params, ylin, xlin)
+    """slices (n,h,w) modified in place on rows slice_ids; params (nvoid,7) device fp32.  slice_ids: HOST int32 tensor of
+    distinct ids in [0, n) -- checked here, where they still are on the host: fsg_slice_void_f32 gives every void a workgroup
+    row of its own, so two voids naming one slice would race (and an id outside the stack would write outside it)."""
+    _need_gpu(slices, params, ylin, xlin)
+    _f32(slices, "slices")
     n, h, w = (int(v) for v in slices.shape)
+    if not isinstance(slice_ids, torch.Tensor) or slice_ids.is_cuda or slice_ids.dtype != torch.int32:
+        raise TypeError("slice_void_: slice_ids must be a host int32 tensor")
     nv = int(slice_ids.numel())
-    if slice_ids.dtype != torch.int32 or tuple(params.shape) != (nv, 7) or ylin.numel() != h or xlin.numel() != w:
+    if tuple(params.shape) != (nv, 7) or ylin.numel() != h or xlin.numel() != w:
         raise ValueError("slice_void_: bad argument shapes")
-    rc = _lib.load().fsg_slice_void_f32(_p(slices), h, w, _p(slice_ids), _p(params), nv, _p(ylin), _p(xlin), _stream(slices))
+    ids = slice_ids.reshape(-1).numpy()
+    if nv and (ids.min() < 0 or ids.max() >= n or np.unique(ids).size != nv):
+        raise ValueError("slice_void_: slice ids must be distinct and inside the stack")
+    d_ids = _upload(slice_ids.reshape(-1), slices.device)
+    rc = _lib.load().fsg_slice_void_f32(_p(slices), h, w, _p(d_ids), _p(params), nv, _p(ylin), _p(xlin), _stream(slices))
     _lib.check(rc, "fsg_slice_void_f32")
     return slices
 

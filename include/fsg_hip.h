@@ -243,6 +243,21 @@ int fsg_add_noise_f32(const float* x, size_t n, const float* noise, uint64_t see
                       float noise_std, float* out, void* stream);
 
 /* ---- K9/K10 stand-alone reductions / scaling --------------------------------------------------- */
+/* Empty inputs: in the entry points whose work is one flat range of `size_t n` elements, n == 0 is success with no launch
+ * and outputs are not touched (one exception: fsg_gmm_sample_u8x4_mm with mm given still resets mm to its identities).
+ * In fsg_artifacts.hip and fsg_reduce.hip the n == 0 test comes first, so pointers may then be null; fsg_randn_f32,
+ * fsg_label_stats_*, fsg_gamma_f32 and fsg_add_noise_f32 check their pointers first and refuse null ones even then.
+ * The calls that follow the rule are the K1/K5/K8/K9/K10 element-wise calls of this header
+ * (fsg_gmm_sample_*, fsg_randn_f32, fsg_label_stats_*, fsg_gamma_f32, fsg_add_noise_f32, fsg_reduce_minmax_f32,
+ * fsg_scale_f32, fsg_cast_f32_to_f16) and, of the artifact helpers, fsg_blend_f32, fsg_slice_noise_f32,
+ * fsg_nonzero_count_* / fsg_nonzero_select_*, fsg_compact_f32, fsg_ewise_f32, fsg_boundary_mask_f32,
+ * fsg_bernoulli_keep_f32 and fsg_scatter_const_f32.  Not covered, FSG_E_BADARG as before: every int dimension or count
+ * (D, H, W, k, nreq, nvoid, ...); the slice size `hw` of fsg_slice_sums_f32 (the sum of an empty slice would have to be
+ * written, which is a launch); fsg_copy_bytes (nbytes == 0); and the entry points that take n next to a plan or a table
+ * it must agree with -- fsg_sample_head_f32, fsg_sample_head_codes_f32, fsg_equalize_f32, fsg_seed_codes_build,
+ * fsg_seed_meta_pack -- where an empty volume can only be a caller's mistake.
+ * NaN: fminf / fmaxf ignore it, so mm is the min / max of the non-NaN elements; an all-NaN (or empty) input leaves the
+ * identities of fsg_minmax_init (+inf, -inf).  torch.min / max would return NaN; the generator never produces one here. */
 int fsg_reduce_minmax_f32(const float* x, size_t n, int32_t* mm, void* stream); /* mm[0]=min key, mm[1]=max key */
 /* mode 0: out = x / max;  mode 1: out = (x - min) / (max - min) (0*x if flat);  mode 2: (x-min)/(max-min)*255 */
 int fsg_scale_f32(const float* x, size_t n, const int32_t* mm, int mode, float* out, void* stream);
@@ -326,7 +341,9 @@ int fsg_blend_f32(const float* a, const float* b, const float* w, size_t n, int 
 int fsg_slice_noise_f32(float* slices, size_t n, float threshold, float sigma, const float* noise1, const float* noise2,
                         uint64_t seed, uint64_t stream_id, void* stream);
 /* Scanner.signal_void (simulate_reco.py:258-298), in place on the nvoid slices slice_ids[t]:
- * s *= 1 - A exp(sx x'^2 + sy y'^2); params (nvoid,7) = {yc, xc, cos, sin, A, sx, sy}; ylin (h), xlin (w). */
+ * s *= 1 - A exp(sx x'^2 + sy y'^2); params (nvoid,7) = {yc, xc, cos, sin, A, sx, sy}; ylin (h), xlin (w).
+ * slice_ids must be DISTINCT and inside the stack: every void has a workgroup row of its own, two voids naming one slice
+ * race, and the ids are on the device, where this call cannot look at them.  kernels.slice_void_ checks them on the host. */
 int fsg_slice_void_f32(float* slices, int h, int w, const int32_t* slice_ids, const float* params, int nvoid,
                        const float* ylin, const float* xlin, void* stream);
 /* sums[i] = sum of slice i (simulate_reco.py:409), deterministic. */
@@ -363,7 +380,9 @@ int fsg_dist_pass_f32(const float* src, float* dst, int n0, int n1, int n2, int 
                       void* stream);
 /* SimulatedBoundaries' fuzzy mask (augmentation/artifacts.py:565-604) fused: k = clamp(rint(p n_dilate - 1), 0) with
  * p = mog where mask_modif added voxels to mask (0 elsewhere); m = mask_modif * (dist <= max(k-1, 0)), dist = city-block
- * distance to mask; out = image * m (out/image may be NULL), mask_out = m (may be NULL). */
+ * distance to mask; out = image * m (out/image may be NULL), mask_out = m (may be NULL).
+ * p n_dilate - 1 is two float32 roundings, as in the reference (the library is built with -ffp-contract=off: no fused
+ * multiply-add), and rint rounds ties to even. */
 int fsg_boundary_mask_f32(const float* image, const float* mask, const float* mask_modif, const float* mog, const float* dist,
                           int n_dilate, size_t n, float* out, float* mask_out, void* stream);
 /* out = a * (u < p), u ~ U[0,1) from Philox(seed, stream_id) per element: device-RNG thinning of a voxel set. */
