@@ -21,7 +21,7 @@ import numpy as np
 import torch
 
 from ..generator.model import FetalSynthGen
-from ..utils.image_reading import NiftiReader
+from ..utils.image_reading import NiftiReader, ras_reorient_affine, read_nifti
 
 
 class SeedBank:
@@ -207,8 +207,146 @@ class FetalDataset:
         raise NotImplementedError("This method should be implemented in the child class.")
 
 
+def _compact_label(label: torch.Tensor) -> torch.Tensor:
+    """An integer label volume in the narrowest dtype the resample kernel reads (uint8 / int16), float32 as it is."""
+    if label.dtype in (torch.uint8, torch.int16, torch.float32):
+        return label
+    if label.is_floating_point():
+        return label.float()
+    lo, hi = (int(label.min()), int(label.max())) if label.numel() else (0, 0)
+    if 0 <= lo and hi <= 255:
+        return label.to(torch.uint8)
+    if -32768 <= lo and hi <= 32767:
+        return label.to(torch.int16)
+    raise ValueError(f"label values {lo}..{hi} do not fit the 16-bit labels the resample kernel reads")
+
+
+class InferenceTransform:
+    """The chain of the reference's configs/dataset/transforms/inference.yaml -- Orientation("RAS"), SignalFillEmpty,
+    CropForeground (image > 0), Spacing (image bilinear, label nearest), SpatialPad + CenterSpatialCrop to `size`,
+    ScaleIntensity(0, 1) -- as ONE resample on the device (`regrid.working_grid` + `kernels.affine_resample`) followed
+    by the min/max and scale kernels, and its inverse.
+
+    Callable on {"image", "label", "name", "affine"}: image / label (H,W,D) or (1,H,W,D), on any device; `affine` the
+    voxel->world affine of those arrays (absent: the identity).  Returns a new dict: image (1,*size) float32 in [0,1],
+    label (1,*size) in the dtype it came in, `affine` = the working grid's, and `native_shape`, `native_affine`, `M`
+    (3x4 float64, working voxel index -> native voxel coordinate) and `box` for the way back.  `inverse(data)` resamples
+    image (linear) and label (nearest) onto the native grid; intensities stay scaled, as with monai's ScaleIntensity.
+    Outputs are on the CPU unless `return_device`."""
+
+    def __init__(self, pixdim=(0.5, 0.5, 0.5), size=(256, 256, 256), crop_foreground=True, fill_empty=True, scale01=True,
+                 align="input", device="cuda:0", return_device=False):
+        self.pixdim = tuple(float(v) for v in np.broadcast_to(np.asarray(pixdim, dtype=np.float64), (3,)))
+        self.size = tuple(int(v) for v in np.broadcast_to(np.asarray(size), (3,)))
+        self.crop_foreground, self.fill_empty, self.scale01 = crop_foreground, fill_empty, scale01
+        self.align, self.device, self.return_device = align, device, return_device
+
+    def _volume(self, t, name):
+        if t is None:
+            return None, None
+        t = torch.as_tensor(t)
+        if t.dim() == 4 and t.shape[0] == 1:
+            t = t[0]
+        if t.dim() != 3:
+            raise ValueError(f"{name}: expected (H,W,D) or (1,H,W,D), got {tuple(t.shape)}")
+        return t, t.dtype
+
+    def _resample(self, data, M, box, out_shape):
+        from .. import kernels as K
+
+        image, _ = self._volume(data.get("image"), "image")
+        label, label_dtype = self._volume(data.get("label"), "label")
+        if image is not None:
+            image = image.to(self.device).float().contiguous()
+        if label is not None:
+            label = _compact_label(label.to(self.device)).contiguous()
+        out, lab = K.affine_resample(image, label, M, box, out_shape, nan_is_zero=self.fill_empty)
+        if lab is not None:
+            lab = lab.to(label_dtype)
+        return image, out, lab
+
+    def _finish(self, data, out, lab, **extra):
+        res = dict(data)
+        if out is not None:
+            res["image"] = (out if self.return_device else out.cpu()).unsqueeze(0)
+        if lab is not None:
+            res["label"] = (lab if self.return_device else lab.cpu()).unsqueeze(0)
+        res.update(extra)
+        return res
+
+    def __call__(self, data: dict) -> dict:
+        from .. import kernels as K
+        from .. import regrid as R
+
+        ref, _ = self._volume(data.get("image") if data.get("image") is not None else data.get("label"), "image")
+        if ref is None:
+            raise ValueError("need an image or a label")
+        shape = tuple(int(n) for n in ref.shape)
+        affine = np.asarray(data.get("affine", np.eye(4)), dtype=np.float64)
+        box = None
+        if self.crop_foreground and data.get("image") is not None:
+            box = R.foreground_box(self._volume(data["image"], "image")[0].to(self.device).float().contiguous())
+        affine_out, M, box = R.working_grid(shape, affine, self.pixdim, self.size, self.align, box)
+        _src, out, lab = self._resample(data, M, box, self.size)
+        if out is not None and self.scale01:
+            out = K.scale(out, K.reduce_minmax(out), mode=1)
+        return self._finish(data, out, lab, affine=affine_out, native_shape=shape, native_affine=affine, M=M,
+                            box=[int(v) for v in box])
+
+    def inverse(self, data: dict) -> dict:
+        from .. import regrid as R
+
+        for key in ("native_shape", "native_affine", "affine"):
+            if key not in data:
+                raise KeyError(f"inverse needs the {key!r} this transform recorded")
+        shape = tuple(int(n) for n in data["native_shape"])
+        M, box = R.inverse_map(shape, data["native_affine"], data["affine"], self.size)
+        _src, out, lab = self._resample(data, M, box, shape)
+        res = self._finish(data, out, lab, affine=np.asarray(data["native_affine"], dtype=np.float64))
+        for key in ("native_shape", "native_affine", "M", "box"):
+            res.pop(key, None)
+        return res
+
+
+class FetalTestDataset(FetalDataset):
+    """Mirror of `fetalsyngen.data.datasets.FetalTestDataset` (reference datasets.py:106-186): loads image and
+    segmentation of a subject for validation / inference.  `transforms`: any callable on the data dict with an optional
+    `.inverse` (the reference passes a monai Compose; `InferenceTransform` is the device-side equivalent of its
+    inference.yaml).  None returns the raw volumes, as the reference does; that path needs no GPU.  The dict additionally
+    carries `affine`, the voxel->world affine of the RAS-oriented arrays (the reference's MetaTensors carry theirs)."""
+
+    def __init__(self, bids_path: str, sub_list: list[str] | None, transforms=None):
+        super().__init__(bids_path, sub_list)
+        self.transforms = transforms
+
+    def _load_data(self, idx):
+        image = self.loader(self.img_paths[idx])
+        segm = self.loader(self.segm_paths[idx])
+        raw, affine, _ = read_nifti(self.img_paths[idx])
+        if len(image.shape) == 3:
+            image = image.unsqueeze(0)
+            segm = segm.unsqueeze(0)
+        elif len(image.shape) != 4:
+            raise ValueError(f"Expected 3D or 4D image, got {len(image.shape)}D image.")
+        name = self._sub_ses_string(*self.sub_ses[idx])
+        return {"image": image, "label": segm.long(), "name": name, "affine": ras_reorient_affine(affine, raw.shape[:3])}
+
+    def __getitem__(self, idx) -> dict:
+        data = self._load_data(idx)
+        if self.transforms:
+            data = self.transforms(data)
+        data["label"] = data["label"].long()
+        return data
+
+    def reverse_transform(self, data: dict) -> dict:
+        if self.transforms:
+            data = self.transforms.inverse(data)
+        return data
+
+
 class FetalSynthDataset(FetalDataset):
     seeds_from_images = None  # subclasses that build themselves without this constructor read seeds from what they were given
+    regrid = None             # ... and their volumes are on the working grid already
 
     def __init__(
         self,
@@ -223,6 +361,7 @@ class FetalSynthDataset(FetalDataset):
         cache_bytes: int | None = None,
         base_seed: int | None = None,
         seeds_from_images: int | None = None,
+        regrid=None,
     ):
         """`cache_bytes`: HBM budget of the decoded-label cache (`LabelCache`; None = half of the free HBM).
         `base_seed`: None keeps the reference's behaviour (`__getitem__` draws from the global generators as they stand);
@@ -232,7 +371,12 @@ class FetalSynthDataset(FetalDataset):
         `seeds_from_images`: None keeps the reference's behaviour (seeds come from the files under `seed_path`).  An integer,
         with `seed_path=None`: a subject's seed volumes for 1..`seeds_from_images` subclasses are generated on the device from
         its T2w + dseg on first use (`seedgen.generate_seeds`, key `seedgen.subject_key(base_seed, idx)`) and cached like
-        file-loaded ones."""
+        file-loaded ones.
+        `regrid`: None keeps today's behaviour (the files are on the working grid already).  `(pixdim, size)`: the T2w and
+        dseg of a subject are regridded on load (`regrid.working_grid` with the file's affine, one `affine_resample`),
+        before seed generation and the label cache see them; excludes `seed_path`, whose files are on the old grid."""
+        if regrid is not None and seed_path is not None:
+            raise ValueError("regrid and seed_path exclude each other: seed files are on the grid the volumes had before")
         if seed_path is not None and seeds_from_images is not None:
             raise ValueError("seed_path and seeds_from_images exclude each other: seeds are read from files or generated, not both")
         super().__init__(bids_path, sub_list)
@@ -245,6 +389,11 @@ class FetalSynthDataset(FetalDataset):
         self.cache_on_device = cache_on_device
         self.return_device = return_device
         self.base_seed, self.epoch = base_seed, 0
+        self.regrid = None
+        if regrid is not None:
+            pixdim, size = regrid
+            self.regrid = (tuple(float(v) for v in np.broadcast_to(np.asarray(pixdim, dtype=np.float64), (3,))),
+                           tuple(int(v) for v in np.broadcast_to(np.asarray(size), (3,))))
         self._labels = LabelCache(generator.device, cache_bytes)
         if not self.image_as_intensity and isinstance(self.seed_path, Path):
             if not self.seed_path.exists():
@@ -272,6 +421,21 @@ class FetalSynthDataset(FetalDataset):
     def __getstate__(self):
         return dict(self.__dict__)  # LabelCache / FetalSynthGen / SeedBank drop their process-local state themselves
 
+    def _regridded(self, idx):
+        """(float32 device image, float32 device segmentation) of subject `idx` on the working grid of `self.regrid`."""
+        from .. import kernels as K
+        from .. import regrid as R
+
+        img, affine, _ = read_nifti(self.img_paths[idx])
+        seg, _seg_affine, _ = read_nifti(self.segm_paths[idx])
+        if img.shape != seg.shape or img.ndim != 3:
+            raise ValueError(f"{self.img_paths[idx]}: image {img.shape} and segmentation {seg.shape} must be 3-D and of one shape")
+        dev = self.generator.device
+        _affine_out, M, box = R.working_grid(img.shape, affine, self.regrid[0], self.regrid[1])
+        image = torch.from_numpy(np.ascontiguousarray(img, dtype=np.float32)).to(dev)
+        label = torch.from_numpy(np.ascontiguousarray(seg, dtype=np.float32)).to(dev)
+        return K.affine_resample(image, label, M, box, self.regrid[1])
+
     def _subject(self, idx):
         """(bank | None, float32 device segmentation, uint8 twin | None) of subject `idx` through the LRU."""
         name = self._sub_ses_idx(idx)
@@ -282,12 +446,18 @@ class FetalSynthDataset(FetalDataset):
                 vols = {n: {m: self.loader(p).numpy() for m, p in d.items()} for n, d in self.seed_paths[name].items()}
                 bank = SeedBank(vols, self.generator.device)
                 nbytes += bank.nbytes
-            host = self.loader(self.segm_paths[idx]).float()
-            dev = host.to(self.generator.device)
+            if self.regrid is not None:
+                image, dev = self._regridded(idx)
+                host = dev.cpu()
+            else:
+                image = None
+                host = self.loader(self.segm_paths[idx]).float()
+                dev = host.to(self.generator.device)
             if self.seeds_from_images is not None and not self.image_as_intensity:
                 from .. import seedgen
 
-                image = self.loader(self.img_paths[idx]).float().to(self.generator.device)
+                if image is None:
+                    image = self.loader(self.img_paths[idx]).float().to(self.generator.device)
                 bank = SeedBank(seedgen.generate_seeds(image, dev, self.seeds_from_images, self.seeds_annotation,
                                                        key=seedgen.subject_key(self.base_seed, idx)), self.generator.device)
                 nbytes += bank.nbytes
@@ -311,7 +481,7 @@ class FetalSynthDataset(FetalDataset):
 
     def _segmentation(self, idx):
         if not self.cache_on_device:
-            return self.loader(self.segm_paths[idx])
+            return self._regridded(idx)[1] if self.regrid is not None else self.loader(self.segm_paths[idx])
         return self._subject(idx)[1]
 
     def _segmentation_u8(self, idx):
@@ -321,7 +491,9 @@ class FetalSynthDataset(FetalDataset):
         return hit[2] if hit is not None else None
 
     def sample(self, idx, genparams: dict = {}):
-        image = self.loader(self.img_paths[idx]).float() if self.load_image else None
+        image = None
+        if self.load_image:
+            image = self._regridded(idx)[0] if self.regrid is not None else self.loader(self.img_paths[idx]).float()
         segm = self._segmentation(idx)
         name = self._sub_ses_idx(idx)
         seeds = None

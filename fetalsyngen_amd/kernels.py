@@ -993,3 +993,46 @@ def scatter_ones(shape, flat_idx, device):
         _lib.check(_lib.load().fsg_scatter_const_f32(_p(out), out.numel(), _p(flat_idx.contiguous()), int(flat_idx.numel()),
                                                      1.0, _stream(out)), "fsg_scatter_const_f32")
     return out
+
+
+# ---- regridding of real volumes (fsg_regrid.hip) -------------------------------------------------------
+_LABEL_DTYPES = {torch.uint8: _lib.LABEL_U8, torch.int16: _lib.LABEL_I16, torch.float32: _lib.LABEL_F32}
+
+
+def affine_resample(image, label, M, box, out_shape, fill=0.0, fill_label=0, nan_is_zero=True):
+    """`fsg_affine_resample`: image (float32, trilinear) and / or label (uint8 / int16 / float32, nearest voxel) of one
+    source shape through the 3x4 map `M` (output voxel index -> source voxel coordinate, rounded to float32 here) with the
+    inclusive source index `box` as the inside region -> (image | None, label | None) of `out_shape`."""
+    _need_gpu(image, label)
+    if image is None and label is None:
+        raise ValueError("give an image, a label volume or both")
+    ref = image if image is not None else label
+    s0, s1, s2 = _dims3(ref)
+    if image is not None:
+        _f32(image, "image")
+    code = 0
+    if label is not None:
+        if label.dtype not in _LABEL_DTYPES:
+            raise TypeError(f"label must be uint8, int16 or float32, got {label.dtype}")
+        if label.device != ref.device or tuple(label.shape) != (s0, s1, s2):
+            raise ValueError("image and label must share device and shape")
+        code = _LABEL_DTYPES[label.dtype]
+    Mh = np.ascontiguousarray(np.asarray(M, dtype=np.float64).reshape(3, 4), dtype=np.float32)
+    bh = np.ascontiguousarray(np.asarray(box).reshape(6), dtype=np.int32)
+    d0, d1, d2 = (int(v) for v in out_shape)
+    out = torch.empty((d0, d1, d2), dtype=F32, device=ref.device) if image is not None else None
+    out_lab = torch.empty((d0, d1, d2), dtype=label.dtype, device=ref.device) if label is not None else None
+    _lib.check(_lib.load().fsg_affine_resample(_p(image), _p(label), code, s0, s1, s2, Mh.ctypes.data_as(C.POINTER(C.c_float)),
+                                               bh.ctypes.data_as(C.POINTER(C.c_int32)), d0, d1, d2, _p(out), _p(out_lab),
+                                               float(fill), float(fill_label), 1 if nan_is_zero else 0, _stream(ref)),
+               "fsg_affine_resample")
+    return out, out_lab
+
+
+def bbox_gt(v, threshold: float = 0.0) -> torch.Tensor:
+    """`fsg_bbox_gt_f32`: device int32[6] = lo0,hi0,lo1,hi1,lo2,hi2 of `v > threshold`; empty set: lo = n, hi = -1."""
+    _need_gpu(v)
+    n0, n1, n2 = _dims3(_f32(v))
+    box = torch.empty(6, dtype=torch.int32, device=v.device)
+    _lib.check(_lib.load().fsg_bbox_gt_f32(_p(v), n0, n1, n2, float(threshold), _p(box), _stream(v)), "fsg_bbox_gt_f32")
+    return box

@@ -158,6 +158,23 @@ def ras_reorient(arr: np.ndarray, affine: np.ndarray):
     return np.ascontiguousarray(out.transpose(order))
 
 
+def ras_reorient_affine(affine: np.ndarray, shape) -> np.ndarray:
+    """The voxel->world affine of `ras_reorient(arr, affine)` for an array of spatial `shape`: the same world positions,
+    indexed by the flipped and permuted axes."""
+    affine = np.asarray(affine, dtype=np.float64)
+    ornt = io_orientation(affine)
+    flip = np.eye(4)
+    for in_ax in range(3):
+        if ornt[in_ax, 1] < 0:  # new index i' = n - 1 - i
+            flip[in_ax, in_ax] = -1.0
+            flip[in_ax, 3] = shape[in_ax] - 1
+    perm = np.zeros((4, 4))
+    perm[3, 3] = 1.0
+    for out_ax, in_ax in enumerate(int(v) for v in np.argsort(ornt[:, 0])):
+        perm[in_ax, out_ax] = 1.0
+    return affine @ flip @ perm
+
+
 class NiftiReader:
     """`reader(path) -> torch.Tensor` (x,y,z), oriented to RAS."""
 

@@ -725,6 +725,34 @@ int fsg_em1d_fit(const float* x, size_t nx, int njobs, const int64_t* jobs_host,
 int fsg_seed_assign(const float* x, size_t nx, const int32_t* packed_idx, int njobs, const int64_t* jobs_host, int nwin,
                     const int64_t* wins_host, const double* params, void* work, size_t work_bytes, void* stream);
 
+/* ---------------------------------------------------------------------------------------------------------------------
+ * Regridding of real volumes (fsg_regrid.hip): what scripts/resample.py and the transforms of data/datasets.py:106-186
+ * (FetalTestDataset; transforms/inference.yaml) do on the host with monai -- spacing change, RAS reorientation, foreground
+ * crop, centre crop and zero pad, and their inverses -- as ONE resample through a composed voxel-to-voxel affine.
+ *
+ * For every output voxel (i,j,k) of (d0,d1,d2): p = M (i,j,k,1), M_host = 12 HOST floats, row-major 3x4, output index ->
+ * source voxel coordinate, evaluated in float32 as (m0 i + m1 j) + m2 k + m3 with separate multiplies and adds from the
+ * voxel's index (never accumulated): exact whenever every product and partial sum is representable, within 2^-13 of the
+ * float64 value for extents <= 512.  box_host = 6 HOST int32 lo0,hi0,lo1,hi1,lo2,hi2: the inclusive source index box that
+ * counts as inside.  A voxel is inside iff lo_a - 0.5 <= p_a <= hi_a + 0.5 on all axes; outside voxels receive fill /
+ * fill_label (converted to the label dtype).  Inside, p is clamped to [lo_a, hi_a] (border replication within the box) and
+ *   out       = trilinear(src): f = floor(p), upper neighbour clamped to hi_a, weights 1-w and w, z then y then x,
+ *               separate multiplies and adds; nan_is_zero != 0: a NaN source voxel reads as 0;
+ *   out_label = src_label at rint(p) (ties to even), copied; label_dtype = FSG_LABEL_* of BOTH label volumes.
+ * Either pair (src, out) / (src_label, out_label) may be NULL, not both.  One launch, no coordinate volumes.
+ * FSG_E_BADARG: a pair given by half, in place, a non-positive extent, a box that is empty or leaves the source, a
+ * non-finite entry of M, an unknown label_dtype; FSG_E_TOOBIG: an extent above 1024. */
+#define FSG_LABEL_U8 0
+#define FSG_LABEL_I16 1
+#define FSG_LABEL_F32 2
+int fsg_affine_resample(const float* src, const void* src_label, int label_dtype, int s0, int s1, int s2, const float* M_host,
+                        const int32_t* box_host, int d0, int d1, int d2, float* out, void* out_label, float fill,
+                        float fill_label, int nan_is_zero, void* stream);
+/* box6_dev (DEVICE, 6 int32) = lo0,hi0,lo1,hi1,lo2,hi2 of the voxels with v > thr (NaN compares false); an empty set gives
+ * lo = n, hi = -1 on every axis.  Per-workgroup reduction, then integer atomicMin / atomicMax: independent of the order.
+ * Two launches (the reset of the six words, the reduction).  What CropForeground's select_fn = (x > 0) computes. */
+int fsg_bbox_gt_f32(const float* v, int n0, int n1, int n2, float thr, int32_t* box6_dev, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
