@@ -313,10 +313,11 @@ __device__ __forceinline__ int xcd_tile(int b, int nb) {
 }
 
 // fsg_warp_lean.hip: the lean fused warp (-> FSG_E_ALIGN when the configuration is outside its domain).
-// label_in_bytes / label_out_bytes: 4 = float32, 1 = uint8.
+// label_in_bytes / label_out_bytes: 4 = float32, 1 = uint8.  src_img -> out_img: an optional second trilinear source at src_lin's
+// positions, no epilogue (needs src_lin; FSG_E_BADARG, nothing launched, when only one of the two is given).
 int fsg_launch_warp_lean(const FsgDeformK& D, const EpiK& E, const int32_t* mm6, const float* src_lin, float* out_lin,
                          const void* src_nn, void* out_nn, int label_in_bytes, int label_out_bytes, bool fast,
-                         void* stream);
+                         void* stream, const float* src_img = nullptr, float* out_img = nullptr);
 
 // launch geometry: x = 64 lanes along z, y = 4 rows along y; grid (z chunks, y chunks, x)
 static inline dim3 fsg_block3() { return dim3(64, 4, 1); }

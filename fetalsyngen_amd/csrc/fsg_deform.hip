@@ -1031,6 +1031,15 @@ extern "C" int fsg_internal_floormin_rest_ride(const fsg_deform* d, int32_t* mm3
   FSG_RETURN_LAUNCH();
 }
 
+// the one-launch head of a sample whose intensities are given (fsg_sample_image::prior_in): the rows and faces jobs, no GMM job
+extern "C" int fsg_internal_head_no_gmm(size_t n, const fsg_deform* d, const fsg_epilogue* epi, float* rows, int row_stride,
+                                        int32_t* mm3, void* stream) {
+  if (n == 0 || !mm3) return FSG_E_BADARG;
+  HeadGmm G{};  // G.out == nullptr: no workgroup is launched for the GMM job
+  G.n = n;
+  return launch_sample_head(G, n, d, epi, rows, row_stride, mm3, stream);
+}
+
 int fsg_sample_head_f32(const uint8_t* l0, const uint8_t* l1, const uint8_t* l2, const uint8_t* l3, size_t n,
                         const float* mus, const float* sigmas, int ntab, const float* noise, uint64_t seed,
                         uint64_t stream_id, float* out, const fsg_deform* d, const fsg_epilogue* epi, float* rows,
@@ -1076,6 +1085,7 @@ static int launch_sample_head(const HeadGmm& G, size_t n, const fsg_deform* d, c
   int nfaces = (faces + 255) / 256;
   if (nfaces > 1024) nfaces = 1024;
   size_t ngmm = ((n + 3) / 4 + 255) / 256;
+  if (!G.out) ngmm = 0;  // fsg_internal_head_no_gmm
   if (ngmm > 4096) ngmm = 4096;  // 4 groups per thread: 33.8 us (8 192: 34.8, 16 384: 39.0); codes mode, 2 x 8 voxels per thread: 30.5 us
                                  // (1 024: 34.7, 2 048: 37.0, 8 192: 33.6)
   if (nrows > 1000000) return FSG_E_TOOBIG;
@@ -1120,6 +1130,31 @@ int fsg_warp_f32_u8_to_f32(const fsg_deform* d, const int32_t* mm6, const float*
   // served by the lean kernel alone (the uint8 -> uint8 case reaches it through launch_warp)
   return fsg_launch_warp_lean(D, E, mm6, src_lin, out_lin, src_nn, out_nn, 1, 4, !(g_tuning_flags & FSG_TUNE_PRECISE_MATH),
                               stream);
+}
+
+int fsg_warp_dual_f32(const fsg_deform* d, const int32_t* mm6, const float* src_lin, float* out_lin, const float* src_img,
+                      float* out_img, size_t img_voxels, const void* src_nn, void* out_nn, int label_dtype_in, int label_dtype_out,
+                      const fsg_epilogue* epi, void* stream) {
+  FsgDeformK D;
+  int rc = fsg_fill_deform(d, D);
+  if (rc) return rc;
+  if (!mm6 || !src_lin || !out_lin || src_lin == out_lin) return FSG_E_BADARG;
+  if ((src_img == nullptr) != (out_img == nullptr)) return FSG_E_BADARG;
+  if (src_img && (img_voxels != (size_t)D.n0 * D.n1 * D.n2 || out_img == src_img || out_img == src_lin || out_img == out_lin ||
+                  out_lin == src_img))  // an output over a source other lanes still gather from
+    return FSG_E_BADARG;
+  if ((src_nn == nullptr) != (out_nn == nullptr)) return FSG_E_BADARG;
+  const int lin = label_dtype_in == FSG_LABEL_F32 ? 4 : label_dtype_in == FSG_LABEL_U8 ? 1 : 0;
+  const int lout = label_dtype_out == FSG_LABEL_F32 ? 4 : label_dtype_out == FSG_LABEL_U8 ? 1 : 0;
+  if (src_nn && (!lin || !lout || (lin == 4 && lout == 1))) return FSG_E_BADARG;
+  EpiK E;
+  rc = fill_epilogue(epi, E);
+  if (rc) return rc;
+  const int need = (D.field ? 3 * D.f2 : 0) + (E.bias ? E.b2 : 0);
+  if (D.rows && D.row_stride < need) return FSG_E_BADARG;
+  if (g_tuning_flags & (FSG_TUNE_GENERIC_WARP | FSG_TUNE_NO_PATCH | FSG_TUNE_NO_LEAN)) return FSG_E_ALIGN;
+  return fsg_launch_warp_lean(D, E, mm6, src_lin, out_lin, src_nn, out_nn, src_nn ? lin : 4, src_nn ? lout : 4,
+                              !(g_tuning_flags & FSG_TUNE_PRECISE_MATH), stream, src_img, out_img);
 }
 
 int fsg_interp3d_f32(const float* src, int sx, int sy, int sz, const float* ii, const float* jj, const float* kk,

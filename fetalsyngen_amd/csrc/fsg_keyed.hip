@@ -304,11 +304,16 @@ int fsg_keyed_sample_run(void* ctx, const int64_t* iv, int niv, fsg_keyed_draws*
   fsg_sample_plan q;
   std::memset(&q, 0, sizeof q);
   for (int a = 0; a < 3; ++a) q.shape[a] = c.shape[a];
-  for (int m = 0; m < c.meta_labels; ++m) {
+  fsg_sample_image im;
+  im.prior_in = (const float*)(uintptr_t)iv[FSG_KEYED_I_PRIOR_IN];  // given intensities: no seed volume is read
+  im.image_in = (const float*)(uintptr_t)iv[FSG_KEYED_I_IMAGE_IN];
+  im.image_out = (float*)(uintptr_t)iv[FSG_KEYED_I_IMAGE_OUT];
+  if (im.image_in && !im.image_out) return FSG_E_BADARG;
+  for (int m = 0; m < c.meta_labels && !im.prior_in; ++m) {
     q.label_parts[m] = (const uint8_t*)(uintptr_t)iv[FSG_KEYED_I_BANK + 4 * (d.subclusters[m] - c.min_subclusters) + m];
     if (!q.label_parts[m]) return FSG_E_BADARG;
   }
-  if (iv[FSG_KEYED_I_CODES] && iv[FSG_KEYED_I_CODE_TUPLES]) {  // the subject's code volume: selection = one byte of a tuple per meta label
+  if (!im.prior_in && iv[FSG_KEYED_I_CODES] && iv[FSG_KEYED_I_CODE_TUPLES]) {  // the subject's code volume: selection = one byte of a tuple per meta label
     q.label_codes = (const uint16_t*)(uintptr_t)iv[FSG_KEYED_I_CODES];
     q.code_tuples = (const uint8_t*)(uintptr_t)iv[FSG_KEYED_I_CODE_TUPLES];
     q.code_ntuples = (int32_t)iv[FSG_KEYED_I_CODE_NTUPLES];
@@ -429,7 +434,7 @@ int fsg_keyed_sample_run(void* ctx, const int64_t* iv, int niv, fsg_keyed_draws*
     rc = launch_draw(*K, d, base, stream);
     if (rc) return rc;
   }
-  rc = fsg_sample_run(&q, stream);
+  rc = fsg_sample_run_image(&q, &im, stream);
   if (draws_out) draws_out->rode = rode;
   return rc;
 }

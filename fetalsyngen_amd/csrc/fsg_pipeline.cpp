@@ -11,6 +11,9 @@
 
 // look-ahead launches (fsg_deform.hip, fsg_zoom.hip): not part of the public header
 extern "C" int fsg_internal_floormin_rest_ride(const fsg_deform* d, int32_t* mm3, const void* drawk, unsigned draw_blocks, void* stream);
+// the one-launch head without its GMM job (fsg_deform.hip; fsg_sample_image::prior_in)
+extern "C" int fsg_internal_head_no_gmm(size_t n, const fsg_deform* d, const fsg_epilogue* epi, float* rows, int row_stride,
+                                        int32_t* mm3, void* stream);
 
 
 extern int g_tuning_flags;
@@ -29,12 +32,18 @@ extern "C" int fsg_pipeline_teardown(void) { return 0; }
     if (e_ != hipSuccess) return (int)e_;      \
   } while (0)
 
-extern "C" int fsg_sample_run(const fsg_sample_plan* p, void* stream) {
+extern "C" int fsg_sample_run(const fsg_sample_plan* p, void* stream) { return fsg_sample_run_image(p, nullptr, stream); }
+
+extern "C" int fsg_sample_run_image(const fsg_sample_plan* p, const fsg_sample_image* im, void* stream) {
   if (!p || !p->out || !p->ws0 || !p->ws1 || !p->mm8) return FSG_E_BADARG;
   const int n0 = p->shape[0], n1 = p->shape[1], n2 = p->shape[2];
   if (n0 <= 0 || n1 <= 0 || n2 <= 0) return FSG_E_BADARG;
   const size_t n = (size_t)n0 * n1 * n2;
   if (n > (size_t)0x7FFFFFFF) return FSG_E_TOOBIG;
+  const float* const image_in = im ? im->image_in : nullptr;
+  float* const image_out = im ? im->image_out : nullptr;
+  if (image_in && !image_out) return FSG_E_BADARG;
+  const float* const prior = im ? im->prior_in : nullptr;  // given intensities instead of the GMM draw
   hipStream_t st = (hipStream_t)stream;
   int rode = 0;  // look-ahead jobs that really went out (fsg_sample_plan::rode)
   if (p->rode) *p->rode = 0;
@@ -68,11 +77,13 @@ extern "C" int fsg_sample_run(const fsg_sample_plan* p, void* stream) {
     dh.rows = nullptr;
     dh.row_stride = 0;
     head_rc = FSG_E_ALIGN;
-    if (p->label_codes && p->code_tuples && !p->gmm_noise && !(g_tuning_flags & FSG_TUNE_NO_SEED_CODES))  // 6 instead of 8 B/voxel
+    if (prior)  // rows + faces; the GMM job has nothing to draw
+      head_rc = fsg_internal_head_no_gmm(n, &dh, &p->epi, p->ws_rows, p->row_stride, p->mm8, stream);
+    else if (p->label_codes && p->code_tuples && !p->gmm_noise && !(g_tuning_flags & FSG_TUNE_NO_SEED_CODES))  // 6 instead of 8 B/voxel
       head_rc = fsg_sample_head_codes_f32(p->label_codes, p->code_tuples, p->code_ntuples, p->code_stride, p->code_sel, n, p->mus,
                                           p->sigmas, p->ntab, p->gmm_seed, p->gmm_stream, p->ws0, &dh, &p->epi, p->ws_rows,
                                           p->row_stride, p->mm8, stream);
-    if (head_rc == FSG_E_ALIGN || head_rc == FSG_E_TOOBIG)  // no codes, or outside their domain: the four label volumes
+    if (!prior && (head_rc == FSG_E_ALIGN || head_rc == FSG_E_TOOBIG))  // no codes, or outside their domain: the four label volumes
       head_rc = fsg_sample_head_f32(p->label_parts[0], p->label_parts[1], p->label_parts[2], p->label_parts[3], n, p->mus,
                                     p->sigmas, p->ntab, p->gmm_noise, p->gmm_seed, p->gmm_stream, p->ws0, &dh, &p->epi,
                                     p->ws_rows, p->row_stride, p->mm8, stream);
@@ -82,13 +93,22 @@ extern "C" int fsg_sample_run(const fsg_sample_plan* p, void* stream) {
   if (head_rc != 0 && head_rc != FSG_E_TOOBIG && head_rc != FSG_E_ALIGN) return head_rc;
   // K1: GMM draw -> ws0; the same launch resets every min/max key of the sample (unless they arrived initialised):
   // [min x,y,z | zoom min] [zoom max | 3 unused]
-  if (!head_done)
+  if (!head_done && prior) {
+    if (!p->mm8_preset) FSG_TRY(fsg_minmax_init(p->mm8, 4, 4, stream));
+  } else if (!head_done)
     FSG_TRY(fsg_gmm_sample_u8x4_mm(p->label_parts[0], p->label_parts[1], p->label_parts[2], p->label_parts[3], n,
                                    p->mus, p->sigmas, p->ntab, p->gmm_noise, p->gmm_seed, p->gmm_stream, p->ws0,
                                    p->mm8_preset ? nullptr : p->mm8, 4, 4, stream));
-  if (!head_done) FSG_TRY(mark(FSG_ST_GMM));
-  float* cur = p->ws0;
-  float* other = p->ws1;
+  if (!head_done && !prior) FSG_TRY(mark(FSG_ST_GMM));
+  // `cur` holds the volume so far, `other` receives the next stage.  The prior is read-only: it starts as `cur` and leaves the
+  // rotation at the first stage that consumes it.
+  float* cur = prior ? const_cast<float*>(prior) : p->ws0;
+  float* other = prior ? p->ws0 : p->ws1;
+  auto rotate = [&]() {
+    float* t = cur;
+    cur = other;
+    other = t == prior ? p->ws1 : t;
+  };
 
   if (p->deform_active) {
     // K2/K3: coarse rows, floor(min) margins; K4(+K5): fused warp of the image and the labels -> ws1
@@ -125,27 +145,47 @@ extern "C" int fsg_sample_run(const fsg_sample_plan* p, void* stream) {
       FSG_TRY(mark(FSG_ST_FLOORMIN));
     }
     int rw = FSG_E_ALIGN;
-    if (p->seg_out_u8) {  // uint8 labels in and out (same values: labels are integers 0..255)
+    bool image_done = false;
+    if (image_in) {  // the real image in the same launch (same label sources as below); FSG_E_ALIGN: the two-launch form
+      if (p->seg_out_u8)
+        rw = fsg_warp_dual_f32(&d, p->mm8, cur, other, image_in, image_out, n, p->seg_in_u8, p->seg_out_u8, FSG_LABEL_U8,
+                               FSG_LABEL_U8, &p->epi, stream);
+      else if (p->seg_in_u8)
+        rw = fsg_warp_dual_f32(&d, p->mm8, cur, other, image_in, image_out, n, p->seg_in_u8, p->seg_out, FSG_LABEL_U8,
+                               FSG_LABEL_F32, &p->epi, stream);
+      else
+        rw = fsg_warp_dual_f32(&d, p->mm8, cur, other, image_in, image_out, n, p->seg_in, p->seg_out, FSG_LABEL_F32,
+                               FSG_LABEL_F32, &p->epi, stream);
+      image_done = rw == 0;
+    }
+    if (image_done) {
+    } else if (p->seg_out_u8) {  // uint8 labels in and out (same values: labels are integers 0..255)
       rw = fsg_warp_f32_u8(&d, p->mm8, cur, other, p->seg_in_u8, p->seg_out_u8, &p->epi, stream);
     } else {
+      rw = FSG_E_ALIGN;
       if (p->seg_in_u8)  // uint8 copy of the labels: 1 B/voxel gathered instead of 4 (same output)
         rw = fsg_warp_f32_u8_to_f32(&d, p->mm8, cur, other, p->seg_in_u8, p->seg_out, &p->epi, stream);
       if (rw == FSG_E_ALIGN) rw = fsg_warp_f32(&d, p->mm8, cur, other, p->seg_in, p->seg_out, &p->epi, stream);
     }
     FSG_TRY(rw);
     FSG_TRY(mark(FSG_ST_WARP));
-    float* t = cur; cur = other; other = t;
+    if (image_in && !image_done) {
+      const fsg_epilogue none = {};
+      FSG_TRY(fsg_warp_f32(&d, p->mm8, image_in, image_out, nullptr, nullptr, &none, stream));
+      FSG_TRY(mark(FSG_ST_WARP));
+    }
+    rotate();
   } else {
     if (has_gamma) {
       FSG_TRY(fsg_gamma_f32(cur, n, p->epi.gamma, other, stream));
       FSG_TRY(mark(FSG_ST_POINTWISE));
-      float* t = cur; cur = other; other = t;
+      rotate();
     }
     if (has_bias) {
       FSG_TRY(fsg_bias_mul_f32(cur, n0, n1, n2, p->epi.bias, p->epi.bias_dims[0], p->epi.bias_dims[1],
                                p->epi.bias_dims[2], p->epi.bx, p->epi.by, p->epi.bz, other, stream));
       FSG_TRY(mark(FSG_ST_POINTWISE));
-      float* t = cur; cur = other; other = t;
+      rotate();
     }
   }
 
@@ -177,7 +217,7 @@ extern "C" int fsg_sample_run(const fsg_sample_plan* p, void* stream) {
                                            stream);
         if (rf == 0) {
           FSG_TRY(mark(FSG_ST_BLUR_YZ));
-          float* t = cur; cur = other; other = t;
+          rotate();
           break;
         }
         if (rf != FSG_E_ALIGN) return rf;
@@ -186,7 +226,7 @@ extern "C" int fsg_sample_run(const fsg_sample_plan* p, void* stream) {
       if (rc == FSG_E_ALIGN) return FSG_E_ALIGN;  // shape outside the tuned kernels: stage-by-stage path
       FSG_TRY(rc);
       FSG_TRY(mark(FSG_ST_BLUR_X + axis));
-      float* t = cur; cur = other; other = t;
+      rotate();
     }
     if (p->ev_blur_end) FSG_HIP(hipEventRecord((hipEvent_t)p->ev_blur_end, st));
     // K7+K8: resample + noise -> low
@@ -246,6 +286,7 @@ extern "C" int64_t fsg_sample_plan_layout(int which) {
     case 3: return (int64_t)offsetof(fsg_sample_plan, seg_in_u8);
     case 4: return (int64_t)offsetof(fsg_sample_plan, ws_seq);
     case 5: return (int64_t)offsetof(fsg_sample_plan, code_sel);
+    case FSG_SIZEOF_SAMPLE_IMAGE: return (int64_t)sizeof(fsg_sample_image);
     default: return -1;
   }
 }

@@ -54,11 +54,26 @@ __device__ __forceinline__ void lean_store_label(__amdgpu_buffer_rsrc_t r, unsig
 
 // ABL (diagnostic instantiations only, tools/kernel_bench.py --variant 8 / 9): 1 = every vector-memory access predicated off at run time (arithmetic and
 // LDS traffic only), 2 = trivial sampling positions (memory traffic and blends only).  0 in every product launch.
-template <typename ST, typename DT, bool HAS_LIN, bool HAS_NN, bool FAST, int KZ, int WI, int ABL = 0>
+// The second source's pointers as a kernel argument that is empty when there is none, so that the kernels without it keep
+// their argument block.
+template <bool HAS_IMG> struct LeanImg {};
+template <> struct LeanImg<true> { const float* src; float* out; };
+// What a pending step keeps for the second source, and nothing without one (an empty base: the step's state is what it was).
+template <bool HAS_IMG> struct LeanPendImg {};
+template <> struct LeanPendImg<true> { unsigned o; };  // byte offset of the (x0, y0, z0) corner, for the gathers in finish()
+
+// HAS_IMG (needs HAS_LIN): a second trilinear source, src_img -> out_img, sampled at the position (and with the weights and the
+// strict > 0 rule) the lane has for src_lin, stored without the gamma / bias epilogue -- the real image of a `load_image`
+// sample beside its synthetic channel.  Same operation sequence per output as a launch of its own, so the same bits.
+template <typename ST, typename DT, bool HAS_LIN, bool HAS_NN, bool FAST, int KZ, int WI, int ABL = 0, bool HAS_IMG = false>
 __global__ __launch_bounds__(1024, 8) void warp_lean_kernel(FsgDeformK D, const int32_t* __restrict__ mm6,
                                                          const float* __restrict__ src_lin, float* __restrict__ out_lin,
                                                          const ST* __restrict__ src_nn, DT* __restrict__ out_nn, EpiK E,
-                                                         int pace) {
+                                                         int pace, LeanImg<HAS_IMG> I) {
+  const float* __restrict__ src_img = nullptr;
+  float* __restrict__ out_img = nullptr;
+  if constexpr (HAS_IMG) { src_img = I.src; out_img = I.out; }
+  static_assert(!HAS_IMG || (HAS_LIN && ABL == 0), "the second source rides on the first one's positions");
   constexpr int RJ = 64 / KZ;  // rows (along j) per wave
   constexpr int WJ = 16 / WI;  // waves along j
   constexpr int PI = WI, PJ = WJ * RJ, NROW = PI * PJ;
@@ -107,6 +122,8 @@ __global__ __launch_bounds__(1024, 8) void warp_lean_kernel(FsgDeformK D, const 
       __builtin_amdgcn_make_buffer_rsrc((void*)src_nn, 0, HAS_NN ? nvox * (unsigned)sizeof(ST) : 0u, 0x00020000);
   const __amdgpu_buffer_rsrc_t r_onn =
       __builtin_amdgcn_make_buffer_rsrc((void*)out_nn, 0, HAS_NN ? nvox * (unsigned)sizeof(DT) : 0u, 0x00020000);
+  const __amdgpu_buffer_rsrc_t r_img = __builtin_amdgcn_make_buffer_rsrc((void*)src_img, 0, HAS_IMG ? nvox * 4u : 0u, 0x00020000);
+  const __amdgpu_buffer_rsrc_t r_oimg = __builtin_amdgcn_make_buffer_rsrc((void*)out_img, 0, HAS_IMG ? nvox * 4u : 0u, 0x00020000);
   // element offset of source voxel (x, y, z) = base + x * sxs + y * sy + z, the flip folded into base / sxs
   const int sy = D.n2;
   const int sx = D.n1 * D.n2;
@@ -123,7 +140,7 @@ __global__ __launch_bounds__(1024, 8) void warp_lean_kernel(FsgDeformK D, const 
   // The arithmetic is written on register PAIRS (f2v) wherever two results share their operation sequence -- (y, z) of
   // the affine map, the two z-neighbours of every blend -- so that it lands on v_pk_mul_f32 / v_pk_add_f32 with the pairs
   // where the loads put them (no v_mov / v_pk_mov shuffles); each half is the reference's own operation order.
-  struct Pend {
+  struct Pend : LeanPendImg<HAS_IMG> {
     f2v p00, p10, p01, p11;
     float bx;
     f2v byz;
@@ -181,6 +198,7 @@ __global__ __launch_bounds__(1024, 8) void warp_lean_kernel(FsgDeformK D, const 
         const float t = __builtin_bit_cast(float, (o & 0xFFFFu) | 0x3F800000u);
         P.p00 = f2v{t, t + 1.f}; P.p10 = f2v{t + 2.f, t}; P.p01 = f2v{t, t + 3.f}; P.p11 = f2v{t + 1.f, t};
       }
+      if constexpr (HAS_IMG) P.o = o;
     }
   };
   auto finish = [&](int kb, Pend& P) {
@@ -188,8 +206,32 @@ __global__ __launch_bounds__(1024, 8) void warp_lean_kernel(FsgDeformK D, const 
     const bool live = live_row && kk < D.n2;
     const unsigned oelem = orow + (unsigned)kk;
     if (HAS_LIN) {
+      // HAS_IMG: the second source's corners are gathered here, not in issue(): with both sources' corners of two steps in
+      // flight the kernel needs more than the 64 registers of 8 waves/SIMD and spills; this way they overlap the first
+      // source's blend and epilogue of the same step, and the next step's gathers are already out.  The general variant's
+      // OCML powf / expf take the registers themselves: there the second source is gathered, blended and stored first.
+      f2v q00, q10, q01, q11;
+      auto gather_img = [&]() {
+        if constexpr (HAS_IMG) {
+        q00 = __builtin_bit_cast(f2v, __builtin_amdgcn_raw_buffer_load_b64(r_img, P.o, 0, 0));
+        q10 = __builtin_bit_cast(f2v, __builtin_amdgcn_raw_buffer_load_b64(r_img, P.o + (unsigned)dxb, 0, 0));
+        q01 = __builtin_bit_cast(f2v, __builtin_amdgcn_raw_buffer_load_b64(r_img, P.o + (unsigned)oyb, 0, 0));
+        q11 = __builtin_bit_cast(f2v, __builtin_amdgcn_raw_buffer_load_b64(r_img, P.o + (unsigned)(dxb + oyb), 0, 0));
+        }
+      };
+      if (HAS_IMG && FAST) gather_img();
       const float bx = P.bx, ax = 1.f - bx;
       const f2v byz = P.byz, ayz = 1.f - byz;
+      auto blend_img = [&]() {  // the same blend on the second source's corners, stored as it is
+        const f2v dx0 = q00 * ax + q10 * bx;
+        const f2v dx1 = q01 * ax + q11 * bx;
+        const f2v dy = dx0 * ayz.x + dx1 * byz.x;
+        float d0z = dy.x * ayz.y;
+        asm("" : "+v"(d0z));
+        const float w = P.ok ? (d0z + dy.y * byz.y) : 0.f;
+        if (live) __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, w), r_oimg, oelem * 4u, 0, 0);
+      };
+      if (HAS_IMG && !FAST) { gather_img(); blend_img(); }
       const f2v cx0 = P.p00 * ax + P.p10 * bx;      // (c00, c01): the two z-neighbours at y0
       const f2v cx1 = P.p01 * ax + P.p11 * bx;      // (c10, c11): at y0 + 1
       const f2v cy = cx0 * ayz.x + cx1 * byz.x;     // (c0, c1)
@@ -208,6 +250,7 @@ __global__ __launch_bounds__(1024, 8) void warp_lean_kernel(FsgDeformK D, const 
       }
       if (live && (ABL != 1 || v == 1.2345e30f))
         __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), r_olin, oelem * 4u, 0, 0);
+      if (HAS_IMG && FAST) blend_img();
     }
     if (HAS_NN && live && (ABL != 1 || P.bx == 1.2345e30f)) lean_store_label(r_onn, oelem, (DT)P.lab);
   };
@@ -231,7 +274,7 @@ __global__ __launch_bounds__(1024, 8) void warp_lean_kernel(FsgDeformK D, const 
 
 template <typename ST, typename DT>
 int launch_lean(const FsgDeformK& D, const EpiK& E, const int32_t* mm6, const float* src_lin, float* out_lin,
-                const ST* src_nn, DT* out_nn, bool fast, hipStream_t st) {
+                const ST* src_nn, DT* out_nn, bool fast, hipStream_t st, const float* src_img = nullptr, float* out_img = nullptr) {
   constexpr int KZ = 32, WI = 8;
   constexpr int PI = WI, PJ = (16 / WI) * (64 / KZ);
   const dim3 grid((unsigned)(((D.n0 + PI - 1) / PI) * ((D.n1 + PJ - 1) / PJ))), block(1024);
@@ -243,21 +286,29 @@ int launch_lean(const FsgDeformK& D, const EpiK& E, const int32_t* mm6, const fl
   const int pace = g_lean_pace >= 0 ? g_lean_pace : (slope < 0.27f ? 2 : 1);
 #define FSG_LEAN(L, N, F) \
   hipLaunchKernelGGL((warp_lean_kernel<ST, DT, L, N, F, KZ, WI>), grid, block, 0, st, D, mm6, src_lin, out_lin, src_nn, out_nn, E, \
-                     pace)
+                     pace, LeanImg<false>{})
 #ifdef FSG_DIAG  // ablation instantiations (results are wrong; tools/kernel_bench.py --variant 8 / 9 on a -DFSG_DIAG build)
   if (src_lin && src_nn && fast && g_lean_ablate && sizeof(ST) == 4 && sizeof(DT) == 4) {
     if (g_lean_ablate == 1)
       hipLaunchKernelGGL((warp_lean_kernel<ST, DT, true, true, true, KZ, WI, 1>), grid, block, 0, st, D, mm6, src_lin, out_lin,
-                         src_nn, out_nn, E, pace);
+                         src_nn, out_nn, E, pace, LeanImg<false>{});
     else
       hipLaunchKernelGGL((warp_lean_kernel<ST, DT, true, true, true, KZ, WI, 2>), grid, block, 0, st, D, mm6, src_lin, out_lin,
-                         src_nn, out_nn, E, pace);
+                         src_nn, out_nn, E, pace, LeanImg<false>{});
     FSG_RETURN_LAUNCH();
   }
 #endif
-  if (src_lin && src_nn) { if (fast) FSG_LEAN(true, true, true); else FSG_LEAN(true, true, false); }
+#define FSG_LEAN_IMG(N, F) \
+  hipLaunchKernelGGL((warp_lean_kernel<ST, DT, true, N, F, KZ, WI, 0, true>), grid, block, 0, st, D, mm6, src_lin, out_lin, src_nn, \
+                     out_nn, E, pace, LeanImg<true>{src_img, out_img})
+  if (src_img) {  // the dual-source family (checked by the entry point: src_lin given, out_img given)
+    if (src_nn) { if (fast) FSG_LEAN_IMG(true, true); else FSG_LEAN_IMG(true, false); }
+    else        { if (fast) FSG_LEAN_IMG(false, true); else FSG_LEAN_IMG(false, false); }
+  }
+  else if (src_lin && src_nn) { if (fast) FSG_LEAN(true, true, true); else FSG_LEAN(true, true, false); }
   else if (src_lin)      { if (fast) FSG_LEAN(true, false, true); else FSG_LEAN(true, false, false); }
   else                   { FSG_LEAN(false, true, true); }
+#undef FSG_LEAN_IMG
 #undef FSG_LEAN
   FSG_RETURN_LAUNCH();
 }
@@ -266,7 +317,8 @@ int launch_lean(const FsgDeformK& D, const EpiK& E, const int32_t* mm6, const fl
 
 int fsg_launch_warp_lean(const FsgDeformK& D, const EpiK& E, const int32_t* mm6, const float* src_lin, float* out_lin,
                          const void* src_nn, void* out_nn, int label_in_bytes, int label_out_bytes, bool fast,
-                         void* stream) {
+                         void* stream, const float* src_img, float* out_img) {
+  if ((src_img == nullptr) != (out_img == nullptr) || (src_img && !src_lin)) return FSG_E_BADARG;
   const bool has_field = D.field != nullptr, has_bias = E.bias != nullptr;
   const int need = (has_field ? 3 * D.f2 : 0) + (has_bias ? E.b2 : 0);
   if (need > 0 && (!D.rows || D.row_stride < need)) return FSG_E_ALIGN;
@@ -275,12 +327,13 @@ int fsg_launch_warp_lean(const FsgDeformK& D, const EpiK& E, const int32_t* mm6,
   const long long plane = (long long)D.n1 * D.n2, nvox = plane * D.n0;
   if (plane >= (1ll << 22) || nvox >= (1ll << 30) || D.n0 >= (1 << 22)) return FSG_E_ALIGN;
   hipStream_t st = fsg_stream(stream);
-  if (!src_nn) return launch_lean<float, float>(D, E, mm6, src_lin, out_lin, nullptr, nullptr, fast, st);
+  if (!src_nn) return launch_lean<float, float>(D, E, mm6, src_lin, out_lin, nullptr, nullptr, fast, st, src_img, out_img);
   if (label_in_bytes == 4 && label_out_bytes == 4)
-    return launch_lean<float, float>(D, E, mm6, src_lin, out_lin, (const float*)src_nn, (float*)out_nn, fast, st);
+    return launch_lean<float, float>(D, E, mm6, src_lin, out_lin, (const float*)src_nn, (float*)out_nn, fast, st, src_img, out_img);
   if (label_in_bytes == 1 && label_out_bytes == 1)
-    return launch_lean<uint8_t, uint8_t>(D, E, mm6, src_lin, out_lin, (const uint8_t*)src_nn, (uint8_t*)out_nn, fast, st);
+    return launch_lean<uint8_t, uint8_t>(D, E, mm6, src_lin, out_lin, (const uint8_t*)src_nn, (uint8_t*)out_nn, fast, st, src_img,
+                                         out_img);
   if (label_in_bytes == 1 && label_out_bytes == 4)
-    return launch_lean<uint8_t, float>(D, E, mm6, src_lin, out_lin, (const uint8_t*)src_nn, (float*)out_nn, fast, st);
+    return launch_lean<uint8_t, float>(D, E, mm6, src_lin, out_lin, (const uint8_t*)src_nn, (float*)out_nn, fast, st, src_img, out_img);
   return FSG_E_BADARG;
 }

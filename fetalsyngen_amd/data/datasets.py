@@ -436,8 +436,17 @@ class FetalSynthDataset(FetalDataset):
         label = torch.from_numpy(np.ascontiguousarray(seg, dtype=np.float32)).to(dev)
         return K.affine_resample(image, label, M, box, self.regrid[1])
 
+    def _keyed_images(self) -> bool:
+        """Keyed mode with `load_image`: the subject's device image (and, without seeds, its intensity prior) are cached with
+        its labels, so that the sample takes the keyed single-call path.  The other modes load the image per sample as before."""
+        return bool(self.load_image and self.cache_on_device and self.generator._is_keyed())
+
+    def _has_seeds(self) -> bool:
+        return (self.seed_path is not None or self.seeds_from_images is not None) and not self.image_as_intensity
+
     def _subject(self, idx):
-        """(bank | None, float32 device segmentation, uint8 twin | None) of subject `idx` through the LRU."""
+        """(bank | None, float32 device segmentation, uint8 twin | None[, device image, prior | None]) of subject `idx` through
+        the LRU; the last two in keyed mode with `load_image` only (`_keyed_images`), counted against the byte budget."""
         name = self._sub_ses_idx(idx)
 
         def build():
@@ -468,6 +477,16 @@ class FetalSynthDataset(FetalDataset):
             if ok:
                 self.generator.register_label_twin(dev, twin)
             nbytes += dev.numel() * 4 + (dev.numel() if ok else 0)
+            if self._keyed_images():
+                if image is None:
+                    image = self.loader(self.img_paths[idx]).float().to(self.generator.device)
+                image, prior = image.contiguous(), None
+                nbytes += image.numel() * 4
+                if not self._has_seeds():  # the image is the intensity prior: a constant of the subject
+                    prior = self.generator._intensity_prior(image)
+                    self.generator.register_image_prior(image, prior)
+                    nbytes += prior.numel() * 4
+                return (bank, dev, twin, image, prior), nbytes
             return (bank, dev, twin), nbytes
 
         return self._labels.get(idx, build)
@@ -492,7 +511,9 @@ class FetalSynthDataset(FetalDataset):
 
     def sample(self, idx, genparams: dict = {}):
         image = None
-        if self.load_image:
+        if self._keyed_images():
+            image = self._subject(idx)[3]
+        elif self.load_image:
             image = self._regridded(idx)[0] if self.regrid is not None else self.loader(self.img_paths[idx]).float()
         segm = self._segmentation(idx)
         name = self._sub_ses_idx(idx)
@@ -525,33 +546,59 @@ class FetalSynthDataset(FetalDataset):
         return data_out, generation_params
 
     def sample_batch(self, indices, genparams_list=None, streams: int = 1):
-        """B subjects with one `FetalSynthGen.sample_batch` call (seeds-based generation, cached label volumes): what a
+        """B subjects with one `FetalSynthGen.sample_batch` call (cached label volumes): what a
         DataLoader with batch_size=B would collate from B `__getitem__` calls (reference data/datasets.py:310-325) --
         {"image": (B,1,H,W,D) float32 in [0,1], "label": (B,1,H,W,D) int64, "name": [B]} on the CPU, or on the device with
         uint8 labels when `return_device` -- and the list of B generation_params.  Same draws, same values as B
-        consecutive `sample` calls."""
-        if (self.load_image or self.image_as_intensity or (self.seed_path is None and self.seeds_from_images is None)
-                or not self.cache_on_device):
-            raise ValueError("sample_batch serves the seeds-based path with device-cached label volumes "
-                             "(load_image=False, image_as_intensity=False, cache_on_device=True)")
+        consecutive `sample` calls.
+        With `load_image` the batch also carries "real_image": the deformed images scaled to [0,1] as `sample` scales them,
+        (B,1,H,W,D) float32.  In keyed mode with a `base_seed` such a batch takes the keyed path, sample b under the key
+        `__getitem__(indices[b])` would announce, so it equals B `__getitem__` calls bit for bit."""
+        has_seeds = self._has_seeds()
+        if self.image_as_intensity and not self.load_image:
+            raise ValueError("If no seeds are passed, an image must be loaded to be used as intensity prior!")
+        if (not has_seeds and not self.load_image) or not self.cache_on_device:
+            raise ValueError("sample_batch serves device-cached subjects (cache_on_device=True) with seeds, an image "
+                             "(load_image=True), or both")
         indices = [int(i) for i in indices]
         names = [self._sub_ses_idx(i) for i in indices]
         t0 = time.time()
-        items = [(None, self._segmentation(i), self._seeds_for(n, i)) for i, n in zip(indices, names)]
-        out, seg, _imgs, params = self.generator.sample_batch(items, genparams_list, scale01=True, streams=streams,
-                                                              labels_u8=self.return_device)
+        keys = None
+        if self._keyed_images():
+            images = [self._subject(i)[3] for i in indices]
+            if self.base_seed is not None and genparams_list is None:
+                from .. import sharding
+
+                keys = [sharding.sample_key(self.base_seed, self.epoch * len(self) + i) for i in indices]
+        elif self.load_image:
+            images = [self._regridded(i)[0] if self.regrid is not None else self.loader(self.img_paths[i]).float() for i in indices]
+        else:
+            images = [None] * len(indices)
+        items = [(img, self._segmentation(i), self._seeds_for(n, i) if has_seeds else None)
+                 for img, i, n in zip(images, indices, names)]
+        out, seg, imgs, params = self.generator.sample_batch(items, genparams_list, scale01=True, streams=streams,
+                                                             labels_u8=self.return_device, keys=keys)
         if not torch.is_tensor(out):
             raise ValueError("sample_batch needs subjects of one shape")
+        real = None
+        if self.load_image:
+            from .. import kernels as K
+
+            real = torch.stack([K.scale(im.contiguous(), K.reduce_minmax(im.contiguous()), mode=1) for im in imgs]).unsqueeze(1)
         if self.return_device:
             image, label = out.unsqueeze(1), seg.unsqueeze(1)
         else:
             image, label = out.cpu().unsqueeze(1), seg.cpu().long().unsqueeze(1)
+            real = real.cpu() if real is not None else None
         dt = time.time() - t0
         gps = []
         for i, p_ in zip(indices, params):
             gps.append({"idx": i, "img_paths": str(self.img_paths[i]), "segm_paths": str(self.img_paths[i]),
                         "seeds": str(self.seed_path), **p_, "generation_time": dt / max(len(indices), 1)})
-        return {"image": image, "label": label, "name": names}, gps
+        batch = {"image": image, "label": label, "name": names}
+        if real is not None:
+            batch["real_image"] = real
+        return batch, gps
 
     def __getitem__(self, idx) -> dict:
         if self.base_seed is not None:

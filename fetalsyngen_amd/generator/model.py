@@ -49,6 +49,7 @@ _K_BLOCK, _K_WS0, _K_WS1, _K_WS_LOW, _K_WS_ROWS, _K_ROW_STRIDE = _KI.BLOCK, _KI.
 _K_SCALE01, _K_TRACE_EVENTS, _K_TRACE_IDS, _K_TRACE_CAP, _K_BANK = _KI.SCALE01, _KI.TRACE_EVENTS, _KI.TRACE_IDS, _KI.TRACE_CAP, _KI.BANK
 _K_EV_BLUR_BEGIN, _K_EV_BLUR_END, _K_CODES, _K_CODE_TUPLES = _KI.EV_BLUR_BEGIN, _KI.EV_BLUR_END, _KI.CODES, _KI.CODE_TUPLES
 _K_CODE_NTUPLES, _K_CODE_STRIDE, _K_FLAGS, _K_NEXT_KEY, _K_NEXT_BLOCK = _KI.CODE_NTUPLES, _KI.CODE_STRIDE, _KI.FLAGS, _KI.NEXT_KEY, _KI.NEXT_BLOCK
+_K_IMAGE_IN, _K_IMAGE_OUT, _K_PRIOR_IN = _KI.IMAGE_IN, _KI.IMAGE_OUT, _KI.PRIOR_IN
 _KF_BLOCK_FILLED, _KF_NEXT_NAMED = _KF.BLOCK_FILLED, _KF.NEXT_NAMED
 
 
@@ -147,7 +148,7 @@ class FetalSynthGen:
     # DataLoader pattern: `num_workers=2, multiprocessing_context="spawn"`, fetalsyngen/test_dl.py:17-24, docs/datasets.md:4-6)
     # carries none of it into the worker.
     _PROCESS_LOCAL = ("_ws", "_flat", "_twins", "_rs_dt", "_batch_streams", "blur_events", "_blur_tick", "_keyed",
-                      "stage_traces", "_pre")
+                      "stage_traces", "_pre", "_priors")
 
     def __getstate__(self):
         state = {k: v for k, v in self.__dict__.items() if k not in self._PROCESS_LOCAL}
@@ -250,6 +251,7 @@ class FetalSynthGen:
         (`_version`); it cannot notice a label volume rewritten through its raw pointer (another HIP library, the `fsg_*`
         entry points themselves) -- call this after such a write."""
         self.__dict__.pop("_twins", None)
+        self.__dict__.pop("_priors", None)
         for kc in (self.__dict__.get("_keyed") or {}).values():  # keyed mode: the subjects' pointer blocks and code volumes
             for ent in kc._subjects.values():
                 bank = ent.bank_ref()
@@ -294,6 +296,55 @@ class FetalSynthGen:
                     ent[2] = seg.to(torch.uint8)
                     cache["bytes"] += seg.numel()
         return ent[2]
+
+    # ---- per-subject constant of a real image: its intensity prior --------------------------------------------------------
+    def _prior_cache(self):
+        return self.__dict__.setdefault("_priors", {"by_id": {}, "bytes": 0})
+
+    def _prior_drop(self, key):
+        cache = self.__dict__.get("_priors")
+        ent = cache["by_id"].pop(key, None) if cache else None
+        if ent is not None and ent[3]:
+            cache["bytes"] -= ent[2].numel() * 4
+
+    def register_image_prior(self, image, prior):
+        """Hand over the intensity prior of the device image `image` (what `_intensity_prior(image)` returns) that the caller
+        already holds and accounts for -- the datasets do, per cached subject -- so that keyed samples do not recompute it."""
+        if prior.dtype != torch.float32 or prior.shape != image.shape or prior.device != image.device or not prior.is_contiguous():
+            raise ValueError("image prior must be a contiguous float32 tensor of the image's shape on its device")
+        key = id(image)
+        self._prior_drop(key)
+        self._prior_cache()["by_id"][key] = [weakref.ref(image, lambda _r, k=key, me=weakref.ref(self): me() and me()._prior_drop(k)),
+                                             image._version, prior, False]
+
+    def _image_prior(self, image):
+        """`_intensity_prior(image)` -- (x - min) / (max - min) * 255, a constant of the subject -- computed once per image
+        tensor OBJECT with the same two kernels, so the very bits the stage-wise path produces on every sample.  Cached through
+        a weak reference with the tensor's in-place version, like the label twins.  The priors have a byte count of their own,
+        held to the size `label_twin_budget_bytes` also gives the twins (so the two caches together may take twice that;
+        oldest prior dropped first; a prior that does not fit is computed per sample)."""
+        cache = self._prior_cache()
+        by_id = cache["by_id"]
+        key = id(image)
+        ent = by_id.get(key)
+        if ent is not None and ent[0]() is image and ent[1] == image._version:
+            return ent[2]
+        self._prior_drop(key)
+        prior = self._intensity_prior(image)
+        nbytes = prior.numel() * 4
+        while cache["bytes"] + nbytes > self.label_twin_budget_bytes:
+            victim = next((k for k, e in by_id.items() if e[3]), None)
+            if victim is None:
+                break
+            self._prior_drop(victim)
+        if cache["bytes"] + nbytes <= self.label_twin_budget_bytes:
+            if len(by_id) > 4096:
+                by_id.clear()
+                cache["bytes"] = 0
+            by_id[key] = [weakref.ref(image, lambda _r, k=key, me=weakref.ref(self): me() and me()._prior_drop(k)),
+                          image._version, prior, True]
+            cache["bytes"] += nbytes
+        return prior
 
     def _native_ok(self, c, labels_u8: bool = False) -> bool:
         """labels_u8: the caller wants uint8 labels -- the fused path then writes them itself and a caller-supplied uint8
@@ -798,14 +849,25 @@ class FetalSynthGen:
         return (self.rng or _rng.get_mode()) == "keyed"
 
     def _keyed_applies(self, image, segmentation, seeds, genparams, segmentation_u8, labels_u8) -> bool:
-        return (self.native_pipeline and image is None and not genparams and hasattr(seeds, "parts")
+        """image: None, or a CUDA float32 contiguous tensor of the segmentation's shape (anything else takes the fallback);
+        seeds: a device-resident bank, or None with an image (the image is the intensity prior)."""
+        if image is not None:
+            if not (torch.is_tensor(image) and image.is_cuda and image.dtype == torch.float32 and image.is_contiguous()
+                    and torch.is_tensor(segmentation) and image.shape == segmentation.shape and image.device == segmentation.device):
+                return False
+        return (self.native_pipeline and not genparams and (hasattr(seeds, "parts") or (seeds is None and image is not None))
                 and self.intensity_generator.meta_labels <= 4 and torch.is_tensor(segmentation) and segmentation.is_cuda
                 and segmentation.dtype == torch.float32 and segmentation.is_contiguous()
                 and (segmentation_u8 is None or labels_u8) and not any(a is not None for a in self.artifacts.values()))
 
-    def _pipeline_keyed(self, segmentation, bank, key, scale01, labels_u8, out=None, seg_out=None, next_key=None):
+    def _pipeline_keyed(self, segmentation, bank, key, scale01, labels_u8, out=None, seg_out=None, next_key=None, image=None,
+                        image_out=None):
         """One keyed sample: pointers + key -> ONE native call (draws, the draw kernel, the launch sequence).  Returns
-        (image, labels, None, synth_params) or None when the sample is outside the fused kernels' domain.
+        (image, labels, warped real image | None, synth_params) or None when the sample is outside the fused kernels' domain.
+
+        image: the subject's real image (checked by `_keyed_applies`), deformed by the same warp launch as the labels.  With
+        `bank=None` its cached prior (`_image_prior`) takes the place of the GMM draw; with a bank the synthetic channel is that
+        of the same key without an image.
 
         next_key: the key of the sample the caller will ask for NEXT on this stream (a batch, a stream of indices): its draw job
         then rides in this sample's floor(min) launch (fsg_keyed_sample_run's look-ahead) -- one launch less on the next sample's
@@ -821,6 +883,10 @@ class FetalSynthGen:
             return None
         ent = kc.subject(bank, segmentation, twin)
         dev = segmentation.device
+        prior = self._image_prior(image) if (image is not None and bank is None) else None
+        img_given = image_out is not None
+        if image is not None and image_out is None:
+            image_out = torch.empty(shape, dtype=torch.float32, device=dev)
         ws = self._workspace(shape, kc.rows_need)
         given = seg_out is not None
         if out is None:
@@ -866,6 +932,8 @@ class FetalSynthGen:
         iv[_K_EV_BLUR_BEGIN], iv[_K_EV_BLUR_END] = events if events is not None else (0, 0)
         # the subject's code volume (0: four label volumes)
         iv[_K_CODES], iv[_K_CODE_TUPLES], iv[_K_CODE_NTUPLES], iv[_K_CODE_STRIDE] = ent.codes, ent.code_tuples, ent.code_ntuples, ent.code_stride
+        iv[_K_IMAGE_IN], iv[_K_IMAGE_OUT] = (image.data_ptr(), image_out.data_ptr()) if image is not None else (0, 0)
+        iv[_K_PRIOR_IN] = prior.data_ptr() if prior is not None else 0
         iv[_K_FLAGS] = flags
         if nblock is not None:
             iv[_K_NEXT_KEY], iv[_K_NEXT_BLOCK] = (next_key if next_key < (1 << 63) else next_key - (1 << 64)), nblock.data_ptr()
@@ -898,7 +966,15 @@ class FetalSynthGen:
                 seg_out.copy_(twin if labels_u8 else segmentation)
             else:
                 seg_out = twin if labels_u8 else segmentation
-        return out, seg_out, None, keyed.params_of(d, block)
+            if image is not None:  # ... and so does the image
+                if img_given:
+                    image_out.copy_(image)
+                else:
+                    image_out = image
+        params = keyed.params_of(d, block)
+        if bank is None:  # no seeds were selected and no intensities drawn, as in the stage-by-stage path
+            params["selected_seeds"], params["seed_intensities"] = {}, {}
+        return out, seg_out, image_out, params
 
     def _pipeline(self, image, segmentation, seeds, genparams, scale01: bool, segmentation_u8=None, labels_u8: bool = False,
                   key: int | None = None, next_key: int | None = None):
@@ -914,7 +990,7 @@ class FetalSynthGen:
                 key = int(np.random.randint(0, 1 << 62)) << 1
             key &= 0xFFFFFFFFFFFFFFFF
             if self._keyed_applies(image, segmentation, seeds, genparams, segmentation_u8, labels_u8):
-                got = self._pipeline_keyed(segmentation, seeds, key, scale01, labels_u8, next_key=next_key)
+                got = self._pipeline_keyed(segmentation, seeds, key, scale01, labels_u8, next_key=next_key, image=image)
                 if got is not None:
                     return got
             # outside the keyed path's domain: a "device"-mode sample of the global generators seeded from the key
@@ -963,8 +1039,8 @@ class FetalSynthGen:
             got = self._sample_batch_keyed(list(items), [int(k) for k in keys], scale01, streams, labels_u8)
             if got is not None:
                 return got
-            raise ValueError("keyed sample_batch: items outside the fused keyed path (need device-resident SeedBank subjects "
-                             "of one shape, no image, no SR-artifact stages)")
+            raise ValueError("keyed sample_batch: items outside the fused keyed path (need subjects of one shape with device-resident "
+                             "volumes -- a SeedBank, or a float32 image as intensity prior --, no SR-artifact stages)")
         genparams_list = list(genparams_list) if genparams_list is not None else [{}] * B
         if len(genparams_list) != B:
             raise ValueError("genparams_list must have one entry per item")
@@ -1051,16 +1127,25 @@ class FetalSynthGen:
         nstreams = max(1, min(int(streams), B))
         main = torch.cuda.current_stream(dev)
         side = self._side_streams(nstreams) if nstreams > 1 else [main]
+        params, images = [], [None] * B
+        with_img = [b for b, (img, _s, _b) in enumerate(items) if img is not None]
+        if with_img:  # the deformed real images of the batch as one tensor, like the other outputs
+            img_all = torch.empty((len(with_img), *shape), dtype=torch.float32, device=dev)
+            for q, b in enumerate(with_img):
+                images[b] = img_all[q]
+            for img, _s, bank in items:  # priors are subject constants: computed (once) on the main stream, ahead of the fork
+                if img is not None and bank is None:
+                    self._image_prior(img)
         if nstreams > 1:
             fork = torch.cuda.Event()
             fork.record(main)
             for q in range(nstreams):
                 side[q].wait_event(fork)
-        params = []
-        for b, ((_img, seg, seeds), key) in enumerate(zip(items, keys)):
+        for b, ((img, seg, seeds), key) in enumerate(zip(items, keys)):
             with torch.cuda.stream(side[b % nstreams]):  # (the next sample of THIS stream: its draw job rides along)
                 got = self._pipeline_keyed(seg, seeds, key & 0xFFFFFFFFFFFFFFFF, scale01, labels_u8, out=out_all[b],
-                                           seg_out=seg_all[b], next_key=keys[b + nstreams] if b + nstreams < B else None)
+                                           seg_out=seg_all[b], next_key=keys[b + nstreams] if b + nstreams < B else None,
+                                           image=img, image_out=images[b])
             if got is None:
                 return None
             params.append(got[3])
@@ -1069,7 +1154,7 @@ class FetalSynthGen:
                 join = torch.cuda.Event()
                 join.record(side[q])
                 main.wait_event(join)
-        return out_all, seg_all, [None] * B, params
+        return out_all, seg_all, images, params
 
     def _side_streams(self, n):
         cur = self.__dict__.setdefault("_batch_streams", [])

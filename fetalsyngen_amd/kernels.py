@@ -431,12 +431,16 @@ def coords(spec: DeformSpec, mm6):
     return out
 
 
-def warp(spec: DeformSpec, mm6, src_lin=None, src_nn=None, gamma=None, bias=None, bias_tabs=None, nn_out=None):
-    """Fused warp: returns (out_lin | None, out_nn | None).
+def warp(spec: DeformSpec, mm6, src_lin=None, src_nn=None, gamma=None, bias=None, bias_tabs=None, nn_out=None, src_img=None):
+    """Fused warp: returns (out_lin | None, out_nn | None), and (out_lin, out_nn | None, out_img) when `src_img` is given.
 
     `src_nn` float32 -> float32 labels (reference contract); uint8 -> uint8, or float32 when
-    `nn_out=torch.float32` (uint8 device copy of a float32 segmentation, exact for 0..255)."""
+    `nn_out=torch.float32` (uint8 device copy of a float32 segmentation, exact for 0..255).
+    `src_img`: a second float32 volume sampled trilinearly at `src_lin`'s positions in the same launch, without the
+    gamma / bias epilogue (fsg_warp_dual_f32); outside the lean kernel's domain it is a second launch, same values."""
     _need_gpu(mm6, src_lin, src_nn, bias)
+    if src_img is not None:
+        return _warp_dual(spec, mm6, src_lin, src_nn, gamma, bias, bias_tabs, nn_out, src_img)
     for s_ in (src_lin, src_nn):
         if s_ is not None and tuple(s_.shape) != spec.shape:
             raise ValueError(f"volume shape {tuple(s_.shape)} != grid {spec.shape}")
@@ -466,6 +470,37 @@ def warp(spec: DeformSpec, mm6, src_lin=None, src_nn=None, gamma=None, bias=None
     else:
         raise TypeError("nearest-neighbour volume must be float32 or uint8")
     return out_lin, out_nn
+
+
+def _warp_dual(spec, mm6, src_lin, src_nn, gamma, bias, bias_tabs, nn_out, src_img):
+    _need_gpu(src_img)
+    if src_lin is None:
+        raise ValueError("src_img rides on src_lin's sampling positions: src_lin is required")
+    for s_ in (src_lin, src_nn, src_img):
+        if s_ is not None and tuple(s_.shape) != spec.shape:
+            raise ValueError(f"volume shape {tuple(s_.shape)} != grid {spec.shape}")
+    if src_nn is not None and src_nn.dtype not in (F32, torch.uint8):
+        raise TypeError("nearest-neighbour volume must be float32 or uint8")
+    if nn_out not in (None, torch.uint8, F32) or (nn_out == torch.uint8 and src_nn is not None and src_nn.dtype == F32):
+        raise TypeError("nn_out must be torch.uint8 or torch.float32 (float32 labels stay float32)")
+    if spec.c.rows and (int(bias.shape[2]) if bias is not None else 0) > getattr(spec, "_rows_bias", 0):
+        raise ValueError("row workspace was prepared without this bias grid; call prepare_rows(bias, bias_tabs)")
+    out_lin, out_img = torch.empty_like(_f32(src_lin)), torch.empty_like(_f32(src_img, "src_img"))
+    out_nn, din, dout = None, _lib.LABEL_F32, _lib.LABEL_F32
+    if src_nn is not None:
+        odt = src_nn.dtype if nn_out is None else nn_out
+        out_nn = torch.empty(src_nn.shape, dtype=odt, device=src_nn.device)
+        din = _lib.LABEL_U8 if src_nn.dtype == torch.uint8 else _lib.LABEL_F32
+        dout = _lib.LABEL_U8 if odt == torch.uint8 else _lib.LABEL_F32
+    epi = _epilogue(gamma, bias, bias_tabs, spec.shape)
+    rc = _lib.load().fsg_warp_dual_f32(C.byref(spec.c), _p(mm6), _p(src_lin), _p(out_lin), _p(src_img), _p(out_img),
+                                       src_img.numel(), _p(src_nn), _p(out_nn), din, dout, C.byref(epi), _stream(mm6))
+    if rc == _lib.E_ALIGN:  # outside the lean kernel's domain: the two launches it stands for
+        out_lin, out_nn = warp(spec, mm6, src_lin=src_lin, src_nn=src_nn, gamma=gamma, bias=bias, bias_tabs=bias_tabs, nn_out=nn_out)
+        out_img, _ = warp(spec, mm6, src_lin=src_img)
+        return out_lin, out_nn, out_img
+    _lib.check(rc, "fsg_warp_dual_f32")
+    return out_lin, out_nn, out_img
 
 
 def interp3d(src, ii, jj, kk, mode: str, default_value=0.0) -> torch.Tensor:

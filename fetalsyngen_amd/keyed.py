@@ -73,7 +73,9 @@ class Subject:
                  "code_stride")
 
     def __init__(self, bank, seg, bank_ptrs, twin_ptr):
-        self.bank_ref, self.seg_ref, self.seg_version = weakref.ref(bank), weakref.ref(seg), seg._version
+        # bank None: a subject without seeds (its image is the intensity prior), no seed volume is read
+        self.bank_ref = weakref.ref(bank) if bank is not None else (lambda: None)
+        self.seg_ref, self.seg_version = weakref.ref(seg), seg._version
         self.bank_ptrs, self.twin_ptr, self.seg_ptr = bank_ptrs, twin_ptr, seg.data_ptr()  # twin_ptr 0: no uint8 twin yet
         self.codes = self.code_tuples = self.code_ntuples = self.code_stride = 0  # 0: no code volume (KeyedContext._codes)
 
@@ -155,8 +157,8 @@ class KeyedContext:
         if tuple(seg.shape) != shape or seg.dtype != torch.float32 or not seg.is_cuda or not seg.is_contiguous():
             raise ValueError(f"segmentation: expected a contiguous float32 tensor of shape {shape} on {dev}")
         ptrs = np.zeros(BANK_SLOTS, dtype=np.int64)
-        vol = bank.vol
-        for n in range(c.min_subclusters, c.max_subclusters + 1):
+        vol = bank.vol if bank is not None else {}
+        for n in range(c.min_subclusters, c.max_subclusters + 1) if bank is not None else ():
             for m in range(1, c.meta_labels + 1):
                 part = vol[n][m]
                 off_dev = part.device.type != dev.type or (dev.index is not None and part.device.index != dev.index)
@@ -175,7 +177,7 @@ class KeyedContext:
         """The code fields of `ent` = the subject's code volume (seedcodes.build), kept ON the bank object so that it lives and dies with it.
         A seed volume rewritten through torch bumps its `_version`: the codes are rebuilt; a rewrite through a raw pointer needs
         `FetalSynthGen.invalidate_label_twins()` (which drops them)."""
-        if not self.use_codes:
+        if not self.use_codes or bank is None:
             ent.codes = ent.code_tuples = ent.code_ntuples = ent.code_stride = 0
             return
         c = self.cfg

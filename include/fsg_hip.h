@@ -28,7 +28,8 @@
 extern "C" {
 #endif
 
-#define FSG_ABI_VERSION 3  /* 2: fsg_sample_plan grew (mm_slots .. seg_out_u8) after version 1 shipped; 3: label_codes .. code_sel, FSG_KEYED_I_CODES */
+#define FSG_ABI_VERSION 4  /* 2: fsg_sample_plan grew (mm_slots .. seg_out_u8) after version 1 shipped; 3: label_codes .. code_sel, FSG_KEYED_I_CODES;
+                              4: fsg_sample_image / fsg_sample_run_image, FSG_KEYED_I_IMAGE_IN .. PRIOR_IN, fsg_warp_dual_f32 */
 
 #define FSG_E_BADARG (-1)   /* null pointer / non-positive size / bad enum */
 #define FSG_E_TOOBIG (-2)   /* size exceeds what the kernel indexes (2^31-1 voxels per volume) */
@@ -210,6 +211,22 @@ int fsg_warp_f32_u8(const fsg_deform* d_host, const int32_t* mm6, const float* s
  * and the caller uses fsg_warp_f32 / fsg_warp_f32_u8. */
 int fsg_warp_f32_u8_to_f32(const fsg_deform* d_host, const int32_t* mm6, const float* src_lin, float* out_lin,
                            const uint8_t* src_nn, float* out_nn, const fsg_epilogue* epi_host, void* stream);
+
+/* The fused warp with a SECOND trilinear source in the same launch: out_img = trilinear(src_img) at the positions (and with the
+ * in-kernel flip, the weights and the strict > 0 rule) of src_lin -> out_lin, float32, WITHOUT the epilogue, which stays on
+ * out_lin alone.  The real image of a `load_image` sample beside its synthetic channel (affine_nonrigid.py:186-193 interpolates
+ * output, segmentation and image on one set of coordinates): one launch instead of fsg_warp_* for (src_lin, src_nn) plus
+ * fsg_warp_f32 for src_img alone, and bit for bit their three outputs.  img_voxels: the number of float32 elements behind
+ * src_img AND out_img.  label_dtype_in / label_dtype_out: FSG_LABEL_F32 or FSG_LABEL_U8 of src_nn / out_nn (float32 -> float32,
+ * uint8 -> uint8, uint8 -> float32); the label pair may be NULL.
+ * FSG_E_BADARG, and nothing is launched: src_img without out_img or the reverse, src_img without src_lin, img_voxels different
+ * from the grid's voxel count, out_img aliasing src_img / src_lin / out_lin, out_lin aliasing src_img, or any argument
+ * fsg_warp_f32 refuses.
+ * Served by the lean kernel alone (csrc/fsg_warp_lean.hip); FSG_E_ALIGN outside its domain or with it switched off
+ * (fsg_set_tuning), and the caller issues the two launches. */
+int fsg_warp_dual_f32(const fsg_deform* d_host, const int32_t* mm6, const float* src_lin, float* out_lin, const float* src_img,
+                      float* out_img, size_t img_voxels, const void* src_nn, void* out_nn, int label_dtype_in,
+                      int label_dtype_out, const fsg_epilogue* epi_host, void* stream);
 
 /* Generic gather with explicit coordinate volumes (utils/generation.py:204-288 fast_3D_interp_torch).
  * mode 0 = linear (default_value outside), 1 = nearest.  src (sx,sy,sz); npts coordinates. */
@@ -520,15 +537,34 @@ enum {
   FSG_ST_ROWS = 14, FSG_ST_POINTWISE = 15, FSG_ST_BLUR_RS_X = 16, FSG_ST_BLUR_RS_YZ = 17, FSG_ST_COUNT = 18
 };
 int fsg_sample_run(const fsg_sample_plan* plan_host, void* stream);
+/* Real-image samples (ABI 4): the volumes of a sample that carries an image, beside its plan.  They live in a struct of their
+ * own, not at the end of fsg_sample_plan: the plan and its flat form (FSG_PLAN_I_*, one slot per field) keep their layout.
+ * All three optional.
+ * prior_in: a float32 volume of shape[] that REPLACES the GMM draw (the reference's image-as-intensity prior, model.py:138:
+ *   the subject's image scaled to 0..255 -- a constant of the subject, computed by the caller once).  The plan's label_parts, mus,
+ *   sigmas and code volume are then not read and may be NULL / 0; the rows and faces jobs of the one-launch head stay.  Never
+ *   written: gamma and the bias field run on it as they do on the GMM volume when no deformation is drawn.
+ * image_in / image_out: the raw image (float32, shape[]) and its deformed copy, written by the SAME warp launch as out and the
+ *   labels (fsg_warp_dual_f32; two launches where that declines).  deform_active only: without a deformation image_out is not
+ *   written and the caller passes the image through, as it does with the labels.  image_in without image_out: FSG_E_BADARG,
+ *   nothing launched.
+ * fsg_sample_run_image(plan, NULL, stream) is fsg_sample_run(plan, stream). */
+typedef struct fsg_sample_image {
+  const float* image_in;
+  float* image_out;
+  const float* prior_in;
+} fsg_sample_image;
+int fsg_sample_run_image(const fsg_sample_plan* plan_host, const fsg_sample_image* image_host, void* stream);
 /* Layout check for FFI mirrors of the structs: which = FSG_SIZEOF_x -> sizeof(fsg_x) (0: fsg_sample_plan, 6 .. 10: fsg_tap,
- * fsg_deform, fsg_epilogue, fsg_keyed_config, fsg_keyed_draws); 1 / 2 / 3 / 4 / 5 -> offsetof blur_taps / out / seg_in_u8 /
- * ws_seq / code_sel in fsg_sample_plan; anything else -> -1.  Callable without a GPU. */
+ * fsg_deform, fsg_epilogue, fsg_keyed_config, fsg_keyed_draws; 12: fsg_sample_image); 1 / 2 / 3 / 4 / 5 -> offsetof blur_taps /
+ * out / seg_in_u8 / ws_seq / code_sel in fsg_sample_plan; anything else (11 included) -> -1.  Callable without a GPU. */
 #define FSG_SIZEOF_SAMPLE_PLAN 0
 #define FSG_SIZEOF_TAP 6
 #define FSG_SIZEOF_DEFORM 7
 #define FSG_SIZEOF_EPILOGUE 8
 #define FSG_SIZEOF_KEYED_CONFIG 9
 #define FSG_SIZEOF_KEYED_DRAWS 10
+#define FSG_SIZEOF_SAMPLE_IMAGE 12
 int64_t fsg_sample_plan_layout(int which);
 /* B samples with one call: plan b runs on streams[b % nstreams] (hipStream_t handles).  The caller orders those streams
  * behind the upload of every plan's parameters and waits for them afterwards; per sample the work is exactly
@@ -633,6 +669,9 @@ typedef struct fsg_keyed_draws {
   int32_t noise_active;
   double noise_std;
   float noise_std32;
+  /* Prior mode (FSG_KEYED_I_PRIOR_IN): every draw keeps its fixed counter, so the deformation, gamma, bias, resampling and noise
+   * fields above and below are those of the same key in seed mode; subclusters / ntab (and mus / sigmas in the block) are
+   * UNSPECIFIED there -- nothing reads them. */
   /* byte offsets into the sample's device parameter block of what the draw kernel writes there */
   int32_t off_mm8, off_slots, off_mus, off_sigmas, off_bias, off_field, block_bytes;
   int32_t rode; /* fsg_keyed_sample_run: 1 when the draw job of the NEXT sample went out with this one (look-ahead) */
@@ -669,7 +708,11 @@ enum {
    * when the deformation gate is off).  A caller that then runs something else simply does not set bit 0.  (r03: the next sample's GMM draw beside the zoom-back launches was built
    * and measured too -- 224 -> 230-244 us per step, the two jobs slow each other down -- and removed.) */
   FSG_KEYED_I_FLAGS = 16 + 70, FSG_KEYED_I_NEXT_KEY = 16 + 71, FSG_KEYED_I_NEXT_BLOCK = 16 + 72,
-  FSG_KEYED_I_COUNT = 16 + 73
+  /* real-image samples (optional, 0 = none): fsg_sample_image::image_in / image_out / prior_in.  With PRIOR_IN the BANK and CODES
+   * slots are not read (a subject without seeds); with a bank and IMAGE_IN the synthetic channel is that of the same key without an image.
+   * The look-ahead does not care which kind the next sample is: its draw job is the same. */
+  FSG_KEYED_I_IMAGE_IN = 16 + 73, FSG_KEYED_I_IMAGE_OUT = 16 + 74, FSG_KEYED_I_PRIOR_IN = 16 + 75,
+  FSG_KEYED_I_COUNT = 16 + 76
 };
 #define FSG_KEYED_FLAG_BLOCK_FILLED 1
 #define FSG_KEYED_FLAG_NEXT_NAMED 4
