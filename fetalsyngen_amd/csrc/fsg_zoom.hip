@@ -431,7 +431,8 @@ __global__ __launch_bounds__(256) void zoom_tile_kernel(ZoomK Z, EpiZ E, int TY,
       t = Z.ty[j0 + tid];
       tb[tid] = t;
     }
-    int smin = t.lo >= 0 ? t.lo : 0x7FFFFFFF, smax = t.lo >= 0 ? t.hi : -1;
+    // a tap is w_lo * src[lo] + w_hi * src[hi], nothing says hi >= lo: the window spans both indices of every tap
+    int smin = t.lo >= 0 ? min(t.lo, t.hi) : 0x7FFFFFFF, smax = t.lo >= 0 ? max(t.lo, t.hi) : -1;
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) {
       smin = min(smin, __shfl_xor(smin, o, FSG_WAVE));
@@ -615,7 +616,8 @@ __device__ __forceinline__ void zoom_slab_body(const ZoomK& Z, const EpiZ& E, co
       t = Z.ty[j0 + tid];
       tb[tid] = t;
     }
-    int smin = t.lo >= 0 ? t.lo : 0x7FFFFFFF, smax = t.lo >= 0 ? t.hi : -1;
+    // a tap is w_lo * src[lo] + w_hi * src[hi], nothing says hi >= lo: the window spans both indices of every tap
+    int smin = t.lo >= 0 ? min(t.lo, t.hi) : 0x7FFFFFFF, smax = t.lo >= 0 ? max(t.lo, t.hi) : -1;
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) {
       smin = min(smin, __shfl_xor(smin, o, FSG_WAVE));
@@ -644,7 +646,10 @@ __device__ __forceinline__ void zoom_slab_body(const ZoomK& Z, const EpiZ& E, co
   const UniDiv udd = unidiv_make(den);  // the scaling's second divisor (1 - min/max) is uniform as well
   // which arithmetic follows the first quotient (uniform): 0 none, 1 "* 0" (min == max), 2 "- min/max" (den == 1), 3 "(- min/max) / den"
   // (min == 0, the usual case: "- 0" leaves every float as it is -> 0)
-  const int nmode = (EPI == EPI_NORM && E.norm_mode == 1) ? (mnq == 1.0f ? 1 : (den == 1.0f ? (mnq == 0.0f ? 0 : 2) : 3)) : 0;
+  // ("- 0" only for +0.0: t - (-0.0) turns a -0.0 voxel into +0.0, so a minimum of -0.0 keeps its subtraction)
+  const int nmode = (EPI == EPI_NORM && E.norm_mode == 1)
+                        ? (mnq == 1.0f ? 1 : (den == 1.0f ? (__builtin_bit_cast(unsigned, mnq) == 0u ? 0 : 2) : 3))
+                        : 0;
 #ifdef FSG_NO_UNIDIV
   const bool uni_ok = false;
 #else
@@ -689,7 +694,8 @@ __device__ __forceinline__ void zoom_slab_body(const ZoomK& Z, const EpiZ& E, co
         const float q = v[u] * ud.r;
         const float e = __builtin_fmaf(-q, ud.d, v[u]);
         t[u] = __builtin_fmaf(e, ud.r, q);
-        bad |= !((q > 1e-18f && q < 1e18f) || v[u] == 0.f);
+        // +0.0 only: for v = -0.0 the two FMAs give +0.0 where the quotient is -0.0 -- that row takes the IEEE division
+        bad |= !((q > 1e-18f && q < 1e18f) || __builtin_bit_cast(unsigned, v[u]) == 0u);
       }
       if (nmode == 3) {
 #pragma unroll

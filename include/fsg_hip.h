@@ -137,11 +137,13 @@ int fsg_resample_noise_f32(const float* src, int sx, int sy, int sz, const fsg_t
                            const float* noise, uint64_t seed, uint64_t stream_id, float noise_std,
                            void* stream);
 
-/* Tile shape of the zoom kernels: output y rows per workgroup (1..32, default 16) and the LDS floats reserved for the
- * x-blended source-row window (default 12288); a tile whose window does not fit is evaluated without staging. */
+/* Tile shape of the zoom kernels: output y rows per workgroup (1..64, default 16) and the LDS floats reserved for the
+ * x-blended source-row window (256..16000, default 12288); a tile whose window does not fit is evaluated without staging.
+ * FSG_E_BADARG (setting unchanged) outside those ranges. */
 int fsg_zoom_set_tuning(int y_rows, int cap_floats);
 /* K9 pass A (synthseg.py:111-112): min and max of zoom(src) without storing it; mm[0]=min, mm[1]=max as
- * order-preserving int32 keys (see fsg_minmax_init). */
+ * order-preserving int32 keys (see fsg_minmax_init).  An outside output (lo < 0 on any axis) counts as the +0.0 that
+ * fsg_zoom3d_f32 stores there.  NaN outputs are ignored (all NaN: the keys are left as they were); -0.0 orders below +0.0. */
 int fsg_zoom3d_minmax_f32(const float* src, int sx, int sy, int sz, const fsg_tap* tx, const fsg_tap* ty,
                           const fsg_tap* tz, int dx, int dy, int dz, int32_t* mm, void* stream);
 /* K9 pass B (+K10): mode 0: dst = y / max            (synthseg.py:112, what FetalSynthGen.sample returns)
