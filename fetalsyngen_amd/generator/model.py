@@ -17,7 +17,8 @@ The optional SR-artifact stages (`blur_cortex`, `struct_noise`, `simulate_motion
 """
 from __future__ import annotations
 
-import weakref
+import contextlib
+import ctypes as C
 from typing import Iterable
 
 import numpy as np
@@ -27,6 +28,7 @@ from .. import kernels as K
 from .. import rng as _rng
 from .. import tables as T
 from .. import _lib
+from ..identity import IdentityCache
 from ..utils.generation import make_affine_matrix
 from .augmentation.synthseg import BiasPlan, NoisePlan, RandBiasField, RandGamma, RandNoise, RandResample, ResamplePlan
 from .deformation.affine_nonrigid import DeformPlan, SpatialDeformation
@@ -51,6 +53,12 @@ _K_EV_BLUR_BEGIN, _K_EV_BLUR_END, _K_CODES, _K_CODE_TUPLES = _KI.EV_BLUR_BEGIN, 
 _K_CODE_NTUPLES, _K_CODE_STRIDE, _K_FLAGS, _K_NEXT_KEY, _K_NEXT_BLOCK = _KI.CODE_NTUPLES, _KI.CODE_STRIDE, _KI.FLAGS, _KI.NEXT_KEY, _KI.NEXT_BLOCK
 _K_IMAGE_IN, _K_IMAGE_OUT, _K_PRIOR_IN = _KI.IMAGE_IN, _KI.IMAGE_OUT, _KI.PRIOR_IN
 _KF_BLOCK_FILLED, _KF_NEXT_NAMED = _KF.BLOCK_FILLED, _KF.NEXT_NAMED
+_SEEN_ONCE, _NO_TWIN = object(), object()  # what `_twins` holds for a label volume that has no uint8 twin
+
+
+def _i64(key):
+    """An unsigned 64-bit key as the signed value an int64 slot takes."""
+    return key if key < (1 << 63) else key - (1 << 64)
 
 
 class _Ctx:
@@ -64,22 +72,16 @@ class StageTrace:
     CAP = 16
 
     def __init__(self):
-        import ctypes as C
-
         lib = _lib.load()
         self.events = (C.c_void_p * self.CAP)(*[lib.fsg_event_create() for _ in range(self.CAP)])
         self.ids = np.zeros(self.CAP + 1, dtype=np.int32)
         self.meta = None
 
     def slots(self):
-        import ctypes as C
-
         return C.addressof(self.events), self.ids.ctypes.data, self.CAP
 
     def elapsed_us(self):
         """[(stage name, microseconds between the previous event and this launch's event)]; synchronises."""
-        import ctypes as C
-
         lib, ms, out = _lib.load(), C.c_float(), []
         n = int(self.ids[self.CAP])
         for k in range(1, n):
@@ -151,8 +153,7 @@ class FetalSynthGen:
                       "stage_traces", "_pre", "_priors")
 
     def __getstate__(self):
-        state = {k: v for k, v in self.__dict__.items() if k not in self._PROCESS_LOCAL}
-        return state
+        return {k: v for k, v in self.__dict__.items() if k not in self._PROCESS_LOCAL}
 
     def __setstate__(self, state):
         self.__dict__.update({k: v for k, v in state.items() if k not in self._PROCESS_LOCAL})
@@ -225,125 +226,72 @@ class FetalSynthGen:
 
     label_twin_budget_bytes = 1 << 30  # HBM the uint8 twins of caller-owned label volumes may take (64 at 256^3)
 
-    def _twin_cache(self):
-        return self.__dict__.setdefault("_twins", {"by_id": {}, "bytes": 0})
-
-    def _twin_drop(self, key):
-        cache = self.__dict__.get("_twins")
-        ent = cache["by_id"].pop(key, None) if cache else None
-        if ent is not None and ent[2] is not None:
-            cache["bytes"] -= ent[2].numel()
+    def _cache(self, name):
+        """The generator's IdentityCache `name` (`_twins`, `_priors`): process-local, made on first use."""
+        cache = self.__dict__.get(name)
+        return cache if cache is not None else self.__dict__.setdefault(name, IdentityCache())
 
     def register_label_twin(self, seg, twin):
         """Hand over a uint8 copy of the float32 label volume `seg` (same values) that the caller already holds -- the
         datasets do, for every subject they cache -- so that no check and no second copy is made here."""
         if twin is None or twin.dtype != torch.uint8 or twin.shape != seg.shape or twin.device != seg.device:
             raise ValueError("label twin must be a uint8 tensor of the segmentation's shape on its device")
-        cache = self._twin_cache()
-        key = id(seg)
-        self._twin_drop(key)
-        cache["by_id"][key] = [weakref.ref(seg, lambda _r, k=key, me=weakref.ref(self): me() and me()._twin_drop(k)),
-                               seg._version, twin, 2]
-        cache["bytes"] += twin.numel()
+        twins = self._cache("_twins")
+        twins.drop(seg)
+        twins.put(seg, twin, twin.numel(), seg._version)
 
     def invalidate_label_twins(self):
         """Forget every cached uint8 label twin.  The cache notices a new tensor object and an in-place torch write
         (`_version`); it cannot notice a label volume rewritten through its raw pointer (another HIP library, the `fsg_*`
         entry points themselves) -- call this after such a write."""
-        self.__dict__.pop("_twins", None)
-        self.__dict__.pop("_priors", None)
+        for cache in (self._cache("_twins"), self._cache("_priors"), self._flat_buffers()["validated"]):
+            cache.clear()
         for kc in (self.__dict__.get("_keyed") or {}).values():  # keyed mode: the subjects' pointer blocks and code volumes
-            for ent in kc._subjects.values():
-                bank = ent.bank_ref()
-                if bank is not None:
-                    bank.__dict__.pop("_seed_codes", None)
-            kc._subjects.clear()
-        fb = self.__dict__.get("_flat")
-        if fb is not None:
-            fb["validated"].clear()
+            kc.forget_subjects()
 
     def _label_twin(self, seg):
         """uint8 copy of a float32 label volume whose values are integers in 0..255 (dseg volumes always are): the fused warp
-        then gathers 1 B/voxel instead of 4, the output stays float32.  Cached per tensor OBJECT through a weak reference
-        (the entry goes when the tensor dies, nothing keeps a caller's volume alive) together with its in-place version.
-        A volume is converted on its SECOND sighting: a caller who passes a fresh segmentation on every call never pays the
+        then gathers 1 B/voxel instead of 4, the output stays float32.  Cached per tensor OBJECT and in-place version
+        (identity.IdentityCache: nothing keeps a caller's volume alive).  A volume is converted on its SECOND sighting: a caller who passes a fresh segmentation on every call never pays the
         synchronising integer check and the extra passes, a caller who re-uses volumes pays them once.  Twins take at most
         `label_twin_budget_bytes` (oldest dropped first).  None: no twin (yet), the warp reads the float32 volume."""
-        cache = self._twin_cache()
-        by_id = cache["by_id"]
-        key = id(seg)
-        ent = by_id.get(key)
-        if ent is not None and (ent[0]() is not seg or ent[1] != seg._version):
-            self._twin_drop(key)
-            ent = None
-        if ent is None:
-            if len(by_id) > 4096:
-                by_id.clear()
-                cache["bytes"] = 0
-            by_id[key] = [weakref.ref(seg, lambda _r, k=key, me=weakref.ref(self): me() and me()._twin_drop(k)),
-                          seg._version, None, 1]
+        twins = self._cache("_twins")
+        twin = twins.get(seg, seg._version)
+        if twin is None:
+            twins.put(seg, _SEEN_ONCE, 0, seg._version)
             return None
-        if ent[3] == 1:  # second sighting: check and convert (synchronises once per volume)
-            ent[3] = 2
+        if twin is _SEEN_ONCE:  # second sighting: check and convert (synchronises once per volume)
+            twin, nbytes = _NO_TWIN, 0
             ok = bool(torch.equal(seg.round(), seg)) and float(seg.min()) >= 0 and float(seg.max()) <= 255
-            if ok:
-                while cache["bytes"] + seg.numel() > self.label_twin_budget_bytes:
-                    victim = next((k for k, e in by_id.items() if e[2] is not None), None)
-                    if victim is None:
-                        break
-                    self._twin_drop(victim)
-                if cache["bytes"] + seg.numel() <= self.label_twin_budget_bytes:
-                    ent[2] = seg.to(torch.uint8)
-                    cache["bytes"] += seg.numel()
-        return ent[2]
+            if ok and twins.make_room(seg.numel(), self.label_twin_budget_bytes):
+                twin, nbytes = seg.to(torch.uint8), seg.numel()
+            twins.put(seg, twin, nbytes, seg._version)  # (in the place of its first sighting)
+        return None if twin is _NO_TWIN else twin
 
     # ---- per-subject constant of a real image: its intensity prior --------------------------------------------------------
-    def _prior_cache(self):
-        return self.__dict__.setdefault("_priors", {"by_id": {}, "bytes": 0})
-
-    def _prior_drop(self, key):
-        cache = self.__dict__.get("_priors")
-        ent = cache["by_id"].pop(key, None) if cache else None
-        if ent is not None and ent[3]:
-            cache["bytes"] -= ent[2].numel() * 4
-
     def register_image_prior(self, image, prior):
         """Hand over the intensity prior of the device image `image` (what `_intensity_prior(image)` returns) that the caller
-        already holds and accounts for -- the datasets do, per cached subject -- so that keyed samples do not recompute it."""
+        already holds and accounts for -- the datasets do, per cached subject -- so that keyed samples do not recompute it.
+        It holds no bytes here: it is not counted and never evicted."""
         if prior.dtype != torch.float32 or prior.shape != image.shape or prior.device != image.device or not prior.is_contiguous():
             raise ValueError("image prior must be a contiguous float32 tensor of the image's shape on its device")
-        key = id(image)
-        self._prior_drop(key)
-        self._prior_cache()["by_id"][key] = [weakref.ref(image, lambda _r, k=key, me=weakref.ref(self): me() and me()._prior_drop(k)),
-                                             image._version, prior, False]
+        priors = self._cache("_priors")
+        priors.drop(image)
+        priors.put(image, prior, 0, image._version)
 
     def _image_prior(self, image):
         """`_intensity_prior(image)` -- (x - min) / (max - min) * 255, a constant of the subject -- computed once per image
-        tensor OBJECT with the same two kernels, so the very bits the stage-wise path produces on every sample.  Cached through
-        a weak reference with the tensor's in-place version, like the label twins.  The priors have a byte count of their own,
-        held to the size `label_twin_budget_bytes` also gives the twins (so the two caches together may take twice that;
-        oldest prior dropped first; a prior that does not fit is computed per sample)."""
-        cache = self._prior_cache()
-        by_id = cache["by_id"]
-        key = id(image)
-        ent = by_id.get(key)
-        if ent is not None and ent[0]() is image and ent[1] == image._version:
-            return ent[2]
-        self._prior_drop(key)
-        prior = self._intensity_prior(image)
-        nbytes = prior.numel() * 4
-        while cache["bytes"] + nbytes > self.label_twin_budget_bytes:
-            victim = next((k for k, e in by_id.items() if e[3]), None)
-            if victim is None:
-                break
-            self._prior_drop(victim)
-        if cache["bytes"] + nbytes <= self.label_twin_budget_bytes:
-            if len(by_id) > 4096:
-                by_id.clear()
-                cache["bytes"] = 0
-            by_id[key] = [weakref.ref(image, lambda _r, k=key, me=weakref.ref(self): me() and me()._prior_drop(k)),
-                          image._version, prior, True]
-            cache["bytes"] += nbytes
+        tensor OBJECT with the same two kernels, so the very bits the stage-wise path produces on every sample.  Cached with
+        the tensor's in-place version, like the label twins.  The priors have a byte count of their own, held to the size
+        `label_twin_budget_bytes` also gives the twins (so the two caches together may take twice that; oldest prior dropped
+        first; a prior that does not fit is computed per sample)."""
+        priors = self._cache("_priors")
+        prior = priors.get(image, image._version)
+        if prior is None:
+            prior = self._intensity_prior(image)
+            nbytes = prior.numel() * 4
+            if priors.make_room(nbytes, self.label_twin_budget_bytes):
+                priors.put(image, prior, nbytes, image._version)
         return prior
 
     def _native_ok(self, c, labels_u8: bool = False) -> bool:
@@ -363,9 +311,9 @@ class FetalSynthGen:
         seg = c.segmentation
         val = self._flat_buffers()["validated"]
         known = torch.is_tensor(seg) and seg.is_cuda and seg.dtype == torch.float32 and seg.is_contiguous()
+        checked = val.get
         for t_ in (seg, *c.label_parts) if known else ():
-            hit = val.get(id(t_))
-            if hit is None or hit[0]() is not t_ or hit[1] != shape:
+            if checked(t_) != shape:
                 known = False
                 break
         if not known:
@@ -385,10 +333,8 @@ class FetalSynthGen:
                         f"seed label volume {q}: expected a contiguous uint8 tensor of shape {shape} on {dev}, got "
                         f"{part.dtype} {tuple(part.shape)} on {part.device} (contiguous={part.is_contiguous()})")
             if seg is c.segmentation:
-                if len(val) > 4096:
-                    val.clear()
                 for t_ in (seg, *c.label_parts):
-                    val[id(t_)] = (weakref.ref(t_), shape)
+                    val.put(t_, shape)
         c.seg = seg
         if not 1 <= c.gm_off[2] <= 256:
             raise ValueError(f"mus / sigmas tables of {c.gm_off[2]} entries (need 1..256)")
@@ -418,7 +364,7 @@ class FetalSynthGen:
             tb = np.zeros((3, _lib.PLAN_TAPS_STRIDE), dtype=np.float32)
             centre = (np.array(self.spatial_deform.size) - 1) / 2
             fb = self._flat = dict(iv=iv, fv=fv, tb=tb, ivp=iv.ctypes.data, fvp=fv.ctypes.data, tbp=tb.ctypes.data,
-                                   centre=np.asarray(centre, dtype=np.float32).tolist(), validated={})
+                                   centre=np.asarray(centre, dtype=np.float32).tolist(), validated=IdentityCache())
         return fb
 
     def _flat_plan(self, c, scale01, out, seg_out, ws, twin=None):
@@ -505,6 +451,20 @@ class FetalSynthGen:
         fb["fv"][:] = fv
         return True
 
+    def _instrument(self, resampling=True):
+        """(blur events | None, StageTrace | None) of the sample about to be enqueued.  Events: for every `blur_events_every`-th
+        sample that resamples (a caller that cannot know yet destroys those of a sample that did not); trace: for every sample."""
+        events = None
+        if self.blur_events is not None and resampling:
+            self._blur_tick += 1
+            if self._blur_tick % self.blur_events_every == 0:
+                events = (_lib.load().fsg_event_create(), _lib.load().fsg_event_create())
+        return events, (StageTrace() if self.stage_traces is not None else None)
+
+    def _keep_blur_events(self, events, blur_ntaps, low_shape):
+        self.blur_events.append((events[0], events[1], [(a_, int(blur_ntaps[a_]) // 2) for a_ in range(3) if blur_ntaps[a_]],
+                                 tuple(int(v) for v in low_shape)))
+
     def _run_native(self, c, scale01, labels_u8=False):
         """Enqueue prepared sample `c` (arena uploaded) with one fsg_sample_pack_run call.  Returns (image, labels), or None
         when the sample is outside the fused kernels' domain (the caller then launches stage by stage).  labels_u8: the
@@ -523,16 +483,11 @@ class FetalSynthGen:
             return None
         I, fb, lib = _lib.PLAN_I, self._flat, _lib.load()
         iv = fb["iv"]
-        if self.blur_events is not None and c.rplan.active:
-            self._blur_tick += 1
-            if self._blur_tick % self.blur_events_every == 0:
-                events = (lib.fsg_event_create(), lib.fsg_event_create())
-                iv[I.EV_BEGIN], iv[I.EV_END] = events
-                nt = iv[I.BLUR_NTAPS:I.BLUR_NTAPS + 3].tolist()
-                self.blur_events.append((events[0], events[1], [(a_, nt[a_] // 2) for a_ in range(3) if nt[a_]],
-                                         tuple(int(v) for v in c.rplan.new_size)))
-        if self.stage_traces is not None:
-            tr = StageTrace()
+        events, tr = self._instrument(c.rplan.active)
+        if events is not None:
+            iv[I.EV_BEGIN], iv[I.EV_END] = events
+            self._keep_blur_events(events, iv[I.BLUR_NTAPS:I.BLUR_NTAPS + 3].tolist(), c.rplan.new_size)
+        if tr is not None:
             tr.meta = {"shape": tuple(c.shape), "low_shape": tuple(c.rplan.new_size) if c.rplan.active else None,
                        "blur_ntaps": iv[I.BLUR_NTAPS:I.BLUR_NTAPS + 3].tolist()}
             iv[I.TRACE_EVENTS], iv[I.TRACE_IDS], iv[I.TRACE_CAP] = tr.slots()
@@ -541,9 +496,7 @@ class FetalSynthGen:
         if rc in (_lib.E_ALIGN, _lib.E_TOOBIG):
             return None
         _lib.check(rc, "fsg_sample_pack_run")
-        f32_view = c.arena.f32
-        c.mus, c.sigmas = f32_view(c.gm_off[0], (c.gm_off[2],)), f32_view(c.gm_off[1], (c.gm_off[2],))
-        c.seed_intensities = {"mus": c.mus, "sigmas": c.sigmas}
+        self._intensity_views(c)
         return out, seg_out
 
     @staticmethod
@@ -622,8 +575,13 @@ class FetalSynthGen:
     # ---- fused path -----------------------------------------------------------------------------
     def sample(self, image, segmentation, seeds, genparams: dict = {}, key: int | None = None):
         """`key`: keyed mode only (`rng="keyed"`), the sample's 64-bit key."""
-        out, seg, img, params = self._pipeline(image, segmentation, seeds, genparams, scale01=False, key=key)
-        return out, seg, img, params
+        return self._pipeline(image, segmentation, seeds, genparams, scale01=False, key=key)
+
+    def _resolution64(self):
+        res = self.__dict__.get("_res64")
+        if res is None:
+            res = self._res64 = np.array(self.resolution)
+        return res
 
     def _draw_plans(self, shape, genparams):
         """Host draws of everything after the intensity plan, in the reference's order:
@@ -631,10 +589,7 @@ class FetalSynthGen:
         dplan = self.spatial_deform.plan(shape, random_shift=True, genparams=genparams.get("deform_params", {}))
         g = self.gamma.plan(genparams.get("gamma_params", {}))
         bplan = self.biasfield.plan(shape, genparams.get("bf_params", {}))
-        res = self.__dict__.get("_res64")
-        if res is None:
-            res = self._res64 = np.array(self.resolution)
-        rplan = self.resampled.plan(shape, res, genparams.get("resample_params", {}))
+        rplan = self.resampled.plan(shape, self._resolution64(), genparams.get("resample_params", {}))
         low_shape = rplan.new_size if rplan.active else shape
         nplan = self.noise.plan(low_shape, genparams.get("noise_params", {}))
         return dplan, g, bplan, rplan, nplan
@@ -729,16 +684,13 @@ class FetalSynthGen:
             gate_res = rs(1)[0]
         # ---- resampling (synthseg.py:63-80), then the noise gate
         rplan = ResamplePlan()
-        res = self.__dict__.get("_res64")
-        if res is None:
-            res = self._res64 = np.array(self.resolution)
         if gate_res < rs_.prob:
             u = rs(3)
             rplan.active = True
             # np.random.uniform(lo, hi) == lo + (hi - lo) * random_sample()
             spacing = np.array([1.0, 1.0, 1.0]) * (rs_.min_resolution + (rs_.max_resolution - rs_.min_resolution) * float(u[0]))
             rplan.spacing = spacing
-            rplan.stds, rplan.new_size, rplan.factors, rplan.tabs = T.resample_plan(tuple(shape), res, spacing, float(u[1]))
+            rplan.stds, rplan.new_size, rplan.factors, rplan.tabs = T.resample_plan(tuple(shape), self._resolution64(), spacing, float(u[1]))
             gate_noise = u[2]
         else:
             gate_noise = rs(1)[0]
@@ -819,13 +771,18 @@ class FetalSynthGen:
         c.keep = []
         return c
 
-    def _resolve(self, c):
-        f32_view = c.arena.f32
+    @staticmethod
+    def _intensity_views(c):
+        """mus / sigmas of the sample as device views of its uploaded arena."""
         c.seed_intensities, c.mus, c.sigmas = {}, None, None
         if c.gmm_plan is not None:
-            c.mus, c.sigmas = f32_view(c.gm_off[0], (c.gm_off[2],)), f32_view(c.gm_off[1], (c.gm_off[2],))
+            off_mus, off_sigmas, ntab = c.gm_off
+            c.mus, c.sigmas = c.arena.f32(off_mus, (ntab,)), c.arena.f32(off_sigmas, (ntab,))
             c.seed_intensities = {"mus": c.mus, "sigmas": c.sigmas}
-        c.bias_dev = f32_view(c.bias_off, tuple(c.bplan.grid.shape)) if c.bplan.active else None
+
+    def _resolve(self, c):
+        self._intensity_views(c)
+        c.bias_dev = c.arena.f32(c.bias_off, tuple(c.bplan.grid.shape)) if c.bplan.active else None
         c.gam = float(c.g) if c.g is not None else None
         c.spec = c.sb.build() if c.dplan.active else None
 
@@ -894,59 +851,40 @@ class FetalSynthGen:
         if seg_out is None:
             seg_out = torch.empty(shape, dtype=torch.uint8 if labels_u8 else torch.float32, device=dev)
         # what the previous call carried for this one (see next_key): the parameter block of exactly this key, on this stream
-        flags, block = 0, None
         stream_id = K._stream(dev).value
         pre = self.__dict__.setdefault("_pre", {}).pop(stream_id, None)  # one carried block per launch stream
         if pre is not None and pre[0] == key and pre[1] is kc:
             block, flags = pre[2], _KF_BLOCK_FILLED
-        if block is None:
-            block = torch.empty(kc.block_bytes, dtype=torch.uint8, device=dev)
+        else:
+            block, flags = torch.empty(kc.block_bytes, dtype=torch.uint8, device=dev), 0
         nblock = None
         if next_key is not None:
             next_key &= 0xFFFFFFFFFFFFFFFF
             nblock = torch.empty(kc.block_bytes, dtype=torch.uint8, device=dev)
             flags |= _KF_NEXT_NAMED
         iv = kc.iv
-        iv[_K_KEY] = key if key < (1 << 63) else key - (1 << 64)
+        iv[_K_KEY] = _i64(key)
         iv[_K_OUT] = out.data_ptr()
-        if labels_u8:
-            iv[_K_SEG_OUT], iv[_K_SEG_OUT_U8] = 0, seg_out.data_ptr()
-        else:
-            iv[_K_SEG_OUT], iv[_K_SEG_OUT_U8] = seg_out.data_ptr(), 0
+        iv[_K_SEG_OUT], iv[_K_SEG_OUT_U8] = (0, seg_out.data_ptr()) if labels_u8 else (seg_out.data_ptr(), 0)
         iv[_K_SEG_IN], iv[_K_SEG_IN_U8], iv[_K_BLOCK] = ent.seg_ptr, ent.twin_ptr, block.data_ptr()
         iv[_K_WS0], iv[_K_WS1], iv[_K_WS_LOW] = ws["ws0"].data_ptr(), ws["ws1"].data_ptr(), ws["low"].data_ptr()
         iv[_K_WS_ROWS], iv[_K_ROW_STRIDE] = (ws["rows"].data_ptr() if ws["rows"] is not None else 0), ws["stride"]
         iv[_K_SCALE01] = int(bool(scale01))
-        tr = None
-        if self.stage_traces is not None:
-            tr = StageTrace()
-            iv[_K_TRACE_EVENTS], iv[_K_TRACE_IDS], iv[_K_TRACE_CAP] = tr.slots()
-        else:
-            iv[_K_TRACE_EVENTS] = iv[_K_TRACE_IDS] = iv[_K_TRACE_CAP] = 0
+        events, tr = self._instrument()  # (whether this sample resamples is drawn inside the call)
+        iv[_K_TRACE_EVENTS], iv[_K_TRACE_IDS], iv[_K_TRACE_CAP] = tr.slots() if tr is not None else (0, 0, 0)
         iv[_K_BANK:_K_BANK + keyed.BANK_SLOTS] = ent.bank_ptrs
-        events = None
-        if self.blur_events is not None:
-            self._blur_tick += 1
-            if self._blur_tick % self.blur_events_every == 0:
-                events = (kc.lib.fsg_event_create(), kc.lib.fsg_event_create())
         iv[_K_EV_BLUR_BEGIN], iv[_K_EV_BLUR_END] = events if events is not None else (0, 0)
         # the subject's code volume (0: four label volumes)
         iv[_K_CODES], iv[_K_CODE_TUPLES], iv[_K_CODE_NTUPLES], iv[_K_CODE_STRIDE] = ent.codes, ent.code_tuples, ent.code_ntuples, ent.code_stride
         iv[_K_IMAGE_IN], iv[_K_IMAGE_OUT] = (image.data_ptr(), image_out.data_ptr()) if image is not None else (0, 0)
         iv[_K_PRIOR_IN] = prior.data_ptr() if prior is not None else 0
         iv[_K_FLAGS] = flags
-        if nblock is not None:
-            iv[_K_NEXT_KEY], iv[_K_NEXT_BLOCK] = (next_key if next_key < (1 << 63) else next_key - (1 << 64)), nblock.data_ptr()
-        else:
-            iv[_K_NEXT_KEY] = iv[_K_NEXT_BLOCK] = 0
+        iv[_K_NEXT_KEY], iv[_K_NEXT_BLOCK] = (_i64(next_key), nblock.data_ptr()) if nblock is not None else (0, 0)
         d = _lib.KeyedDraws()
-        import ctypes as C
-
         rc = kc.lib.fsg_keyed_sample_run(kc.handle, kc.ivp, len(kc.iv), C.byref(d), K._stream(dev))
         if events is not None:
             if rc == 0 and d.resample_active:
-                self.blur_events.append((events[0], events[1], [(a_, int(d.blur_ntaps[a_]) // 2) for a_ in range(3) if d.blur_ntaps[a_]],
-                                         tuple(int(v) for v in d.low_shape)))
+                self._keep_blur_events(events, d.blur_ntaps, d.low_shape)
             else:
                 kc.lib.fsg_event_destroy(events[0])
                 kc.lib.fsg_event_destroy(events[1])
@@ -961,16 +899,11 @@ class FetalSynthGen:
             tr.meta = {"shape": shape, "low_shape": tuple(d.low_shape) if d.resample_active else None,
                        "blur_ntaps": list(d.blur_ntaps), "label_bytes": 2 if ent.codes else 4, "draw_carried": flags & _KF_BLOCK_FILLED}
             self.stage_traces.append(tr)
-        if not d.deform_active:  # no warp ran: the labels pass through
-            if given:
-                seg_out.copy_(twin if labels_u8 else segmentation)
-            else:
-                seg_out = twin if labels_u8 else segmentation
-            if image is not None:  # ... and so does the image
-                if img_given:
-                    image_out.copy_(image)
-                else:
-                    image_out = image
+        if not d.deform_active:  # no warp ran: the labels pass through, and so does the image
+            passed = twin if labels_u8 else segmentation
+            seg_out = seg_out.copy_(passed) if given else passed
+            if image is not None:
+                image_out = image_out.copy_(image) if img_given else image
         params = keyed.params_of(d, block)
         if bank is None:  # no seeds were selected and no intensities drawn, as in the stage-by-stage path
             params["selected_seeds"], params["seed_intensities"] = {}, {}
@@ -1027,9 +960,6 @@ class FetalSynthGen:
         lazy_items=B: `items` is an iterator of B entries consumed one at a time, each right before that sample's host
         draws (callers that re-seed the global generators per sample, e.g. PrefetchingStream).
         labels_u8: the labels tensor as uint8 (same values), written as such by the fused warp."""
-        import ctypes as C
-
-
         if lazy_items is None:
             items = list(items)
             B = len(items)
@@ -1080,21 +1010,9 @@ class FetalSynthGen:
                         _lib.check(lib.fsg_sample_plan_pack(C.byref(plans[b]), fb["ivp"], _lib.PLAN_I.COUNT, fb["fvp"], _lib.PLAN_F.COUNT,
                                                             fb["tbp"]), "fsg_sample_plan_pack")
                 if ok:
-                    handles = (C.c_void_p * nstreams)()
-                    if nstreams > 1:
-                        fork = torch.cuda.Event()
-                        fork.record(main)
-                        for q in range(nstreams):
-                            side[q].wait_event(fork)
-                            handles[q] = side[q].cuda_stream
-                    else:
-                        handles[0] = K._stream(dev).value
-                    rc = lib.fsg_sample_run_batch(plans, B, handles, nstreams)
-                    if nstreams > 1:
-                        for q in range(nstreams):
-                            join = torch.cuda.Event()
-                            join.record(side[q])
-                            main.wait_event(join)
+                    handles = (C.c_void_p * nstreams)(*[s_.cuda_stream for s_ in side])
+                    with self._forked(main, side):
+                        rc = lib.fsg_sample_run_batch(plans, B, handles, nstreams)
                     if rc not in (_lib.E_ALIGN, _lib.E_TOOBIG):
                         _lib.check(rc, "fsg_sample_run_batch")
                         return out_all, seg_all, [None] * B, [self._synth_params(c, {}) for c in ctxs]
@@ -1136,25 +1054,33 @@ class FetalSynthGen:
             for img, _s, bank in items:  # priors are subject constants: computed (once) on the main stream, ahead of the fork
                 if img is not None and bank is None:
                     self._image_prior(img)
-        if nstreams > 1:
+        with self._forked(main, side):
+            for b, ((img, seg, seeds), key) in enumerate(zip(items, keys)):
+                with torch.cuda.stream(side[b % nstreams]):  # (the next sample of THIS stream: its draw job rides along)
+                    got = self._pipeline_keyed(seg, seeds, key & 0xFFFFFFFFFFFFFFFF, scale01, labels_u8, out=out_all[b],
+                                               seg_out=seg_all[b], next_key=keys[b + nstreams] if b + nstreams < B else None,
+                                               image=img, image_out=images[b])
+                if got is None:
+                    return None
+                params.append(got[3])
+        return out_all, seg_all, images, params
+
+    @staticmethod
+    @contextlib.contextmanager
+    def _forked(main, side):
+        """What the block enqueues on the `side` streams starts after what `main` holds now (one fork event), and `main` waits
+        for it afterwards (one join event per side stream).  `[main]`: nothing to order.  A block that raises is not joined."""
+        if len(side) > 1:
             fork = torch.cuda.Event()
             fork.record(main)
-            for q in range(nstreams):
-                side[q].wait_event(fork)
-        for b, ((img, seg, seeds), key) in enumerate(zip(items, keys)):
-            with torch.cuda.stream(side[b % nstreams]):  # (the next sample of THIS stream: its draw job rides along)
-                got = self._pipeline_keyed(seg, seeds, key & 0xFFFFFFFFFFFFFFFF, scale01, labels_u8, out=out_all[b],
-                                           seg_out=seg_all[b], next_key=keys[b + nstreams] if b + nstreams < B else None,
-                                           image=img, image_out=images[b])
-            if got is None:
-                return None
-            params.append(got[3])
-        if nstreams > 1:
-            for q in range(nstreams):
+            for s_ in side:
+                s_.wait_event(fork)
+        yield
+        if len(side) > 1:
+            for s_ in side:
                 join = torch.cuda.Event()
-                join.record(side[q])
+                join.record(s_)
                 main.wait_event(join)
-        return out_all, seg_all, images, params
 
     def _side_streams(self, n):
         cur = self.__dict__.setdefault("_batch_streams", [])
@@ -1171,52 +1097,51 @@ class FetalSynthGen:
         gmm_plan, dplan, bplan, rplan, nplan = c.gmm_plan, c.dplan, c.bplan, c.rplan, c.nplan
         mus, sigmas, gam, bias_dev, bias_tabs, spec = c.mus, c.sigmas, c.gam, c.bias_dev, c.bias_tabs, c.spec
         rs_tabs, back_tabs, has_art = c.rs_tabs, c.back_tabs, c.has_art
-        if True:
-            if gmm_plan is not None:
-                f = gmm_plan.field
-                z = f.device_tensor(dev) if f.host is not None else None
-                if c.label_parts is not None:
-                    output = K.gmm_sample_parts(c.label_parts, mus, sigmas, noise=z, seed=f.seed or 0,
-                                                stream_id=f.stream_id)
-                else:
-                    labels = c.labels
-                    if labels.dtype not in (torch.uint8, torch.int64):
-                        labels = labels.long()
-                    labels = labels.to(dev).contiguous()
-                    output = K.gmm_sample(labels, mus, sigmas, noise=z, seed=f.seed or 0, stream_id=f.stream_id)
+        if gmm_plan is not None:
+            f = gmm_plan.field
+            z = f.device_tensor(dev) if f.host is not None else None
+            if c.label_parts is not None:
+                output = K.gmm_sample_parts(c.label_parts, mus, sigmas, noise=z, seed=f.seed or 0,
+                                            stream_id=f.stream_id)
             else:
-                output = self._intensity_prior(image)
-            image = image.to(dev) if image is not None else None
-            # one init launch for every min/max key of the sample: [min x,y,z | zoom min] [zoom max | unused x3]
-            mm8 = K.new_minmax(dev, 4, 4)
-            if dplan.active:
-                image, segmentation, output = sd.run(dplan, image, segmentation, output, spec=spec,
-                                                     mm6=K.coords_floormin(spec, mm8), gamma=gam, bias=bias_dev,
-                                                     bias_tabs=bias_tabs, segmentation_u8=c.segmentation_u8)
-            else:
-                segmentation = segmentation.to(dev)
-                if gam is not None:
-                    output = K.gamma(output, gam)
-                if bplan.active:
-                    output = K.bias_mul(output, bias_dev, bias_tabs)
+                labels = c.labels
+                if labels.dtype not in (torch.uint8, torch.int64):
+                    labels = labels.long()
+                labels = labels.to(dev).contiguous()
+                output = K.gmm_sample(labels, mus, sigmas, noise=z, seed=f.seed or 0, stream_id=f.stream_id)
+        else:
+            output = self._intensity_prior(image)
+        image = image.to(dev) if image is not None else None
+        # one init launch for every min/max key of the sample: [min x,y,z | zoom min] [zoom max | unused x3]
+        mm8 = K.new_minmax(dev, 4, 4)
+        if dplan.active:
+            image, segmentation, output = sd.run(dplan, image, segmentation, output, spec=spec,
+                                                 mm6=K.coords_floormin(spec, mm8), gamma=gam, bias=bias_dev,
+                                                 bias_tabs=bias_tabs, segmentation_u8=c.segmentation_u8)
+        else:
+            segmentation = segmentation.to(dev)
+            if gam is not None:
+                output = K.gamma(output, gam)
+            if bplan.active:
+                output = K.bias_mul(output, bias_dev, bias_tabs)
 
-            fuse_scale = scale01 and not has_art
-            f = nplan.field if nplan.active else None
-            z = f.device_tensor(dev) if (f is not None and f.host is not None) else None
-            if rplan.active:
-                low = self.resampled.blur_resample(output.contiguous(), rplan.stds, rs_tabs,
-                                                   noise_std=nplan.std32 if nplan.active else 0.0, noise=z,
-                                                   seed=(f.seed if (f is not None and f.host is None) else None),
-                                                   stream_id=f.stream_id if f is not None else 0)
-                mm2 = K.zoom_minmax(low, back_tabs, mm=mm8[3:5])
-                output = K.zoom_normalise(low, back_tabs, mm2, mode=1 if fuse_scale else 0)
-            else:
-                if nplan.active:
-                    output = K.add_noise(output, nplan.std32, noise=z, seed=f.seed or 0, stream_id=f.stream_id)
-                if fuse_scale:
-                    output = K.scale(output, K.reduce_minmax(output), mode=1)
-            output, artifacts = self._apply_artifacts(output, segmentation, genparams)
-            if scale01 and has_art:
-                output = K.scale(output.contiguous(), K.reduce_minmax(output.contiguous()), mode=1)
+        fuse_scale = scale01 and not has_art
+        f = nplan.field if nplan.active else None
+        z = f.device_tensor(dev) if (f is not None and f.host is not None) else None
+        if rplan.active:
+            low = self.resampled.blur_resample(output.contiguous(), rplan.stds, rs_tabs,
+                                               noise_std=nplan.std32 if nplan.active else 0.0, noise=z,
+                                               seed=(f.seed if (f is not None and f.host is None) else None),
+                                               stream_id=f.stream_id if f is not None else 0)
+            mm2 = K.zoom_minmax(low, back_tabs, mm=mm8[3:5])
+            output = K.zoom_normalise(low, back_tabs, mm2, mode=1 if fuse_scale else 0)
+        else:
+            if nplan.active:
+                output = K.add_noise(output, nplan.std32, noise=z, seed=f.seed or 0, stream_id=f.stream_id)
+            if fuse_scale:
+                output = K.scale(output, K.reduce_minmax(output), mode=1)
+        output, artifacts = self._apply_artifacts(output, segmentation, genparams)
+        if scale01 and has_art:
+            output = K.scale(output.contiguous(), K.reduce_minmax(output.contiguous()), mode=1)
 
         return output, segmentation, image, self._synth_params(c, artifacts)

@@ -22,6 +22,7 @@ from . import _lib
 from . import kernels as K
 from . import seedcodes
 from . import tables as T
+from .identity import IdentityCache
 
 
 def config_of(gen, shape) -> _lib.KeyedConfig:
@@ -66,16 +67,12 @@ BANK_SLOTS = 64  # seed volumes the BANK slots of fsg_keyed_sample_run's argumen
 
 
 class Subject:
-    """Addresses of one subject's volumes as fsg_keyed_sample_run takes them (the C side only sees addresses), and the
-    objects they were taken from: weak references, and the segmentation's in-place version."""
+    """Addresses of one subject's volumes as fsg_keyed_sample_run takes them (the C side only sees addresses); which objects
+    they were taken from is the business of `KeyedContext._subjects`."""
 
-    __slots__ = ("bank_ref", "seg_ref", "seg_version", "bank_ptrs", "twin_ptr", "seg_ptr", "codes", "code_tuples", "code_ntuples",
-                 "code_stride")
+    __slots__ = ("bank_ptrs", "twin_ptr", "seg_ptr", "codes", "code_tuples", "code_ntuples", "code_stride")
 
-    def __init__(self, bank, seg, bank_ptrs, twin_ptr):
-        # bank None: a subject without seeds (its image is the intensity prior), no seed volume is read
-        self.bank_ref = weakref.ref(bank) if bank is not None else (lambda: None)
-        self.seg_ref, self.seg_version = weakref.ref(seg), seg._version
+    def __init__(self, seg, bank_ptrs, twin_ptr):
         self.bank_ptrs, self.twin_ptr, self.seg_ptr = bank_ptrs, twin_ptr, seg.data_ptr()  # twin_ptr 0: no uint8 twin yet
         self.codes = self.code_tuples = self.code_ntuples = self.code_stride = 0  # 0: no code volume (KeyedContext._codes)
 
@@ -94,7 +91,8 @@ class KeyedContext:
         self.block_bytes = int(self.lib.fsg_keyed_block_bytes(h))
         self.iv = np.zeros(_lib.KEYED_I.COUNT, dtype=np.int64)
         self.ivp = self.iv.ctypes.data
-        self._subjects = {}
+        self._subjects = IdentityCache()  # (bank | None, segmentation) under the segmentation's version -> Subject
+        self._banks = weakref.WeakSet()   # every bank a subject was made of: `forget_subjects` drops their code volumes
         self.use_codes = True  # the subject's seed volumes as one uint16 code volume (seedcodes.py, built on first use)
         self._tables_ready = False
         self._keep = []  # device tables registered with the context
@@ -145,9 +143,8 @@ class KeyedContext:
     def subject(self, bank, seg, twin):
         """The `Subject` of (bank slots, float32 segmentation, its uint8 twin), validated once per (bank, segmentation) object
         pair -- the C side only sees addresses."""
-        key = (id(bank), id(seg))
-        ent = self._subjects.get(key)
-        if ent is not None and ent.bank_ref() is bank and ent.seg_ref() is seg and ent.seg_version == seg._version:
+        ent = self._subjects.get((bank, seg), seg._version)
+        if ent is not None:
             if twin is not None and ent.twin_ptr == 0:
                 ent.twin_ptr = twin.data_ptr()
             self._codes(bank, ent)  # (built once per bank object; a rewrite of a seed volume through torch rebuilds it)
@@ -166,12 +163,18 @@ class KeyedContext:
                     raise ValueError(f"seed volume ({n}, {m}): expected a contiguous uint8 tensor of shape {shape} on {dev}, "
                                      f"got {part.dtype} {tuple(part.shape)} on {part.device}")
                 ptrs[4 * (n - c.min_subclusters) + (m - 1)] = part.data_ptr()
-        ent = Subject(bank, seg, ptrs, 0 if twin is None else twin.data_ptr())
+        ent = Subject(seg, ptrs, 0 if twin is None else twin.data_ptr())
         self._codes(bank, ent)  # ~1 ms once per bank object (one pass over its volumes), little next to loading the subject
-        if len(self._subjects) > 4096:
-            self._subjects.clear()
-        self._subjects[key] = ent
+        self._subjects.put((bank, seg), ent, stamp=seg._version)
+        if bank is not None:  # (None: a subject without seeds -- its image is the intensity prior -- reads no seed volume)
+            self._banks.add(bank)
         return ent
+
+    def forget_subjects(self):
+        """Drop every pointer block, and the code volume of every bank one was made of (`FetalSynthGen.invalidate_label_twins`)."""
+        self._subjects.clear()
+        for bank in self._banks:
+            bank.__dict__.pop("_seed_codes", None)
 
     def _codes(self, bank, ent):
         """The code fields of `ent` = the subject's code volume (seedcodes.build), kept ON the bank object so that it lives and dies with it.

@@ -48,13 +48,16 @@ def test_generator_pickle_drops_its_process_local_state():
     parent_addresses = {fb["ivp"], fb["fvp"], fb["tbp"]}
     # what a generator that has produced samples carries (device tensors stood in for by CPU tensors: no GPU here)
     gen._ws[(shape, 0, 0)] = {"ws0": torch.zeros(8), "ws1": torch.zeros(8), "low": torch.zeros(8), "rows": None, "stride": 0}
-    gen.__dict__["_twins"] = {"by_id": {1: [None, 0, torch.zeros(8, dtype=torch.uint8), 2]}, "bytes": 8}
+    seg, image = torch.zeros(8), torch.zeros(8)
+    gen.register_label_twin(seg, torch.zeros(8, dtype=torch.uint8))
+    gen.register_image_prior(image, torch.zeros(8))
     gen.__dict__["_rs_dt"] = {((8, 8, 8), shape): object()}
     gen.blur_events = [(1, 2, [])]
-    fb["validated"][42] = (None, shape)
+    fb["validated"].put(seg, shape)
 
     clone = pickle.loads(pickle.dumps(gen))
-    for name in ("_flat", "_twins", "_rs_dt", "_batch_streams", "_keyed"):
+    assert len(gen._twins) == 1 and len(gen._priors) == 1 and len(fb["validated"]) == 1
+    for name in ("_flat", "_twins", "_priors", "_rs_dt", "_batch_streams", "_keyed"):
         assert name not in clone.__dict__, name
     assert clone._ws == {} and clone.blur_events is None
     _assert_clean(clone, parent_addresses)
@@ -65,7 +68,7 @@ def test_generator_pickle_drops_its_process_local_state():
     # and the rebuilt flat buffers point at the clone's own arrays
     fb2 = clone._flat_buffers()
     assert fb2["ivp"] == fb2["iv"].ctypes.data and fb2["fvp"] == fb2["fv"].ctypes.data and fb2["tbp"] == fb2["tb"].ctypes.data
-    assert fb2["validated"] == {}
+    assert len(fb2["validated"]) == 0
     # the host plans of the clone are those of the original under the same seeds
     for g in (gen, clone):
         np.random.seed(3)
