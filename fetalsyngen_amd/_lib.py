@@ -25,7 +25,7 @@ PKG = Path(__file__).resolve().parent
 LIB_PATH = Path(os.environ.get("FSG_LIB", PKG / "libfsg_hip.so"))  # FSG_LIB: A/B another build of the same ABI
 HEADER_PATH = PKG.parent / "include" / "fsg_hip.h"
 
-GROUPS = ("PLAN_I", "PLAN_F", "KEYED_I", "KEYED_FLAG", "TUNE", "ST", "KT", "SA", "SIZEOF")
+GROUPS = ("PLAN_I", "PLAN_F", "KEYED_I", "KEYED_FLAG", "KO", "TUNE", "ST", "KT", "SA", "SIZEOF")
 # fsg_tap only ever crosses the boundary as the address of a DEVICE table (tensor.data_ptr()), which POINTER(Tap) would refuse
 DEVICE_STRUCTS = ("fsg_tap",)
 

@@ -104,25 +104,47 @@ int gaussian_taps(double sigma, float* taps, int cap) {
   return n;
 }
 
-int draw(const KeyedCtx& C, uint64_t key, fsg_keyed_draws& d) {
+// Every scalar of sample `key`.  o (may be null): values the caller fixed (fsg_keyed_overrides).  A draw keeps its slot whether
+// or not it is used, so an override replaces one value and shifts nothing; a forced stage takes its other members from the
+// key's slots.  The gates follow the reference's plan() methods (affine_nonrigid.py:140-145, synthseg.py:157-160,:63-66,:218-221,
+// :263-266: "gate or the parameter is given").
+int draw(const KeyedCtx& C, uint64_t key, const fsg_keyed_overrides* o, fsg_keyed_draws& d) {
   const fsg_keyed_config& c = C.cfg;
+  const uint32_t m = o ? o->mask : 0u;
+  auto has = [m](uint32_t bit) { return (m & bit) != 0; };
+  auto finite3 = [](const double v[3]) { return std::isfinite(v[0]) && std::isfinite(v[1]) && std::isfinite(v[2]); };
   std::memset(&d, 0, sizeof d);
   d.key = key;
   d.ntab = c.nlabels;
+  d.overridden = m;
   const int span = c.max_subclusters - c.min_subclusters + 1;
-  for (int m = 0; m < c.meta_labels; ++m) {
-    int pick = c.min_subclusters + (int)(slot_u(key, S_SUB0 + m) * span);
-    d.subclusters[m] = pick > c.max_subclusters ? c.max_subclusters : pick;
+  for (int l = 0; l < c.meta_labels; ++l) {
+    if (has(FSG_KO_SUBCLUSTERS)) {
+      if (o->subclusters[l] < c.min_subclusters || o->subclusters[l] > c.max_subclusters) return FSG_E_BADARG;
+      d.subclusters[l] = o->subclusters[l];
+      continue;
+    }
+    int pick = c.min_subclusters + (int)(slot_u(key, S_SUB0 + l) * span);
+    d.subclusters[l] = pick > c.max_subclusters ? c.max_subclusters : pick;
+  }
+  if (m & (FSG_KO_MUS | FSG_KO_SIGMAS)) {
+    if (o->ntab != c.nlabels || (has(FSG_KO_MUS) && !o->mus_dev) || (has(FSG_KO_SIGMAS) && !o->sigmas_dev)) return FSG_E_BADARG;
+    d.mus_in = has(FSG_KO_MUS) ? o->mus_dev : 0;
+    d.sigmas_in = has(FSG_KO_SIGMAS) ? o->sigmas_dev : 0;
   }
   // ---- deformation
-  if (slot_u(key, S_DEFORM) < c.deform_prob) {
+  const uint32_t deform_bits = FSG_KO_FORCE_DEFORM | FSG_KO_FLIP | FSG_KO_ROTATIONS | FSG_KO_SHEARS | FSG_KO_SCALINGS |
+                               FSG_KO_NONLIN_SCALE | FSG_KO_NONLIN_STD | FSG_KO_FIELD_DIMS;
+  if (slot_u(key, S_DEFORM) < c.deform_prob || (m & deform_bits)) {
     d.deform_active = 1;
-    d.flip = slot_u(key, S_FLIP) < c.flip_prb ? 1 : 0;
+    d.flip = has(FSG_KO_FLIP) ? (o->flip ? 1 : 0) : (slot_u(key, S_FLIP) < c.flip_prb ? 1 : 0);
     for (int a = 0; a < 3; ++a) {
-      d.rotations[a] = (2 * c.max_rotation * slot_u(key, S_ROT + a) - c.max_rotation) / 180.0 * 3.141592653589793;
-      d.shears[a] = 2 * c.max_shear * slot_u(key, S_SHEAR + a) - c.max_shear;
-      d.scalings[a] = 1 + (2 * c.max_scaling * slot_u(key, S_SCALE + a) - c.max_scaling);
+      d.rotations[a] = has(FSG_KO_ROTATIONS) ? o->rotations[a]
+                                             : (2 * c.max_rotation * slot_u(key, S_ROT + a) - c.max_rotation) / 180.0 * 3.141592653589793;
+      d.shears[a] = has(FSG_KO_SHEARS) ? o->shears[a] : 2 * c.max_shear * slot_u(key, S_SHEAR + a) - c.max_shear;
+      d.scalings[a] = has(FSG_KO_SCALINGS) ? o->scalings[a] : 1 + (2 * c.max_scaling * slot_u(key, S_SCALE + a) - c.max_scaling);
     }
+    if (!finite3(d.rotations) || !finite3(d.shears) || !finite3(d.scalings)) return FSG_E_BADARG;
     affine_matrix(d.rotations, d.shears, d.scalings, d.A);
     for (int a = 0; a < 3; ++a) {
       // float32 centre + float64 shift (affine_nonrigid.py:271-290); with no room the shift is exactly 0
@@ -133,55 +155,86 @@ int draw(const KeyedCtx& C, uint64_t key, fsg_keyed_draws& d) {
     }
     if (c.nonlinear) {
       d.nonlinear = 1;
-      d.nonlin_scale = c.nonlin_scale_min + slot_u(key, S_NL_SCALE) * (c.nonlin_scale_max - c.nonlin_scale_min);
-      for (int a = 0; a < 3; ++a) d.field_dims[a] = (int)std::nearbyint(d.nonlin_scale * (double)c.shape[a]);
-      d.nonlin_std = c.nonlin_std_max * slot_u(key, S_NL_STD);
+      d.nonlin_scale = has(FSG_KO_NONLIN_SCALE)
+                           ? o->nonlin_scale
+                           : c.nonlin_scale_min + slot_u(key, S_NL_SCALE) * (c.nonlin_scale_max - c.nonlin_scale_min);
+      d.nonlin_std = has(FSG_KO_NONLIN_STD) ? o->nonlin_std : c.nonlin_std_max * slot_u(key, S_NL_STD);
+      if (!std::isfinite(d.nonlin_scale) || !std::isfinite(d.nonlin_std)) return FSG_E_BADARG;
+      for (int a = 0; a < 3; ++a) {
+        if (has(FSG_KO_FIELD_DIMS)) {
+          d.field_dims[a] = o->field_dims[a];
+        } else {
+          const double v = std::nearbyint(d.nonlin_scale * (double)c.shape[a]);
+          if (has(FSG_KO_NONLIN_SCALE) && v > (double)KT_CAP) return FSG_E_TOOBIG;
+          d.field_dims[a] = (int)v;
+        }
+        if (m & (FSG_KO_FIELD_DIMS | FSG_KO_NONLIN_SCALE)) {  // (a drawn size outside the tables is refused by the run, as before)
+          if (d.field_dims[a] < 1) return FSG_E_BADARG;
+          if (d.field_dims[a] > KT_CAP) return FSG_E_TOOBIG;
+        }
+      }
     }
   }
   // ---- gamma
-  if (slot_u(key, S_GAMMA_GATE) < c.gamma_prob) {
+  if (slot_u(key, S_GAMMA_GATE) < c.gamma_prob || has(FSG_KO_GAMMA)) {
     d.gamma_active = 1;
-    d.gamma = std::exp(c.gamma_std * slot_n(key, S_GAMMA));
+    d.gamma = has(FSG_KO_GAMMA) ? o->gamma : std::exp(c.gamma_std * slot_n(key, S_GAMMA));
+    if (has(FSG_KO_GAMMA) && !(std::isfinite(d.gamma) && d.gamma > 0)) return FSG_E_BADARG;
   }
   // ---- bias field
-  if (slot_u(key, S_BIAS_GATE) < c.bias_prob) {
+  if (slot_u(key, S_BIAS_GATE) < c.bias_prob || (m & (FSG_KO_FORCE_BIAS | FSG_KO_BF_SCALE | FSG_KO_BF_STD))) {
     d.bias_active = 1;
-    d.bf_scale = c.bf_scale_min + slot_u(key, S_BF_SCALE) * (c.bf_scale_max - c.bf_scale_min);
+    d.bf_scale = has(FSG_KO_BF_SCALE) ? o->bf_scale : c.bf_scale_min + slot_u(key, S_BF_SCALE) * (c.bf_scale_max - c.bf_scale_min);
+    d.bf_std = has(FSG_KO_BF_STD) ? o->bf_std : c.bf_std_min + (c.bf_std_max - c.bf_std_min) * slot_u(key, S_BF_STD);
+    if (!std::isfinite(d.bf_scale) || !std::isfinite(d.bf_std)) return FSG_E_BADARG;
     for (int a = 0; a < 3; ++a) {
-      const int v = (int)std::nearbyint(d.bf_scale * (double)c.shape[a]);
-      d.bias_dims[a] = v < 1 ? 1 : v;
+      const double v = std::nearbyint(d.bf_scale * (double)c.shape[a]);
+      if (has(FSG_KO_BF_SCALE) && v > (double)KT_CAP) return FSG_E_TOOBIG;
+      d.bias_dims[a] = v < 1 ? 1 : (int)v;
     }
-    d.bf_std = c.bf_std_min + (c.bf_std_max - c.bf_std_min) * slot_u(key, S_BF_STD);
   }
-  // ---- resampling (synthseg.py:63-84)
+  // ---- resampling (synthseg.py:63-84), per axis
   for (int a = 0; a < 3; ++a) d.low_shape[a] = c.shape[a];
-  if (slot_u(key, S_RES_GATE) < c.resample_prob) {
+  if (slot_u(key, S_RES_GATE) < c.resample_prob || has(FSG_KO_SPACING)) {
     d.resample_active = 1;
-    d.spacing = c.min_resolution + (c.max_resolution - c.min_resolution) * slot_u(key, S_SPACING);
+    const double drawn = c.min_resolution + (c.max_resolution - c.min_resolution) * slot_u(key, S_SPACING);
     d.u_std = slot_u(key, S_RES_STD);
     for (int a = 0; a < 3; ++a) {
-      double sd = (0.85 + 0.3 * d.u_std) * 1.6094379124341003 / 3.141592653589793 * d.spacing / c.resolution[a];
-      if (d.spacing <= c.resolution[a]) sd = 0.0;
+      const double sp = has(FSG_KO_SPACING) ? o->spacing[a] : drawn;
+      if (has(FSG_KO_SPACING) && !(std::isfinite(sp) && sp > 0)) return FSG_E_BADARG;
+      d.spacing3[a] = sp;
+      double sd = (0.85 + 0.3 * d.u_std) * 1.6094379124341003 / 3.141592653589793 * sp / c.resolution[a];
+      if (sp <= c.resolution[a]) sd = 0.0;
       d.stds[a] = sd;
-      d.low_shape[a] = (int)((double)c.shape[a] * c.resolution[a] / d.spacing);
+      const double low = (double)c.shape[a] * c.resolution[a] / sp;
+      if (has(FSG_KO_SPACING)) {
+        if (low < 1) return FSG_E_BADARG;
+        if (low >= (double)(KT_CAP + 1)) return FSG_E_TOOBIG;
+      }
+      d.low_shape[a] = (int)low;
       d.blur_ntaps[a] = sd > 0 ? 2 * (int)std::ceil(3.0 * sd) + 1 : 0;
     }
+    d.spacing = d.spacing3[0];
   }
   // ---- noise
-  if (slot_u(key, S_NOISE_GATE) < c.noise_prob) {
+  if (slot_u(key, S_NOISE_GATE) < c.noise_prob || has(FSG_KO_NOISE_STD)) {
     d.noise_active = 1;
-    d.noise_std = c.noise_std_min + (c.noise_std_max - c.noise_std_min) * slot_u(key, S_NOISE_STD);
+    d.noise_std = has(FSG_KO_NOISE_STD) ? o->noise_std : c.noise_std_min + (c.noise_std_max - c.noise_std_min) * slot_u(key, S_NOISE_STD);
+    if (!std::isfinite(d.noise_std)) return FSG_E_BADARG;
     d.noise_std32 = (float)d.noise_std;
   }
   // ---- layout of the device parameter block
-  int off = 0;
-  d.off_mm8 = off; off = align256(off + 8 * 4);
-  d.off_slots = off; off = align256(off + FSG_MM_NSLOTS * FSG_MM_SLOT_STRIDE * 4);
-  d.off_mus = off; off = align256(off + 256 * 4);
-  d.off_sigmas = off; off = align256(off + 256 * 4);
-  d.off_bias = off; off = align256(off + (d.bias_active ? d.bias_dims[0] * d.bias_dims[1] * d.bias_dims[2] * 4 : 0));
-  d.off_field = off; off = align256(off + (d.nonlinear ? d.field_dims[0] * d.field_dims[1] * d.field_dims[2] * 12 : 0));
-  d.block_bytes = off;
+  auto align256l = [](int64_t v) { return (v + 255) & ~(int64_t)255; };
+  int64_t off = 0;
+  d.off_mm8 = (int32_t)off; off = align256l(off + 8 * 4);
+  d.off_slots = (int32_t)off; off = align256l(off + FSG_MM_NSLOTS * FSG_MM_SLOT_STRIDE * 4);
+  d.off_mus = (int32_t)off; off = align256l(off + 256 * 4);
+  d.off_sigmas = (int32_t)off; off = align256l(off + 256 * 4);
+  d.off_bias = (int32_t)off; off = align256l(off + (d.bias_active ? (int64_t)d.bias_dims[0] * d.bias_dims[1] * d.bias_dims[2] * 4 : 0));
+  if (off > 0x7FFFFF00LL) return FSG_E_TOOBIG;
+  d.off_field = (int32_t)off; off = align256l(off + (d.nonlinear ? (int64_t)d.field_dims[0] * d.field_dims[1] * d.field_dims[2] * 12 : 0));
+  if (off > 0x7FFFFF00LL) return FSG_E_TOOBIG;
+  d.block_bytes = (int32_t)off;
   return 0;
 }
 
@@ -210,6 +263,8 @@ int fill_draw(const KeyedCtx& C, const fsg_keyed_draws& d, void* block_dev, Draw
   P.field_std = (float)d.nonlin_std;
   std::memcpy(P.seed_labels, C.cfg.seed_labels, 256);
   std::memcpy(P.gen_classes, C.cfg.generation_classes, 256);
+  P.mus_in = (const float*)(uintptr_t)d.mus_in;
+  P.sigmas_in = (const float*)(uintptr_t)d.sigmas_in;
   const int work = ((P.nbias + 3) >> 2) + ((P.nfield + 3) >> 2);
   grid = 1u + (unsigned)((work + 255) / 256);
   return 0;
@@ -281,7 +336,12 @@ int64_t fsg_keyed_block_bytes(void* ctx) { return ctx ? ((KeyedCtx*)ctx)->block_
 
 int fsg_keyed_draw(void* ctx, uint64_t key, fsg_keyed_draws* out) {
   if (!ctx || !out) return FSG_E_BADARG;
-  return draw(*(KeyedCtx*)ctx, key, *out);
+  return draw(*(KeyedCtx*)ctx, key, nullptr, *out);
+}
+
+int fsg_keyed_draw_with(void* ctx, uint64_t key, const fsg_keyed_overrides* overrides, fsg_keyed_draws* out) {
+  if (!ctx || !out) return FSG_E_BADARG;
+  return draw(*(KeyedCtx*)ctx, key, overrides, *out);
 }
 
 int fsg_keyed_fill_block(void* ctx, const fsg_keyed_draws* d, void* block_dev, void* stream) {
@@ -294,10 +354,13 @@ int fsg_keyed_sample_run(void* ctx, const int64_t* iv, int niv, fsg_keyed_draws*
   if (!K || !iv || niv < FSG_KEYED_I_COUNT) return FSG_E_BADARG;
   const fsg_keyed_config& c = K->cfg;
   fsg_keyed_draws d;
-  int rc = draw(*K, (uint64_t)iv[FSG_KEYED_I_KEY], d);
+  const bool ext = niv >= FSG_KEYED_I_COUNT_OV;  // the two slots behind FSG_KEYED_I_COUNT
+  const fsg_keyed_overrides* ov = ext ? (const fsg_keyed_overrides*)(uintptr_t)iv[FSG_KEYED_I_OVERRIDES] : nullptr;
+  int rc = draw(*K, (uint64_t)iv[FSG_KEYED_I_KEY], ov, d);
   if (rc) return rc;
   if (draws_out) *draws_out = d;
-  if (d.block_bytes > K->block_bytes) return FSG_E_TOOBIG;
+  const int64_t cap = ext && iv[FSG_KEYED_I_BLOCK_BYTES] > 0 ? iv[FSG_KEYED_I_BLOCK_BYTES] : K->block_bytes;
+  if (d.block_bytes > cap) return FSG_E_TOOBIG;
   char* base = (char*)(uintptr_t)iv[FSG_KEYED_I_BLOCK];
   if (!base) return FSG_E_BADARG;
 
@@ -405,13 +468,14 @@ int fsg_keyed_sample_run(void* ctx, const int64_t* iv, int niv, fsg_keyed_draws*
 
   // ---- look-ahead: the caller names the next sample of this stream; its draw job rides in this sample's floor(min) launch -----
   const int64_t flags = iv[FSG_KEYED_I_FLAGS];
-  const bool draw_done = (flags & 1) != 0;  // this sample's block was filled beside the previous sample's floor(min) pass
+  // this sample's block was filled beside the previous sample's floor(min) pass (never one with overrides: a carried job drew every table)
+  const bool draw_done = (flags & 1) != 0 && !ov;
   DrawK next_draw;
   int32_t rode = 0;
   char* nbase = (char*)(uintptr_t)iv[FSG_KEYED_I_NEXT_BLOCK];
   if (nbase && (flags & 4)) {
     fsg_keyed_draws dn;
-    rc = draw(*K, (uint64_t)iv[FSG_KEYED_I_NEXT_KEY], dn);
+    rc = draw(*K, (uint64_t)iv[FSG_KEYED_I_NEXT_KEY], nullptr, dn);
     if (rc) return rc;
     if (dn.block_bytes > K->block_bytes) return FSG_E_TOOBIG;
     unsigned grid = 0;

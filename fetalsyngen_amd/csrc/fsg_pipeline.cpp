@@ -287,6 +287,7 @@ extern "C" int64_t fsg_sample_plan_layout(int which) {
     case 4: return (int64_t)offsetof(fsg_sample_plan, ws_seq);
     case 5: return (int64_t)offsetof(fsg_sample_plan, code_sel);
     case FSG_SIZEOF_SAMPLE_IMAGE: return (int64_t)sizeof(fsg_sample_image);
+    case FSG_SIZEOF_KEYED_OVERRIDES: return (int64_t)sizeof(fsg_keyed_overrides);
     default: return -1;
   }
 }

@@ -24,6 +24,8 @@ struct DrawK {
   float bias_std, field_std;
   uint8_t seed_labels[256];
   uint8_t gen_classes[256];
+  const float* mus_in;     // given tables (fsg_keyed_overrides), null = drawn; may alias mus / sigmas
+  const float* sigmas_in;
 };
 
 __device__ __forceinline__ float keyed_uniform(uint64_t key, uint64_t stream, uint32_t e) {
@@ -33,7 +35,9 @@ __device__ __forceinline__ float keyed_uniform(uint64_t key, uint64_t stream, ui
   return (float)(w >> 8) * 5.9604644775390625e-08f;  // [0, 1), 24 bits: torch.rand's float32 grid
 }
 
-// Workgroup 0: min/max keys, GMM tables (rand_gmm.py:120-145).  Workgroups >= 1: one Philox block (4 normals) per thread of
+// Workgroup 0: min/max keys, GMM tables (rand_gmm.py:120-145; a given table is loaded where it would have been drawn -- every
+// entry is read before the barrier and stored after the last one, so it may be the block's own table --, the tie step and
+// the stores are the same).  Workgroups >= 1: one Philox block (4 normals) per thread of
 // the bias grid (stream 4, synthseg.py:172-176) and the coarse displacement grid (stream 3, affine_nonrigid.py:318).
 __device__ __forceinline__ void keyed_draw_body(const DrawK& P, const int blk) {
   const int tid = threadIdx.x;
@@ -46,8 +50,8 @@ __device__ __forceinline__ void keyed_draw_body(const DrawK& P, const int blk) {
     __shared__ float s_mu[256];
     float sg = 0.f;
     if (tid < P.nlabels) {
-      s_mu[tid] = 25.f + 200.f * keyed_uniform(P.key, 5, (uint32_t)tid);
-      sg = 5.f + 20.f * keyed_uniform(P.key, 5, (uint32_t)(P.nlabels + tid));
+      s_mu[tid] = P.mus_in ? P.mus_in[tid] : 25.f + 200.f * keyed_uniform(P.key, 5, (uint32_t)tid);
+      sg = P.sigmas_in ? P.sigmas_in[tid] : 5.f + 20.f * keyed_uniform(P.key, 5, (uint32_t)(P.nlabels + tid));
     }
     __syncthreads();
     float tied = 0.f;

@@ -526,9 +526,15 @@ class FetalSynthDataset(FetalDataset):
             "segm_paths": str(self.img_paths[idx]),  # sic: the reference logs the image path here (ref :301)
             "seeds": str(self.seed_path),
         }
+        key = None
+        if genparams and self.base_seed is not None and "key" not in genparams and self.generator._is_keyed():
+            # keyed mode: `sample_with_meta(idx, {...})` is `self[idx]` with those parameters fixed
+            from .. import sharding
+
+            key = sharding.sample_key(self.base_seed, self.epoch * len(self) + int(idx))
         t0 = time.time()
         gen_output, segmentation, image, synth_params = self.generator._pipeline(
-            image, segm, seeds, genparams, scale01=True,
+            image, segm, seeds, genparams, scale01=True, key=key,
             segmentation_u8=self._segmentation_u8(idx) if self.return_device else None, labels_u8=self.return_device)
         if image is not None:
             from .. import kernels as K
@@ -566,7 +572,7 @@ class FetalSynthDataset(FetalDataset):
         keys = None
         if self._keyed_images():
             images = [self._subject(i)[3] for i in indices]
-            if self.base_seed is not None and genparams_list is None:
+            if self.base_seed is not None:  # (with a genparams_list too: sample b is its key's sample with those values fixed)
                 from .. import sharding
 
                 keys = [sharding.sample_key(self.base_seed, self.epoch * len(self) + i) for i in indices]

@@ -52,6 +52,7 @@ _K_SCALE01, _K_TRACE_EVENTS, _K_TRACE_IDS, _K_TRACE_CAP, _K_BANK = _KI.SCALE01, 
 _K_EV_BLUR_BEGIN, _K_EV_BLUR_END, _K_CODES, _K_CODE_TUPLES = _KI.EV_BLUR_BEGIN, _KI.EV_BLUR_END, _KI.CODES, _KI.CODE_TUPLES
 _K_CODE_NTUPLES, _K_CODE_STRIDE, _K_FLAGS, _K_NEXT_KEY, _K_NEXT_BLOCK = _KI.CODE_NTUPLES, _KI.CODE_STRIDE, _KI.FLAGS, _KI.NEXT_KEY, _KI.NEXT_BLOCK
 _K_IMAGE_IN, _K_IMAGE_OUT, _K_PRIOR_IN = _KI.IMAGE_IN, _KI.IMAGE_OUT, _KI.PRIOR_IN
+_K_OVERRIDES, _K_BLOCK_BYTES = _KI.OVERRIDES, _KI.BLOCK_BYTES
 _KF_BLOCK_FILLED, _KF_NEXT_NAMED = _KF.BLOCK_FILLED, _KF.NEXT_NAMED
 _SEEN_ONCE, _NO_TWIN = object(), object()  # what `_twins` holds for a label volume that has no uint8 twin
 
@@ -807,18 +808,19 @@ class FetalSynthGen:
 
     def _keyed_applies(self, image, segmentation, seeds, genparams, segmentation_u8, labels_u8) -> bool:
         """image: None, or a CUDA float32 contiguous tensor of the segmentation's shape (anything else takes the fallback);
-        seeds: a device-resident bank, or None with an image (the image is the intensity prior)."""
+        seeds: a device-resident bank, or None with an image (the image is the intensity prior).  `genparams` do not
+        matter: the keyed path honours them (`keyed.overrides_of`)."""
         if image is not None:
             if not (torch.is_tensor(image) and image.is_cuda and image.dtype == torch.float32 and image.is_contiguous()
                     and torch.is_tensor(segmentation) and image.shape == segmentation.shape and image.device == segmentation.device):
                 return False
-        return (self.native_pipeline and not genparams and (hasattr(seeds, "parts") or (seeds is None and image is not None))
+        return (self.native_pipeline and (hasattr(seeds, "parts") or (seeds is None and image is not None))
                 and self.intensity_generator.meta_labels <= 4 and torch.is_tensor(segmentation) and segmentation.is_cuda
                 and segmentation.dtype == torch.float32 and segmentation.is_contiguous()
                 and (segmentation_u8 is None or labels_u8) and not any(a is not None for a in self.artifacts.values()))
 
     def _pipeline_keyed(self, segmentation, bank, key, scale01, labels_u8, out=None, seg_out=None, next_key=None, image=None,
-                        image_out=None):
+                        image_out=None, genparams=None):
         """One keyed sample: pointers + key -> ONE native call (draws, the draw kernel, the launch sequence).  Returns
         (image, labels, warped real image | None, synth_params) or None when the sample is outside the fused kernels' domain.
 
@@ -828,7 +830,12 @@ class FetalSynthGen:
 
         next_key: the key of the sample the caller will ask for NEXT on this stream (a batch, a stream of indices): its draw job
         then rides in this sample's floor(min) launch (fsg_keyed_sample_run's look-ahead) -- one launch less on the next sample's
-        critical path, the same volumes.  If the next call is for another key or stream, the carried block is simply not used."""
+        critical path, the same volumes.  If the next call is for another key or stream, the carried block is simply not used.
+
+        genparams (validated): the values the caller fixed (`keyed.overrides_of`); everything else is the key's.  Such a sample
+        never uses a carried block (that one holds the key's own tables), and its block, row workspace and low-res scratch are
+        sized from its own draws: overridden grids and low-res sizes may exceed what the configuration can draw.  What cannot
+        be honoured raises ValueError."""
         from .. import keyed
 
         shape = tuple(segmentation.shape)
@@ -844,7 +851,16 @@ class FetalSynthGen:
         img_given = image_out is not None
         if image is not None and image_out is None:
             image_out = torch.empty(shape, dtype=torch.float32, device=dev)
-        ws = self._workspace(shape, kc.rows_need)
+        ov = keyed.overrides_of(genparams, kc.cfg, dev) if genparams else None
+        rows_need, block_bytes, low = kc.rows_need, kc.block_bytes, None
+        if ov is not None:
+            d0 = kc.draws(key, ov)
+            kc.ensure_tables(d0)
+            rows_need = max(rows_need, 3 * d0.field_dims[2] + d0.bias_dims[2])
+            block_bytes = max(block_bytes, d0.block_bytes)
+            if d0.resample_active and int(np.prod(list(d0.low_shape))) > int(np.prod(shape)):  # a spacing below the resolution
+                low = torch.empty(int(np.prod(list(d0.low_shape))), dtype=torch.float32, device=dev)
+        ws = self._workspace(shape, rows_need)
         given = seg_out is not None
         if out is None:
             out = torch.empty(shape, dtype=torch.float32, device=dev)
@@ -853,10 +869,10 @@ class FetalSynthGen:
         # what the previous call carried for this one (see next_key): the parameter block of exactly this key, on this stream
         stream_id = K._stream(dev).value
         pre = self.__dict__.setdefault("_pre", {}).pop(stream_id, None)  # one carried block per launch stream
-        if pre is not None and pre[0] == key and pre[1] is kc:
+        if pre is not None and pre[0] == key and pre[1] is kc and ov is None:
             block, flags = pre[2], _KF_BLOCK_FILLED
         else:
-            block, flags = torch.empty(kc.block_bytes, dtype=torch.uint8, device=dev), 0
+            block, flags = torch.empty(block_bytes, dtype=torch.uint8, device=dev), 0
         nblock = None
         if next_key is not None:
             next_key &= 0xFFFFFFFFFFFFFFFF
@@ -867,9 +883,10 @@ class FetalSynthGen:
         iv[_K_OUT] = out.data_ptr()
         iv[_K_SEG_OUT], iv[_K_SEG_OUT_U8] = (0, seg_out.data_ptr()) if labels_u8 else (seg_out.data_ptr(), 0)
         iv[_K_SEG_IN], iv[_K_SEG_IN_U8], iv[_K_BLOCK] = ent.seg_ptr, ent.twin_ptr, block.data_ptr()
-        iv[_K_WS0], iv[_K_WS1], iv[_K_WS_LOW] = ws["ws0"].data_ptr(), ws["ws1"].data_ptr(), ws["low"].data_ptr()
+        iv[_K_WS0], iv[_K_WS1], iv[_K_WS_LOW] = ws["ws0"].data_ptr(), ws["ws1"].data_ptr(), (low if low is not None else ws["low"]).data_ptr()
         iv[_K_WS_ROWS], iv[_K_ROW_STRIDE] = (ws["rows"].data_ptr() if ws["rows"] is not None else 0), ws["stride"]
         iv[_K_SCALE01] = int(bool(scale01))
+        iv[_K_OVERRIDES], iv[_K_BLOCK_BYTES] = (C.addressof(ov.c), block_bytes) if ov is not None else (0, 0)
         events, tr = self._instrument()  # (whether this sample resamples is drawn inside the call)
         iv[_K_TRACE_EVENTS], iv[_K_TRACE_IDS], iv[_K_TRACE_CAP] = tr.slots() if tr is not None else (0, 0, 0)
         iv[_K_BANK:_K_BANK + keyed.BANK_SLOTS] = ent.bank_ptrs
@@ -917,13 +934,19 @@ class FetalSynthGen:
         if self._is_keyed():
             from .. import sharding
 
+            if genparams:
+                genparams = self._validated_genparams(genparams)
+            announced = sharding.take_key()  # consumed whichever key is used: it must not reach a later call
+            if key is None and genparams and "key" in genparams:  # a keyed sample's own synth_params handed back
+                key = int(genparams["key"])
             if key is None:
-                key = sharding.take_key()
+                key = announced
             if key is None:
                 key = int(np.random.randint(0, 1 << 62)) << 1
             key &= 0xFFFFFFFFFFFFFFFF
             if self._keyed_applies(image, segmentation, seeds, genparams, segmentation_u8, labels_u8):
-                got = self._pipeline_keyed(segmentation, seeds, key, scale01, labels_u8, next_key=next_key, image=image)
+                got = self._pipeline_keyed(segmentation, seeds, key, scale01, labels_u8, next_key=next_key, image=image,
+                                           genparams=genparams)
                 if got is not None:
                     return got
             # outside the keyed path's domain: a "device"-mode sample of the global generators seeded from the key
@@ -965,12 +988,14 @@ class FetalSynthGen:
             B = len(items)
         else:
             B = int(lazy_items)
-        if keys is not None and self._is_keyed() and genparams_list is None:
-            got = self._sample_batch_keyed(list(items), [int(k) for k in keys], scale01, streams, labels_u8)
+        if keys is not None and self._is_keyed():
+            items = list(items)
+            got = self._sample_batch_keyed(items, [int(k) for k in keys], scale01, streams, labels_u8, genparams_list)
             if got is not None:
                 return got
-            raise ValueError("keyed sample_batch: items outside the fused keyed path (need subjects of one shape with device-resident "
-                             "volumes -- a SeedBank, or a float32 image as intensity prior --, no SR-artifact stages)")
+            if genparams_list is None:
+                    raise ValueError("keyed sample_batch: items outside the fused keyed path (need subjects of one shape with device-resident "
+                                 "volumes -- a SeedBank, or a float32 image as intensity prior --, no SR-artifact stages)")
         genparams_list = list(genparams_list) if genparams_list is not None else [{}] * B
         if len(genparams_list) != B:
             raise ValueError("genparams_list must have one entry per item")
@@ -1028,11 +1053,15 @@ class FetalSynthGen:
         labels = torch.stack([o[1].to(ldt) for o in outs]) if same else [o[1].to(ldt) if labels_u8 else o[1] for o in outs]
         return images, labels, [o[2] for o in outs], [o[3] for o in outs]
 
-    def _sample_batch_keyed(self, items, keys, scale01, streams, labels_u8):
-        """B keyed samples written straight into one (B,H,W,D) tensor per output; sample b is `sample(..., key=keys[b])`."""
+    def _sample_batch_keyed(self, items, keys, scale01, streams, labels_u8, genparams_list=None):
+        """B keyed samples written straight into one (B,H,W,D) tensor per output; sample b is `sample(..., key=keys[b])`, with
+        `genparams=genparams_list[b]` where that list is given."""
         B = len(items)
         if B == 0 or len(keys) != B:
             return None
+        gps = [self._validated_genparams(gp) if gp else None for gp in genparams_list] if genparams_list is not None else [None] * B
+        if len(gps) != B:
+            raise ValueError("genparams_list must have one entry per item")
         if not all(self._keyed_applies(img, seg, seeds, {}, None, labels_u8) for img, seg, seeds in items):
             return None
         shapes = {tuple(seg.shape) for _i, seg, _s in items}
@@ -1057,9 +1086,10 @@ class FetalSynthGen:
         with self._forked(main, side):
             for b, ((img, seg, seeds), key) in enumerate(zip(items, keys)):
                 with torch.cuda.stream(side[b % nstreams]):  # (the next sample of THIS stream: its draw job rides along)
+                    nxt = b + nstreams  # (named only when it has nothing fixed: a carried block holds the key's own tables)
                     got = self._pipeline_keyed(seg, seeds, key & 0xFFFFFFFFFFFFFFFF, scale01, labels_u8, out=out_all[b],
-                                               seg_out=seg_all[b], next_key=keys[b + nstreams] if b + nstreams < B else None,
-                                               image=img, image_out=images[b])
+                                               seg_out=seg_all[b], next_key=keys[nxt] if nxt < B and not gps[nxt] else None,
+                                               image=img, image_out=images[b], genparams=gps[b])
                 if got is None:
                     return None
                 params.append(got[3])

@@ -63,6 +63,142 @@ def config_dict(cfg: _lib.KeyedConfig) -> dict:
     return out
 
 
+KT_CAP = 1024  # largest low-res / coarse-grid size a tap table can be registered for (csrc/fsg_keyed.hip)
+
+
+def _vec3(v, what):
+    a = np.asarray(v, dtype=np.float64).reshape(-1)
+    if a.size != 3:
+        raise ValueError(f"keyed genparams: {what} takes three values, got {a.size}")
+    return a.tolist()
+
+
+def _scalar(v, what):
+    a = np.asarray(v.detach().cpu() if torch.is_tensor(v) else v, dtype=np.float64).reshape(-1)
+    if a.size != 1:  # (params_of emits 1-element arrays where the reference does: nonlin_scale, bf_scale, bf_std)
+        raise ValueError(f"keyed genparams: {what} takes one value, got {a.size}")
+    return float(a[0])
+
+
+def _table(v, n, device, what):
+    """A given GMM table as a float32 device tensor of `n` entries (host values are uploaded)."""
+    t = v if torch.is_tensor(v) else torch.as_tensor(np.asarray(v, dtype=np.float32))
+    t = t.detach().reshape(-1)
+    if t.numel() != n:
+        raise ValueError(f"keyed genparams: {what} takes {n} entries (max(seed_labels) + 1), got {t.numel()}")
+    dev = torch.device(device)
+    if t.dtype != torch.float32 or t.device.type != dev.type or (dev.index is not None and t.device.index != dev.index):
+        t = t.to(device=dev, dtype=torch.float32)
+    return t.contiguous()
+
+
+class Overrides:
+    """A `fsg_keyed_overrides` and the device tables it points to (alive as long as this object)."""
+
+    __slots__ = ("c", "keep")
+
+    def __init__(self):
+        self.c, self.keep = _lib.KeyedOverrides(), []
+
+
+def overrides_of(genparams, cfg: _lib.KeyedConfig, device) -> Overrides | None:
+    """The reference's `genparams` (None values already stripped: `FetalSynthGen._validated_genparams`) as a
+    `fsg_keyed_overrides`; None when nothing in them counts.  The keys that count are the ones the stage plan() methods
+    read (ImageFromSeeds.draw_subclusters / plan_intensities, SpatialDeformation.plan, RandGamma / RandBiasField /
+    RandResample / RandNoise.plan); a stage's gate is forced where its plan() forces it.  Values that the C side would
+    refuse raise ValueError here, in words.  Host "mus" / "sigmas" are uploaded to `device` (nothing else needs one)."""
+    KO = _lib.KO
+    ov = Overrides()
+    o = ov.c
+    mask = 0
+
+    def finite(vals, what):
+        if not np.all(np.isfinite(vals)):
+            raise ValueError(f"keyed genparams: {what} is not finite")
+        return vals
+
+    m2s = genparams.get("selected_seeds", {}).get("mlabel2subclusters")
+    if m2s is not None:
+        for m in range(cfg.meta_labels):
+            n = m2s.get(m + 1, m2s.get(str(m + 1)))
+            if n is None or not (cfg.min_subclusters <= int(n) <= cfg.max_subclusters):
+                raise ValueError(f"keyed genparams: mlabel2subclusters[{m + 1}] = {n!r} outside "
+                                 f"[{cfg.min_subclusters}, {cfg.max_subclusters}]")
+            o.subclusters[m] = int(n)
+        mask |= KO.SUBCLUSTERS
+    si = genparams.get("seed_intensities", {})
+    for name, bit in (("mus", KO.MUS), ("sigmas", KO.SIGMAS)):
+        if name in si:
+            t = _table(si[name], cfg.nlabels, device, name)
+            ov.keep.append(t)
+            setattr(o, name + "_dev", t.data_ptr())
+            o.ntab = cfg.nlabels
+            mask |= bit
+    dp = genparams.get("deform_params", {})
+    if len(dp) > 0:  # SpatialDeformation.plan: any key forces the stage ({"flip": False} alone does)
+        mask |= KO.FORCE_DEFORM
+        if "flip" in dp:
+            o.flip = int(bool(dp["flip"]))
+            mask |= KO.FLIP
+        ga = dp.get("affine", {})
+        for name, bit in (("rotations", KO.ROTATIONS), ("shears", KO.SHEARS), ("scalings", KO.SCALINGS)):
+            if name in ga:
+                getattr(o, name)[:] = finite(_vec3(ga[name], name), name)
+                mask |= bit
+        gn = dp.get("non_rigid", {}) if cfg.nonlinear else {}
+        if "nonlin_scale" in gn:
+            o.nonlin_scale = finite(_scalar(gn["nonlin_scale"], "nonlin_scale"), "nonlin_scale")
+            mask |= KO.NONLIN_SCALE
+        if "nonlin_std" in gn:
+            o.nonlin_std = finite(_scalar(gn["nonlin_std"], "nonlin_std"), "nonlin_std")
+            mask |= KO.NONLIN_STD
+        if "size_F_small" in gn:
+            dims = [int(v) for v in np.asarray(gn["size_F_small"]).reshape(-1)]
+            if len(dims) != 3 or min(dims) < 1 or max(dims) > KT_CAP:
+                raise ValueError(f"keyed genparams: size_F_small {dims} must be three sizes in [1, {KT_CAP}]")
+            o.field_dims[:] = dims
+            mask |= KO.FIELD_DIMS
+        elif "nonlin_scale" in gn:
+            dims = [int(np.round(o.nonlin_scale * n)) for n in cfg.shape]
+            if min(dims) < 1 or max(dims) > KT_CAP:
+                raise ValueError(f"keyed genparams: nonlin_scale {o.nonlin_scale} gives the grid {dims}, outside [1, {KT_CAP}]")
+    gp = genparams.get("gamma_params", {})
+    if "gamma" in gp:
+        o.gamma = finite(_scalar(gp["gamma"], "gamma"), "gamma")
+        if not o.gamma > 0:
+            raise ValueError(f"keyed genparams: gamma {o.gamma} must be positive")
+        mask |= KO.GAMMA
+    bp = genparams.get("bf_params", {})
+    if len(bp) > 0:  # RandBiasField.plan: any key forces the stage; "bf_size" is not read (the size follows bf_scale)
+        mask |= KO.FORCE_BIAS
+        if "bf_scale" in bp:
+            o.bf_scale = finite(_scalar(bp["bf_scale"], "bf_scale"), "bf_scale")
+            if max(int(np.round(o.bf_scale * n)) for n in cfg.shape) > KT_CAP:
+                raise ValueError(f"keyed genparams: bf_scale {o.bf_scale} gives a grid above {KT_CAP}")
+            mask |= KO.BF_SCALE
+        if "bf_std" in bp:
+            o.bf_std = finite(_scalar(bp["bf_std"], "bf_std"), "bf_std")
+            mask |= KO.BF_STD
+    rp = genparams.get("resample_params", {})
+    if "spacing" in rp:
+        sp = finite(_vec3(rp["spacing"], "spacing"), "spacing")
+        for a in range(3):
+            low = cfg.shape[a] * cfg.resolution[a] / sp[a] if sp[a] > 0 else 0
+            if not (sp[a] > 0 and 1 <= low < KT_CAP + 1):
+                raise ValueError(f"keyed genparams: spacing {sp} (axis {a}: low-res size {int(low)}) must be positive and give "
+                                 f"sizes in [1, {KT_CAP}]")
+        o.spacing[:] = sp
+        mask |= KO.SPACING
+    npar = genparams.get("noise_params", {})
+    if "noise_std" in npar:
+        o.noise_std = finite(_scalar(npar["noise_std"], "noise_std"), "noise_std")
+        mask |= KO.NOISE_STD
+    if not mask:
+        return None
+    o.mask = mask
+    return ov
+
+
 BANK_SLOTS = 64  # seed volumes the BANK slots of fsg_keyed_sample_run's argument array hold: 4 meta labels x 16 sub-cluster counts
 
 
@@ -89,13 +225,14 @@ class KeyedContext:
         _lib.check(self.lib.fsg_keyed_create(C.byref(self.cfg), C.byref(h)), "fsg_keyed_create")
         self.handle = h
         self.block_bytes = int(self.lib.fsg_keyed_block_bytes(h))
-        self.iv = np.zeros(_lib.KEYED_I.COUNT, dtype=np.int64)
+        self.iv = np.zeros(_lib.KEYED_I.COUNT_OV, dtype=np.int64)  # with the two override slots behind COUNT
         self.ivp = self.iv.ctypes.data
         self._subjects = IdentityCache()  # (bank | None, segmentation) under the segmentation's version -> Subject
         self._banks = weakref.WeakSet()   # every bank a subject was made of: `forget_subjects` drops their code volumes
         self.use_codes = True  # the subject's seed volumes as one uint16 code volume (seedcodes.py, built on first use)
         self._tables_ready = False
         self._keep = []  # device tables registered with the context
+        self._have = set()  # (kind, axis, n) of them
         # rows of the per-(x,y) coarse workspace the largest grids need (3 * field_dims[2] + bias_dims[2])
         f2 = int(np.round(self.cfg.nonlin_scale_max * self.shape[2])) if self.cfg.nonlinear else 0
         b2 = max(int(np.round(self.cfg.bf_scale_max * self.shape[2])), 1)
@@ -114,6 +251,7 @@ class KeyedContext:
 
     # ---- tables: built by the same cached builders as the other modes, registered by device pointer ----------------------
     def _register(self, kind, axis, n, tab):
+        self._have.add((kind, axis, int(n)))
         d = K._device_table(tab, self.device)
         self._keep.append(d)
         _lib.check(self.lib.fsg_keyed_set_table(self.handle, kind, axis, int(n), C.c_void_p(d.data_ptr())), "fsg_keyed_set_table")
@@ -138,6 +276,32 @@ class KeyedContext:
             for s_ in range(max(int(np.floor(c.bf_scale_min * size)) - 1, 1), int(np.ceil(c.bf_scale_max * size)) + 2):
                 self._register(_lib.KT.BIAS, a, s_, T.zoom_table(s_, float(np.float64(size) / np.float64(s_)), size))
         self._tables_ready = True
+
+    def _table_of(self, kind, axis, n):
+        size = self.shape[axis]
+        if kind == _lib.KT.RESAMPLE:
+            return T._resample_axis_table(n, size)
+        if kind == _lib.KT.BACK:
+            f = np.float64(n) / np.float64(size)
+            return T.zoom_table(n, float(1 / f), int(np.round(n * (1 / f))))
+        return T.zoom_table(n, float(np.float64(size) / np.float64(n)), size)  # FIELD, BIAS: coarse grid -> volume
+
+    def ensure_tables(self, d: _lib.KeyedDraws):
+        """Register what the sample of draws `d` needs beyond `register_tables` (overrides reach sizes the configuration's
+        ranges do not: a spacing outside [min, max] resolution, a given grid size)."""
+        need = []
+        for a in range(3):
+            if d.resample_active:
+                need += [(_lib.KT.RESAMPLE, a, d.low_shape[a]), (_lib.KT.BACK, a, d.low_shape[a])]
+            if d.deform_active and d.nonlinear:
+                need.append((_lib.KT.FIELD, a, d.field_dims[a]))
+            if d.bias_active:
+                need.append((_lib.KT.BIAS, a, d.bias_dims[a]))
+        for kind, a, n in need:
+            if (kind, a, n) not in self._have:
+                if not 1 <= n <= KT_CAP:
+                    raise ValueError(f"keyed genparams: a tap table of size {n} is outside [1, {KT_CAP}]")
+                self._register(kind, a, n, self._table_of(kind, a, n))
 
     # ---- per-subject pointer block --------------------------------------------------------------------------------------
     def subject(self, bank, seg, twin):
@@ -211,9 +375,18 @@ class KeyedContext:
             ent.codes, ent.code_tuples = built[0].data_ptr(), built[1].data_ptr()
             ent.code_ntuples, ent.code_stride = int(built[1].shape[0]), int(have[3])
 
-    def draws(self, key: int) -> _lib.KeyedDraws:
+    def draws(self, key: int, overrides: Overrides | None = None) -> _lib.KeyedDraws:
+        """Host draws of `key` (with `overrides_of(...)` honoured).  What the C side refuses of an override is a ValueError."""
         d = _lib.KeyedDraws()
-        _lib.check(self.lib.fsg_keyed_draw(self.handle, C.c_uint64(key & 0xFFFFFFFFFFFFFFFF), C.byref(d)), "fsg_keyed_draw")
+        if overrides is None:
+            _lib.check(self.lib.fsg_keyed_draw(self.handle, C.c_uint64(key & 0xFFFFFFFFFFFFFFFF), C.byref(d)), "fsg_keyed_draw")
+            return d
+        rc = self.lib.fsg_keyed_draw_with(self.handle, C.c_uint64(key & 0xFFFFFFFFFFFFFFFF), C.byref(overrides.c), C.byref(d))
+        if rc in (_lib.E_BADARG, _lib.E_TOOBIG):
+            raise ValueError(f"keyed genparams cannot be honoured for key {key}: "
+                             + ("a value is non-finite, non-positive or outside its range" if rc == _lib.E_BADARG
+                                else f"a grid or low-res size is above {KT_CAP}, or the parameter block above 2 GiB"))
+        _lib.check(rc, "fsg_keyed_draw_with")
         return d
 
 
@@ -244,7 +417,7 @@ def params_of(d: _lib.KeyedDraws, block: torch.Tensor | None) -> dict:
         "deform_params": dp,
         "gamma_params": {"gamma": d.gamma if d.gamma_active else None},
         "bf_params": bp,
-        "resample_params": {"spacing": [d.spacing] * 3 if d.resample_active else None},
+        "resample_params": {"spacing": list(d.spacing3) if d.resample_active else None},
         "noise_params": {"noise_std": float(d.noise_std32) if d.noise_active else None},
         "artifacts": {},
         "key": int(d.key),

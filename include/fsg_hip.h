@@ -28,8 +28,10 @@
 extern "C" {
 #endif
 
-#define FSG_ABI_VERSION 4  /* 2: fsg_sample_plan grew (mm_slots .. seg_out_u8) after version 1 shipped; 3: label_codes .. code_sel, FSG_KEYED_I_CODES;
-                              4: fsg_sample_image / fsg_sample_run_image, FSG_KEYED_I_IMAGE_IN .. PRIOR_IN, fsg_warp_dual_f32 */
+#define FSG_ABI_VERSION 5  /* 2: fsg_sample_plan grew (mm_slots .. seg_out_u8) after version 1 shipped; 3: label_codes .. code_sel, FSG_KEYED_I_CODES;
+                              4: fsg_sample_image / fsg_sample_run_image, FSG_KEYED_I_IMAGE_IN .. PRIOR_IN, fsg_warp_dual_f32;
+                              5: fsg_keyed_overrides / fsg_keyed_draw_with, fsg_keyed_draws grew (spacing3 .. sigmas_in),
+                                 FSG_KEYED_I_OVERRIDES / BLOCK_BYTES */
 
 #define FSG_E_BADARG (-1)   /* null pointer / non-positive size / bad enum */
 #define FSG_E_TOOBIG (-2)   /* size exceeds what the kernel indexes (2^31-1 voxels per volume) */
@@ -558,7 +560,7 @@ typedef struct fsg_sample_image {
 } fsg_sample_image;
 int fsg_sample_run_image(const fsg_sample_plan* plan_host, const fsg_sample_image* image_host, void* stream);
 /* Layout check for FFI mirrors of the structs: which = FSG_SIZEOF_x -> sizeof(fsg_x) (0: fsg_sample_plan, 6 .. 10: fsg_tap,
- * fsg_deform, fsg_epilogue, fsg_keyed_config, fsg_keyed_draws; 12: fsg_sample_image); 1 / 2 / 3 / 4 / 5 -> offsetof blur_taps /
+ * fsg_deform, fsg_epilogue, fsg_keyed_config, fsg_keyed_draws; 12: fsg_sample_image; 13: fsg_keyed_overrides); 1 / 2 / 3 / 4 / 5 -> offsetof blur_taps /
  * out / seg_in_u8 / ws_seq / code_sel in fsg_sample_plan; anything else (11 included) -> -1.  Callable without a GPU. */
 #define FSG_SIZEOF_SAMPLE_PLAN 0
 #define FSG_SIZEOF_TAP 6
@@ -567,6 +569,7 @@ int fsg_sample_run_image(const fsg_sample_plan* plan_host, const fsg_sample_imag
 #define FSG_SIZEOF_KEYED_CONFIG 9
 #define FSG_SIZEOF_KEYED_DRAWS 10
 #define FSG_SIZEOF_SAMPLE_IMAGE 12
+#define FSG_SIZEOF_KEYED_OVERRIDES 13
 int64_t fsg_sample_plan_layout(int which);
 /* B samples with one call: plan b runs on streams[b % nstreams] (hipStream_t handles).  The caller orders those streams
  * behind the upload of every plan's parameters and waits for them afterwards; per sample the work is exactly
@@ -628,6 +631,22 @@ int fsg_blur_resample_yz_noise_f32(const float* src, int m0, int n1, int n2, con
  * two large fields in the kernels that consume them (as in "device" mode).  The host hands over pointers and the key.
  * A sample depends on its key only -- not on the process, the GPU count or what ran before ("(base_seed,
  * sample_index) keyed RNG").  Parity: fsg_keyed_draws exports what was drawn; tests feed it to the oracle.
+ *
+ * Overrides (fsg_keyed_overrides: the reference's `genparams`, generator/model.py:231-276).  Because every draw sits at a fixed
+ * counter, a caller can replace the VALUE of single draws and leave the rest of the key's sample alone:
+ *   - no draw moves: an override replaces one value; only what is derived from it changes (A from rotations / shears /
+ *     scalings, field_dims from field_dims | nonlin_scale, bias_dims from bf_scale, per-axis stds / low_shape / blur_ntaps from
+ *     the 3-vector spacing, noise_std32 from noise_std), by the same code that derives it from drawn values; c2 and u_std always
+ *     come from the key;
+ *   - gates are forced where the reference's plan() methods force them: deformation by FSG_KO_FORCE_DEFORM or any deformation
+ *     field, bias by FSG_KO_FORCE_BIAS or bf_scale / bf_std, gamma / resampling / noise by their value; the members of a forced
+ *     stage that are not given take the key's own slot values (they exist whether or not the key's gate fired);
+ *   - mus_dev / sigmas_dev (ntab floats each, DEVICE) replace the respective table draw of the draw kernel, each on its own;
+ *     with tied classes the tie step still runs on top of given means, with the key's normals (rand_gmm.py:139-145);
+ *   - what cannot be honoured is refused: FSG_E_BADARG for a non-finite value, gamma <= 0, spacing <= 0, a low-res or grid
+ *     size < 1, a sub-cluster count outside [min_subclusters, max_subclusters], ntab != nlabels or a null table; FSG_E_TOOBIG
+ *     for a low-res or grid size above the table cap (1024) or a parameter block of 2 GiB or more.
+ * With no override every byte of the draws and of the block is what it is without the argument.
  */
 typedef struct fsg_keyed_config {
   int32_t shape[3];
@@ -677,7 +696,43 @@ typedef struct fsg_keyed_draws {
   /* byte offsets into the sample's device parameter block of what the draw kernel writes there */
   int32_t off_mm8, off_slots, off_mus, off_sigmas, off_bias, off_field, block_bytes;
   int32_t rode; /* fsg_keyed_sample_run: 1 when the draw job of the NEXT sample went out with this one (look-ahead) */
+  double spacing3[3];              /* per-axis spacing (an override may give three); spacing == spacing3[0] */
+  uint32_t overridden;             /* FSG_KO_* of what the caller fixed (0: every value is the key's)       */
+  uint64_t mus_in, sigmas_in;      /* DEVICE addresses of given GMM tables (0: drawn), read by the draw kernel */
 } fsg_keyed_draws;
+
+/* Presence bits of fsg_keyed_overrides::mask.  FORCE_DEFORM / FORCE_BIAS carry no value: the stage's gate alone. */
+#define FSG_KO_SUBCLUSTERS 1
+#define FSG_KO_FLIP 2
+#define FSG_KO_ROTATIONS 4
+#define FSG_KO_SHEARS 8
+#define FSG_KO_SCALINGS 16
+#define FSG_KO_NONLIN_SCALE 32
+#define FSG_KO_NONLIN_STD 64
+#define FSG_KO_FIELD_DIMS 128
+#define FSG_KO_GAMMA 256
+#define FSG_KO_BF_SCALE 512
+#define FSG_KO_BF_STD 1024
+#define FSG_KO_SPACING 2048
+#define FSG_KO_NOISE_STD 4096
+#define FSG_KO_MUS 8192
+#define FSG_KO_SIGMAS 16384
+#define FSG_KO_FORCE_DEFORM 32768
+#define FSG_KO_FORCE_BIAS 65536
+typedef struct fsg_keyed_overrides {
+  uint32_t mask;                   /* which of the fields below are given                           */
+  int32_t subclusters[4];          /* mlabel m+1 -> number of sub-clusters (the first meta_labels)   */
+  int32_t flip;
+  double rotations[3], shears[3], scalings[3];
+  double nonlin_scale, nonlin_std;
+  int32_t field_dims[3];           /* size_F_small: wins over nonlin_scale                           */
+  double gamma;
+  double bf_scale, bf_std;
+  double spacing[3];
+  double noise_std;
+  int32_t ntab;                    /* entries of each given table: must equal nlabels                */
+  uint64_t mus_dev, sigmas_dev;    /* DEVICE float32 tables (FSG_KO_MUS / FSG_KO_SIGMAS)             */
+} fsg_keyed_overrides;
 
 enum { FSG_KT_RESAMPLE = 0, FSG_KT_BACK = 1, FSG_KT_FIELD = 2, FSG_KT_BIAS = 3 };
 /* Host-only object (no HIP call, usable without a GPU).  *ctx receives the handle. */
@@ -692,6 +747,9 @@ int fsg_keyed_set_table(void* ctx, int kind, int axis, int n, const fsg_tap* tab
 int64_t fsg_keyed_block_bytes(void* ctx);
 /* Host draws of the sample `key` (no device work): what fsg_keyed_sample_run will use. */
 int fsg_keyed_draw(void* ctx, uint64_t key, fsg_keyed_draws* out);
+/* The same with overrides (NULL or mask 0: exactly fsg_keyed_draw).  out->block_bytes may exceed fsg_keyed_block_bytes: the
+ * caller then allocates that much (FSG_KEYED_I_BLOCK_BYTES). */
+int fsg_keyed_draw_with(void* ctx, uint64_t key, const fsg_keyed_overrides* overrides, fsg_keyed_draws* out);
 /* One sample: draws + the draw kernel + fsg_sample_run's launch sequence.  iv (int64): FSG_KEYED_I_*.
  * bank: FSG_KEYED_I_BANK + 4 * (n_sub - min_subclusters) + (mlabel - 1) -> uint8 seed volume of (n_sub, mlabel).
  * draws_out may be NULL. */
@@ -714,12 +772,18 @@ enum {
    * slots are not read (a subject without seeds); with a bank and IMAGE_IN the synthetic channel is that of the same key without an image.
    * The look-ahead does not care which kind the next sample is: its draw job is the same. */
   FSG_KEYED_I_IMAGE_IN = 16 + 73, FSG_KEYED_I_IMAGE_OUT = 16 + 74, FSG_KEYED_I_PRIOR_IN = 16 + 75,
-  FSG_KEYED_I_COUNT = 16 + 76
+  FSG_KEYED_I_COUNT = 16 + 76,
+  /* overrides: two slots BEHIND the count every caller passes, read only when niv >= FSG_KEYED_I_COUNT_OV (a caller of the
+   * shorter array gets a sample without overrides).  OVERRIDES: HOST address of a fsg_keyed_overrides for THIS sample (0 = none;
+   * the look-ahead's next sample never has any).  BLOCK_BYTES: capacity of the block at FSG_KEYED_I_BLOCK
+   * (0 = fsg_keyed_block_bytes): overridden grids may be larger than the configuration's maximum. */
+  FSG_KEYED_I_OVERRIDES = 16 + 76, FSG_KEYED_I_BLOCK_BYTES = 16 + 77, FSG_KEYED_I_COUNT_OV = 16 + 78
 };
 #define FSG_KEYED_FLAG_BLOCK_FILLED 1
 #define FSG_KEYED_FLAG_NEXT_NAMED 4
 int fsg_keyed_sample_run(void* ctx, const int64_t* iv, int niv, fsg_keyed_draws* draws_out, void* stream);
-/* The draw kernel alone (tests): fills the parameter block of `draws` at block_dev. */
+/* The draw kernel alone (tests): fills the parameter block of `draws` at block_dev (at least draws->block_bytes; given
+ * tables are read from draws->mus_in / sigmas_in, which may be the block's own table addresses). */
 int fsg_keyed_fill_block(void* ctx, const fsg_keyed_draws* draws, void* block_dev, void* stream);
 
 /* Retired with fsg_sample_plan::overlap: the library owns no streams or events any more.  Kept for the ABI; returns 0. */

@@ -1,0 +1,307 @@
+"""Keyed mode honours `genparams` (GPU): a key's sample with named draws fixed is that sample in everything else.
+
+Whole samples against the pinned oracle on the exported draws (labels bit-exact, image atol 2e-5 on [0,1] -- the bar of
+tests/test_keyed_draws.py), given GMM tables in the draw kernel, forced gates, replay of a sample from its own
+`synth_params`, real-image samples, batches and the look-ahead, the dataset's `sample_with_meta`.
+"""
+import numpy as np
+import pytest
+import torch
+
+from oracle import fsg_keyed_draws as R
+from tests.util_cases import make_generator
+from tests.util_keyed_overrides import DEV, oracle_sample
+
+pytestmark = pytest.mark.gpu
+KW = dict(nonlin_scale=(0.08, 0.2), bf_scale=(0.05, 0.2))
+S48, S64 = (48, 48, 48), (64, 56, 72)
+ATOL01 = 2e-5
+
+
+@pytest.fixture(scope="module")
+def K():
+    from fetalsyngen_amd import kernels
+
+    return kernels
+
+
+@pytest.fixture(scope="module")
+def subject():
+    """shape -> (segmentation, seed volumes, SeedBank, device segmentation) of one phantom subject, built once per shape
+    (variant 1: unlike variant 0 its label map is not mirror-symmetric along axis 0, so a flip shows in the labels)."""
+    from fetalsyngen_amd.data.datasets import SeedBank
+    from fetalsyngen_amd.phantom import make_seed_volumes
+
+    have = {}
+
+    def get(shape):
+        if shape not in have:
+            seg, seeds = make_seed_volumes(shape, 1)
+            have[shape] = (seg, seeds, SeedBank(seeds, DEV), torch.from_numpy(seg).to(DEV))
+        return have[shape]
+
+    return get
+
+
+def _generator(shape, prob=1.0, tied=True):
+    """tests/util_cases.make_generator in keyed mode; tied=False: generation classes = seed labels (no class-tied means)."""
+    gen = make_generator(shape, DEV, rng="keyed", prob=prob, **KW)
+    if not tied:
+        gen.intensity_generator.generation_classes = list(gen.intensity_generator.seed_labels)
+    return gen
+
+
+@pytest.fixture(scope="module")
+def generators():
+    have = {}
+
+    def get(shape, prob=1.0, tied=True):
+        k = (shape, prob, tied)
+        if k not in have:
+            have[k] = _generator(shape, prob, tied)
+        return have[k]
+
+    return get
+
+
+def _key(i, base=31):
+    from fetalsyngen_amd import sharding
+
+    return sharding.sample_key(base, i)
+
+
+def _same(a, b):
+    """Equality of two synth_params values (dicts of scalars, lists, arrays and tensors)."""
+    if isinstance(a, dict):
+        return isinstance(b, dict) and a.keys() == b.keys() and all(_same(a[k], b[k]) for k in a)
+    if torch.is_tensor(a):
+        return torch.is_tensor(b) and torch.equal(a, b)
+    if isinstance(a, np.ndarray):
+        return np.array_equal(a, np.asarray(b))
+    return a == b
+
+
+def _against_oracle(K, gen, subject, shape, key, gp, prob=1.0):
+    """The sample of `key` with `gp` fixed, held against the oracle on its exported draws; returns (got, draws, exported)."""
+    seg, seeds, bank, seg_d = subject(shape)
+    got = gen._pipeline(None, seg_d, bank, gp, scale01=True, key=key)
+    d, ex, r = oracle_sample(gen.keyed_context(shape), K, shape, key, seg, seeds, dict(prob=prob, **KW), gp)
+    assert np.array_equal(got[1].cpu().numpy().astype(np.uint8), r["seg"].numpy().astype(np.uint8)), "labels"
+    np.testing.assert_allclose(got[0].cpu().numpy(), r["scaled"].numpy(), rtol=0, atol=ATOL01)
+    assert got[3]["key"] == key
+    return got, d, ex
+
+
+def test_empty_genparams_change_nothing(generators, subject):
+    """Rule 9's guard (passes without the feature too), and rule 7: an announced key is consumed even when not used."""
+    from fetalsyngen_amd import sharding
+
+    gen = generators(S48)
+    _seg, _seeds, bank, seg_d = subject(S48)
+    k = _key(0)
+    a = gen.sample(None, seg_d, bank, key=k)
+    b = gen.sample(None, seg_d, bank, genparams={}, key=k)
+    assert torch.equal(a[0], b[0]) and torch.equal(a[1], b[1]) and _same(a[3], b[3])
+    sharding.announce_key(31, 5)
+    c = gen.sample(None, seg_d, bank, key=k)
+    assert sharding.take_key() is None and torch.equal(a[0], c[0])
+
+
+def test_gamma_override_is_the_keys_sample_with_gamma_fixed(K, generators, subject):
+    gen = generators(S48)
+    _seg, _seeds, bank, seg_d = subject(S48)
+    gp = {"gamma_params": {"gamma": 1.3}}
+    for i in range(2):
+        k = _key(i)
+        plain = gen._pipeline(None, seg_d, bank, {}, scale01=True, key=k)
+        got, d, _ex = _against_oracle(K, gen, subject, S48, k, gp)
+        assert torch.equal(got[1], plain[1]), "labels of the key"
+        assert got[3]["gamma_params"] == {"gamma": 1.3} and d.gamma == 1.3 and plain[3]["gamma_params"]["gamma"] != 1.3
+        for name in plain[3]:
+            if name != "gamma_params":
+                assert _same(got[3][name], plain[3][name]), name
+        assert not torch.equal(got[0], plain[0])
+
+
+OVERRIDES = {
+    "spacing_inside": (S48, {"resample_params": {"spacing": [1.2, 1.2, 1.2]}}, True),
+    "spacing_outside": (S48, {"resample_params": {"spacing": [2.0, 2.0, 2.0]}}, True),
+    "spacing_vector": (S64, {"resample_params": {"spacing": [0.5, 0.8, 1.3]}}, True),
+    "noise_std": (S48, {"noise_params": {"noise_std": 12.0}}, True),
+    "subclusters": (S48, {"selected_seeds": {"mlabel2subclusters": {1: 2, 2: 5, 3: 1, 4: 6}}}, True),
+    "rotations": (S48, {"deform_params": {"affine": {"rotations": np.array([0.2, -0.1, 0.05])}}}, False),
+    "flip": (S48, {"deform_params": {"flip": None}}, False),  # (the opposite of the key's own flip: set in the test)
+    "big_field": (S64, {"deform_params": {"non_rigid": {"size_F_small": [15, 13, 26]}}}, False),
+}
+
+
+@pytest.mark.parametrize("name", list(OVERRIDES))
+def test_overridden_samples_equal_the_oracle(K, generators, subject, name):
+    from fetalsyngen_amd import _lib
+
+    shape, gp, deformation_untouched = OVERRIDES[name]
+    gen = generators(shape)
+    kc = gen.keyed_context(shape)
+    _seg, _seeds, bank, seg_d = subject(shape)
+    k = _key(3)
+    plain = gen._pipeline(None, seg_d, bank, {}, scale01=True, key=k)
+    if name == "spacing_outside":  # 48 * 0.5 / 2.0 = 12: below what res_range (0.5, 1.5) can draw -> registered on demand
+        assert plain is not None and (_lib.KT.RESAMPLE, 0, 12) not in kc._have
+    if name == "flip":
+        gp = {"deform_params": {"flip": not plain[3]["deform_params"]["flip"]}}
+    got, d, _ex = _against_oracle(K, gen, subject, shape, k, gp)
+    if deformation_untouched:
+        assert torch.equal(got[1], plain[1])
+    else:
+        assert not torch.equal(got[1], plain[1])
+    assert not torch.equal(got[0], plain[0])
+    p = got[3]
+    if name.startswith("spacing"):
+        assert p["resample_params"]["spacing"] == gp["resample_params"]["spacing"] == list(d.spacing3)
+    if name == "spacing_outside":
+        assert list(d.low_shape) == [12, 12, 12] and (_lib.KT.RESAMPLE, 0, 12) in kc._have and (_lib.KT.BACK, 2, 12) in kc._have
+    if name == "spacing_vector":
+        assert d.low_shape[0] == shape[0] and d.blur_ntaps[0] == 0 and d.blur_ntaps[1] > 0
+    if name == "noise_std":
+        assert p["noise_params"] == {"noise_std": 12.0}
+    if name == "subclusters":
+        assert p["selected_seeds"]["mlabel2subclusters"] == gp["selected_seeds"]["mlabel2subclusters"] != plain[3]["selected_seeds"]["mlabel2subclusters"]
+    if name == "rotations":
+        assert np.array_equal(p["deform_params"]["affine"]["rotations"], gp["deform_params"]["affine"]["rotations"])
+        assert np.array_equal(p["deform_params"]["affine"]["shears"], plain[3]["deform_params"]["affine"]["shears"])
+        assert np.array_equal(p["deform_params"]["affine"]["scalings"], plain[3]["deform_params"]["affine"]["scalings"])
+    if name == "flip":
+        assert p["deform_params"]["flip"] is gp["deform_params"]["flip"] and _same(p["deform_params"]["affine"], plain[3]["deform_params"]["affine"])
+    if name == "big_field":  # beyond the configuration's largest grid: its own block, its own row workspace
+        assert d.block_bytes > kc.block_bytes and 3 * d.field_dims[2] + d.bias_dims[2] > max(kc.rows_need, 64)
+        assert p["deform_params"]["non_rigid"]["size_F_small"] == [15, 13, 26]
+
+
+@pytest.mark.parametrize("how", ["host", "device", "sigmas_only"])
+def test_given_gmm_tables(K, generators, subject, how):
+    gen = generators(S48, tied=False)
+    _seg, _seeds, bank, seg_d = subject(S48)
+    k = _key(4)
+    rs = np.random.RandomState(5)
+    mus = (30 + 180 * rs.rand(50)).astype(np.float32)
+    sigmas = (4 + 10 * rs.rand(50)).astype(np.float32)
+    if how == "host":
+        si = {"mus": mus.tolist(), "sigmas": sigmas.tolist()}
+    elif how == "device":
+        si = {"mus": torch.from_numpy(mus).to(DEV), "sigmas": torch.from_numpy(sigmas).to(DEV)}
+    else:
+        si = {"sigmas": sigmas}
+    plain = gen._pipeline(None, seg_d, bank, {}, scale01=True, key=k)
+    got, _d, ex = _against_oracle(K, gen, subject, S48, k, {"seed_intensities": si})
+    tab = got[3]["seed_intensities"]
+    assert np.array_equal(tab["sigmas"].cpu().numpy(), sigmas) and np.array_equal(ex["sigmas"].numpy(), sigmas)
+    if "mus" in si:
+        assert np.array_equal(tab["mus"].cpu().numpy(), mus) and np.array_equal(ex["mus"].numpy(), mus)
+    else:
+        assert torch.equal(tab["mus"], plain[3]["seed_intensities"]["mus"])
+    assert torch.equal(got[1], plain[1]) and not torch.equal(got[0], plain[0])
+
+
+def test_given_means_are_tied_like_drawn_ones(K, generators, subject):
+    """generation_classes != seed_labels: mus[seed_labels] = clamp(given[generation_classes] + 25 z, 0, 225) with the key's
+    normals (rand_gmm.py:139-145 on top of given means, as `plan_intensities` does); labels outside seed_labels keep the
+    given value bit for bit."""
+    from fetalsyngen_amd import keyed
+
+    gen = generators(S48, tied=True)
+    kc = gen.keyed_context(S48)
+    cfg = keyed.config_dict(kc.cfg)
+    assert cfg["tie_classes"] == 1
+    k = _key(6)
+    mus = np.linspace(20, 230, 50).astype(np.float32)
+    got, _d, _ex = _against_oracle(K, gen, subject, S48, k, {"seed_intensities": {"mus": mus}})
+    sl, gc = np.asarray(cfg["seed_labels"]), np.asarray(cfg["generation_classes"])
+    want = mus.copy()
+    want[sl] = np.minimum(np.maximum(mus[gc] + np.float32(25) * R.device_normals(k, 6, len(sl)), np.float32(0)), np.float32(225))
+    have = got[3]["seed_intensities"]["mus"].cpu().numpy()
+    untied = [l for l in range(50) if l not in cfg["seed_labels"]]
+    assert np.array_equal(have[untied], mus[untied])
+    np.testing.assert_allclose(have, want, rtol=0, atol=2e-4)  # 25 * (GPU normal): the bar of test_draw_kernel_equals_the_restatement
+    _mus_drawn, sigmas_drawn = R.gmm_tables(cfg, k)
+    assert np.array_equal(got[3]["seed_intensities"]["sigmas"].cpu().numpy(), sigmas_drawn)
+
+
+def test_forced_gate_takes_the_keys_slots(K, generators, subject):
+    """prob = 0: no gate fires.  A given spacing forces the resampling alone, with the key's own blur jitter."""
+    gen = generators(S48, prob=0.0)
+    _seg, _seeds, _bank, seg_d = subject(S48)
+    k = _key(7)
+    got, d, _ex = _against_oracle(K, gen, subject, S48, k, {"resample_params": {"spacing": [1, 1, 1]}}, prob=0.0)
+    assert (d.deform_active, d.gamma_active, d.bias_active, d.resample_active, d.noise_active) == (0, 0, 0, 1, 0)
+    assert d.u_std == R.slot_u(k, R.S["RES_STD"]) and list(d.low_shape) == [24, 24, 24]
+    p = got[3]
+    assert p["resample_params"] == {"spacing": [1.0, 1.0, 1.0]} and p["deform_params"]["affine"] is None
+    assert p["gamma_params"] == {"gamma": None} and p["noise_params"] == {"noise_std": None} and p["bf_params"]["bf_scale"] is None
+    assert torch.equal(got[1], seg_d)
+
+
+def test_a_samples_own_params_replay_it(generators, subject):
+    """Rule 6: untied classes, every gate on -> `sample(genparams=params_k)` is `sample(key=k)` bit for bit, the key taken
+    from the params."""
+    gen = generators(S48, tied=False)
+    _seg, _seeds, bank, seg_d = subject(S48)
+    for i in range(4):
+        k = _key(10 + i)
+        a = gen.sample(None, seg_d, bank, key=k)
+        b = gen.sample(None, seg_d, bank, genparams=a[3])
+        assert b[3]["key"] == k and torch.equal(a[0], b[0]) and torch.equal(a[1], b[1]), i
+        assert torch.equal(a[3]["seed_intensities"]["mus"], b[3]["seed_intensities"]["mus"])
+    other = gen.sample(None, seg_d, bank, genparams=a[3], key=_key(99))  # the key argument comes first
+    assert other[3]["key"] == _key(99) and not torch.equal(other[0], a[0])
+
+
+def test_real_image_sample_with_an_override(generators, subject):
+    from tests.util_real_image import phantom_image
+
+    gen = generators(S64)
+    _seg, _seeds, _bank, seg_d = subject(S64)
+    img_d = torch.from_numpy(phantom_image(S64)).to(DEV)
+    k = _key(20)
+    plain = gen._pipeline(img_d, seg_d, None, {}, scale01=True, key=k)
+    got = gen._pipeline(img_d, seg_d, None, {"gamma_params": {"gamma": 0.8}}, scale01=True, key=k)
+    assert torch.equal(got[2], plain[2]) and torch.equal(got[1], plain[1]) and not torch.equal(got[0], plain[0])
+    assert got[3]["gamma_params"] == {"gamma": 0.8} and got[3]["key"] == k and got[3]["seed_intensities"] == {}
+
+
+def test_batches_and_the_look_ahead(generators, subject):
+    """`sample_batch(keys=, genparams_list=)` is the per-sample calls; a carried block (look-ahead) is never used for a
+    sample with overrides, and such a sample is never named as the next one."""
+    _seg, _seeds, bank, seg_d = subject(S64)
+    keys = [_key(30 + i) for i in range(5)]
+    gps = [{}, {"gamma_params": {"gamma": 1.2}}, {"noise_params": {"noise_std": 9.0}}, {}, {"resample_params": {"spacing": [1.0, 1.3, 0.9]}}]
+    ref_gen = _generator(S64)
+    ref = [ref_gen._pipeline(None, seg_d, bank, gp, scale01=True, key=k) for k, gp in zip(keys, gps)]
+    plain = [ref_gen._pipeline(None, seg_d, bank, {}, scale01=True, key=k) for k in keys]
+    gen = generators(S64)
+    out, seg_o, _imgs, params = gen.sample_batch([(None, seg_d, bank)] * 5, gps, scale01=True, streams=2, keys=keys)
+    for b in range(5):
+        assert torch.equal(out[b], ref[b][0]) and torch.equal(seg_o[b], ref[b][1]), b
+        assert params[b]["key"] == keys[b] and _same(params[b]["gamma_params"], ref[b][3]["gamma_params"])
+    # one stream: a plain sample naming the next key, that key with an override, then a plain one
+    seq = _generator(S64)
+    a = seq._pipeline(None, seg_d, bank, {}, scale01=True, key=keys[0], next_key=keys[1])
+    assert seq.__dict__.get("_pre"), "the next sample's draw job rode along (deformation gate on)"
+    b = seq._pipeline(None, seg_d, bank, gps[1], scale01=True, key=keys[1])
+    c = seq._pipeline(None, seg_d, bank, {}, scale01=True, key=keys[2])
+    assert torch.equal(a[0], plain[0][0]) and torch.equal(b[0], ref[1][0]) and torch.equal(b[1], ref[1][1])
+    assert torch.equal(c[0], plain[2][0]) and torch.equal(c[1], plain[2][1])
+
+
+def test_dataset_sample_with_meta_is_the_items_sample_with_values_fixed(generators):
+    from fetalsyngen_amd import sharding
+    from fetalsyngen_amd.data.datasets import MemorySynthDataset
+    from fetalsyngen_amd.phantom import make_seed_volumes
+
+    segs, banks = zip(*[make_seed_volumes(S64, v) for v in range(2)])
+    ds = MemorySynthDataset(generators(S64), list(segs), list(banks), base_seed=21)
+    for i in range(2):
+        item = ds[i]
+        meta = ds.sample_with_meta(i, {"noise_params": {"noise_std": 12.0}})
+        assert torch.equal(meta["label"], item["label"]) and not torch.equal(meta["image"], item["image"])
+        gp = meta["generation_params"]
+        assert gp["key"] == sharding.sample_key(21, i) and gp["noise_params"] == {"noise_std": 12.0}
