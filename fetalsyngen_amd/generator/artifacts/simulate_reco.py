@@ -364,6 +364,8 @@ class PSFReconstructor:
     def _gaussian_centers(self, vol_mask):
         """`_ngaussians_merge` distinct voxels of the mask, as the reference's randperm over them (ref :661-664)."""
         m = vol_mask.reshape(vol_mask.shape[-3:]).contiguous()  # bool mask, or the float label map itself (> 0)
+        if _rng.in_keyed_scope():
+            return _rng.scoped_pick(m, ">", 0.0, self._ngaussians_merge)
         count, select = K.nonzero_ranks(m, ">", 0.0)
         idx = _rng.distinct_ranks(count, self._ngaussians_merge)
         return select(idx)  # (k,3) int64 host, first-axis index first

@@ -20,6 +20,7 @@ import numpy as np
 import torch
 
 from ... import kernels as K
+from ... import rng as _rng
 from ... import tables as T
 
 
@@ -186,12 +187,18 @@ def generate_perlin_noise_3d(shape, res, tileable=(True, True, True), interpolan
 RESEED_NUMPY_FROM_CLOCK = True  # the reference re-seeds numpy's global generator from the wall clock (ref :365-367)
 
 
-def fractal_noise_plan(shape, res, octaves=1, persistence=0.5, lacunarity=2, tileable=(True, True, True), device=None):
-    """Host side of generate_fractal_noise_3d: the clock re-seed and the per-octave lattices (ref :365-384)."""
-    if RESEED_NUMPY_FROM_CLOCK:
+def reseed_from_clock() -> None:
+    """The reference's clock re-seed of numpy's global generator.  Not inside a keyed scope (rng.keyed_scope): there the
+    generator's state belongs to the sample's key, and neither it nor PYTHONHASHSEED is touched."""
+    if RESEED_NUMPY_FROM_CLOCK and not _rng.in_keyed_scope():
         seed = int(time.time())
         os.environ["PYTHONHASHSEED"] = str(seed)
         np.random.seed(seed)
+
+
+def fractal_noise_plan(shape, res, octaves=1, persistence=0.5, lacunarity=2, tileable=(True, True, True), device=None):
+    """Host side of generate_fractal_noise_3d: the clock re-seed and the per-octave lattices (ref :365-384)."""
+    reseed_from_clock()
     octs, frequency, amplitude = [], 1, 1
     for _ in range(int(octaves)):
         octs.append(_octave(shape, (frequency * res[0], frequency * res[1], frequency * res[2]), tileable, amplitude))

@@ -30,10 +30,13 @@ def _need_gpu(t):
         raise RuntimeError("fetalsyngen_amd artifact stages run on an MI355X only (device='cuda:N'); there is no CPU fallback")
 
 
-def _pick_voxels(vol, op, value, ranks_fn):
-    """ranks_fn(count) -> int64 ranks among the voxels with `vol op value` (raster order); returns (k,3) coordinates."""
+def _uniform_pick(vol, op, value, k):
+    """(<= k, 3) host coordinates of k distinct random voxels with `vol op value`: on the device inside a keyed scope,
+    bucket counts + `distinct_ranks` otherwise."""
+    if _rng.in_keyed_scope():
+        return _rng.scoped_pick(vol, op, value, k)
     count, select = K.nonzero_ranks(vol.contiguous(), op, value)
-    return select(ranks_fn(count))
+    return select(_rng.distinct_ranks(count, k))
 
 
 class BlurCortex(RandTransform):
@@ -59,9 +62,21 @@ class BlurCortex(RandTransform):
 
     def _cortex_weights(self, shape, seg, device):
         """The blob field at the cortex voxels, not normalised (host float32, raster order)."""
+        return K.compact_values(self._blob_field(shape, device), seg, "==", float(self.cortex_label)).cpu()
+
+    def _blob_field(self, shape, device):
         x, y, z = shape
-        prob = K.mog3d(shape, *mog_params([(0, y, z // 2), (x, y, z // 2)], [x // 5, y // 5]), device)
-        return K.compact_values(prob, seg, "==", float(self.cortex_label)).cpu()
+        return K.mog3d(shape, *mog_params([(0, y, z // 2), (x, y, z // 2)], [x // 5, y // 5]), device)
+
+    def _centers(self, shape, seg, device, nblur):
+        """`nblur` distinct cortex voxels, frontal ones preferred: (nblur,3) int64 on the host."""
+        if _rng.in_keyed_scope():  # the blob field is the weight, the label map the predicate: nothing O(mask) on the host
+            return _rng.scoped_pick(seg, "==", float(self.cortex_label), nblur, weight=self._blob_field(shape, device))
+        cortex_prob = (self.blur_proba(shape, seg, device) if _rng.get_mode() == "reference"
+                       else self._cortex_weights(shape, seg, device))
+        idx = _rng.multinomial_distinct(cortex_prob, nblur)  # CPU generator
+        count, select = K.nonzero_ranks(seg, "==", float(self.cortex_label))
+        return select(idx)
 
     def __call__(self, output, seg, device, genparams: dict = {}, **kwargs):
         if np.random.rand() < self.prob or len(genparams.keys()) > 0:
@@ -71,11 +86,7 @@ class BlurCortex(RandTransform):
             seg = seg.to(output.device).float().contiguous()
             # reference mode: the normalised probabilities into torch.multinomial, as the reference (:110); otherwise the
             # inverse-CDF draw scales by the total itself, and the million-element divide stays off the host
-            cortex_prob = (self.blur_proba(output.shape, seg, output.device) if _rng.get_mode() == "reference"
-                           else self._cortex_weights(output.shape, seg, output.device))
-            idx = _rng.multinomial_distinct(cortex_prob, nblur)  # CPU generator
-            count, select = K.nonzero_ranks(seg, "==", float(self.cortex_label))
-            centers = select(idx)
+            centers = self._centers(output.shape, seg, output.device, nblur)
             sigmas = np.random.gamma(self.sigma_gamma_loc, self.sigma_gamma_scale, (nblur, 3))
             gaussian = K.mog3d(output.shape, centers.numpy().astype(np.float32), sigmas.astype(np.float32), output.device)
             out = output.float().contiguous()
@@ -137,8 +148,7 @@ class StructNoise(RandTransform):
         """(weight volume or raw Perlin noise, its min/max keys or None)."""
         mp = self.merge_params
         if mp.merge_type == "gaussian":
-            count, select = K.nonzero_ranks(seg, "==", float(self.wm_label))
-            centers = select(_rng.distinct_ranks(count, self.gauss_nloc))
+            centers = _uniform_pick(seg, "==", float(self.wm_label), self.gauss_nloc)
             sig = torch.clamp(mp.gauss_sigma_mu + mp.gauss_sigma_std * torch.randn(len(centers)), 1, 40).numpy()
             c, s = mog_params([tuple(v) for v in centers.tolist()], sig)
             return K.mog3d(shape, c, s, device), None
@@ -152,8 +162,7 @@ class StructNoise(RandTransform):
         """The weight volume itself (ref :185-236); `__call__` blends without materialising it.  `mask` is the white
         matter mask (bool / uint8 / float)."""
         if self.merge_params.merge_type == "gaussian":
-            count, select = K.nonzero_ranks(mask.reshape(mask.shape[-3:]).contiguous(), ">", 0.0)
-            centers = select(_rng.distinct_ranks(count, self.gauss_nloc))
+            centers = _uniform_pick(mask.reshape(mask.shape[-3:]).contiguous(), ">", 0.0, self.gauss_nloc)
             mp = self.merge_params
             sig = torch.clamp(mp.gauss_sigma_mu + mp.gauss_sigma_std * torch.randn(len(centers)), 1, 40).numpy()
             return K.mog3d(shape, *mog_params([tuple(v) for v in centers.tolist()], sig), device)
@@ -305,8 +314,7 @@ class SimulatedBoundaries(RandTransform):
             for _ in range(self.n_generate_fuzzy):
                 mask_modif = self.generate_fuzzy_boundaries(mask_modif)
             # centres of the probability blobs: random voxels among those the fuzzy growth added (ref :565-574)
-            count, select = K.nonzero_ranks(K.sub_gt(mask_modif, mask, 0.0), ">", 0.0)
-            centers = select(_rng.distinct_ranks(count, self.n_centers))
+            centers = _uniform_pick(K.sub_gt(mask_modif, mask, 0.0), ">", 0.0, self.n_centers)
             sigmas = [self.base_sigma + 10 * np.random.beta(2, 5) for _ in range(len(centers))]
             if len(centers):
                 mog = K.mog3d(mask.shape, *mog_params([tuple(v) for v in centers.tolist()], sigmas), out.device)

@@ -817,7 +817,7 @@ class FetalSynthGen:
         return (self.native_pipeline and (hasattr(seeds, "parts") or (seeds is None and image is not None))
                 and self.intensity_generator.meta_labels <= 4 and torch.is_tensor(segmentation) and segmentation.is_cuda
                 and segmentation.dtype == torch.float32 and segmentation.is_contiguous()
-                and (segmentation_u8 is None or labels_u8) and not any(a is not None for a in self.artifacts.values()))
+                and (segmentation_u8 is None or labels_u8))
 
     def _pipeline_keyed(self, segmentation, bank, key, scale01, labels_u8, out=None, seg_out=None, next_key=None, image=None,
                         image_out=None, genparams=None):
@@ -831,6 +831,12 @@ class FetalSynthGen:
         next_key: the key of the sample the caller will ask for NEXT on this stream (a batch, a stream of indices): its draw job
         then rides in this sample's floor(min) launch (fsg_keyed_sample_run's look-ahead) -- one launch less on the next sample's
         critical path, the same volumes.  If the next call is for another key or stream, the carried block is simply not used.
+
+        SR-artifact stages (any of `self.artifacts` configured): the fused call leaves the image divided by its maximum, as
+        the stage-wise path hands it to the stages; each configured stage then runs in the reference's order on the call's
+        image and labels inside `rng.keyed_scope(key, rng.STAGE_STREAMS[name])`, the [0,1] scaling (if asked for) runs last,
+        and `synth_params["artifacts"]` carries the stages' metadata.  The stages synchronise with the host (their picks and
+        plans), so on several streams they serialise the streams' host side; their kernels still run on the sample's stream.
 
         genparams (validated): the values the caller fixed (`keyed.overrides_of`); everything else is the key's.  Such a sample
         never uses a carried block (that one holds the key's own tables), and its block, row workspace and low-res scratch are
@@ -861,7 +867,7 @@ class FetalSynthGen:
             if d0.resample_active and int(np.prod(list(d0.low_shape))) > int(np.prod(shape)):  # a spacing below the resolution
                 low = torch.empty(int(np.prod(list(d0.low_shape))), dtype=torch.float32, device=dev)
         ws = self._workspace(shape, rows_need)
-        given = seg_out is not None
+        given, out_given = seg_out is not None, out is not None
         if out is None:
             out = torch.empty(shape, dtype=torch.float32, device=dev)
         if seg_out is None:
@@ -885,7 +891,8 @@ class FetalSynthGen:
         iv[_K_SEG_IN], iv[_K_SEG_IN_U8], iv[_K_BLOCK] = ent.seg_ptr, ent.twin_ptr, block.data_ptr()
         iv[_K_WS0], iv[_K_WS1], iv[_K_WS_LOW] = ws["ws0"].data_ptr(), ws["ws1"].data_ptr(), (low if low is not None else ws["low"]).data_ptr()
         iv[_K_WS_ROWS], iv[_K_ROW_STRIDE] = (ws["rows"].data_ptr() if ws["rows"] is not None else 0), ws["stride"]
-        iv[_K_SCALE01] = int(bool(scale01))
+        has_art = any(a is not None for a in self.artifacts.values())
+        iv[_K_SCALE01] = int(bool(scale01) and not has_art)
         iv[_K_OVERRIDES], iv[_K_BLOCK_BYTES] = (C.addressof(ov.c), block_bytes) if ov is not None else (0, 0)
         events, tr = self._instrument()  # (whether this sample resamples is drawn inside the call)
         iv[_K_TRACE_EVENTS], iv[_K_TRACE_IDS], iv[_K_TRACE_CAP] = tr.slots() if tr is not None else (0, 0, 0)
@@ -924,7 +931,26 @@ class FetalSynthGen:
         params = keyed.params_of(d, block)
         if bank is None:  # no seeds were selected and no intensities drawn, as in the stage-by-stage path
             params["selected_seeds"], params["seed_intensities"] = {}, {}
+        if has_art:
+            result, params["artifacts"] = self._apply_artifacts_keyed(out, seg_out, key, genparams or {})
+            if scale01:
+                result = result.contiguous()
+                result = K.scale(result, K.reduce_minmax(result), mode=1)
+            if result is not out:
+                out = out.copy_(result) if out_given else result
         return out, seg_out, image_out, params
+
+    def _apply_artifacts_keyed(self, output, segmentation, key, genparams):
+        """`_apply_artifacts` with every stage's host draws under the sample's key: stage `name` runs inside
+        `keyed_scope(key, STAGE_STREAMS[name])`, so its draws depend on nothing but the key and its own inputs."""
+        artifacts = {}
+        for name, artifact in self.artifacts.items():
+            if artifact is not None:
+                with _rng.keyed_scope(key, _rng.STAGE_STREAMS[name]):
+                    output, metadata = artifact(output, segmentation, self.device, genparams.get("artifact_params", {}),
+                                                resolution=self.resolution)
+                artifacts[name] = metadata
+        return output, artifacts
 
     def _pipeline(self, image, segmentation, seeds, genparams, scale01: bool, segmentation_u8=None, labels_u8: bool = False,
                   key: int | None = None, next_key: int | None = None):
@@ -995,7 +1021,7 @@ class FetalSynthGen:
                 return got
             if genparams_list is None:
                     raise ValueError("keyed sample_batch: items outside the fused keyed path (need subjects of one shape with device-resident "
-                                 "volumes -- a SeedBank, or a float32 image as intensity prior --, no SR-artifact stages)")
+                                 "volumes -- a SeedBank, or a float32 image as intensity prior)")
         genparams_list = list(genparams_list) if genparams_list is not None else [{}] * B
         if len(genparams_list) != B:
             raise ValueError("genparams_list must have one entry per item")
@@ -1055,7 +1081,8 @@ class FetalSynthGen:
 
     def _sample_batch_keyed(self, items, keys, scale01, streams, labels_u8, genparams_list=None):
         """B keyed samples written straight into one (B,H,W,D) tensor per output; sample b is `sample(..., key=keys[b])`, with
-        `genparams=genparams_list[b]` where that list is given."""
+        `genparams=genparams_list[b]` where that list is given.  Configured SR-artifact stages run per sample on the sample's
+        stream; their host synchronisations serialise the streams (accepted: the stages dominate such a sample anyway)."""
         B = len(items)
         if B == 0 or len(keys) != B:
             return None

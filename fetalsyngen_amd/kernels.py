@@ -902,6 +902,46 @@ def nonzero_ranks(vol, op=">", value=0.0):
     return total, select
 
 
+def voxel_pick(pred, op, value, k: int, u, weight=None, out=None) -> torch.Tensor:
+    """fsg_voxel_pick_* (contract in fsg_hip.h): the device tensor `out` of k + 2 int64 -- eligible voxels, distinct picks
+    found, then the flat indices of the first k distinct candidates in the order of `u`, padded with -1.  `pred`: float32 /
+    uint8 / bool of any shape; `u`: float64 uniforms in [0,1), host or device; `weight`: float32 of pred's size or None
+    (1 per voxel).  Four launches on the current stream, no host synchronisation."""
+    _need_gpu(pred, weight, out)
+    u8 = pred.dtype in (torch.bool, torch.uint8)
+    if not u8:
+        _f32(pred, "pred")
+    n, k = int(pred.numel()), int(k)
+    if weight is not None and (_f32(weight, "weight").numel() != n):
+        raise ValueError("weight and pred must have one size")
+    if not (isinstance(u, torch.Tensor) and u.dtype == torch.float64 and u.dim() == 1):
+        raise TypeError("u must be a 1-D float64 tensor")
+    if not u.is_cuda:
+        u = _upload(u, pred.device)
+    _need_gpu(u)
+    if out is None:
+        out = torch.empty(max(k, 0) + 2, dtype=torch.int64, device=pred.device)
+    elif out.dtype != torch.int64 or out.numel() < k + 2:
+        raise ValueError("out must hold k + 2 int64")
+    lib = _lib.load()
+    need = int(lib.fsg_voxel_pick_ws_bytes(n))
+    ws = torch.empty(need, dtype=torch.uint8, device=pred.device)
+    fn = lib.fsg_voxel_pick_u8 if u8 else lib.fsg_voxel_pick_f32
+    _lib.check(fn(_p(pred), n, _NZ_MODES[op], float(value), _p(weight), _p(u), int(u.numel()), k, _p(out), _p(ws), need,
+                  _stream(pred)), "fsg_voxel_pick")
+    return out
+
+
+def pick_voxels(pred, op, value, k: int, u, weight=None):
+    """(eligible, coords): the number of voxels with `pred op value` and weight > 0, and the coordinates, (found, pred.dim())
+    int64 on the host, of the first k distinct voxels that the uniforms `u` select with probability proportional to `weight`
+    (None: uniformly).  One small device -> host copy of k + 2 words."""
+    got = voxel_pick(pred, op, value, k, u, weight).cpu().numpy()
+    eligible, found = int(got[0]), int(got[1])
+    flat = got[2:2 + found]
+    return eligible, torch.from_numpy(np.stack(np.unravel_index(flat, tuple(pred.shape)), -1).astype(np.int64).reshape(found, pred.dim()))
+
+
 def box_sum3d(v, k: int) -> torch.Tensor:
     """Zero-padded k x k x k box sum (the reference convolves with a ones kernel, padding k//2): three passes of the blur kernels
     with unit taps (exact for the small integers of a binary mask)."""

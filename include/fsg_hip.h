@@ -28,10 +28,11 @@
 extern "C" {
 #endif
 
-#define FSG_ABI_VERSION 5  /* 2: fsg_sample_plan grew (mm_slots .. seg_out_u8) after version 1 shipped; 3: label_codes .. code_sel, FSG_KEYED_I_CODES;
+#define FSG_ABI_VERSION 6  /* 2: fsg_sample_plan grew (mm_slots .. seg_out_u8) after version 1 shipped; 3: label_codes .. code_sel, FSG_KEYED_I_CODES;
                               4: fsg_sample_image / fsg_sample_run_image, FSG_KEYED_I_IMAGE_IN .. PRIOR_IN, fsg_warp_dual_f32;
                               5: fsg_keyed_overrides / fsg_keyed_draw_with, fsg_keyed_draws grew (spacing3 .. sigmas_in),
-                                 FSG_KEYED_I_OVERRIDES / BLOCK_BYTES */
+                                 FSG_KEYED_I_OVERRIDES / BLOCK_BYTES;
+                              6: fsg_voxel_pick_f32 / _u8, fsg_voxel_pick_ws_bytes */
 
 #define FSG_E_BADARG (-1)   /* null pointer / non-positive size / bad enum */
 #define FSG_E_TOOBIG (-2)   /* size exceeds what the kernel indexes (2^31-1 voxels per volume) */
@@ -382,6 +383,26 @@ int fsg_nonzero_select_f32(const float* v, size_t n, int mode, float value, cons
                            int nreq, long long* out, void* stream);
 int fsg_nonzero_select_u8(const uint8_t* v, size_t n, int mode, float value, const int32_t* bucket, const int32_t* rank,
                           int nreq, long long* out, void* stream);
+
+/* Weighted random voxel picks without a host pass over the mask (keyed mode's picks of the SR-artifact stages).
+ * A voxel is ELIGIBLE when `pred` satisfies the predicate (mode / value as for fsg_nonzero_count_*) and its weight is > 0
+ * (weight: DEVICE float32, n elements, NaN and negative count as 0; NULL = 1 per voxel).  S_e = inclusive float64 prefix sum
+ * of the weights over the eligible voxels in raster order, total = the last S_e.  Candidate q (q < m) is the first eligible
+ * voxel with S_e > u[q] * total (product in float64; u: DEVICE, m doubles in [0,1)); the last eligible voxel if rounding
+ * leaves none.  out (DEVICE, k + 2 int64): out[0] = eligible voxels, out[1] = found = distinct picks (<= k),
+ * out[2 .. 2+found) = flat indices of the first k distinct candidates in candidate order, the rest -1.  Nothing eligible:
+ * out[0] = out[1] = 0 and all -1; n == 0 the same with one launch that writes `out` (pred, weight, ws may be NULL).
+ * 1 <= k <= m, m <= 4096, k <= 1024: FSG_E_BADARG (k > m, k or m < 1) / FSG_E_TOOBIG otherwise, `out` untouched.
+ * The float64 sums are taken in a fixed order (lane quads, a wave scan per 256 voxels, chunks, buckets of FSG_NZ_BUCKET,
+ * segments of buckets) with no floating-point atomics: the same inputs give the same `out` bit for bit; where the sums
+ * are exact the result is the exact-arithmetic one, otherwise it may differ from a sequential float64 sum only for a
+ * u[q] * total within 2^-40 total of a prefix boundary.  ws: DEVICE scratch, 16-byte aligned, >= fsg_voxel_pick_ws_bytes(n).
+ * Four launches, no host synchronisation. */
+size_t fsg_voxel_pick_ws_bytes(size_t n);
+int fsg_voxel_pick_f32(const float* pred, size_t n, int mode, float value, const float* weight, const double* u, int m, int k,
+                       long long* out, void* ws, size_t ws_bytes, void* stream);
+int fsg_voxel_pick_u8(const uint8_t* pred, size_t n, int mode, float value, const float* weight, const double* u, int m, int k,
+                      long long* out, void* ws, size_t ws_bytes, void* stream);
 
 /* out[offsets[b] + r] = values[e] for the r-th voxel e of bucket b with `pred[e]` satisfying the predicate: the
  * boolean-mask gather `values[mask]` (augmentation/artifacts.py:78-80) in raster order; offsets = exclusive prefix sum
