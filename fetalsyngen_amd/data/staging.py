@@ -113,7 +113,7 @@ class PrefetchingStream:
 
     def _produce(self, i, i_next=None):
         # keyed mode: the sample is a function of its key alone -- no re-seeding of the global generators; the stream knows the
-        # next index, whose draw job then rides in this sample's launches (FetalSynthGen._pipeline_keyed: next_key)
+        # next index, whose draw job then rides in this sample's launches (KeyedContext.run: next_key)
         next_key = None
         if self.ds.generator._is_keyed():
             sharding.announce_key(self.base_seed, i)

@@ -44,22 +44,7 @@ MM_NSLOTS = 64
 _MM_SLOTS_INIT = np.zeros((MM_NSLOTS, _lib.MM_SLOT_STRIDE), dtype=np.int32)
 _MM_SLOTS_INIT[:, 0], _MM_SLOTS_INIT[:, 1] = 0x7F800000, -2139095041
 _MM_SLOTS_INIT.setflags(write=False)
-# slots of fsg_keyed_sample_run's argument array as plain module names: _pipeline_keyed fills them once per sample
-_KI, _KF = _lib.KEYED_I, _lib.KEYED_FLAG
-_K_KEY, _K_OUT, _K_SEG_OUT, _K_SEG_OUT_U8, _K_SEG_IN, _K_SEG_IN_U8 = _KI.KEY, _KI.OUT, _KI.SEG_OUT, _KI.SEG_OUT_U8, _KI.SEG_IN, _KI.SEG_IN_U8
-_K_BLOCK, _K_WS0, _K_WS1, _K_WS_LOW, _K_WS_ROWS, _K_ROW_STRIDE = _KI.BLOCK, _KI.WS0, _KI.WS1, _KI.WS_LOW, _KI.WS_ROWS, _KI.ROW_STRIDE
-_K_SCALE01, _K_TRACE_EVENTS, _K_TRACE_IDS, _K_TRACE_CAP, _K_BANK = _KI.SCALE01, _KI.TRACE_EVENTS, _KI.TRACE_IDS, _KI.TRACE_CAP, _KI.BANK
-_K_EV_BLUR_BEGIN, _K_EV_BLUR_END, _K_CODES, _K_CODE_TUPLES = _KI.EV_BLUR_BEGIN, _KI.EV_BLUR_END, _KI.CODES, _KI.CODE_TUPLES
-_K_CODE_NTUPLES, _K_CODE_STRIDE, _K_FLAGS, _K_NEXT_KEY, _K_NEXT_BLOCK = _KI.CODE_NTUPLES, _KI.CODE_STRIDE, _KI.FLAGS, _KI.NEXT_KEY, _KI.NEXT_BLOCK
-_K_IMAGE_IN, _K_IMAGE_OUT, _K_PRIOR_IN = _KI.IMAGE_IN, _KI.IMAGE_OUT, _KI.PRIOR_IN
-_K_OVERRIDES, _K_BLOCK_BYTES = _KI.OVERRIDES, _KI.BLOCK_BYTES
-_KF_BLOCK_FILLED, _KF_NEXT_NAMED = _KF.BLOCK_FILLED, _KF.NEXT_NAMED
 _SEEN_ONCE, _NO_TWIN = object(), object()  # what `_twins` holds for a label volume that has no uint8 twin
-
-
-def _i64(key):
-    """An unsigned 64-bit key as the signed value an int64 slot takes."""
-    return key if key < (1 << 63) else key - (1 << 64)
 
 
 class _Ctx:
@@ -151,7 +136,7 @@ class FetalSynthGen:
     # DataLoader pattern: `num_workers=2, multiprocessing_context="spawn"`, fetalsyngen/test_dl.py:17-24, docs/datasets.md:4-6)
     # carries none of it into the worker.
     _PROCESS_LOCAL = ("_ws", "_flat", "_twins", "_rs_dt", "_batch_streams", "blur_events", "_blur_tick", "_keyed",
-                      "stage_traces", "_pre", "_priors")
+                      "stage_traces", "_priors")
 
     def __getstate__(self):
         return {k: v for k, v in self.__dict__.items() if k not in self._PROCESS_LOCAL}
@@ -173,13 +158,12 @@ class FetalSynthGen:
             size = shape[a]
             lo = int(size * res[a] / max(rs.max_resolution, res[a]))
             for m in range(max(lo - 1, 1), size + 1):
-                K._device_table(T._resample_axis_table(m, size), self.device)
-                f = np.float64(m) / np.float64(size)
-                K._device_table(T.zoom_table(m, float(1 / f), int(np.round(m * (1 / f)))), self.device)
+                K._device_table(T.axis_table(_lib.KT.RESAMPLE, m, size), self.device)
+                K._device_table(T.axis_table(_lib.KT.BACK, m, size), self.device)
                 n += 2
-            for lo_s, hi_s in ((sd.nonlin_scale_min, sd.nonlin_scale_max), (bf.scale_min, bf.scale_max)):
+            for kind, lo_s, hi_s in ((_lib.KT.FIELD, sd.nonlin_scale_min, sd.nonlin_scale_max), (_lib.KT.BIAS, bf.scale_min, bf.scale_max)):
                 for s_ in range(max(int(np.floor(lo_s * size)) - 1, 1), int(np.ceil(hi_s * size)) + 2):
-                    K._device_table(T.zoom_table(s_, float(np.float64(size) / np.float64(s_)), size), self.device)
+                    K._device_table(T.axis_table(kind, s_, size), self.device)
                     n += 1
         return n
 
@@ -547,13 +531,24 @@ class FetalSynthGen:
             "deform_params": deform_params,
         }
 
-    def _apply_artifacts(self, output, segmentation, genparams):
+    def _apply_artifacts(self, output, segmentation, genparams, key=None):
+        """The configured SR-artifact stages in the reference's order.  key (keyed mode): stage `name` runs inside
+        `keyed_scope(key, STAGE_STREAMS[name])`, so its host draws depend on nothing but the key and its own inputs."""
         artifacts = {}
         for name, artifact in self.artifacts.items():
             if artifact is not None:
-                output, metadata = artifact(output, segmentation, self.device, genparams.get("artifact_params", {}),
-                                            resolution=self.resolution)
+                with _rng.keyed_scope(key, _rng.STAGE_STREAMS[name]) if key is not None else contextlib.nullcontext():
+                    output, metadata = artifact(output, segmentation, self.device, genparams.get("artifact_params", {}),
+                                                resolution=self.resolution)
                 artifacts[name] = metadata
+        return output, artifacts
+
+    def _artifact_tail(self, output, segmentation, genparams, scale01, key=None):
+        """The configured stages, then -- last, and only with stages: any other sample was scaled before -- the [0,1] scaling."""
+        output, artifacts = self._apply_artifacts(output, segmentation, genparams, key)
+        if scale01 and artifacts:
+            output = output.contiguous()
+            output = K.scale(output, K.reduce_minmax(output), mode=1)
         return output, artifacts
 
     def augment(self, image, segmentation, genparams: dict = {}):
@@ -821,107 +816,50 @@ class FetalSynthGen:
 
     def _pipeline_keyed(self, segmentation, bank, key, scale01, labels_u8, out=None, seg_out=None, next_key=None, image=None,
                         image_out=None, genparams=None):
-        """One keyed sample: pointers + key -> ONE native call (draws, the draw kernel, the launch sequence).  Returns
-        (image, labels, warped real image | None, synth_params) or None when the sample is outside the fused kernels' domain.
+        """One keyed sample: the generator's own (label twin, image prior, workspace, outputs, instrumentation) handed to
+        `KeyedContext.run` -- ONE native call -- then the pass-through of unwarped volumes, `synth_params` and the SR-artifact
+        stages.  Returns (image, labels, warped real image | None, synth_params), or None outside the fused kernels' domain.
 
         image: the subject's real image (checked by `_keyed_applies`), deformed by the same warp launch as the labels.  With
         `bank=None` its cached prior (`_image_prior`) takes the place of the GMM draw; with a bank the synthetic channel is that
-        of the same key without an image.
-
-        next_key: the key of the sample the caller will ask for NEXT on this stream (a batch, a stream of indices): its draw job
-        then rides in this sample's floor(min) launch (fsg_keyed_sample_run's look-ahead) -- one launch less on the next sample's
-        critical path, the same volumes.  If the next call is for another key or stream, the carried block is simply not used.
-
-        SR-artifact stages (any of `self.artifacts` configured): the fused call leaves the image divided by its maximum, as
-        the stage-wise path hands it to the stages; each configured stage then runs in the reference's order on the call's
-        image and labels inside `rng.keyed_scope(key, rng.STAGE_STREAMS[name])`, the [0,1] scaling (if asked for) runs last,
-        and `synth_params["artifacts"]` carries the stages' metadata.  The stages synchronise with the host (their picks and
-        plans), so on several streams they serialise the streams' host side; their kernels still run on the sample's stream.
-
-        genparams (validated): the values the caller fixed (`keyed.overrides_of`); everything else is the key's.  Such a sample
-        never uses a carried block (that one holds the key's own tables), and its block, row workspace and low-res scratch are
-        sized from its own draws: overridden grids and low-res sizes may exceed what the configuration can draw.  What cannot
-        be honoured raises ValueError."""
+        of the same key without an image.  next_key (a batch, a stream of indices) and genparams (validated; what cannot be
+        honoured raises ValueError): see `run`.  SR-artifact stages: the fused call leaves the image divided by its maximum, as
+        the stage-wise path hands it to them; `_artifact_tail` runs them under the key.  They synchronise with the host (picks,
+        plans), so on several streams they serialise the streams' host side; their kernels still run on the sample's stream."""
         from .. import keyed
 
         shape = tuple(segmentation.shape)
         kc = self.keyed_context(shape)
-        if not kc._tables_ready:
-            kc.register_tables()
+        kc.register_tables()
         twin = self._label_twin(segmentation)
         if labels_u8 and twin is None:
             return None
         ent = kc.subject(bank, segmentation, twin)
         dev = segmentation.device
         prior = self._image_prior(image) if (image is not None and bank is None) else None
-        img_given = image_out is not None
+        img_given, given, out_given = image_out is not None, seg_out is not None, out is not None
         if image is not None and image_out is None:
             image_out = torch.empty(shape, dtype=torch.float32, device=dev)
-        ov = keyed.overrides_of(genparams, kc.cfg, dev) if genparams else None
-        rows_need, block_bytes, low = kc.rows_need, kc.block_bytes, None
-        if ov is not None:
-            d0 = kc.draws(key, ov)
-            kc.ensure_tables(d0)
-            rows_need = max(rows_need, 3 * d0.field_dims[2] + d0.bias_dims[2])
-            block_bytes = max(block_bytes, d0.block_bytes)
-            if d0.resample_active and int(np.prod(list(d0.low_shape))) > int(np.prod(shape)):  # a spacing below the resolution
-                low = torch.empty(int(np.prod(list(d0.low_shape))), dtype=torch.float32, device=dev)
-        ws = self._workspace(shape, rows_need)
-        given, out_given = seg_out is not None, out is not None
-        if out is None:
-            out = torch.empty(shape, dtype=torch.float32, device=dev)
-        if seg_out is None:
-            seg_out = torch.empty(shape, dtype=torch.uint8 if labels_u8 else torch.float32, device=dev)
-        # what the previous call carried for this one (see next_key): the parameter block of exactly this key, on this stream
-        stream_id = K._stream(dev).value
-        pre = self.__dict__.setdefault("_pre", {}).pop(stream_id, None)  # one carried block per launch stream
-        if pre is not None and pre[0] == key and pre[1] is kc and ov is None:
-            block, flags = pre[2], _KF_BLOCK_FILLED
-        else:
-            block, flags = torch.empty(block_bytes, dtype=torch.uint8, device=dev), 0
-        nblock = None
-        if next_key is not None:
-            next_key &= 0xFFFFFFFFFFFFFFFF
-            nblock = torch.empty(kc.block_bytes, dtype=torch.uint8, device=dev)
-            flags |= _KF_NEXT_NAMED
-        iv = kc.iv
-        iv[_K_KEY] = _i64(key)
-        iv[_K_OUT] = out.data_ptr()
-        iv[_K_SEG_OUT], iv[_K_SEG_OUT_U8] = (0, seg_out.data_ptr()) if labels_u8 else (seg_out.data_ptr(), 0)
-        iv[_K_SEG_IN], iv[_K_SEG_IN_U8], iv[_K_BLOCK] = ent.seg_ptr, ent.twin_ptr, block.data_ptr()
-        iv[_K_WS0], iv[_K_WS1], iv[_K_WS_LOW] = ws["ws0"].data_ptr(), ws["ws1"].data_ptr(), (low if low is not None else ws["low"]).data_ptr()
-        iv[_K_WS_ROWS], iv[_K_ROW_STRIDE] = (ws["rows"].data_ptr() if ws["rows"] is not None else 0), ws["stride"]
         has_art = any(a is not None for a in self.artifacts.values())
-        iv[_K_SCALE01] = int(bool(scale01) and not has_art)
-        iv[_K_OVERRIDES], iv[_K_BLOCK_BYTES] = (C.addressof(ov.c), block_bytes) if ov is not None else (0, 0)
         events, tr = self._instrument()  # (whether this sample resamples is drawn inside the call)
-        iv[_K_TRACE_EVENTS], iv[_K_TRACE_IDS], iv[_K_TRACE_CAP] = tr.slots() if tr is not None else (0, 0, 0)
-        iv[_K_BANK:_K_BANK + keyed.BANK_SLOTS] = ent.bank_ptrs
-        iv[_K_EV_BLUR_BEGIN], iv[_K_EV_BLUR_END] = events if events is not None else (0, 0)
-        # the subject's code volume (0: four label volumes)
-        iv[_K_CODES], iv[_K_CODE_TUPLES], iv[_K_CODE_NTUPLES], iv[_K_CODE_STRIDE] = ent.codes, ent.code_tuples, ent.code_ntuples, ent.code_stride
-        iv[_K_IMAGE_IN], iv[_K_IMAGE_OUT] = (image.data_ptr(), image_out.data_ptr()) if image is not None else (0, 0)
-        iv[_K_PRIOR_IN] = prior.data_ptr() if prior is not None else 0
-        iv[_K_FLAGS] = flags
-        iv[_K_NEXT_KEY], iv[_K_NEXT_BLOCK] = (_i64(next_key), nblock.data_ptr()) if nblock is not None else (0, 0)
-        d = _lib.KeyedDraws()
-        rc = kc.lib.fsg_keyed_sample_run(kc.handle, kc.ivp, len(kc.iv), C.byref(d), K._stream(dev))
-        if events is not None:
-            if rc == 0 and d.resample_active:
-                self._keep_blur_events(events, d.blur_ntaps, d.low_shape)
-            else:
-                kc.lib.fsg_event_destroy(events[0])
-                kc.lib.fsg_event_destroy(events[1])
-        if rc in (_lib.E_ALIGN, _lib.E_TOOBIG):
+        got = None
+        try:
+            got = kc.run(key, ent, self._workspace, dev, out, seg_out, labels_u8, scale01 and not has_art, events=events, tr=tr,
+                         next_key=next_key, image=image, image_out=image_out, prior=prior, genparams=genparams)
+        finally:  # (also when the call raises: genparams that cannot be honoured, an error of the native call)
+            if events is not None and (got is None or not got[0].resample_active):
+                for e in events:
+                    _lib.load().fsg_event_destroy(e)
+            if tr is not None and got is None:
+                tr.close()
+        if got is None:
             return None
-        _lib.check(rc, "fsg_keyed_sample_run")
-        if nblock is not None and d.rode:
-            if len(self._pre) > 8:
-                self._pre.clear()
-            self._pre[stream_id] = (next_key, kc, nblock)
+        d, block, carried, out, seg_out = got
+        if events is not None and d.resample_active:
+            self._keep_blur_events(events, d.blur_ntaps, d.low_shape)
         if tr is not None:
             tr.meta = {"shape": shape, "low_shape": tuple(d.low_shape) if d.resample_active else None,
-                       "blur_ntaps": list(d.blur_ntaps), "label_bytes": 2 if ent.codes else 4, "draw_carried": flags & _KF_BLOCK_FILLED}
+                       "blur_ntaps": list(d.blur_ntaps), "label_bytes": 2 if ent.codes else 4, "draw_carried": carried}
             self.stage_traces.append(tr)
         if not d.deform_active:  # no warp ran: the labels pass through, and so does the image
             passed = twin if labels_u8 else segmentation
@@ -932,25 +870,10 @@ class FetalSynthGen:
         if bank is None:  # no seeds were selected and no intensities drawn, as in the stage-by-stage path
             params["selected_seeds"], params["seed_intensities"] = {}, {}
         if has_art:
-            result, params["artifacts"] = self._apply_artifacts_keyed(out, seg_out, key, genparams or {})
-            if scale01:
-                result = result.contiguous()
-                result = K.scale(result, K.reduce_minmax(result), mode=1)
+            result, params["artifacts"] = self._artifact_tail(out, seg_out, genparams or {}, scale01, key)
             if result is not out:
                 out = out.copy_(result) if out_given else result
         return out, seg_out, image_out, params
-
-    def _apply_artifacts_keyed(self, output, segmentation, key, genparams):
-        """`_apply_artifacts` with every stage's host draws under the sample's key: stage `name` runs inside
-        `keyed_scope(key, STAGE_STREAMS[name])`, so its draws depend on nothing but the key and its own inputs."""
-        artifacts = {}
-        for name, artifact in self.artifacts.items():
-            if artifact is not None:
-                with _rng.keyed_scope(key, _rng.STAGE_STREAMS[name]):
-                    output, metadata = artifact(output, segmentation, self.device, genparams.get("artifact_params", {}),
-                                                resolution=self.resolution)
-                artifacts[name] = metadata
-        return output, artifacts
 
     def _pipeline(self, image, segmentation, seeds, genparams, scale01: bool, segmentation_u8=None, labels_u8: bool = False,
                   key: int | None = None, next_key: int | None = None):
@@ -1025,7 +948,6 @@ class FetalSynthGen:
         genparams_list = list(genparams_list) if genparams_list is not None else [{}] * B
         if len(genparams_list) != B:
             raise ValueError("genparams_list must have one entry per item")
-        dev = torch.device(self.device)
         with _rng.use(self.rng):
             arena = T.Arena()
             ctxs = [self._prepare(img, seg, seeds, gp, arena) for (img, seg, seeds), gp in zip(items, genparams_list)]
@@ -1040,16 +962,8 @@ class FetalSynthGen:
                 for c in ctxs:
                     self._native_operands(c)
                 shape = ctxs[0].shape
-                nstreams = max(1, min(int(streams), B))
-                main = torch.cuda.current_stream(dev)
-                side = self._side_streams(nstreams) if nstreams > 1 else [main]
-                need = max(self._rows_needed(c) for c in ctxs)
-                wss = []
-                for q in range(nstreams):  # one scratch set per stream the batch runs on
-                    with torch.cuda.stream(side[q]):
-                        wss.append(self._workspace(shape, need))
-                out_all = torch.empty((B, *shape), dtype=torch.float32, device=dev)
-                seg_all = torch.empty((B, *shape), dtype=torch.uint8 if labels_u8 else torch.float32, device=dev)
+                out_all, seg_all, nstreams, main, side, wss = self._batch_outputs(B, shape, streams, labels_u8,
+                                                                                  max(self._rows_needed(c) for c in ctxs))
                 plans = (_lib.SamplePlan * B)()
                 lib, fb, ok = _lib.load(), self._flat, True
                 for b, c in enumerate(ctxs):
@@ -1095,16 +1009,11 @@ class FetalSynthGen:
         if len(shapes) != 1:
             return None
         shape = shapes.pop()
-        dev = torch.device(self.device)
-        out_all = torch.empty((B, *shape), dtype=torch.float32, device=dev)
-        seg_all = torch.empty((B, *shape), dtype=torch.uint8 if labels_u8 else torch.float32, device=dev)
-        nstreams = max(1, min(int(streams), B))
-        main = torch.cuda.current_stream(dev)
-        side = self._side_streams(nstreams) if nstreams > 1 else [main]
+        out_all, seg_all, nstreams, main, side, _wss = self._batch_outputs(B, shape, streams, labels_u8)
         params, images = [], [None] * B
         with_img = [b for b, (img, _s, _b) in enumerate(items) if img is not None]
         if with_img:  # the deformed real images of the batch as one tensor, like the other outputs
-            img_all = torch.empty((len(with_img), *shape), dtype=torch.float32, device=dev)
+            img_all = torch.empty((len(with_img), *shape), dtype=torch.float32, device=out_all.device)
             for q, b in enumerate(with_img):
                 images[b] = img_all[q]
             for img, _s, bank in items:  # priors are subject constants: computed (once) on the main stream, ahead of the fork
@@ -1121,6 +1030,21 @@ class FetalSynthGen:
                     return None
                 params.append(got[3])
         return out_all, seg_all, images, params
+
+    def _batch_outputs(self, B, shape, streams, labels_u8, rows=None):
+        """(images, labels, stream count, current stream, the streams its samples go round-robin on, [with `rows`: one scratch
+        set of that many rows per stream, allocated ahead of the outputs]) of a fused batch."""
+        dev = torch.device(self.device)
+        nstreams = max(1, min(int(streams), B))
+        main = torch.cuda.current_stream(dev)
+        side = self._side_streams(nstreams) if nstreams > 1 else [main]
+        wss = []
+        for q in range(nstreams if rows is not None else 0):
+            with torch.cuda.stream(side[q]):
+                wss.append(self._workspace(shape, rows))
+        out_all = torch.empty((B, *shape), dtype=torch.float32, device=dev)
+        seg_all = torch.empty((B, *shape), dtype=torch.uint8 if labels_u8 else torch.float32, device=dev)
+        return out_all, seg_all, nstreams, main, side, wss
 
     @staticmethod
     @contextlib.contextmanager
@@ -1197,8 +1121,5 @@ class FetalSynthGen:
                 output = K.add_noise(output, nplan.std32, noise=z, seed=f.seed or 0, stream_id=f.stream_id)
             if fuse_scale:
                 output = K.scale(output, K.reduce_minmax(output), mode=1)
-        output, artifacts = self._apply_artifacts(output, segmentation, genparams)
-        if scale01 and has_art:
-            output = K.scale(output.contiguous(), K.reduce_minmax(output.contiguous()), mode=1)
-
+        output, artifacts = self._artifact_tail(output, segmentation, genparams, scale01)
         return output, segmentation, image, self._synth_params(c, artifacts)

@@ -63,6 +63,17 @@ def config_dict(cfg: _lib.KeyedConfig) -> dict:
     return out
 
 
+# slots of fsg_keyed_sample_run's argument array as plain module names: KeyedContext.fill writes them once per sample
+_KI, _KF = _lib.KEYED_I, _lib.KEYED_FLAG
+_K_KEY, _K_OUT, _K_SEG_OUT, _K_SEG_OUT_U8, _K_SEG_IN, _K_SEG_IN_U8 = _KI.KEY, _KI.OUT, _KI.SEG_OUT, _KI.SEG_OUT_U8, _KI.SEG_IN, _KI.SEG_IN_U8
+_K_BLOCK, _K_WS0, _K_WS1, _K_WS_LOW, _K_WS_ROWS, _K_ROW_STRIDE = _KI.BLOCK, _KI.WS0, _KI.WS1, _KI.WS_LOW, _KI.WS_ROWS, _KI.ROW_STRIDE
+_K_SCALE01, _K_TRACE_EVENTS, _K_TRACE_IDS, _K_TRACE_CAP, _K_BANK = _KI.SCALE01, _KI.TRACE_EVENTS, _KI.TRACE_IDS, _KI.TRACE_CAP, _KI.BANK
+_K_EV_BLUR_BEGIN, _K_EV_BLUR_END, _K_CODES, _K_CODE_TUPLES = _KI.EV_BLUR_BEGIN, _KI.EV_BLUR_END, _KI.CODES, _KI.CODE_TUPLES
+_K_CODE_NTUPLES, _K_CODE_STRIDE, _K_FLAGS, _K_NEXT_KEY, _K_NEXT_BLOCK = _KI.CODE_NTUPLES, _KI.CODE_STRIDE, _KI.FLAGS, _KI.NEXT_KEY, _KI.NEXT_BLOCK
+_K_IMAGE_IN, _K_IMAGE_OUT, _K_PRIOR_IN, _K_OVERRIDES, _K_BLOCK_BYTES = _KI.IMAGE_IN, _KI.IMAGE_OUT, _KI.PRIOR_IN, _KI.OVERRIDES, _KI.BLOCK_BYTES
+_KF_BLOCK_FILLED, _KF_NEXT_NAMED = _KF.BLOCK_FILLED, _KF.NEXT_NAMED
+
+
 KT_CAP = 1024  # largest low-res / coarse-grid size a tap table can be registered for (csrc/fsg_keyed.hip)
 
 
@@ -226,19 +237,21 @@ class KeyedContext:
         self.handle = h
         self.block_bytes = int(self.lib.fsg_keyed_block_bytes(h))
         self.iv = np.zeros(_lib.KEYED_I.COUNT_OV, dtype=np.int64)  # with the two override slots behind COUNT
-        self.ivp = self.iv.ctypes.data
+        self.ivp, self._uv = self.iv.ctypes.data, self.iv.view(np.uint64)  # (_uv: the same slots for the unsigned 64-bit keys)
         self._subjects = IdentityCache()  # (bank | None, segmentation) under the segmentation's version -> Subject
         self._banks = weakref.WeakSet()   # every bank a subject was made of: `forget_subjects` drops their code volumes
         self.use_codes = True  # the subject's seed volumes as one uint16 code volume (seedcodes.py, built on first use)
         self._tables_ready = False
         self._keep = []  # device tables registered with the context
         self._have = set()  # (kind, axis, n) of them
+        self._carried = {}  # launch stream -> (key, parameter block) the previous sample on it filled for its next one (`run`)
         # rows of the per-(x,y) coarse workspace the largest grids need (3 * field_dims[2] + bias_dims[2])
         f2 = int(np.round(self.cfg.nonlin_scale_max * self.shape[2])) if self.cfg.nonlinear else 0
         b2 = max(int(np.round(self.cfg.bf_scale_max * self.shape[2])), 1)
         self.rows_need = 3 * f2 + b2
 
     def close(self):
+        self._carried.clear()
         if self.handle:
             self.lib.fsg_keyed_destroy(self.handle)
             self.handle = None
@@ -250,9 +263,9 @@ class KeyedContext:
             pass
 
     # ---- tables: built by the same cached builders as the other modes, registered by device pointer ----------------------
-    def _register(self, kind, axis, n, tab):
+    def _register(self, kind, axis, n):
         self._have.add((kind, axis, int(n)))
-        d = K._device_table(tab, self.device)
+        d = K._device_table(T.axis_table(kind, n, self.shape[axis]), self.device)
         self._keep.append(d)
         _lib.check(self.lib.fsg_keyed_set_table(self.handle, kind, axis, int(n), C.c_void_p(d.data_ptr())), "fsg_keyed_set_table")
 
@@ -267,41 +280,25 @@ class KeyedContext:
             lo = int(size * c.resolution[a] / max(c.max_resolution, c.resolution[a]))
             hi = int(size * c.resolution[a] / c.min_resolution)
             for m in range(max(lo - 1, 1), min(max(hi, lo) + 1, 4 * size) + 1):
-                self._register(_lib.KT.RESAMPLE, a, m, T._resample_axis_table(m, size))
-                f = np.float64(m) / np.float64(size)
-                self._register(_lib.KT.BACK, a, m, T.zoom_table(m, float(1 / f), int(np.round(m * (1 / f)))))
+                self._register(_lib.KT.RESAMPLE, a, m)
+                self._register(_lib.KT.BACK, a, m)
             if c.nonlinear:
                 for s_ in range(max(int(np.floor(c.nonlin_scale_min * size)) - 1, 1), int(np.ceil(c.nonlin_scale_max * size)) + 2):
-                    self._register(_lib.KT.FIELD, a, s_, T.zoom_table(s_, float(np.float64(size) / np.float64(s_)), size))
+                    self._register(_lib.KT.FIELD, a, s_)
             for s_ in range(max(int(np.floor(c.bf_scale_min * size)) - 1, 1), int(np.ceil(c.bf_scale_max * size)) + 2):
-                self._register(_lib.KT.BIAS, a, s_, T.zoom_table(s_, float(np.float64(size) / np.float64(s_)), size))
+                self._register(_lib.KT.BIAS, a, s_)
         self._tables_ready = True
-
-    def _table_of(self, kind, axis, n):
-        size = self.shape[axis]
-        if kind == _lib.KT.RESAMPLE:
-            return T._resample_axis_table(n, size)
-        if kind == _lib.KT.BACK:
-            f = np.float64(n) / np.float64(size)
-            return T.zoom_table(n, float(1 / f), int(np.round(n * (1 / f))))
-        return T.zoom_table(n, float(np.float64(size) / np.float64(n)), size)  # FIELD, BIAS: coarse grid -> volume
 
     def ensure_tables(self, d: _lib.KeyedDraws):
         """Register what the sample of draws `d` needs beyond `register_tables` (overrides reach sizes the configuration's
         ranges do not: a spacing outside [min, max] resolution, a given grid size)."""
-        need = []
-        for a in range(3):
-            if d.resample_active:
-                need += [(_lib.KT.RESAMPLE, a, d.low_shape[a]), (_lib.KT.BACK, a, d.low_shape[a])]
-            if d.deform_active and d.nonlinear:
-                need.append((_lib.KT.FIELD, a, d.field_dims[a]))
-            if d.bias_active:
-                need.append((_lib.KT.BIAS, a, d.bias_dims[a]))
-        for kind, a, n in need:
+        kinds = ((_lib.KT.RESAMPLE, d.resample_active, d.low_shape), (_lib.KT.BACK, d.resample_active, d.low_shape),
+                 (_lib.KT.FIELD, d.deform_active and d.nonlinear, d.field_dims), (_lib.KT.BIAS, d.bias_active, d.bias_dims))
+        for kind, a, n in [(kind, a, dims[a]) for kind, active, dims in kinds if active for a in range(3)]:
             if (kind, a, n) not in self._have:
                 if not 1 <= n <= KT_CAP:
                     raise ValueError(f"keyed genparams: a tap table of size {n} is outside [1, {KT_CAP}]")
-                self._register(kind, a, n, self._table_of(kind, a, n))
+                self._register(kind, a, n)
 
     # ---- per-subject pointer block --------------------------------------------------------------------------------------
     def subject(self, bank, seg, twin):
@@ -388,6 +385,79 @@ class KeyedContext:
                                 else f"a grid or low-res size is above {KT_CAP}, or the parameter block above 2 GiB"))
         _lib.check(rc, "fsg_keyed_draw_with")
         return d
+
+    def fill(self, key, ent, ws, out, seg_out, labels_u8, scale01, block, flags=0, low=None, events=None, tr=None,
+             image=None, image_out=None, prior=None, next_key=0, nblock=None, ov=None, block_bytes=0):
+        """EVERY slot of `fsg_keyed_sample_run`'s argument array (`self.iv`): nothing of the previous call survives.  key,
+        next_key: in [0, 2^64) (they are stored through the array's uint64 view; callers mask).  ent: the
+        `Subject`; ws: the generator's workspace entry (low: a larger low-res scratch in the place of its own); block, nblock:
+        the parameter blocks of this key and of `next_key`; events, tr: the generator's blur event pair and StageTrace."""
+        iv, uv = self.iv, self._uv
+        uv[_K_KEY] = key
+        iv[_K_OUT] = out.data_ptr()
+        iv[_K_SEG_OUT], iv[_K_SEG_OUT_U8] = (0, seg_out.data_ptr()) if labels_u8 else (seg_out.data_ptr(), 0)
+        iv[_K_SEG_IN], iv[_K_SEG_IN_U8], iv[_K_BLOCK] = ent.seg_ptr, ent.twin_ptr, block.data_ptr()
+        iv[_K_WS0], iv[_K_WS1], iv[_K_WS_LOW] = ws["ws0"].data_ptr(), ws["ws1"].data_ptr(), (low if low is not None else ws["low"]).data_ptr()
+        iv[_K_WS_ROWS], iv[_K_ROW_STRIDE] = (ws["rows"].data_ptr() if ws["rows"] is not None else 0), ws["stride"]
+        iv[_K_SCALE01] = int(bool(scale01))
+        iv[_K_OVERRIDES], iv[_K_BLOCK_BYTES] = (C.addressof(ov.c), block_bytes) if ov is not None else (0, 0)
+        iv[_K_TRACE_EVENTS], iv[_K_TRACE_IDS], iv[_K_TRACE_CAP] = tr.slots() if tr is not None else (0, 0, 0)
+        iv[_K_BANK:_K_BANK + BANK_SLOTS] = ent.bank_ptrs
+        iv[_K_EV_BLUR_BEGIN], iv[_K_EV_BLUR_END] = events if events is not None else (0, 0)
+        # the subject's code volume (0: four label volumes)
+        iv[_K_CODES], iv[_K_CODE_TUPLES], iv[_K_CODE_NTUPLES], iv[_K_CODE_STRIDE] = ent.codes, ent.code_tuples, ent.code_ntuples, ent.code_stride
+        iv[_K_IMAGE_IN], iv[_K_IMAGE_OUT] = (image.data_ptr(), image_out.data_ptr()) if image is not None else (0, 0)
+        iv[_K_PRIOR_IN] = prior.data_ptr() if prior is not None else 0
+        iv[_K_FLAGS] = flags
+        uv[_K_NEXT_KEY], iv[_K_NEXT_BLOCK] = (next_key, nblock.data_ptr()) if nblock is not None else (0, 0)
+
+    def run(self, key, ent, workspace, dev, out, seg_out, labels_u8, scale01, events=None, tr=None, next_key=None, image=None,
+            image_out=None, prior=None, genparams=None):
+        """The sample of `key` on the current stream in ONE native call (draws, the draw kernel, the launch sequence).  Returns
+        (draws, parameter block, whether that block was carried, image, labels), or None outside the fused kernels' domain.
+        workspace(shape, rows): the caller's scratch entry; out, seg_out: the caller's output tensors, None: made here, behind
+        the workspace (the order the memory pool has always seen).  next_key: the key this context will be asked for NEXT on this
+        stream; its draw job rides in this sample's floor(min) launch and the block it fills waits in `_carried` (a call for
+        another key drops it).  genparams (validated): the values the caller fixed (`overrides_of`); such a sample uses no
+        carried block (that one holds the key's own tables) and sizes its block, row workspace and low-res scratch itself."""
+        ov = overrides_of(genparams, self.cfg, dev) if genparams else None
+        rows_need, block_bytes, low = self.rows_need, self.block_bytes, None
+        if ov is not None:
+            d0 = self.draws(key, ov)
+            self.ensure_tables(d0)
+            rows_need = max(rows_need, 3 * d0.field_dims[2] + d0.bias_dims[2])
+            block_bytes = max(block_bytes, d0.block_bytes)
+            if d0.resample_active and int(np.prod(list(d0.low_shape))) > int(np.prod(self.shape)):  # a spacing below the resolution
+                low = torch.empty(int(np.prod(list(d0.low_shape))), dtype=torch.float32, device=dev)
+        ws = workspace(self.shape, rows_need)
+        if out is None:
+            out = torch.empty(self.shape, dtype=torch.float32, device=dev)
+        if seg_out is None:
+            seg_out = torch.empty(self.shape, dtype=torch.uint8 if labels_u8 else torch.float32, device=dev)
+        # what the previous call carried for this one: the parameter block of exactly this key, on this stream
+        stream = K._stream(dev)
+        pre = self._carried.pop(stream.value, None)  # one carried block per launch stream
+        if pre is not None and pre[0] == key and ov is None:
+            block, flags = pre[1], _KF_BLOCK_FILLED
+        else:
+            block, flags = torch.empty(block_bytes, dtype=torch.uint8, device=dev), 0
+        nblock = None
+        if next_key is not None:
+            next_key &= 0xFFFFFFFFFFFFFFFF
+            nblock = torch.empty(self.block_bytes, dtype=torch.uint8, device=dev)
+            flags |= _KF_NEXT_NAMED
+        self.fill(key, ent, ws, out, seg_out, labels_u8, scale01, block, flags=flags, low=low, events=events, tr=tr, image=image,
+                  image_out=image_out, prior=prior, next_key=next_key, nblock=nblock, ov=ov, block_bytes=block_bytes)
+        d = _lib.KeyedDraws()
+        rc = self.lib.fsg_keyed_sample_run(self.handle, self.ivp, len(self.iv), C.byref(d), stream)
+        if rc in (_lib.E_ALIGN, _lib.E_TOOBIG):
+            return None
+        _lib.check(rc, "fsg_keyed_sample_run")
+        if nblock is not None and d.rode:
+            if len(self._carried) > 8:
+                self._carried.clear()
+            self._carried[stream.value] = (next_key, nblock)
+        return d, block, flags & _KF_BLOCK_FILLED, out, seg_out
 
 
 def params_of(d: _lib.KeyedDraws, block: torch.Tensor | None) -> dict:

@@ -116,6 +116,20 @@ def _resample_axis_table(n_new: int, n_src: int) -> np.ndarray:
     return tab
 
 
+def axis_table(kind: int, n: int, size: int) -> np.ndarray:
+    """The tap table of kind `_lib.KT.*` between a `size`-long volume axis and its `n`-long low-res axis (RESAMPLE: down,
+    as in `resample_plan`; BACK: up again, `zoom_tables_between(.., True)`) or coarse grid (FIELD, BIAS: up,
+    `zoom_tables_between`): the one place prewarming and the keyed registration take the (cached) builders' arguments from."""
+    if kind == _lib.KT.RESAMPLE:
+        return _resample_axis_table(n, size)
+    if kind == _lib.KT.BACK:
+        f = np.float64(n) / np.float64(size)
+        return zoom_table(n, float(1 / f), int(np.round(n * (1 / f))))
+    if kind in (_lib.KT.FIELD, _lib.KT.BIAS):
+        return zoom_table(n, float(np.float64(size) / np.float64(n)), size)
+    raise ValueError(f"axis_table: unknown table kind {kind!r}")
+
+
 @lru_cache(maxsize=64)
 def _tap_positions(half: int) -> torch.Tensor:
     return torch.linspace(-half, half, 2 * half + 1, dtype=torch.float32)

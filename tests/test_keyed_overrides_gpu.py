@@ -285,7 +285,7 @@ def test_batches_and_the_look_ahead(generators, subject):
     # one stream: a plain sample naming the next key, that key with an override, then a plain one
     seq = _generator(S64)
     a = seq._pipeline(None, seg_d, bank, {}, scale01=True, key=keys[0], next_key=keys[1])
-    assert seq.__dict__.get("_pre"), "the next sample's draw job rode along (deformation gate on)"
+    assert seq.keyed_context(S64)._carried, "the next sample's draw job rode along (deformation gate on)"
     b = seq._pipeline(None, seg_d, bank, gps[1], scale01=True, key=keys[1])
     c = seq._pipeline(None, seg_d, bank, {}, scale01=True, key=keys[2])
     assert torch.equal(a[0], plain[0][0]) and torch.equal(b[0], ref[1][0]) and torch.equal(b[1], ref[1][1])

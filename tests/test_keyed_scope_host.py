@@ -129,3 +129,42 @@ def test_clock_reseed_is_skipped_inside_a_scope(monkeypatch):
     before = np.random.get_state()
     U.reseed_from_clock()
     assert np_state_equal(before, np.random.get_state())
+
+
+def test_apply_artifacts_opens_a_scope_per_stage_only_with_a_key():
+    """The wiring of `FetalSynthGen._apply_artifacts`: without a key no stage runs in a keyed scope (the stage-by-stage
+    path: the stages draw from the caller's generators); with one every stage does, and the caller's generators come back
+    bit for bit."""
+    from fetalsyngen_amd.rng import STAGE_STREAMS
+    from tests.util_cases import make_generator
+
+    seen = []
+
+    def stage(name):
+        def run(output, segmentation, device, genparams, resolution=None):
+            seen.append((name, R.in_keyed_scope(), draws()))
+            return output, {"stage": name}
+
+        return run
+
+    gen = make_generator((8, 8, 8), "cuda:0", rng="keyed", artifacts={name: stage(name) for name in STAGE_STREAMS})
+    vol, seg = torch.zeros(8, 8, 8), torch.zeros(8, 8, 8)
+    np.random.seed(3)
+    torch.manual_seed(4)
+    np.random.standard_normal(), torch.rand(3)
+    n0, t0 = np.random.get_state(), torch.get_rng_state()
+    out, meta = gen._apply_artifacts(vol, seg, {}, key=KEY)
+    assert out is vol and list(meta) == list(STAGE_STREAMS) == [name for name, _s, _d in seen]
+    assert all(in_scope for _n, in_scope, _d in seen), seen
+    assert np_state_equal(n0, np.random.get_state()) and torch.equal(t0, torch.get_rng_state())
+    assert not R.in_keyed_scope()
+    assert [d for _n, _s, d in seen] == [scoped(KEY, STAGE_STREAMS[name]) for name in STAGE_STREAMS]
+    keyed_draws = [d for _n, _s, d in seen]
+    del seen[:]
+    out, meta = gen._apply_artifacts(vol, seg, {})
+    assert out is vol and list(meta) == list(STAGE_STREAMS)
+    assert [in_scope for _n, in_scope, _d in seen] == [False] * len(STAGE_STREAMS), seen
+    assert not np_state_equal(n0, np.random.get_state())  # the stages drew from the caller's generators ...
+    np.random.set_state(n0)
+    torch.set_rng_state(t0)
+    assert [d for _n, _s, d in seen] == [draws() for _ in STAGE_STREAMS] != keyed_draws  # ... these very draws

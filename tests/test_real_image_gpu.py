@@ -180,7 +180,7 @@ def test_keyed_prior_samples_equal_the_oracle(K, subjects):
         got = gen._pipeline(img_d, seg_d, None, {}, scale01=True, key=k, next_key=keys[i + 1] if i + 1 < 3 else None)
         assert got[3]["key"] == k and got[3]["selected_seeds"] == {} and got[3]["seed_intensities"] == {}
         if i < 2:
-            assert gen.__dict__.get("_pre"), "the next sample's draw job did not ride along"
+            assert kc._carried, "the next sample's draw job did not ride along"
         _d, ex = export_draws(kc, K, k)
         _check(got, oracle_with_image(K, SHAPE, k, seg, None, img, ex, KW), f"key {i}")
     # the launches of such a sample: the head without a GMM launch, ONE warp launch (the dual-source kernel, not the two-launch form)

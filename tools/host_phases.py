@@ -69,20 +69,13 @@ acck = {}
 def tickk(name, t0):
     t1 = time.perf_counter(); acck[name] = acck.get(name, 0.0) + (t1 - t0); return t1
 twin = genk._label_twin(segd)
-KI = _lib.KEYED_I
 for i in range(a.n):
     t = time.perf_counter()
     key = sharding.sample_key(1, 100 + i); t = tickk("sample_key (splitmix64, Python ints)", t)
     ent = kc.subject(bank, segd, twin); ws = genk._workspace(shape, kc.rows_need); t = tickk("subject pointers + workspace", t)
     out = torch.empty(shape, dtype=torch.float32, device=dev); so = torch.empty(shape, dtype=torch.float32, device=dev)
     block = torch.empty(kc.block_bytes, dtype=torch.uint8, device=dev); t = tickk("torch.empty x3", t)
-    iv = kc.iv
-    iv[KI.KEY] = key if key < (1 << 63) else key - (1 << 64); iv[KI.OUT] = out.data_ptr(); iv[KI.SEG_OUT], iv[KI.SEG_OUT_U8] = so.data_ptr(), 0
-    iv[KI.SEG_IN], iv[KI.SEG_IN_U8], iv[KI.BLOCK] = ent.seg_ptr, ent.twin_ptr, block.data_ptr()
-    iv[KI.WS0], iv[KI.WS1], iv[KI.WS_LOW] = ws["ws0"].data_ptr(), ws["ws1"].data_ptr(), ws["low"].data_ptr()
-    iv[KI.WS_ROWS], iv[KI.ROW_STRIDE], iv[KI.SCALE01] = (ws["rows"].data_ptr() if ws["rows"] is not None else 0), ws["stride"], 1
-    iv[KI.TRACE_EVENTS] = iv[KI.TRACE_IDS] = iv[KI.TRACE_CAP] = 0; iv[KI.BANK:KI.BANK + _keyed.BANK_SLOTS] = ent.bank_ptrs
-    iv[KI.EV_BLUR_BEGIN] = iv[KI.EV_BLUR_END] = 0; t = tickk("fill the int64 argument array", t)
+    kc.fill(key, ent, ws, out, so, False, True, block); t = tickk("KeyedContext.fill (the int64 argument array)", t)
     d = _lib.KeyedDraws()
     rc = kc.lib.fsg_keyed_sample_run(kc.handle, kc.ivp, len(kc.iv), C.byref(d), K._stream(torch.device(dev))); t = tickk("fsg_keyed_sample_run (C: draws + 8 launches)", t)
     prm = _keyed.params_of(d, block); t = tickk("params_of (synth_params dict)", t)
