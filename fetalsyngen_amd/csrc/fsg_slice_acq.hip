@@ -845,6 +845,357 @@ __global__ __launch_bounds__(256) void sa_adjoint_nn_lds_kernel(SaParams P, cons
 }
 
 // ---------------------------------------------------------------------------------------------------------
+// adjoint, CUDA-kernel semantics, deterministic accumulation (fsg_slice_acq_adjoint_det_f32; the rule is stated in
+// include/fsg_hip.h).  Sibling kernels of the two above, so that the fp32-atomic kernels stay what they are:
+//   * a contribution is formed by the same fp32 operations as in sa_adjoint_nn_lds_kernel (sa_round_pos,
+//     sa_psf_at_fast, pv * (1 / wsum)) in BOTH kernels here -- the float direct kernel's sa_psf_at / division differ
+//     from those in the last bit, which fp32 order noise hides there and nothing would hide here;
+//   * it is quantised once to a multiple of 2^-F, F = 72 (sa_fix2), and added as an integer of two 64-bit limbs, the high
+//     one counting 2^-32 and the low one 2^-72: ds_add_u64 in LDS, global_atomic_add_x2 in the workspace, each limb summed
+//     on its own and the carry resolved at the end.  Integer sums do not depend on their order, so tile size, chunking,
+//     the LDS / direct choice per chunk and the scheduling of workgroups all give the same accumulators.  (One limb at
+//     2^-32 is not enough: equalisation divides by weights that may be a few quanta);
+//   * the per-pixel weight of pass 1 is summed in fixed point too (each tap's PSF value quantised to 2^-32, integer partials
+//     over the waves of an 8x8 tile, one conversion), so `wsum`, its 0.5 cut and 1 / wsum do not depend on the tile either;
+//   * sa_det_finalize_kernel converts every accumulator with one rounding.
+// Cells are 32 B (value and weight, two limbs each), so the LDS accumulator holds at most SA_DET_CAP_MAX cells; the dynamic
+// LDS prefix (PSF and tap products, an odd number of floats for some PSFs) is rounded up to 8 bytes before the 64-bit arrays.
+// No address depends on a slice value: a non-finite value gives an unspecified sum, never a fault.
+// ---------------------------------------------------------------------------------------------------------
+typedef unsigned long long sa_u64;
+constexpr int SA_DET_CAP_MAX = 4096;  // 128 KiB of cells + <= 19 KiB of prefix and partials, inside the 160 KiB of a CU
+constexpr int SA_DET_HI_BITS = FSG_SA_DET_FRAC_BITS - FSG_SA_DET_LIMB_BITS;  // the high limb counts 2^-32
+constexpr double SA_DET_ONE = (double)(1ull << SA_DET_HI_BITS);
+constexpr double SA_DET_LIMB = (double)(1ull << FSG_SA_DET_LIMB_BITS);
+
+// round-half-even(c * k) for k a power of two: the product is exact in double, one rounding (the pixel weight's 2^-32)
+__device__ __forceinline__ sa_u64 sa_fix(float c, double k) { return (sa_u64)__double2ll_rn((double)c * k); }
+__device__ __forceinline__ float sa_unfix(long long q, float k) { return __ll2float_rn(q) * k; }
+// Q = round-half-even(c * k * 2^LIMB) as hi * 2^LIMB + lo: d = c * k is exact in double, d - rint(d) is exact (at most 1/2,
+// a multiple of ulp(d)), and rint(x + even integer) = rint(x) + that integer.  |lo| <= 2^(LIMB-1).  A contribution of
+// 2^-(F-24) and more (d >= 2^-16: ulp(d) >= 2^-LIMB) enters exactly.
+struct sa_q2 { sa_u64 hi, lo; };
+__device__ __forceinline__ sa_q2 sa_fix2(float c, double k) {
+  const double d = (double)c * k, h = rint(d);
+  return sa_q2{(sa_u64)(long long)h, (sa_u64)__double2ll_rn((d - h) * SA_DET_LIMB)};
+}
+// a cell is {value hi, value lo [, weight hi, weight lo]}; zero limbs are not sent
+__device__ __forceinline__ void sa_add2(sa_u64* cell, const sa_q2 q) {
+  if (q.hi) atomicAdd(cell, q.hi);
+  if (q.lo) atomicAdd(cell + 1, q.lo);
+}
+// hi * 2^LIMB + lo -> float32 with ONE rounding to nearest even, times 2^(ex - LIMB): the carry of lo goes into hi, the
+// magnitude is cut to 63 bits that keep a sticky bit far below the rounding position, one conversion rounds, ldexp is exact
+__device__ __forceinline__ float sa_unfix2(long long hi, long long lo, int ex) {
+  constexpr long long ONE = 1ll << FSG_SA_DET_LIMB_BITS;
+  const long long carry = lo >> FSG_SA_DET_LIMB_BITS;  // arithmetic shift: floor
+  hi += carry;
+  lo -= carry * ONE;  // 0 <= lo < ONE
+  const bool neg = hi < 0;
+  sa_u64 mh = (sa_u64)hi, ml = (sa_u64)lo;
+  if (neg) {  // -(hi * ONE + lo) = (-hi - 1) * ONE + (ONE - lo) for lo > 0
+    mh = lo ? (sa_u64)(-(hi + 1)) : (sa_u64)0 - (sa_u64)hi;
+    ml = lo ? (sa_u64)(ONE - lo) : 0;
+  }
+  int t = FSG_SA_DET_LIMB_BITS;
+  if (mh) t = min(t, __clzll((long long)mh) - 1);
+  t = max(t, 0);  // (mh = 2^63, the overflowed sum of an out-of-range input: any value will do)
+  const int down = FSG_SA_DET_LIMB_BITS - t;
+  sa_u64 x = (mh << t) | (ml >> down);
+  if (down && (ml & ((1ull << down) - 1))) x |= 1;  // sticky: x has its top bit at 62 here, rounding happens at bit 38
+  const float f = ldexpf(__ll2float_rn((long long)x), down + ex - FSG_SA_DET_LIMB_BITS);
+  return neg ? -f : f;
+}
+
+template <bool NN, bool VM>
+__global__ __launch_bounds__(SA_TILE* SA_TILE) void sa_adjoint_det_kernel(SaParams P, const float* __restrict__ slices,
+                                                                          sa_u64* __restrict__ acc, int limbs,
+                                                                          double kval) {
+  // acc: `limbs` (2: value only, 4: value and weight) 64-bit words per voxel
+  extern __shared__ float smem[];
+  const int in = blockIdx.z;
+  const float* __restrict__ T = P.tr + (size_t)in * 12;
+  const SaLds L = sa_lds_layout(smem, P);
+  sa_fill_lds(L, P, T);
+  __syncthreads();
+  const int ix = blockIdx.x * SA_TILE + threadIdx.x, iy = blockIdx.y * SA_TILE + threadIdx.y;
+  if (ix >= P.w || iy >= P.h) return;
+  const size_t idx = ((size_t)(P.sid ? P.sid[in] : in) * P.h + iy) * P.w + ix;
+  if (P.smask && !P.smask[idx]) return;
+  const float s = slices[idx];
+  float xc, yc, zc;
+  sa_centre(P, T, ix, iy, xc, yc, zc);
+  const int Sy = P.W, Sz = P.H * P.W;
+  const float hx = (float)(P.W - 1), hy = (float)(P.H - 1), hz = (float)(P.D - 1);
+
+  long long wq = 0;
+  int ip = 0;
+  for (int kz = 0; kz < P.pd; ++kz) {
+    const float zx = L.tz[kz], zy = L.tz[P.pd + kz], zz = L.tz[2 * P.pd + kz];
+    for (int ky = 0; ky < P.ph; ++ky) {
+      const float yx = L.ty[ky], yy = L.ty[P.ph + ky], yz = L.ty[2 * P.ph + ky];
+      for (int kx = 0; kx < P.pw; ++kx, ++ip) {
+        float pv = L.psf[ip];
+        if (pv == 0.f) continue;
+        const float x = xc + L.tx[kx] + yx + zx;
+        const float y = yc + L.tx[P.pw + kx] + yy + zy;
+        const float z = zc + L.tx[2 * P.pw + kx] + yz + zz;
+        if (x < 0 || y < 0 || z < 0 || x >= hx || y >= hy || z >= hz) continue;
+        if (NN && !sa_psf_at_fast(L, P, T, sa_round_pos(x) - xc, sa_round_pos(y) - yc, sa_round_pos(z) - zc, pv)) continue;
+        wq += (long long)sa_fix(pv, SA_DET_ONE);
+      }
+    }
+  }
+  const float weight = sa_unfix(wq, (float)(1.0 / SA_DET_ONE));
+  if (weight < 0.5f) return;  // border
+  const float inv = 1.f / weight;
+
+  ip = 0;
+  for (int kz = 0; kz < P.pd; ++kz) {
+    const float zx = L.tz[kz], zy = L.tz[P.pd + kz], zz = L.tz[2 * P.pd + kz];
+    for (int ky = 0; ky < P.ph; ++ky) {
+      const float yx = L.ty[ky], yy = L.ty[P.ph + ky], yz = L.ty[2 * P.ph + ky];
+      for (int kx = 0; kx < P.pw; ++kx, ++ip) {
+        float pv = L.psf[ip];
+        if (pv == 0.f) continue;
+        const float x = xc + L.tx[kx] + yx + zx;
+        const float y = yc + L.tx[P.pw + kx] + yy + zy;
+        const float z = zc + L.tx[2 * P.pw + kx] + yz + zz;
+        if (x < 0 || y < 0 || z < 0 || x >= hx || y >= hy || z >= hz) continue;
+        if (NN) {
+          const float xr = sa_round_pos(x), yr = sa_round_pos(y), zr = sa_round_pos(z);
+          if (!sa_psf_at_fast(L, P, T, xr - xc, yr - yc, zr - zc, pv)) continue;
+          pv *= inv;
+          const int iv = (int)zr * Sz + (int)yr * Sy + (int)xr;
+          if (VM && !P.vmask[iv]) continue;
+          sa_u64* cell = acc + (size_t)iv * limbs;
+          sa_add2(cell, sa_fix2(pv * s, kval));
+          if (limbs == 4) sa_add2(cell + 2, sa_fix2(pv, SA_DET_ONE));
+        } else {
+          const float xf = floorf(x), yf = floorf(y), zf = floorf(z);
+          const float wx = x - xf, wy = y - yf, wz = z - zf;
+          const int iv = (int)zf * Sz + (int)yf * Sy + (int)xf;
+          pv *= inv;
+          float pw_;
+#define SA_CORNER(OFF, WEXPR)                                                  \
+  if (!VM || P.vmask[iv + (OFF)]) {                                            \
+    pw_ = (WEXPR) * pv;                                                        \
+    sa_u64* cell = acc + (size_t)(iv + (OFF)) * limbs;                         \
+    sa_add2(cell, sa_fix2(pw_ * s, kval));                                     \
+    if (limbs == 4) sa_add2(cell + 2, sa_fix2(pw_, SA_DET_ONE));               \
+  }
+          SA_CORNER(0, (1 - wx) * (1 - wy) * (1 - wz))
+          SA_CORNER(1, wx * (1 - wy) * (1 - wz))
+          SA_CORNER(Sy, (1 - wx) * wy * (1 - wz))
+          SA_CORNER(Sz, (1 - wx) * (1 - wy) * wz)
+          SA_CORNER(1 + Sy, wx * wy * (1 - wz))
+          SA_CORNER(1 + Sz, wx * (1 - wy) * wz)
+          SA_CORNER(Sy + Sz, (1 - wx) * wy * wz)
+          SA_CORNER(Sy + Sz + 1, wx * wy * wz)
+#undef SA_CORNER
+        }
+      }
+    }
+  }
+}
+
+// sa_adjoint_nn_lds_kernel with 64-bit fixed-point cells: the tile / chunk / plate geometry is that kernel's, line by line.
+template <int T_, bool VM>
+__global__ __launch_bounds__(256) void sa_adjoint_nn_lds_det_kernel(SaParams P, const float* __restrict__ slices,
+                                                                    sa_u64* __restrict__ acc, int limbs, int zc, int cap,
+                                                                    double kval) {
+  constexpr int NPIX = T_ * T_, G = 256 / NPIX;
+  extern __shared__ float smem[];
+  extern __shared__ __align__(16) sa_u64 smem64[];  // the same dynamic LDS; raises its alignment to that of the cells
+  const int in = blockIdx.z;
+  const float* __restrict__ T = P.tr + (size_t)in * 12;
+  const SaLds L = sa_lds_layout(smem, P);
+  const int pre = (P.pd * P.ph * P.pw + 3 * (P.pd + P.ph + P.pw) + 1) >> 1;  // prefix in 8-byte units, rounded up
+  long long* part = reinterpret_cast<long long*>(smem64 + pre);  // [256] partial pixel weights
+  sa_u64* cells_lds = smem64 + pre + 256;  // [cap] cells of {value hi, value lo, weight hi, weight lo}
+  {
+    const int tid = threadIdx.x, np = P.pd * P.ph * P.pw;
+    for (int e = tid; e < np; e += 256) L.psf[e] = P.psf[e];
+    for (int e = tid; e < 3 * P.pw; e += 256) { const int a = e / P.pw, i = e - a * P.pw; L.tx[e] = T[a * 4 + 0] * (float)(i - P.pw / 2); }
+    for (int e = tid; e < 3 * P.ph; e += 256) { const int a = e / P.ph, i = e - a * P.ph; L.ty[e] = T[a * 4 + 1] * (float)(i - P.ph / 2); }
+    for (int e = tid; e < 3 * P.pd; e += 256) { const int a = e / P.pd, i = e - a * P.pd; L.tz[e] = T[a * 4 + 2] * (float)(i - P.pd / 2); }
+  }
+  __syncthreads();
+  const int tid = threadIdx.x;
+  const int p = tid % NPIX, g = tid / NPIX;
+  const int ix0 = blockIdx.x * T_, iy0 = blockIdx.y * T_;
+  const int ix = ix0 + p % T_, iy = iy0 + p / T_;
+  bool live = ix < P.w && iy < P.h;
+  const size_t idx = ((size_t)(P.sid ? P.sid[in] : in) * P.h + (live ? iy : 0)) * P.w + (live ? ix : 0);
+  if (live && P.smask && !P.smask[idx]) live = false;
+  const float s = live ? slices[idx] : 0.f;
+  float xc, yc, zc_;
+  sa_centre(P, T, ix, iy, xc, yc, zc_);
+  const int Sy = P.W, Sz = P.H * P.W;
+  const float hx = (float)(P.W - 1), hy = (float)(P.H - 1), hz = (float)(P.D - 1);
+
+  const int ixl = ix0, ixh = min(ix0 + T_ - 1, P.w - 1), iyl = iy0, iyh = min(iy0 + T_ - 1, P.h - 1);
+  const float alo = ((float)ixl - (float)(P.w - 1) * 0.5f) * P.res + T[3] - (float)(P.pw / 2);
+  const float ahi = ((float)ixh - (float)(P.w - 1) * 0.5f) * P.res + T[3] + (float)(P.pw - 1 - P.pw / 2);
+  const float blo = ((float)iyl - (float)(P.h - 1) * 0.5f) * P.res + T[7] - (float)(P.ph / 2);
+  const float bhi = ((float)iyh - (float)(P.h - 1) * 0.5f) * P.res + T[7] + (float)(P.ph - 1 - P.ph / 2);
+  const int dimv[3] = {P.W, P.H, P.D};
+  auto reach = [&](float clo, float chi, int* o, int* b) -> bool {
+    bool inside = true;
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+      const float r0 = T[a * 4], r1 = T[a * 4 + 1], r2 = T[a * 4 + 2];
+      const float off = (float)(dimv[a] - 1) * 0.5f;
+      const float mn = off + fminf(r0 * alo, r0 * ahi) + fminf(r1 * blo, r1 * bhi) + fminf(r2 * clo, r2 * chi);
+      const float mx = off + fmaxf(r0 * alo, r0 * ahi) + fmaxf(r1 * blo, r1 * bhi) + fmaxf(r2 * clo, r2 * chi);
+      const int lo = max((int)floorf(mn + 0.5f - 2e-3f), 0), hi = min((int)floorf(mx + 0.5f + 2e-3f), dimv[a] - 1);
+      o[a] = lo;
+      b[a] = hi - lo + 1;
+      inside = inside && mn - 2e-3f >= 0.f && mx + 2e-3f < (float)(dimv[a] - 1);
+    }
+    return inside;
+  };
+  int o_all[3], b_all[3];
+  const bool inside_all = reach(T[11] + (float)(0 - P.pd / 2), T[11] + (float)(P.pd - 1 - P.pd / 2), o_all, b_all);
+
+  // pass 1: pixel weight in fixed point -- the same integer for a pixel whatever G is
+  long long wq = 0;
+  if (live) {
+    for (int kz = 0; kz < P.pd; ++kz) {
+      const float zx = L.tz[kz], zy = L.tz[P.pd + kz], zz = L.tz[2 * P.pd + kz];
+      for (int ky = g; ky < P.ph; ky += G) {
+        const float yx = L.ty[ky], yy = L.ty[P.ph + ky], yz = L.ty[2 * P.ph + ky];
+        const int ip0 = (kz * P.ph + ky) * P.pw;
+        for (int kx = 0; kx < P.pw; ++kx) {
+          float pv = L.psf[ip0 + kx];
+          if (pv == 0.f) continue;
+          const float x = xc + L.tx[kx] + yx + zx;
+          const float y = yc + L.tx[P.pw + kx] + yy + zy;
+          const float z = zc_ + L.tx[2 * P.pw + kx] + yz + zz;
+          if (!inside_all && (x < 0 || y < 0 || z < 0 || x >= hx || y >= hy || z >= hz)) continue;
+          if (!sa_psf_at_fast(L, P, T, sa_round_pos(x) - xc, sa_round_pos(y) - yc, sa_round_pos(z) - zc_, pv)) continue;
+          wq += (long long)sa_fix(pv, SA_DET_ONE);
+        }
+      }
+    }
+  }
+  if (G > 1) {
+    part[tid] = wq;
+    __syncthreads();
+    wq = 0;
+#pragma unroll
+    for (int q = 0; q < G; ++q) wq += part[q * NPIX + p];
+  }
+  const float wsum = sa_unfix(wq, (float)(1.0 / SA_DET_ONE));
+  if (wsum < 0.5f) live = false;
+  const float inv = live ? 1.f / wsum : 0.f;
+
+  const float n0 = T[2], n1 = T[6], n2 = T[10];
+  const int A = (fabsf(n0) >= fabsf(n1) && fabsf(n0) >= fabsf(n2)) ? 0 : (fabsf(n1) >= fabsf(n2) ? 1 : 2);
+  const int U = A == 0 ? 1 : 0, V = A == 2 ? 1 : 2;
+  const float nA = A == 0 ? n0 : (A == 1 ? n1 : n2), nU = U == 0 ? n0 : n1, nV = V == 1 ? n1 : n2;
+  const float inv_na = 1.f / nA, slope = (fabsf(nU) + fabsf(nV)) * fabsf(inv_na);
+  const float amid = 0.5f * (alo + ahi), bmid = 0.5f * (blo + bhi);
+
+  for (int kz0 = 0; kz0 < P.pd; kz0 += zc) {
+    const int kz1 = min(kz0 + zc, P.pd);
+    const float clo = T[11] + (float)(kz0 - P.pd / 2), chi = T[11] + (float)(kz1 - 1 - P.pd / 2);
+    int o[3], b[3];
+    const bool inside = reach(clo, chi, o, b);
+    if (b[0] <= 0 || b[1] <= 0 || b[2] <= 0) continue;
+    const float cmid = 0.5f * (clo + chi);
+    float pm[3];
+#pragma unroll
+    for (int a = 0; a < 3; ++a)
+      pm[a] = (float)(dimv[a] - 1) * 0.5f + T[a * 4] * amid + T[a * 4 + 1] * bmid + T[a * 4 + 2] * cmid;
+    const int K = (int)ceilf(((float)(kz1 - 1 - kz0) + 1.f) * fabsf(inv_na) + slope + 1.f) + 1;
+    const float hb = 0.5f * (float)K;
+    const int bu = b[U], bv = b[V];
+    const long long cells = (long long)bu * bv * K;
+    const bool use_lds = cells <= (long long)cap;  // cap <= SA_DET_CAP_MAX: 4 * cells and the limb indices stay far inside int
+    const bool xlean = A == 0;
+    if (use_lds) {
+      for (int c = tid; c < 4 * (int)cells; c += 256) cells_lds[c] = 0;
+      __syncthreads();
+    }
+    if (live) {
+      for (int kz = kz0; kz < kz1; ++kz) {
+        const float zx = L.tz[kz], zy = L.tz[P.pd + kz], zz = L.tz[2 * P.pd + kz];
+        for (int ky = g; ky < P.ph; ky += G) {
+          const float yx = L.ty[ky], yy = L.ty[P.ph + ky], yz = L.ty[2 * P.ph + ky];
+          const int ip0 = (kz * P.ph + ky) * P.pw;
+          for (int kx = 0; kx < P.pw; ++kx) {
+            float pv = L.psf[ip0 + kx];
+            if (pv == 0.f) continue;
+            const float x = xc + L.tx[kx] + yx + zx;
+            const float y = yc + L.tx[P.pw + kx] + yy + zy;
+            const float z = zc_ + L.tx[2 * P.pw + kx] + yz + zz;
+            if (!inside && (x < 0 || y < 0 || z < 0 || x >= hx || y >= hy || z >= hz)) continue;
+            const float xr = sa_round_pos(x), yr = sa_round_pos(y), zr = sa_round_pos(z);
+            if (!sa_psf_at_fast(L, P, T, xr - xc, yr - yc, zr - zc_, pv)) continue;
+            pv *= inv;
+            const int vv[3] = {(int)xr, (int)yr, (int)zr};
+            const int iv = vv[2] * Sz + vv[1] * Sy + vv[0];
+            if (VM && !P.vmask[iv]) continue;
+            const sa_q2 qv = sa_fix2(pv * s, kval), qw = sa_fix2(pv, SA_DET_ONE);
+            bool done = false;
+            if (use_lds) {
+              const int cu = vv[U] - o[U], cv = vv[V] - o[V];
+              const float fu = (float)vv[U] - pm[U], fv = (float)vv[V] - pm[V];
+              const int base = (int)floorf(pm[A] - (nU * fu + nV * fv) * inv_na - hb);
+              const int k = vv[A] - base;
+              if ((unsigned)cu < (unsigned)bu && (unsigned)cv < (unsigned)bv && (unsigned)k < (unsigned)K) {
+                const int c = xlean ? (cv * bu + cu) * K + k : (cv * K + k) * bu + cu;
+                sa_add2(cells_lds + 4 * c, qv);
+                sa_add2(cells_lds + 4 * c + 2, qw);
+                done = true;
+              }
+            }
+            if (!done) {
+              sa_u64* cell = acc + (size_t)iv * limbs;
+              sa_add2(cell, qv);
+              if (limbs == 4) sa_add2(cell + 2, qw);
+            }
+          }
+        }
+      }
+    }
+    if (use_lds) {
+      __syncthreads();
+      for (int c = tid; c < (int)cells; c += 256) {
+        const sa_q2 qv{cells_lds[4 * c], cells_lds[4 * c + 1]}, qw{cells_lds[4 * c + 2], cells_lds[4 * c + 3]};
+        if ((qv.hi | qv.lo | qw.hi | qw.lo) == 0) continue;  // untouched (or sums of zero: nothing to add)
+        int cu, cv, k;
+        if (xlean) { k = c % K; const int r = c / K; cu = r % bu; cv = r / bu; }
+        else { cu = c % bu; const int r = c / bu; k = r % K; cv = r / K; }
+        int vv[3];
+        vv[U] = cu + o[U];
+        vv[V] = cv + o[V];
+        const float fu = (float)vv[U] - pm[U], fv = (float)vv[V] - pm[V];
+        vv[A] = (int)floorf(pm[A] - (nU * fu + nV * fv) * inv_na - hb) + k;
+        const int iv = vv[2] * Sz + vv[1] * Sy + vv[0];
+        sa_u64* cell = acc + (size_t)iv * limbs;
+        sa_add2(cell, qv);
+        if (limbs == 4) sa_add2(cell + 2, qw);
+      }
+      __syncthreads();
+    }
+  }
+}
+
+// accumulators -> float32, one rounding each (sa_unfix2); every voxel is written, an untouched accumulator gives +0.
+// ex_v = log2(value_scale) - 32, ex_w = -32: the exponent of the high limb's unit.
+__global__ __launch_bounds__(256) void sa_det_finalize_kernel(const long long* __restrict__ acc, int limbs,
+                                                              float* __restrict__ vol, float* __restrict__ vol_weight, int ex_v,
+                                                              int ex_w, size_t n) {
+  for (size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x; e < n; e += (size_t)gridDim.x * blockDim.x) {
+    const long long* cell = acc + e * limbs;
+    vol[e] = sa_unfix2(cell[0], cell[1], ex_v);
+    if (limbs == 4) vol_weight[e] = sa_unfix2(cell[2], cell[3], ex_w);
+  }
+}
+
+// ---------------------------------------------------------------------------------------------------------
 // torch-fallback semantics (slice_acq.py:272-310): position = (shift + R((off - T) + T)) + R(pixel + T),
 // strict inside test, round half to even, raw PSF value; one kernel serves forward and adjoint.
 // LDS: per-tap rotated offsets (3 floats) next to the PSF.
@@ -1084,6 +1435,80 @@ int fsg_slice_acq_adjoint_f32(const float* transforms, const float* psf, int pd,
     else { if (vol_mask) SA_LAUNCH_LDS(8, true); else SA_LAUNCH_LDS(8, false); }
 #undef SA_LAUNCH_LDS
   }
+  FSG_RETURN_LAUNCH();
+}
+
+size_t fsg_slice_acq_adjoint_det_ws_bytes(int D, int H, int W, int want_weight) {
+  if (D <= 0 || H <= 0 || W <= 0) return 0;
+  return (size_t)D * H * W * sizeof(long long) * (want_weight ? 4 : 2);
+}
+
+int fsg_slice_acq_adjoint_det_f32(const float* transforms, const float* psf, int pd, int ph, int pw, const float* slices,
+                                  const uint8_t* slices_mask, const int32_t* slice_ids, const uint8_t* vol_mask, float* vol,
+                                  float* vol_weight, int D, int H, int W, int n, int h, int w, float res_slice, int mode,
+                                  void* ws, size_t ws_bytes, float value_scale, void* stream) {
+  // every refusal comes before the first write
+  if (!slices || !vol || !ws || (mode != FSG_SA_LINEAR && mode != FSG_SA_NEAREST_PSF)) return FSG_E_BADARG;
+  int ex = 0;
+  if (!(value_scale > 0.f) || frexpf(value_scale, &ex) != 0.5f || ex - 1 < -20 || ex - 1 > 20) return FSG_E_BADARG;
+  SaParams P{transforms, psf, vol_mask, slices_mask, slice_ids, D, H, W, pd, ph, pw, n, h, w, res_slice};
+  size_t lds = 0;
+  const int rc = sa_check(P, lds, false);
+  if (rc) return rc;
+  const size_t nvox = (size_t)D * H * W, need = fsg_slice_acq_adjoint_det_ws_bytes(D, H, W, vol_weight != nullptr);
+  if (ws_bytes < need) return FSG_E_BADARG;
+  if ((uintptr_t)ws & 7) return FSG_E_ALIGN;
+  hipStream_t st = fsg_stream(stream);
+  hipError_t e = hipMemsetAsync(ws, 0, need, st);
+  if (e != hipSuccess) return (int)e;
+  sa_u64* acc = static_cast<sa_u64*>(ws);
+  const int limbs = vol_weight ? 4 : 2;
+  const double kval = SA_DET_ONE / (double)value_scale;
+  const dim3 grid = sa_grid(P), block(SA_TILE, SA_TILE);
+  if (mode == FSG_SA_LINEAR) {
+    if (vol_mask) hipLaunchKernelGGL((sa_adjoint_det_kernel<false, true>), grid, block, lds, st, P, slices, acc, limbs, kval);
+    else hipLaunchKernelGGL((sa_adjoint_det_kernel<false, false>), grid, block, lds, st, P, slices, acc, limbs, kval);
+  } else if (g_tuning_flags & FSG_TUNE_SA_DIRECT) {
+    if (vol_mask) hipLaunchKernelGGL((sa_adjoint_det_kernel<true, true>), grid, block, lds, st, P, slices, acc, limbs, kval);
+    else hipLaunchKernelGGL((sa_adjoint_det_kernel<true, false>), grid, block, lds, st, P, slices, acc, limbs, kval);
+  } else {
+    // the float entry's chooser with this mode's own limit: 32-byte cells, at most SA_DET_CAP_MAX of them whatever
+    // fsg_slice_acq_set_tuning asks for (a chunk that does not fit scatters directly; the sums are the same either way)
+    const int ext = pw > ph ? pw : ph;
+    const bool t16 = res_slice * 15.f + (float)ext <= (float)g_sa_t16_extent;
+    const int tile = t16 ? 16 : 8;
+    const float E = res_slice * (float)(tile - 1) + (float)ext + 1.f;
+    auto est = [&](int z) { return 1.6f * E * E * (1.5f * (float)z + 3.f); };
+    int cap = g_sa_cap < SA_DET_CAP_MAX ? g_sa_cap : SA_DET_CAP_MAX, zc = g_sa_zc < pd ? g_sa_zc : pd;
+    if (g_sa_auto) {
+      zc = 1;
+      for (int z = 4; z >= 1; --z)
+        if (est(z) <= (float)cap) { zc = z; break; }
+      if (est(zc) > (float)cap) cap = (int)fminf(est(zc) * 1.25f, (float)SA_DET_CAP_MAX);
+      if (zc > pd) zc = pd;
+    }
+    // prefix rounded up to 8 bytes, 256 partial weights, cells of four limbs
+    const size_t lds2 = ((lds + 7) & ~(size_t)7) + (256 + 4 * (size_t)cap) * sizeof(sa_u64);
+    const dim3 grid2((unsigned)((w + tile - 1) / tile), (unsigned)((h + tile - 1) / tile), (unsigned)n);
+#define SA_LAUNCH_LDS_DET(TT, VMM)                                                                                     \
+  do {                                                                                                                \
+    auto kfn = sa_adjoint_nn_lds_det_kernel<TT, VMM>;                                                                 \
+    hipError_t ea = hipFuncSetAttribute((const void*)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds2);     \
+    if (ea != hipSuccess) return (int)ea;                                                                             \
+    hipLaunchKernelGGL(kfn, grid2, dim3(256), lds2, st, P, slices, acc, limbs, zc, cap, kval);                      \
+  } while (0)
+    if (t16) { if (vol_mask) SA_LAUNCH_LDS_DET(16, true); else SA_LAUNCH_LDS_DET(16, false); }
+    else { if (vol_mask) SA_LAUNCH_LDS_DET(8, true); else SA_LAUNCH_LDS_DET(8, false); }
+#undef SA_LAUNCH_LDS_DET
+  }
+  {
+    hipError_t el = hipGetLastError();
+    if (el != hipSuccess) return (int)el;
+  }
+  size_t blocks = (nvox + 255) / 256;
+  if (blocks > 8192) blocks = 8192;
+  hipLaunchKernelGGL(sa_det_finalize_kernel, dim3((unsigned)blocks), dim3(256), 0, st, (const long long*)acc, limbs, vol,
+                     vol_weight, ex - 1 - SA_DET_HI_BITS, -SA_DET_HI_BITS, nvox);
   FSG_RETURN_LAUNCH();
 }
 

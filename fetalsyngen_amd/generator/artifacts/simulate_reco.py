@@ -35,10 +35,12 @@ from .svort import (RigidTransform, get_PSF, interleave_index, mat_update_resolu
 from .utils import ReconMergeParams, fractal_noise_plan, mog_3d_tensor
 
 
-def PSFreconstruction(transforms, slices, slices_mask, vol_mask, params, slice_ids=None):
-    """Adjoint of the acquisition with the reconstruction PSF, equalised (ref :38-54)."""
+def PSFreconstruction(transforms, slices, slices_mask, vol_mask, params, slice_ids=None, deterministic=None):
+    """Adjoint of the acquisition with the reconstruction PSF, equalised (ref :38-54).  deterministic: None = inside a
+    keyed scope; True / False force the accumulation rule (slice_acquisition_adjoint)."""
     return slice_acquisition_adjoint(transforms, params["psf"], slices, slices_mask, vol_mask, params["volume_shape"],
-                                     params["res_s"] / params["res_r"], params["interp_psf"], True, slice_ids=slice_ids)
+                                     params["res_s"] / params["res_r"], params["interp_psf"], True, slice_ids=slice_ids,
+                                     deterministic=deterministic)
 
 
 def _axis_resample_tables(n_src, res, res_r, nearest):
@@ -271,7 +273,9 @@ class PSFReconstructor:
 
     def __init__(self, prob_misreg_slice: float, slices_misreg_ratio: float, prob_misreg_stack: float, txy: float,
                  prob_merge: float, merge_params: ReconMergeParams, prob_smooth: float, prob_rm_slices: float,
-                 rm_slices_min: float, rm_slices_max: float):
+                 rm_slices_min: float, rm_slices_max: float, deterministic: bool | None = None):
+        # None: the reconstruction accumulates deterministically inside a keyed scope and with fp32 atomics outside it
+        self.deterministic = deterministic
         self.prob_misreg_slice = prob_misreg_slice
         self.slices_misreg_ratio = slices_misreg_ratio
         self.prob_misreg_stack = prob_misreg_stack
@@ -421,7 +425,9 @@ class PSFReconstructor:
             "s_thick": data["slice_thickness"],
             "volume_shape": data["volume_shape"],
         }
-        rec = partial(PSFreconstruction, slices_mask=None, vol_mask=None, params=params)
+        # a keyed sample is a function of its key: inside a keyed scope the scatter accumulates in fixed point
+        det = _rng.in_keyed_scope() if self.deterministic is None else bool(self.deterministic)
+        rec = partial(PSFreconstruction, slices_mask=None, vol_mask=None, params=params, deterministic=det)
         return self.__recon_volume(data, rec, want_weight)
 
     def __recon_volume(self, data, rec, want_weight=True):

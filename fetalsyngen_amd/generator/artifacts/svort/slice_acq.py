@@ -9,6 +9,7 @@ seed-matched comparison with a CPU run of the reference).  There is no CPU path 
 from __future__ import annotations
 
 from .... import kernels as K
+from .... import rng as _rng
 
 _SEMANTICS = "cuda"
 
@@ -46,8 +47,12 @@ def slice_acquisition(transforms, vol, vol_mask, slices_mask, psf, slice_shape, 
 
 
 def slice_acquisition_adjoint(transforms, psf, slices, slices_mask, vol_mask, vol_shape, res_slice, interp_psf,
-                              equalize, semantics=None, slice_ids=None):
+                              equalize, semantics=None, slice_ids=None, deterministic=None):
+    """deterministic: None = inside a keyed scope (`rng.in_keyed_scope()`), where a sample is a function of its key; True /
+    False force the fixed-point or the fp32-atomic accumulation (kernels.slice_acq_adjoint)."""
     sem = semantics or _SEMANTICS
+    if deterministic is None:
+        deterministic = _rng.in_keyed_scope() and sem == "cuda"
     dev = slices.device
     h, w = slices.shape[-2:]
     s = slices.reshape(-1, h, w).contiguous()
@@ -56,5 +61,6 @@ def slice_acquisition_adjoint(transforms, psf, slices, slices_mask, vol_mask, vo
     vm = None if vol_mask is None or vol_mask.numel() == 0 else _dev(vol_mask, dev).reshape(D, H, W)
     sm = None if slices_mask is None or slices_mask.numel() == 0 else _dev(slices_mask, dev).reshape(n, h, w)
     vol = K.slice_acq_adjoint(_dev(transforms.float(), dev), _dev(psf.float(), dev), s, sm, vm, (D, H, W), res_slice,
-                              interp_psf=interp_psf, equalize=equalize, semantics=sem, slice_ids=slice_ids)
+                              interp_psf=interp_psf, equalize=equalize, semantics=sem, slice_ids=slice_ids,
+                              deterministic=bool(deterministic))
     return vol.view(1, 1, D, H, W)

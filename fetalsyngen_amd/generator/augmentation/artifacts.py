@@ -203,7 +203,10 @@ class StructNoise(RandTransform):
 class SimulateMotion(RandTransform):
     """Acquire motion-corrupted low-resolution slice stacks of the image and reconstruct it from them (ref :345-425)."""
 
-    def __init__(self, prob: float, scanner_params: ScannerParams, recon_params: ReconParams):
+    def __init__(self, prob: float, scanner_params: ScannerParams, recon_params: ReconParams,
+                 deterministic: bool | None = None):
+        # None: the reconstruction is deterministic inside a keyed scope only; True / False force either accumulation
+        self.deterministic = deterministic
         self.scanner_args = scanner_params
         self.recon_args = recon_params
         self.prob = prob
@@ -227,7 +230,8 @@ class SimulateMotion(RandTransform):
             self.scanner_args.resolution_recon = res_
             scanner = Scanner(**asdict(self.scanner_args))
             d_scan = scanner.scan(d)
-            recon = PSFReconstructor(**{f.name: getattr(self.recon_args, f.name) for f in fields(self.recon_args)})
+            recon = PSFReconstructor(**{f.name: getattr(self.recon_args, f.name) for f in fields(self.recon_args)},
+                                     deterministic=self.deterministic)
             output, _ = recon.recon_psf(d_scan, want_weight=False)
             metadata = {
                 "resolution_recon": d_scan["resolution_recon"],

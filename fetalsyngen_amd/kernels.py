@@ -6,6 +6,7 @@ node down), launches on torch's current HIP stream and returns freshly allocated
 from __future__ import annotations
 
 import ctypes as C
+import math
 
 import numpy as np
 import torch
@@ -692,9 +693,19 @@ def slice_acq_forward(transforms, vol, vol_mask, slices_mask, psf, slice_shape, 
 
 
 def slice_acq_adjoint(transforms, psf, slices, slices_mask, vol_mask, vol_shape, res_slice, interp_psf=False,
-                      equalize=False, semantics="cuda", return_weight=False, slice_ids=None):
+                      equalize=False, semantics="cuda", return_weight=False, slice_ids=None, deterministic=False,
+                      value_scale=1.0):
     """(n,h,w) slices -> (D,H,W) volume  (fsg_slice_acq_adjoint_f32 + fsg_equalize_f32).
-    slice_ids (host integer tensor, len(transforms)): use slices[slice_ids[z]] for transform z (subset without a copy)."""
+    slice_ids (host integer tensor, len(transforms)): use slices[slice_ids[z]] for transform z (subset without a copy).
+    deterministic: accumulate in fixed point, two 64-bit limbs (fsg_slice_acq_adjoint_det_f32): the result is a pure function
+    of the inputs, whatever the tuning, the slice order or the run; `semantics="cuda"` only.  value_scale: a power of two in
+    [2^-20, 2^20] the slice values are divided by before they are quantised (1 for slices scaled to about [0, 1])."""
+    if deterministic and semantics == "torch":
+        raise ValueError("the deterministic adjoint follows the CUDA semantics only (semantics='cuda')")
+    if deterministic:
+        m, e = math.frexp(float(value_scale))
+        if m != 0.5 or not -20 <= e - 1 <= 20:
+            raise ValueError(f"value_scale must be a power of two in [2^-20, 2^20], got {value_scale!r}")
     n, (pd, ph, pw) = _sa_common(transforms, psf)
     _need_gpu(slices)
     _f32(slices, "slices")
@@ -716,9 +727,17 @@ def slice_acq_adjoint(transforms, psf, slices, slices_mask, vol_mask, vol_shape,
     wgt = torch.empty_like(vol) if (equalize or return_weight) else None
     mode = _sa_mode(semantics, interp_psf)
     lib, st = _lib.load(), _stream(slices)
-    rc = lib.fsg_slice_acq_adjoint_f32(_p(transforms), _p(psf), pd, ph, pw, _p(slices), _p(sm), _p(slice_ids), _p(vm),
-                                       _p(vol), _p(wgt), D, H, W, n, h, w, float(res_slice), mode, st)
-    _lib.check(rc, "fsg_slice_acq_adjoint_f32")
+    if deterministic:
+        need = int(lib.fsg_slice_acq_adjoint_det_ws_bytes(D, H, W, int(wgt is not None)))
+        ws = torch.empty(need // 8, dtype=torch.int64, device=slices.device)  # zeroed by the call
+        rc = lib.fsg_slice_acq_adjoint_det_f32(_p(transforms), _p(psf), pd, ph, pw, _p(slices), _p(sm), _p(slice_ids),
+                                               _p(vm), _p(vol), _p(wgt), D, H, W, n, h, w, float(res_slice), mode, _p(ws),
+                                               need, float(value_scale), st)
+        _lib.check(rc, "fsg_slice_acq_adjoint_det_f32")
+    else:
+        rc = lib.fsg_slice_acq_adjoint_f32(_p(transforms), _p(psf), pd, ph, pw, _p(slices), _p(sm), _p(slice_ids), _p(vm),
+                                           _p(vol), _p(wgt), D, H, W, n, h, w, float(res_slice), mode, st)
+        _lib.check(rc, "fsg_slice_acq_adjoint_f32")
     torch_sem = mode == SA_MODES["torch"]
     if equalize or (torch_sem and vm is not None):
         rc = lib.fsg_equalize_f32(_p(vol), _p(wgt if equalize else None), _p(vm if torch_sem else None),

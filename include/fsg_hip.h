@@ -28,11 +28,12 @@
 extern "C" {
 #endif
 
-#define FSG_ABI_VERSION 6  /* 2: fsg_sample_plan grew (mm_slots .. seg_out_u8) after version 1 shipped; 3: label_codes .. code_sel, FSG_KEYED_I_CODES;
+#define FSG_ABI_VERSION 7  /* 2: fsg_sample_plan grew (mm_slots .. seg_out_u8) after version 1 shipped; 3: label_codes .. code_sel, FSG_KEYED_I_CODES;
                               4: fsg_sample_image / fsg_sample_run_image, FSG_KEYED_I_IMAGE_IN .. PRIOR_IN, fsg_warp_dual_f32;
                               5: fsg_keyed_overrides / fsg_keyed_draw_with, fsg_keyed_draws grew (spacing3 .. sigmas_in),
                                  FSG_KEYED_I_OVERRIDES / BLOCK_BYTES;
-                              6: fsg_voxel_pick_f32 / _u8, fsg_voxel_pick_ws_bytes */
+                              6: fsg_voxel_pick_f32 / _u8, fsg_voxel_pick_ws_bytes;
+                              7: fsg_slice_acq_adjoint_det_f32, fsg_slice_acq_adjoint_det_ws_bytes, FSG_SA_DET_FRAC_BITS / LIMB_BITS */
 
 #define FSG_E_BADARG (-1)   /* null pointer / non-positive size / bad enum */
 #define FSG_E_TOOBIG (-2)   /* size exceeds what the kernel indexes (2^31-1 voxels per volume) */
@@ -314,9 +315,12 @@ float fsg_key_to_float(int32_t key);
 int fsg_slice_acq_forward_f32(const float* transforms, const float* vol, const uint8_t* vol_mask, const float* psf, int pd,
                               int ph, int pw, const uint8_t* slices_mask, float* slices, float* slices_weight, int D, int H,
                               int W, int n, int h, int w, float res_slice, int mode, void* stream);
-/* vol = A^T(slices), vol_weight = A^T(1) (may be NULL); both are zeroed by the call, then accumulated with
- * fp32 atomics (as the reference does: the summation order is not deterministic).  CUDA modes skip pixels whose
- * PSF weight inside the volume is < 0.5 and divide each contribution by that weight (:560, :600, :616).
+/* vol = A^T(slices), vol_weight = A^T(1) (may be NULL).  CUDA modes skip pixels whose PSF weight inside the volume is
+ * < 0.5 and divide each contribution by that weight (:560, :600, :616).  Two entries, two accumulation rules:
+ *   fsg_slice_acq_adjoint_f32      both outputs are zeroed by the call, then accumulated with fp32 atomics, as the
+ *                                  reference does: the summation order, and with it the last bits of the result, differ
+ *                                  from run to run and with fsg_slice_acq_set_tuning.  NOT deterministic.
+ *   fsg_slice_acq_adjoint_det_f32  deterministic: the result is a pure function of the inputs (below).
  * slice_ids (DEVICE, n x int32, may be NULL): transform z of the launch applies to slices[slice_ids[z]] (and that
  * row of slices_mask) -- the reconstruction keeps a random subset of the slices (simulate_reco.py:768-769)
  * without copying them.
@@ -325,10 +329,50 @@ int fsg_slice_acq_adjoint_f32(const float* transforms, const float* psf, int pd,
                               const uint8_t* slices_mask, const int32_t* slice_ids, const uint8_t* vol_mask, float* vol,
                               float* vol_weight, int D, int H, int W, int n, int h, int w, float res_slice, int mode,
                               void* stream);
+/* The deterministic adjoint (FSG_SA_LINEAR and FSG_SA_NEAREST_PSF; FSG_SA_TORCH is refused with FSG_E_BADARG).
+ * The rule, with F = FSG_SA_DET_FRAC_BITS = 72 and L = FSG_SA_DET_LIMB_BITS = 40:
+ *   1. every contribution is formed in fp32 as in the float entry's LDS kernel: c_w = pv' = pv * (1 / wsum) (times the
+ *      trilinear corner weight in FSG_SA_LINEAR), c_v = fl32(c_w * s) for the pixel value s;
+ *   2. it becomes an integer with ONE rounding: Q_v = rint_half_even(c_v * 2^F / value_scale), Q_w = rint_half_even(c_w * 2^F)
+ *      (the scaling by a power of two is exact).  A contribution of 2^-(F-24) = 2^-48 and more is an exact multiple of
+ *      2^-F: it enters exactly, smaller ones with an error of at most 2^-(F+1);
+ *   3. Q is carried as two 64-bit limbs, Q = hi * 2^L + lo with hi = rint_half_even(c * 2^(F-L)), |lo| <= 2^(L-1); the limbs
+ *      are added with 64-bit integer atomics, in LDS and in `ws`, each on its own.  Integer addition is associative, so
+ *      the sums do not depend on the order;
+ *   4. a last pass forms sum(hi) * 2^L + sum(lo) exactly and converts it with ONE rounding, integer -> float32 to nearest
+ *      even, then multiplies by 2^-F * value_scale (2^-F for the weight), which is exact.  An accumulator nothing was
+ *      added to gives +0.0f.
+ *   The per-pixel weight wsum of the CUDA modes follows the same idea in one limb: each tap's PSF value is quantised to
+ *   2^-32, the integers are summed, and the sum is converted once; the < 0.5 cut and 1 / wsum use that float.
+ * vol and vol_weight are therefore bit-identical for the same inputs under any fsg_slice_acq_set_tuning setting, under
+ * FSG_TUNE_SA_DIRECT, for any order of the slices, for slice_ids against gathered slices, on any stream and in any run.
+ * Why two limbs and not one int64 at 2^-32: equalisation divides value by weight wherever the weight is > 0, and voxels that
+ * only the fringe of a PSF (or a trilinear corner weight near 0) reaches have weights of a few times 2^-32 and less; their
+ * quotient would be noise.  At 2^-72 value and weight are the exact sums of the fp32 contributions for every contribution
+ * of 2^-48 and more, rounded once: closer to the real sum than any fp32 summation order.
+ *   value_scale  a power of two in [2^-20, 2^20], else FSG_E_BADARG; 1 for slices scaled to about [0, 1].  It is given by
+ *                the caller, not derived from the data: a data-derived scale would tie the bits to which slices are passed.
+ *   range        per voxel |sum of weights| and |sum of values / value_scale| must stay below 2^(63-(F-L)) = 2^31 and the
+ *                number of contributions below 2^(63-L) = 2^23; the generator's geometry stays below 2^21 and 2^22
+ *                (DESIGN section 17).  Beyond the range the sums wrap (no fault).
+ *   ws           DEVICE, 8-byte aligned (else FSG_E_ALIGN), ws_bytes >= fsg_slice_acq_adjoint_det_ws_bytes(D, H, W,
+ *                vol_weight != NULL) = 16 * D*H*W bytes, twice that with weights; zeroed by the call on `stream`.
+ * Every refusal leaves vol, vol_weight and ws untouched; otherwise every element of vol (and vol_weight) is written.
+ * Non-finite slice values give unspecified values in the voxels they reach and never a fault: no address depends on them.
+ * Equalisation stays the separate fsg_equalize_f32 launch on the converted floats. */
+#define FSG_SA_DET_FRAC_BITS 72
+#define FSG_SA_DET_LIMB_BITS 40
+size_t fsg_slice_acq_adjoint_det_ws_bytes(int D, int H, int W, int want_weight);
+int fsg_slice_acq_adjoint_det_f32(const float* transforms, const float* psf, int pd, int ph, int pw, const float* slices,
+                                  const uint8_t* slices_mask, const int32_t* slice_ids, const uint8_t* vol_mask, float* vol,
+                                  float* vol_weight, int D, int H, int W, int n, int h, int w, float res_slice, int mode,
+                                  void* ws, size_t ws_bytes, float value_scale, void* stream);
 /* Shape of the LDS pre-summation of the FSG_SA_NEAREST_PSF adjoint: accumulator cells (value + weight, 8 B each,
  * 256..18432), PSF planes per chunk, and the footprint (pixel pitch * 15 + PSF width, voxels) up to which 16x16-pixel
  * tiles are used instead of 8x8.  z_chunk 0 (default) derives the planes per chunk, and a larger capacity when one
- * plane does not fit, from the pixel pitch and the PSF size.  Defaults 3072 / 0 / 20.  Results do not depend on it beyond fp32 summation order. */
+ * plane does not fit, from the pixel pitch and the PSF size.  Defaults 3072 / 0 / 20.  Results do not depend on it beyond fp32 summation order.
+ * The deterministic entry reads the same three values with cells of 32 B and at most 4096 of them; its results do not
+ * depend on them at all. */
 int fsg_slice_acq_set_tuning(int cap_cells, int z_chunk, int t16_extent);
 /* vol[i] /= vol_weight[i] where vol_weight[i] > threshold (0 for the CUDA kernel :681-691, 1e-2 for the
  * fallback slice_acq.py:542-543); then vol[i] *= vol_mask[i] if vol_mask (fallback :544-545).  Either of

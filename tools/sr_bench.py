@@ -2,7 +2,10 @@
 """Time the slice-acquisition kernels at BASELINE config 4 scale (384^3 volume at 0.5 mm, one stack of a
 3 mm-thick, 0.8 mm in-plane acquisition) with HIP events on the launch stream.  Prints one JSON line.
 
-    python tools/sr_bench.py [--size 384] [--slices 80] [--reps 5]
+    python tools/sr_bench.py [--size 384] [--slices 80] [--reps 5] [--deterministic]
+
+--deterministic adds a leg for the adjoint timings: the fixed-point accumulation (fsg_slice_acq_adjoint_det_f32) timed right
+after the fp32-atomic entry on the same inputs (`*_det_ms`, the float figures are the yardstick), and its workspace size.
 """
 import argparse
 import json
@@ -36,6 +39,7 @@ def main():
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--res-slice", type=float, default=0.8)
     ap.add_argument("--thick", type=float, default=3.0)
+    ap.add_argument("--deterministic", action="store_true", help="also time the deterministic adjoint")
     a = ap.parse_args()
     dev, res = "cuda:0", 0.5
     vs = (a.size,) * 3
@@ -67,6 +71,18 @@ def main():
     prev = lib.fsg_set_tuning(_lib.TUNE.SA_DIRECT)
     out["adjoint_direct_ms"] = round(timed(adj, a.reps), 3)
     lib.fsg_set_tuning(prev)
+    if a.deterministic:
+        det = lambda **kw: K.slice_acq_adjoint(tr, psf, s, None, None, vs, rs, deterministic=True, **kw)  # noqa: E731
+        out["adjoint_nearest_psf_eq_det_ms"] = round(timed(lambda: det(interp_psf=True, equalize=True), a.reps), 3)
+        out["adjoint_nearest_psf_eq_again_ms"] = round(timed(adj, a.reps), 3)  # the float leg once more: the session's spread
+        out["adjoint_linear_det_ms"] = round(timed(lambda: det(interp_psf=False), a.reps), 3)
+        prev = lib.fsg_set_tuning(_lib.TUNE.SA_DIRECT)
+        out["adjoint_direct_det_ms"] = round(timed(lambda: det(interp_psf=True, equalize=True), a.reps), 3)
+        lib.fsg_set_tuning(prev)
+        out["det_workspace_bytes"] = int(lib.fsg_slice_acq_adjoint_det_ws_bytes(*vs, 1))
+        a_f, a_d = adj(), det(interp_psf=True, equalize=True)
+        out["det_vs_float_max_abs"] = float((a_f - a_d).abs().max())
+        out["det_twice_equal"] = bool(torch.equal(a_d, det(interp_psf=True, equalize=True)))
     sweep = {}
     cfgs = ((4096, 0, 20), (3072, 0, 20), (6144, 0, 20), (4096, 3, 20), (4096, 2, 20), (6144, 1, 20), (4096, 0, 0), (4096, 0, 40))
     for ang in (0.3, 0.8, 1.5):
