@@ -13,7 +13,7 @@
 // pixels overlap in the volume, so the 2x2x2 gathers of a wave mostly hit lines its neighbours just
 // touched (the 216 MiB of a 384^3 volume sit in the 256 MiB Infinity Cache).  The PSF itself lives in LDS
 // (uniform reads are broadcasts; the interp_psf branch gathers its 2x2x2 neighbourhood from there).
-#include "fsg_common.h"
+#include "fsg_sa.h"  // SaParams, SA_TILE, the LDS image of the PSF, sa_centre, sa_check, sa_grid
 
 int g_sa_cap = 3072;        // LDS accumulator cells (value + weight)
 int g_sa_zc = 3;            // PSF planes per accumulation chunk
@@ -22,24 +22,6 @@ int g_sa_auto = 1;          // derive planes-per-chunk (and a larger capacity if
 
 namespace {
 
-struct SaParams {
-  const float* tr;          // (n, 3, 4)
-  const float* psf;         // (pd, ph, pw)
-  const uint8_t* vmask;     // (D,H,W) or null
-  const uint8_t* smask;     // (n,h,w) or null
-  const int32_t* sid;       // adjoint only: slice z of the launch reads slices[sid[z]] (null: identity)
-  int D, H, W;
-  int pd, ph, pw;
-  int n, h, w;
-  float res;
-  // forward, linear PSF: which slices a launch takes (per workgroup, from the slice's own transform): 0 all, 1 those with
-  // sa_direct_cost(T) <= fwd_thr (direct gathers), 2 the others (plate kernel)
-  int fwd_select;
-  float fwd_thr;
-  float fwd_wy;  // weight of the slice x axis' y component in sa_direct_cost (10 for PSFs of 400 elements and more, 30 below)
-};
-
-constexpr int SA_TILE = 16;
 // Direct gathers cost 4.2 + ~10 |T10| + ~35 |T20| ms for the 80 x 320^2 x 441-tap stack of the bench (lanes run along the
 // slice's x axis: its y component spreads a wave's gather over rows, its z component over planes 590 KB apart), the plate
 // kernel 5.7 ms aligned, 6-9.3 ms for every other orientation
@@ -48,59 +30,6 @@ constexpr int SA_TILE = 16;
 // y tilt is not (crossover |T10| ~ 0.35: the few taps no longer share the rows a wave's gather touches), and both scale with
 // the pixel pitch -- section 8 of the same file, stacks as SimulateMotion draws them.
 __device__ __forceinline__ float sa_direct_cost(const float* T, float wy) { return wy * fabsf(T[4]) + 35.f * fabsf(T[8]); }
-constexpr int SA_MAX_PSF = 4096;  // elements (16 KB of LDS)
-constexpr int SA_MAX_AXIS = 64;
-
-// LDS image of the PSF and of the per-axis products of one slice's rotation with the tap offsets.
-struct SaLds {
-  float* psf;   // [pd*ph*pw]
-  float* tx;    // [3][pw]   r_{a,0} * ix_p
-  float* ty;    // [3][ph]   r_{a,1} * iy_p
-  float* tz;    // [3][pd]   r_{a,2} * iz_p
-};
-
-__device__ __forceinline__ SaLds sa_lds_layout(float* base, const SaParams& P) {
-  SaLds L;
-  L.psf = base;
-  L.tx = L.psf + P.pd * P.ph * P.pw;
-  L.ty = L.tx + 3 * P.pw;
-  L.tz = L.ty + 3 * P.ph;
-  return L;
-}
-
-__device__ __forceinline__ void sa_fill_lds(const SaLds& L, const SaParams& P, const float* __restrict__ T) {
-  const int tid = threadIdx.y * SA_TILE + threadIdx.x;
-  const int np = P.pd * P.ph * P.pw;
-  for (int e = tid; e < np; e += SA_TILE * SA_TILE) L.psf[e] = P.psf[e];
-  // float * int in the reference == float * (float)int
-  for (int e = tid; e < 3 * P.pw; e += SA_TILE * SA_TILE) {
-    const int a = e / P.pw, i = e - a * P.pw;
-    L.tx[e] = T[a * 4 + 0] * (float)(i - P.pw / 2);
-  }
-  for (int e = tid; e < 3 * P.ph; e += SA_TILE * SA_TILE) {
-    const int a = e / P.ph, i = e - a * P.ph;
-    L.ty[e] = T[a * 4 + 1] * (float)(i - P.ph / 2);
-  }
-  for (int e = tid; e < 3 * P.pd; e += SA_TILE * SA_TILE) {
-    const int a = e / P.pd, i = e - a * P.pd;
-    L.tz[e] = T[a * 4 + 2] * (float)(i - P.pd / 2);
-  }
-}
-
-// pixel centre in voxel coordinates (slice_acq_cuda_kernel.cu:46-56): the pixel offset is formed in double
-// (the literal `2.` promotes), the rotation in fp32.
-__device__ __forceinline__ void sa_centre(const SaParams& P, const float* __restrict__ T, int ix, int iy, float& xc,
-                                          float& yc, float& zc) {
-  const float _x = (float)(((double)ix - (P.w - 1) / 2.) * (double)P.res + (double)T[3]);
-  const float _y = (float)(((double)iy - (P.h - 1) / 2.) * (double)P.res + (double)T[7]);
-  const float _z = T[11];
-  xc = T[0] * _x + T[1] * _y + T[2] * _z;
-  yc = T[4] * _x + T[5] * _y + T[6] * _z;
-  zc = T[8] * _x + T[9] * _y + T[10] * _z;
-  xc = (float)((double)xc + (P.W - 1) / 2.);
-  yc = (float)((double)yc + (P.H - 1) / 2.);
-  zc = (float)((double)zc + (P.D - 1) / 2.);
-}
 
 // interp_psf branch (:79-101): PSF value at the snapped voxel, trilinear in the PSF grid.  false = outside.
 __device__ __forceinline__ bool sa_psf_at(const SaLds& L, const SaParams& P, const float* __restrict__ T, float dx,
@@ -1305,22 +1234,6 @@ __global__ __launch_bounds__(256) void sa_equalize_kernel(float* __restrict__ vo
     if (vmask) v = v * (float)vmask[e];
     vol[e] = v;
   }
-}
-
-int sa_check(const SaParams& P, size_t& lds, bool torch_mode) {
-  if (!P.tr || !P.psf) return FSG_E_BADARG;
-  if (P.D < 2 || P.H < 2 || P.W < 2 || P.n <= 0 || P.h <= 0 || P.w <= 0 || P.pd <= 0 || P.ph <= 0 || P.pw <= 0)
-    return FSG_E_BADARG;
-  if ((size_t)P.D * P.H * P.W > (size_t)0x7FFFFFFF || (size_t)P.n * P.h * P.w > (size_t)0x7FFFFFFF) return FSG_E_TOOBIG;
-  if (P.pd > SA_MAX_AXIS || P.ph > SA_MAX_AXIS || P.pw > SA_MAX_AXIS || P.pd * P.ph * P.pw > SA_MAX_PSF) return FSG_E_TOOBIG;
-  if (P.n > 65535) return FSG_E_TOOBIG;
-  const size_t np = (size_t)P.pd * P.ph * P.pw;
-  lds = torch_mode ? np * 4 * sizeof(float) : (np + 3 * (size_t)(P.pd + P.ph + P.pw)) * sizeof(float);
-  return 0;
-}
-
-dim3 sa_grid(const SaParams& P) {
-  return dim3((unsigned)((P.w + SA_TILE - 1) / SA_TILE), (unsigned)((P.h + SA_TILE - 1) / SA_TILE), (unsigned)P.n);
 }
 
 }  // namespace

@@ -1,0 +1,314 @@
+// fsg_slice_acq_bwd.hip -- backward of the slice-acquisition FORWARD operator: gradients of `slices` with respect to the
+// volume and to the (n,3,4) slice transforms (reference SliceAcqFunction.backward, slice_acq_cuda_kernel.cu:173-470,
+// host side :993-1030).  The backward of the adjoint and transform_convert's autograd are not here.
+//
+// The rule (include/fsg_hip.h), per pixel inside slices_mask with grad_slices != 0:
+//   pass 1  weight = sum over the in-volume taps of the PSF value (FSG_SA_NEAREST_PSF: re-interpolated at the rounded voxel,
+//           taps whose PSF coordinate falls outside the PSF grid skipped).  vol_mask plays NO part in it, unlike the forward's
+//           own weight; weight == 0 ends the pixel (the forward tests weight > 0).  gs = grad_slices / weight.
+//   pass 2  grad_vol += gs * psf * corner weight at the up-to-8 unmasked corners (LINEAR), gs * psf' at the rounded voxel if
+//           unmasked (NEAREST_PSF); the 12 transform gradients from the derivative of the trilinear weights with respect to
+//           the sampling position, the weight held constant.
+//
+// MI355X shape of the work: as the forward, one 256-thread workgroup = a 16x16 pixel tile of ONE slice, the PSF and the per-axis
+// products r_ij * tap_offset in LDS.  grad_vol goes out with fp32 vector atomics (memory-side, not ordered).  The transform
+// gradients never touch an atomic: each lane keeps its 12 sums in registers, a wave folds them with shuffles in a fixed order,
+// the four waves meet in LDS and are added in wave order, the workgroup stores ONE 12-float partial at ws[slice][tile], and
+// sa_bwd_reduce_kernel adds a slice's tiles in index order.  The result is a pure function of the inputs.
+//
+// Every range test is written in ACCEPTING form, `if (!(x >= 0 && x < hx ...)) continue;`: a NaN or Inf coordinate (non-finite
+// transforms or res_slice) fails it and the tap is skipped, so no address is ever formed from a value that was not proven to be
+// inside its array.
+#include "fsg_sa.h"
+
+namespace {
+
+constexpr int SAB_WAVES = SA_TILE * SA_TILE / FSG_WAVE;
+
+// Trilinear corner (A,B,C) of the cell at offset OFF: its weight factors along x, y, z.
+#define SAB_FX(A) ((A) ? wx : (1 - wx))
+#define SAB_FY(B) ((B) ? wy : (1 - wy))
+#define SAB_FZ(C) ((C) ? wz : (1 - wz))
+
+template <bool NN, bool VM, bool GV, bool GT>
+__global__ __launch_bounds__(SA_TILE* SA_TILE) void sa_backward_kernel(SaParams P, const float* __restrict__ vol,
+                                                                       const float* __restrict__ gslices,
+                                                                       float* __restrict__ gvol, float* __restrict__ ws) {
+  extern __shared__ float smem[];
+  const int in = blockIdx.z;
+  const float* __restrict__ T = P.tr + (size_t)in * 12;
+  const SaLds L = sa_lds_layout(smem, P);
+  float* red = L.tz + 3 * P.pd;  // [SAB_WAVES][12]
+  sa_fill_lds(L, P, T);
+  __syncthreads();
+  const int ix = blockIdx.x * SA_TILE + threadIdx.x, iy = blockIdx.y * SA_TILE + threadIdx.y;
+  const bool inside = ix < P.w && iy < P.h;
+  const size_t idx = ((size_t)in * P.h + (inside ? iy : 0)) * P.w + (inside ? ix : 0);
+  float gs = inside && !(P.smask && !P.smask[idx]) ? gslices[idx] : 0.f;
+  float g[12];
+#pragma unroll
+  for (int k = 0; k < 12; ++k) g[k] = 0.f;
+
+  // no thread leaves before the reduction: a pixel without a contribution carries twelve zeros into it
+  if (gs != 0.f) {
+    float _x, _y, _z, xc, yc, zc;
+    sa_pixel(P, T, ix, iy, _x, _y, _z);
+    sa_centre(P, T, ix, iy, xc, yc, zc);
+    const int Sy = P.W, Sz = P.H * P.W;
+    const int sy = P.pw, sz = P.pw * P.ph;
+    const float hx = (float)(P.W - 1), hy = (float)(P.H - 1), hz = (float)(P.D - 1);
+    const float qx = (float)(P.pw - 1), qy = (float)(P.ph - 1), qz = (float)(P.pd - 1);
+
+    // ---- pass 1: the pixel's weight (vol_mask not consulted) ----
+    float weight = 0.f;
+    int ip = 0;
+    for (int kz = 0; kz < P.pd; ++kz) {
+      const float zx = L.tz[kz], zy = L.tz[P.pd + kz], zz = L.tz[2 * P.pd + kz];
+      for (int ky = 0; ky < P.ph; ++ky) {
+        const float yx = L.ty[ky], yy = L.ty[P.ph + ky], yz = L.ty[2 * P.ph + ky];
+        for (int kx = 0; kx < P.pw; ++kx, ++ip) {
+          float pv = L.psf[ip];
+          if (pv == 0.f) continue;  // wave-uniform
+          const float x = xc + L.tx[kx] + yx + zx;
+          const float y = yc + L.tx[P.pw + kx] + yy + zy;
+          const float z = zc + L.tx[2 * P.pw + kx] + yz + zz;
+          if (!(x >= 0 && y >= 0 && z >= 0 && x < hx && y < hy && z < hz)) continue;
+          if (NN) {
+            const float dx = roundf(x) - xc, dy = roundf(y) - yc, dz = roundf(z) - zc;
+            const float xp = (float)((double)(T[0] * dx + T[4] * dy + T[8] * dz) + (P.pw - 1) / 2.);
+            const float yp = (float)((double)(T[1] * dx + T[5] * dy + T[9] * dz) + (P.ph - 1) / 2.);
+            const float zp = (float)((double)(T[2] * dx + T[6] * dy + T[10] * dz) + (P.pd - 1) / 2.);
+            if (!(xp >= 0 && yp >= 0 && zp >= 0 && xp < qx && yp < qy && zp < qz)) continue;
+            const float xf = floorf(xp), yf = floorf(yp), zf = floorf(zp);
+            const float wx = xp - xf, wy = yp - yf, wz = zp - zf;
+            const float* q = L.psf + (int)zf * sz + (int)yf * sy + (int)xf;
+            pv = 0.f;
+            pv += (1 - wx) * (1 - wy) * (1 - wz) * q[0];
+            pv += wx * (1 - wy) * (1 - wz) * q[1];
+            pv += (1 - wx) * wy * (1 - wz) * q[sy];
+            pv += (1 - wx) * (1 - wy) * wz * q[sz];
+            pv += wx * wy * (1 - wz) * q[1 + sy];
+            pv += wx * (1 - wy) * wz * q[1 + sz];
+            pv += (1 - wx) * wy * wz * q[sy + sz];
+            pv += wx * wy * wz * q[sy + sz + 1];
+          }
+          weight += pv;
+        }
+      }
+    }
+
+    // ---- pass 2: scatter the volume gradient, gather the transform gradient ----
+    if (weight != 0.f) {  // (`!= 0`, not the forward's `> 0`: the reference's own test; NaN goes on and stays a value)
+      gs = gs / weight;
+      ip = 0;
+      for (int kz = 0; kz < P.pd; ++kz) {
+        const float zx = L.tz[kz], zy = L.tz[P.pd + kz], zz = L.tz[2 * P.pd + kz];
+        for (int ky = 0; ky < P.ph; ++ky) {
+          const float yx = L.ty[ky], yy = L.ty[P.ph + ky], yz = L.ty[2 * P.ph + ky];
+          for (int kx = 0; kx < P.pw; ++kx, ++ip) {
+            const float pv = L.psf[ip];
+            if (pv == 0.f) continue;
+            const float x = xc + L.tx[kx] + yx + zx;
+            const float y = yc + L.tx[P.pw + kx] + yy + zy;
+            const float z = zc + L.tx[2 * P.pw + kx] + yz + zz;
+            if (!(x >= 0 && y >= 0 && z >= 0 && x < hx && y < hy && z < hz)) continue;
+            if (NN) {
+              const float xr = roundf(x), yr = roundf(y), zr = roundf(z);
+              const float ex = xr - xc, ey = yr - yc, ez = zr - zc;
+              const float xp = (float)((double)(T[0] * ex + T[4] * ey + T[8] * ez) + (P.pw - 1) / 2.);
+              const float yp = (float)((double)(T[1] * ex + T[5] * ey + T[9] * ez) + (P.ph - 1) / 2.);
+              const float zp = (float)((double)(T[2] * ex + T[6] * ey + T[10] * ez) + (P.pd - 1) / 2.);
+              if (!(xp >= 0 && yp >= 0 && zp >= 0 && xp < qx && yp < qy && zp < qz)) continue;
+              const float xf = floorf(xp), yf = floorf(yp), zf = floorf(zp);
+              const float wx = xp - xf, wy = yp - yf, wz = zp - zf;
+              const float* q = L.psf + (int)zf * sz + (int)yf * sy + (int)xf;
+              const int iv = (int)zr * Sz + (int)yr * Sy + (int)xr;
+              if (VM && !P.vmask[iv]) continue;
+              if (GV) {
+                float pr = 0.f;
+                pr += (1 - wx) * (1 - wy) * (1 - wz) * q[0];
+                pr += wx * (1 - wy) * (1 - wz) * q[1];
+                pr += (1 - wx) * wy * (1 - wz) * q[sy];
+                pr += (1 - wx) * (1 - wy) * wz * q[sz];
+                pr += wx * wy * (1 - wz) * q[1 + sy];
+                pr += wx * (1 - wy) * wz * q[1 + sz];
+                pr += (1 - wx) * wy * wz * q[sy + sz];
+                pr += wx * wy * wz * q[sy + sz + 1];
+                unsafeAtomicAdd(gvol + iv, pr * gs);
+              }
+              if (GT) {
+                // d psf' / d (PSF coordinate), times gs * vol: the rounded voxel is fixed, the PSF moves under it
+                float dx = 0.f, dy = 0.f, dz = 0.f, t;
+#define SAB_PSF_CORNER(OFF, A, B, C)                                  \
+  t = q[(OFF)];                                                       \
+  dx = (A) ? dx + SAB_FY(B) * SAB_FZ(C) * t : dx - SAB_FY(B) * SAB_FZ(C) * t; \
+  dy = (B) ? dy + SAB_FX(A) * SAB_FZ(C) * t : dy - SAB_FX(A) * SAB_FZ(C) * t; \
+  dz = (C) ? dz + SAB_FX(A) * SAB_FY(B) * t : dz - SAB_FX(A) * SAB_FY(B) * t;
+                SAB_PSF_CORNER(0, 0, 0, 0)
+                SAB_PSF_CORNER(1, 1, 0, 0)
+                SAB_PSF_CORNER(sy, 0, 1, 0)
+                SAB_PSF_CORNER(sz, 0, 0, 1)
+                SAB_PSF_CORNER(1 + sy, 1, 1, 0)
+                SAB_PSF_CORNER(1 + sz, 1, 0, 1)
+                SAB_PSF_CORNER(sy + sz, 0, 1, 1)
+                SAB_PSF_CORNER(sy + sz + 1, 1, 1, 1)
+#undef SAB_PSF_CORNER
+                t = gs * vol[iv];
+                dx *= t; dy *= t; dz *= t;
+                // lever arm: the rounded voxel relative to the volume centre (exact in fp32: half-integers below 2^23)
+                const float lx = xr - hx * 0.5f, ly = yr - hy * 0.5f, lz = zr - hz * 0.5f;
+                g[0] += dx * lx; g[1] += dy * lx; g[2] += dz * lx;
+                g[4] += dx * ly; g[5] += dy * ly; g[6] += dz * ly;
+                g[8] += dx * lz; g[9] += dy * lz; g[10] += dz * lz;
+                g[3] -= dx; g[7] -= dy; g[11] -= dz;
+              }
+            } else {
+              const float xf = floorf(x), yf = floorf(y), zf = floorf(z);
+              const float wx = x - xf, wy = y - yf, wz = z - zf;
+              const int iv = (int)zf * Sz + (int)yf * Sy + (int)xf;
+              const float pg = pv * gs;
+              if (GV) {
+#define SAB_VOL_CORNER(OFF, A, B, C) \
+  if (!VM || P.vmask[iv + (OFF)]) unsafeAtomicAdd(gvol + iv + (OFF), SAB_FX(A) * SAB_FY(B) * SAB_FZ(C) * pg);
+                SAB_VOL_CORNER(0, 0, 0, 0)
+                SAB_VOL_CORNER(1, 1, 0, 0)
+                SAB_VOL_CORNER(Sy, 0, 1, 0)
+                SAB_VOL_CORNER(Sz, 0, 0, 1)
+                SAB_VOL_CORNER(1 + Sy, 1, 1, 0)
+                SAB_VOL_CORNER(1 + Sz, 1, 0, 1)
+                SAB_VOL_CORNER(Sy + Sz, 0, 1, 1)
+                SAB_VOL_CORNER(Sy + Sz + 1, 1, 1, 1)
+#undef SAB_VOL_CORNER
+              }
+              if (GT) {
+                // d (trilinear sample) / d (sampling position), times gs * psf, over the unmasked corners
+                float dx = 0.f, dy = 0.f, dz = 0.f, t;
+#define SAB_LIN_CORNER(OFF, A, B, C)                                    \
+  if (!VM || P.vmask[iv + (OFF)]) {                                     \
+    t = pg * vol[iv + (OFF)];                                           \
+    dx = (A) ? dx + SAB_FY(B) * SAB_FZ(C) * t : dx - SAB_FY(B) * SAB_FZ(C) * t; \
+    dy = (B) ? dy + SAB_FX(A) * SAB_FZ(C) * t : dy - SAB_FX(A) * SAB_FZ(C) * t; \
+    dz = (C) ? dz + SAB_FX(A) * SAB_FY(B) * t : dz - SAB_FX(A) * SAB_FY(B) * t; \
+  }
+                SAB_LIN_CORNER(0, 0, 0, 0)
+                SAB_LIN_CORNER(1, 1, 0, 0)
+                SAB_LIN_CORNER(Sy, 0, 1, 0)
+                SAB_LIN_CORNER(Sz, 0, 0, 1)
+                SAB_LIN_CORNER(1 + Sy, 1, 1, 0)
+                SAB_LIN_CORNER(1 + Sz, 1, 0, 1)
+                SAB_LIN_CORNER(Sy + Sz, 0, 1, 1)
+                SAB_LIN_CORNER(Sy + Sz + 1, 1, 1, 1)
+#undef SAB_LIN_CORNER
+                // lever arm: pixel + translation + tap offset, in slice axes
+                const float lx = _x + (float)(kx - P.pw / 2), ly = _y + (float)(ky - P.ph / 2), lz = _z + (float)(kz - P.pd / 2);
+                g[0] += dx * lx; g[1] += dx * ly; g[2] += dx * lz;
+                g[4] += dy * lx; g[5] += dy * ly; g[6] += dy * lz;
+                g[8] += dz * lx; g[9] += dz * ly; g[10] += dz * lz;
+                g[3] += dx * T[0] + dy * T[4] + dz * T[8];
+                g[7] += dx * T[1] + dy * T[5] + dz * T[9];
+                g[11] += dx * T[2] + dy * T[6] + dz * T[10];
+              }
+            }
+          }
+        }
+      }
+    }
+  }
+
+  if (GT) {
+    // lanes of a wave: a fixed shuffle tree; waves of the workgroup: LDS, added in wave order; one partial per workgroup
+    const int tid = threadIdx.y * SA_TILE + threadIdx.x, lane = tid & (FSG_WAVE - 1), wave = tid / FSG_WAVE;
+#pragma unroll
+    for (int k = 0; k < 12; ++k) {
+      float v = g[k];
+#pragma unroll
+      for (int o = FSG_WAVE / 2; o > 0; o >>= 1) v += __shfl_down(v, o, FSG_WAVE);
+      if (lane == 0) red[wave * 12 + k] = v;
+    }
+    __syncthreads();
+    if (tid < 12) {
+      float v = red[tid];
+#pragma unroll
+      for (int q = 1; q < SAB_WAVES; ++q) v += red[q * 12 + tid];
+      const size_t tile = (size_t)blockIdx.y * gridDim.x + blockIdx.x, tiles = (size_t)gridDim.x * gridDim.y;
+      ws[((size_t)in * tiles + tile) * 12 + tid] = v;
+    }
+  }
+}
+
+#undef SAB_FX
+#undef SAB_FY
+#undef SAB_FZ
+
+// grad_transforms[slice][k] = the slice's tile partials added in tile order.  One wave per slice, 12 lanes busy.
+__global__ __launch_bounds__(FSG_WAVE) void sa_bwd_reduce_kernel(const float* __restrict__ ws, int tiles,
+                                                                 float* __restrict__ gtr) {
+  const int in = blockIdx.x, k = threadIdx.x;
+  if (k >= 12) return;
+  const float* p = ws + (size_t)in * tiles * 12 + k;
+  float v = 0.f;
+  for (int t = 0; t < tiles; ++t) v += p[(size_t)t * 12];
+  gtr[in * 12 + k] = v;
+}
+
+template <bool NN, bool VM>
+void sa_backward_launch(const SaParams& P, const float* vol, const float* gslices, float* gvol, float* ws, bool gt, dim3 grid,
+                        size_t lds, hipStream_t st) {
+  const dim3 block(SA_TILE, SA_TILE);
+  if (gvol && gt) hipLaunchKernelGGL((sa_backward_kernel<NN, VM, true, true>), grid, block, lds, st, P, vol, gslices, gvol, ws);
+  else if (gvol) hipLaunchKernelGGL((sa_backward_kernel<NN, VM, true, false>), grid, block, lds, st, P, vol, gslices, gvol, ws);
+  else hipLaunchKernelGGL((sa_backward_kernel<NN, VM, false, true>), grid, block, lds, st, P, vol, gslices, gvol, ws);
+}
+
+}  // namespace
+
+extern "C" {
+
+size_t fsg_slice_acq_backward_ws_bytes(int n, int h, int w) {
+  if (n <= 0 || h <= 0 || w <= 0) return 0;
+  const size_t tiles = (size_t)((w + SA_TILE - 1) / SA_TILE) * (size_t)((h + SA_TILE - 1) / SA_TILE);
+  return (size_t)n * tiles * 12 * sizeof(float);
+}
+
+int fsg_slice_acq_backward_f32(const float* transforms, const float* vol, const uint8_t* vol_mask, const float* psf, int pd,
+                               int ph, int pw, const float* grad_slices, const uint8_t* slices_mask, float* grad_vol,
+                               float* grad_transforms, int D, int H, int W, int n, int h, int w, float res_slice, int mode,
+                               void* ws, size_t ws_bytes, void* stream) {
+  // every refusal comes before the first write
+  if (!vol || !grad_slices || (!grad_vol && !grad_transforms)) return FSG_E_BADARG;
+  if (mode != FSG_SA_LINEAR && mode != FSG_SA_NEAREST_PSF) return FSG_E_BADARG;
+  SaParams P{transforms, psf, vol_mask, slices_mask, nullptr, D, H, W, pd, ph, pw, n, h, w, res_slice};
+  size_t lds = 0;
+  const int rc = sa_check(P, lds, false);
+  if (rc) return rc;
+  if (grad_transforms) {
+    if (!ws || ws_bytes < fsg_slice_acq_backward_ws_bytes(n, h, w)) return FSG_E_BADARG;
+    if ((uintptr_t)ws & 7) return FSG_E_ALIGN;
+  }
+  hipStream_t st = fsg_stream(stream);
+  if (grad_vol) {
+    const hipError_t e = hipMemsetAsync(grad_vol, 0, (size_t)D * H * W * sizeof(float), st);
+    if (e != hipSuccess) return (int)e;
+  }
+  const dim3 grid = sa_grid(P);
+  lds += (size_t)SAB_WAVES * 12 * sizeof(float);
+  float* wsf = static_cast<float*>(ws);
+  const bool gt = grad_transforms != nullptr;
+  if (mode == FSG_SA_NEAREST_PSF) {
+    if (vol_mask) sa_backward_launch<true, true>(P, vol, grad_slices, grad_vol, wsf, gt, grid, lds, st);
+    else sa_backward_launch<true, false>(P, vol, grad_slices, grad_vol, wsf, gt, grid, lds, st);
+  } else {
+    if (vol_mask) sa_backward_launch<false, true>(P, vol, grad_slices, grad_vol, wsf, gt, grid, lds, st);
+    else sa_backward_launch<false, false>(P, vol, grad_slices, grad_vol, wsf, gt, grid, lds, st);
+  }
+  if (gt) {
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return (int)e;
+    // every workgroup of the first launch stored its partial, so every element of grad_transforms is written here
+    hipLaunchKernelGGL(sa_bwd_reduce_kernel, dim3((unsigned)n), dim3(FSG_WAVE), 0, st, (const float*)wsf, (int)(grid.x * grid.y),
+                       grad_transforms);
+  }
+  FSG_RETURN_LAUNCH();
+}
+
+}  // extern "C"

@@ -1,4 +1,5 @@
 """Mirror of `fetalsyngen.generator.artifacts.svort` (reference svort/__init__.py:1-10)."""
+from .autograd import axisangle2mat_autograd  # noqa: F401
 from .rigid import (RigidTransform, ax_update_resolution, axisangle2mat, init_stack_transform, init_zero_transform,  # noqa: F401
                     mat2axisangle, mat_transform_points, mat_update_resolution, random_angle,
                     random_init_stack_transforms, reset_transform, transform_points)

@@ -5,8 +5,13 @@ Tensor layouts are the reference's: vol (1,1,D,H,W), slices (n,1,h,w), masks boo
 transforms (n,3,4), psf (pd,ph,pw).  `semantics` selects which of the reference's two arithmetics is
 followed: "cuda" (default; what the reference computes on a GPU) or "torch" (its CPU fallback, for
 seed-matched comparison with a CPU run of the reference).  There is no CPU path here.
+
+`slice_acquisition` is differentiable in `transforms` and `vol` under "cuda" semantics, as the reference's SliceAcqFunction
+(fsg_slice_acq_bwd.hip); `slice_acquisition_adjoint` has no backward.
 """
 from __future__ import annotations
+
+import torch
 
 from .... import kernels as K
 from .... import rng as _rng
@@ -31,10 +36,47 @@ def _dev(t, device):
     return None if t is None else t.to(device).contiguous()
 
 
+class SliceAcqFunction(torch.autograd.Function):
+    """`slice_acquisition` with a backward, CUDA semantics (reference slice_acq.py:22-101): gradients with respect to
+    `transforms` and `vol`; the masks, the PSF and the geometry get none, and the gradient that arrives for the weight
+    output is ignored, as in the reference."""
+
+    @staticmethod
+    def forward(ctx, transforms, vol, vol_mask, slices_mask, psf, slice_shape, res_slice, need_weight, interp_psf):
+        out = K.slice_acq_forward(transforms, vol, vol_mask, slices_mask, psf, slice_shape, res_slice,
+                                  need_weight=need_weight, interp_psf=interp_psf, semantics="cuda")
+        ctx.save_for_backward(transforms, vol, vol_mask, slices_mask, psf)
+        ctx.res_slice, ctx.interp_psf = res_slice, interp_psf
+        return out
+
+    @staticmethod
+    def backward(ctx, grad_slices, *_grad_weight):
+        transforms, vol, vol_mask, slices_mask, psf = ctx.saved_tensors
+        grad_vol, grad_transforms = K.slice_acq_backward(
+            transforms, vol, vol_mask, slices_mask, psf, grad_slices.contiguous(), ctx.res_slice, interp_psf=ctx.interp_psf,
+            need_vol_grad=ctx.needs_input_grad[1], need_transforms_grad=ctx.needs_input_grad[0])
+        return grad_transforms, grad_vol, None, None, None, None, None, None, None
+
+
 def slice_acquisition(transforms, vol, vol_mask, slices_mask, psf, slice_shape, res_slice, need_weight, interp_psf,
                       semantics=None):
+    """Differentiable in `transforms` and `vol` under `semantics="cuda"`: when either requires grad the call goes through
+    SliceAcqFunction (kernels.slice_acq_backward); otherwise it is the plain forward launch."""
     sem = semantics or _SEMANTICS
     dev = vol.device
+    if torch.is_grad_enabled() and (transforms.requires_grad or vol.requires_grad):
+        if sem != "cuda":
+            raise NotImplementedError("slice_acquisition is differentiable under semantics='cuda' only: the reference's CPU "
+                                      "fallback (semantics='torch') is a sparse-matrix product with no backward kernel here")
+        n, (h, w) = transforms.shape[0], slice_shape
+        v = vol.reshape(vol.shape[-3:]).contiguous()
+        vm = None if vol_mask is None or vol_mask.numel() == 0 else _dev(vol_mask, dev).reshape(v.shape)
+        sm = None if slices_mask is None or slices_mask.numel() == 0 else _dev(slices_mask, dev).reshape(n, h, w)
+        out = SliceAcqFunction.apply(_dev(transforms.float(), dev), v, vm, sm, _dev(psf.float(), dev), (h, w), res_slice,
+                                     need_weight, interp_psf)
+        if need_weight:
+            return out[0].view(n, 1, h, w), out[1].view(n, 1, h, w)
+        return out.view(n, 1, h, w)
     v = vol.reshape(vol.shape[-3:]).contiguous()
     n, (h, w) = transforms.shape[0], slice_shape
     vm = None if vol_mask is None or vol_mask.numel() == 0 else _dev(vol_mask, dev).reshape(v.shape)

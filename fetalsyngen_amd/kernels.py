@@ -692,6 +692,33 @@ def slice_acq_forward(transforms, vol, vol_mask, slices_mask, psf, slice_shape, 
     return (out, wgt) if need_weight else out
 
 
+def slice_acq_backward(transforms, vol, vol_mask, slices_mask, psf, grad_slices, res_slice, interp_psf=False,
+                       need_vol_grad=True, need_transforms_grad=True):
+    """Backward of `slice_acq_forward` in the CUDA semantics (fsg_slice_acq_backward_f32): (n,h,w) grad_slices ->
+    (grad_vol (D,H,W) | None, grad_transforms (n,3,4) | None).  grad_vol is accumulated with fp32 atomics (its last bits change
+    from run to run); grad_transforms is reduced in a fixed order and is bit-identical for the same inputs."""
+    if not (need_vol_grad or need_transforms_grad):
+        return None, None
+    n, (pd, ph, pw) = _sa_common(transforms, psf)
+    _need_gpu(vol, grad_slices)
+    D, H, W = _dims3(_f32(vol, "vol"))
+    _f32(grad_slices, "grad_slices")
+    if grad_slices.dim() != 3 or int(grad_slices.shape[0]) != n:
+        raise ValueError(f"grad_slices must be (n,h,w) with n={n}, got {tuple(grad_slices.shape)}")
+    h, w = int(grad_slices.shape[1]), int(grad_slices.shape[2])
+    vm, sm = _sa_mask(vol_mask, (D, H, W), "vol_mask"), _sa_mask(slices_mask, (n, h, w), "slices_mask")
+    gvol = torch.empty((D, H, W), dtype=F32, device=vol.device) if need_vol_grad else None
+    gtr = torch.empty((n, 3, 4), dtype=F32, device=vol.device) if need_transforms_grad else None
+    lib = _lib.load()
+    need = int(lib.fsg_slice_acq_backward_ws_bytes(n, h, w)) if need_transforms_grad else 0
+    ws = torch.empty(need // 8, dtype=torch.int64, device=vol.device) if need else None  # 48 bytes per tile: a multiple of 8
+    rc = lib.fsg_slice_acq_backward_f32(_p(transforms), _p(vol), _p(vm), _p(psf), pd, ph, pw, _p(grad_slices), _p(sm),
+                                        _p(gvol), _p(gtr), D, H, W, n, h, w, float(res_slice),
+                                        _sa_mode("cuda", interp_psf), _p(ws), need, _stream(vol))
+    _lib.check(rc, "fsg_slice_acq_backward_f32")
+    return gvol, gtr
+
+
 def slice_acq_adjoint(transforms, psf, slices, slices_mask, vol_mask, vol_shape, res_slice, interp_psf=False,
                       equalize=False, semantics="cuda", return_weight=False, slice_ids=None, deterministic=False,
                       value_scale=1.0):

@@ -28,12 +28,13 @@
 extern "C" {
 #endif
 
-#define FSG_ABI_VERSION 7  /* 2: fsg_sample_plan grew (mm_slots .. seg_out_u8) after version 1 shipped; 3: label_codes .. code_sel, FSG_KEYED_I_CODES;
+#define FSG_ABI_VERSION 8  /* 2: fsg_sample_plan grew (mm_slots .. seg_out_u8) after version 1 shipped; 3: label_codes .. code_sel, FSG_KEYED_I_CODES;
                               4: fsg_sample_image / fsg_sample_run_image, FSG_KEYED_I_IMAGE_IN .. PRIOR_IN, fsg_warp_dual_f32;
                               5: fsg_keyed_overrides / fsg_keyed_draw_with, fsg_keyed_draws grew (spacing3 .. sigmas_in),
                                  FSG_KEYED_I_OVERRIDES / BLOCK_BYTES;
                               6: fsg_voxel_pick_f32 / _u8, fsg_voxel_pick_ws_bytes;
-                              7: fsg_slice_acq_adjoint_det_f32, fsg_slice_acq_adjoint_det_ws_bytes, FSG_SA_DET_FRAC_BITS / LIMB_BITS */
+                              7: fsg_slice_acq_adjoint_det_f32, fsg_slice_acq_adjoint_det_ws_bytes, FSG_SA_DET_FRAC_BITS / LIMB_BITS;
+                              8: fsg_slice_acq_backward_f32, fsg_slice_acq_backward_ws_bytes */
 
 #define FSG_E_BADARG (-1)   /* null pointer / non-positive size / bad enum */
 #define FSG_E_TOOBIG (-2)   /* size exceeds what the kernel indexes (2^31-1 voxels per volume) */
@@ -378,6 +379,43 @@ int fsg_slice_acq_set_tuning(int cap_cells, int z_chunk, int t16_extent);
  * fallback slice_acq.py:542-543); then vol[i] *= vol_mask[i] if vol_mask (fallback :544-545).  Either of
  * vol_weight / vol_mask may be NULL, not both. */
 int fsg_equalize_f32(float* vol, const float* vol_weight, const uint8_t* vol_mask, float threshold, size_t n, void* stream);
+/* Backward of fsg_slice_acq_forward_f32 (fsg_slice_acq_bwd.hip; reference SliceAcqFunction.backward,
+ * slice_acq_cuda_kernel.cu:173-470): grad_vol (D,H,W) and grad_transforms (n,12) from grad_slices (n,h,w).  Either output
+ * may be NULL (not both: FSG_E_BADARG).  FSG_SA_LINEAR and FSG_SA_NEAREST_PSF; FSG_SA_TORCH is refused with FSG_E_BADARG
+ * (the fallback has no backward of its own).  PSF limits as the forward.  The rule is the reference's, quirks included:
+ *   - a pixel outside slices_mask, or with grad_slices == 0, contributes nothing;
+ *   - pass 1: weight = sum over the taps inside the volume (0 <= p < size - 1 per axis) of the raw PSF value (LINEAR) or of
+ *     the PSF re-interpolated at the rounded voxel, taps outside the PSF grid skipped (NEAREST_PSF).  vol_mask is NOT
+ *     consulted here, although the forward's own weight leaves masked voxels out; weight == 0 ends the pixel (the forward
+ *     tests weight > 0), otherwise gs = grad_slices / weight;
+ *   - pass 2, grad_vol: LINEAR adds gs * psf * corner weight to the up-to-8 unmasked corners, NEAREST_PSF gs * psf' to the
+ *     rounded voxel if it is unmasked;
+ *   - pass 2, grad_transforms: d = gs * (derivative of the trilinear weights with respect to the sampling position) summed
+ *     over the same unmasked terms, the weight held constant.  LINEAR: d is in volume axes, g_R[a][b] += d[a] * l[b] with
+ *     the lever l = pixel + translation + tap offset in slice axes, g_t += R^T d.  NEAREST_PSF: d is in PSF axes,
+ *     g_R[a][b] += l[a] * d[b] with l = rounded voxel - volume centre, g_t -= d.
+ *   Arithmetic is fp32 in the reference's operation order except that the NEAREST_PSF lever products are formed in fp32
+ *   (the reference promotes them to double through a literal).
+ * Accumulation:
+ *   grad_vol         zeroed by the call on `stream`, then fp32 vector atomics, as the reference and fsg_slice_acq_adjoint_f32:
+ *                    the order of the additions, and with it the last bits, change from run to run.  NOT deterministic
+ *                    (bit-identical only where a voxel receives at most one contribution).
+ *   grad_transforms  DETERMINISTIC, no atomics: 12 sums per thread in registers, a fixed shuffle tree per wave, the waves of a
+ *                    workgroup added in order through LDS, one 12-float partial per workgroup stored at ws[slice][tile], and a
+ *                    second launch that adds a slice's tiles in index order.  The same bits on any stream, in any run, and
+ *                    with grad_vol requested or not.
+ *   ws               DEVICE; read and written only when grad_transforms is requested, and then it must be 8-byte aligned
+ *                    (else FSG_E_ALIGN) with ws_bytes >= fsg_slice_acq_backward_ws_bytes(n, h, w) = 48 bytes per 16x16 pixel
+ *                    tile of every slice (else FSG_E_BADARG).  It needs no initialisation.
+ * Every refusal leaves grad_vol, grad_transforms and ws untouched; otherwise every element of each requested output is written.
+ * No allocation and no host synchronisation inside.  Every in-volume and in-PSF test accepts (`!(p >= 0 && p < size - 1)`
+ * skips), so a NaN or Inf in transforms or res_slice skips the tap: no address depends on a value that failed a range test.
+ * Non-finite vol, psf or grad_slices values give unspecified values where they reach and never a fault. */
+size_t fsg_slice_acq_backward_ws_bytes(int n, int h, int w);
+int fsg_slice_acq_backward_f32(const float* transforms, const float* vol, const uint8_t* vol_mask, const float* psf, int pd,
+                               int ph, int pw, const float* grad_slices, const uint8_t* slices_mask, float* grad_vol,
+                               float* grad_transforms, int D, int H, int W, int n, int h, int w, float res_slice, int mode,
+                               void* ws, size_t ws_bytes, void* stream);
 
 /* ---- SR-artifact volumetric helpers, fsg_artifacts.hip ------------------------------------ */
 /* out = clamp(sum_g exp(-(((x-c0)/s0)^2 + ((y-c1)/s1)^2 + ((z-c2)/s2)^2) / 2), 0, 1) over a (D,H,W) grid with

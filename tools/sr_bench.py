@@ -2,10 +2,12 @@
 """Time the slice-acquisition kernels at BASELINE config 4 scale (384^3 volume at 0.5 mm, one stack of a
 3 mm-thick, 0.8 mm in-plane acquisition) with HIP events on the launch stream.  Prints one JSON line.
 
-    python tools/sr_bench.py [--size 384] [--slices 80] [--reps 5] [--deterministic]
+    python tools/sr_bench.py [--size 384] [--slices 80] [--reps 5] [--deterministic] [--backward]
 
 --deterministic adds a leg for the adjoint timings: the fixed-point accumulation (fsg_slice_acq_adjoint_det_f32) timed right
 after the fp32-atomic entry on the same inputs (`*_det_ms`, the float figures are the yardstick), and its workspace size.
+--backward adds the backward of the forward operator (fsg_slice_acq_backward_f32) at the same size: `backward_<mode>_<leg>_ms`
+for grad_vol alone, grad_transforms alone and both, in both modes, beside the forward's and the float adjoint's times.
 """
 import argparse
 import json
@@ -40,6 +42,7 @@ def main():
     ap.add_argument("--res-slice", type=float, default=0.8)
     ap.add_argument("--thick", type=float, default=3.0)
     ap.add_argument("--deterministic", action="store_true", help="also time the deterministic adjoint")
+    ap.add_argument("--backward", action="store_true", help="also time the backward of the forward operator")
     a = ap.parse_args()
     dev, res = "cuda:0", 0.5
     vs = (a.size,) * 3
@@ -83,6 +86,18 @@ def main():
         a_f, a_d = adj(), det(interp_psf=True, equalize=True)
         out["det_vs_float_max_abs"] = float((a_f - a_d).abs().max())
         out["det_twice_equal"] = bool(torch.equal(a_d, det(interp_psf=True, equalize=True)))
+    if a.backward:
+        # backward of the forward (fsg_slice_acq_backward_f32) on the forward's own inputs, beside forward_*_ms and the float
+        # adjoint's adjoint_*_ms above: each output alone and both, in both modes
+        gs = torch.randn_like(s)
+        for mode, ipsf in (("linear", False), ("nearest_psf", True)):
+            for leg, kw in (("grad_vol", dict(need_transforms_grad=False)), ("grad_transforms", dict(need_vol_grad=False)),
+                            ("both", {})):
+                fn = lambda: K.slice_acq_backward(tr, vol, None, None, psf, gs, rs, interp_psf=ipsf, **kw)  # noqa: E731
+                out[f"backward_{mode}_{leg}_ms"] = round(timed(fn, a.reps), 3)
+        out["backward_workspace_bytes"] = int(lib.fsg_slice_acq_backward_ws_bytes(a.slices, ss, ss))
+        t1, t2 = (K.slice_acq_backward(tr, vol, None, None, psf, gs, rs, need_vol_grad=False)[1] for _ in range(2))
+        out["backward_grad_transforms_twice_equal"] = bool(torch.equal(t1, t2))
     sweep = {}
     cfgs = ((4096, 0, 20), (3072, 0, 20), (6144, 0, 20), (4096, 3, 20), (4096, 2, 20), (6144, 1, 20), (4096, 0, 0), (4096, 0, 40))
     for ang in (0.3, 0.8, 1.5):
