@@ -1,6 +1,7 @@
 // fsg_sa.h -- what the slice-acquisition translation units share (fsg_slice_acq.hip: forward and adjoint;
-// fsg_slice_acq_bwd.hip: backward of the forward): the kernel-argument block, the LDS image of the PSF and of the
-// per-axis tap products, the pixel-centre arithmetic and the argument checks.  Internal linkage: each unit has its own copy.
+// fsg_slice_acq_bwd.hip: backward of the forward; fsg_slice_acq_adjoint_bwd.hip: backward of the adjoint): the kernel-argument
+// block, the LDS image of the PSF and of the per-axis tap products, the pixel-centre arithmetic, the argument checks and the
+// fixed-order reduction of the 12 transform sums.  Internal linkage: each unit has its own copy.
 #pragma once
 #include "fsg_common.h"
 
@@ -83,6 +84,42 @@ __device__ __forceinline__ void sa_centre(const SaParams& P, const float* __rest
   xc = (float)((double)xc + (P.W - 1) / 2.);
   yc = (float)((double)yc + (P.H - 1) / 2.);
   zc = (float)((double)zc + (P.D - 1) / 2.);
+}
+
+// ---- the fixed-order reduction of the 12 transform sums, shared by the two backward units ----
+constexpr int SAB_WAVES = SA_TILE * SA_TILE / FSG_WAVE;
+
+// Every thread of the workgroup calls this with its 12 sums (a pixel without a contribution carries twelve zeros).  Lanes of a
+// wave: a fixed shuffle tree; waves of the workgroup: LDS (`red`, [SAB_WAVES][12]), added in wave order; one 12-float partial
+// per workgroup at ws[slice][tile].
+__device__ __forceinline__ void sa_fold12(const float (&g)[12], float* red, float* __restrict__ ws, int in) {
+  const int tid = threadIdx.y * SA_TILE + threadIdx.x, lane = tid & (FSG_WAVE - 1), wave = tid / FSG_WAVE;
+#pragma unroll
+  for (int k = 0; k < 12; ++k) {
+    float v = g[k];
+#pragma unroll
+    for (int o = FSG_WAVE / 2; o > 0; o >>= 1) v += __shfl_down(v, o, FSG_WAVE);
+    if (lane == 0) red[wave * 12 + k] = v;
+  }
+  __syncthreads();
+  if (tid < 12) {
+    float v = red[tid];
+#pragma unroll
+    for (int q = 1; q < SAB_WAVES; ++q) v += red[q * 12 + tid];
+    const size_t tile = (size_t)blockIdx.y * gridDim.x + blockIdx.x, tiles = (size_t)gridDim.x * gridDim.y;
+    ws[((size_t)in * tiles + tile) * 12 + tid] = v;
+  }
+}
+
+// grad_transforms[slice][k] = the slice's tile partials added in tile order.  One wave per slice, 12 lanes busy.
+__global__ __launch_bounds__(FSG_WAVE) void sa_bwd_reduce_kernel(const float* __restrict__ ws, int tiles,
+                                                                 float* __restrict__ gtr) {
+  const int in = blockIdx.x, k = threadIdx.x;
+  if (k >= 12) return;
+  const float* p = ws + (size_t)in * tiles * 12 + k;
+  float v = 0.f;
+  for (int t = 0; t < tiles; ++t) v += p[(size_t)t * 12];
+  gtr[in * 12 + k] = v;
 }
 
 inline int sa_check(const SaParams& P, size_t& lds, bool torch_mode) {

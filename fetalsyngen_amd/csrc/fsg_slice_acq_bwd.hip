@@ -1,6 +1,7 @@
 // fsg_slice_acq_bwd.hip -- backward of the slice-acquisition FORWARD operator: gradients of `slices` with respect to the
 // volume and to the (n,3,4) slice transforms (reference SliceAcqFunction.backward, slice_acq_cuda_kernel.cu:173-470,
-// host side :993-1030).  The backward of the adjoint and transform_convert's autograd are not here.
+// host side :993-1030).  The backward of the adjoint is fsg_slice_acq_adjoint_bwd.hip; the fold of the 12 transform sums and
+// sa_bwd_reduce_kernel, which both units use, are in fsg_sa.h.
 //
 // The rule (include/fsg_hip.h), per pixel inside slices_mask with grad_slices != 0:
 //   pass 1  weight = sum over the in-volume taps of the PSF value (FSG_SA_NEAREST_PSF: re-interpolated at the rounded voxel,
@@ -22,8 +23,6 @@
 #include "fsg_sa.h"
 
 namespace {
-
-constexpr int SAB_WAVES = SA_TILE * SA_TILE / FSG_WAVE;
 
 // Trilinear corner (A,B,C) of the cell at offset OFF: its weight factors along x, y, z.
 #define SAB_FX(A) ((A) ? wx : (1 - wx))
@@ -215,41 +214,13 @@ __global__ __launch_bounds__(SA_TILE* SA_TILE) void sa_backward_kernel(SaParams 
     }
   }
 
-  if (GT) {
-    // lanes of a wave: a fixed shuffle tree; waves of the workgroup: LDS, added in wave order; one partial per workgroup
-    const int tid = threadIdx.y * SA_TILE + threadIdx.x, lane = tid & (FSG_WAVE - 1), wave = tid / FSG_WAVE;
-#pragma unroll
-    for (int k = 0; k < 12; ++k) {
-      float v = g[k];
-#pragma unroll
-      for (int o = FSG_WAVE / 2; o > 0; o >>= 1) v += __shfl_down(v, o, FSG_WAVE);
-      if (lane == 0) red[wave * 12 + k] = v;
-    }
-    __syncthreads();
-    if (tid < 12) {
-      float v = red[tid];
-#pragma unroll
-      for (int q = 1; q < SAB_WAVES; ++q) v += red[q * 12 + tid];
-      const size_t tile = (size_t)blockIdx.y * gridDim.x + blockIdx.x, tiles = (size_t)gridDim.x * gridDim.y;
-      ws[((size_t)in * tiles + tile) * 12 + tid] = v;
-    }
-  }
+  // the fold of fsg_sa.h: shuffle tree per wave, waves in order through LDS, one partial per workgroup
+  if (GT) sa_fold12(g, red, ws, in);
 }
 
 #undef SAB_FX
 #undef SAB_FY
 #undef SAB_FZ
-
-// grad_transforms[slice][k] = the slice's tile partials added in tile order.  One wave per slice, 12 lanes busy.
-__global__ __launch_bounds__(FSG_WAVE) void sa_bwd_reduce_kernel(const float* __restrict__ ws, int tiles,
-                                                                 float* __restrict__ gtr) {
-  const int in = blockIdx.x, k = threadIdx.x;
-  if (k >= 12) return;
-  const float* p = ws + (size_t)in * tiles * 12 + k;
-  float v = 0.f;
-  for (int t = 0; t < tiles; ++t) v += p[(size_t)t * 12];
-  gtr[in * 12 + k] = v;
-}
 
 template <bool NN, bool VM>
 void sa_backward_launch(const SaParams& P, const float* vol, const float* gslices, float* gvol, float* ws, bool gt, dim3 grid,

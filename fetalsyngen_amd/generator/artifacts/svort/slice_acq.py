@@ -7,7 +7,10 @@ followed: "cuda" (default; what the reference computes on a GPU) or "torch" (its
 seed-matched comparison with a CPU run of the reference).  There is no CPU path here.
 
 `slice_acquisition` is differentiable in `transforms` and `vol` under "cuda" semantics, as the reference's SliceAcqFunction
-(fsg_slice_acq_bwd.hip); `slice_acquisition_adjoint` has no backward.
+(fsg_slice_acq_bwd.hip).  `slice_acquisition_adjoint` is differentiable in `transforms` and `slices`, as
+the reference's SliceAcqAdjointFunction (fsg_slice_acq_adjoint_bwd.hip), with or without `equalize`; both
+of its gradients are bit-identical from run to run.  Neither has a backward under "torch" semantics, and the adjoint has none
+for a `slice_ids` subset: those calls raise NotImplementedError when a gradient is asked for.
 """
 from __future__ import annotations
 
@@ -88,13 +91,62 @@ def slice_acquisition(transforms, vol, vol_mask, slices_mask, psf, slice_shape, 
     return out.view(n, 1, h, w)
 
 
+class SliceAcqAdjointFunction(torch.autograd.Function):
+    """`slice_acquisition_adjoint` with a backward, CUDA semantics (reference slice_acq.py:104-190): gradients with respect
+    to `transforms` and `slices`; the masks, the PSF and the geometry get none.  With `equalize` the equalised volume and its
+    weight are saved for the backward, as in the reference; the gradient that arrives is read, never written."""
+
+    @staticmethod
+    def forward(ctx, transforms, psf, slices, slices_mask, vol_mask, vol_shape, res_slice, interp_psf, equalize, deterministic):
+        out = K.slice_acq_adjoint(transforms, psf, slices, slices_mask, vol_mask, vol_shape, res_slice, interp_psf=interp_psf,
+                                  equalize=equalize, semantics="cuda", return_weight=equalize, deterministic=deterministic)
+        if equalize:
+            vol, vol_weight = out
+            ctx.save_for_backward(transforms, psf, slices, slices_mask, vol_mask, vol, vol_weight)
+        else:
+            vol = out
+            ctx.save_for_backward(transforms, psf, slices, slices_mask, vol_mask)
+        ctx.res_slice, ctx.interp_psf, ctx.equalize = res_slice, interp_psf, equalize
+        return vol
+
+    @staticmethod
+    def backward(ctx, grad_vol):
+        transforms, psf, slices, slices_mask, vol_mask, *eq = ctx.saved_tensors
+        vol, vol_weight = eq if ctx.equalize else (None, None)
+        grad_slices, grad_transforms = K.slice_acq_adjoint_backward(
+            transforms, grad_vol.contiguous(), psf, slices, slices_mask, vol_mask, ctx.res_slice, interp_psf=ctx.interp_psf,
+            equalize=ctx.equalize, vol=vol, vol_weight=vol_weight, need_slices_grad=ctx.needs_input_grad[2],
+            need_transforms_grad=ctx.needs_input_grad[0])
+        return grad_transforms, None, grad_slices, None, None, None, None, None, None, None
+
+
 def slice_acquisition_adjoint(transforms, psf, slices, slices_mask, vol_mask, vol_shape, res_slice, interp_psf,
                               equalize, semantics=None, slice_ids=None, deterministic=None):
     """deterministic: None = inside a keyed scope (`rng.in_keyed_scope()`), where a sample is a function of its key; True /
-    False force the fixed-point or the fp32-atomic accumulation (kernels.slice_acq_adjoint)."""
+    False force the fixed-point or the fp32-atomic accumulation (kernels.slice_acq_adjoint).
+
+    Differentiable in `transforms` and `slices` under `semantics="cuda"`: when either requires grad the call goes through
+    SliceAcqAdjointFunction (kernels.slice_acq_adjoint_backward); otherwise it is the plain adjoint launch."""
     sem = semantics or _SEMANTICS
     if deterministic is None:
         deterministic = _rng.in_keyed_scope() and sem == "cuda"
+    if torch.is_grad_enabled() and (transforms.requires_grad or slices.requires_grad):
+        if sem != "cuda":
+            raise NotImplementedError("slice_acquisition_adjoint is differentiable under semantics='cuda' only: the reference's "
+                                      "CPU fallback (semantics='torch') is a sparse-matrix product with no backward kernel here")
+        if slice_ids is not None:
+            raise NotImplementedError("slice_acquisition_adjoint has no backward for a slice_ids subset: pass the slices and "
+                                      "transforms of the subset themselves")
+        dev = slices.device
+        h, w = slices.shape[-2:]
+        D, H, W = (int(v) for v in vol_shape)
+        n = transforms.shape[0]
+        vm = None if vol_mask is None or vol_mask.numel() == 0 else _dev(vol_mask, dev).reshape(D, H, W)
+        sm = None if slices_mask is None or slices_mask.numel() == 0 else _dev(slices_mask, dev).reshape(n, h, w)
+        vol = SliceAcqAdjointFunction.apply(_dev(transforms.float(), dev), _dev(psf.float(), dev),
+                                            slices.reshape(-1, h, w).contiguous(), sm, vm, (D, H, W), res_slice, interp_psf,
+                                            bool(equalize), bool(deterministic))
+        return vol.view(1, 1, D, H, W)
     dev = slices.device
     h, w = slices.shape[-2:]
     s = slices.reshape(-1, h, w).contiguous()

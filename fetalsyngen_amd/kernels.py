@@ -719,6 +719,44 @@ def slice_acq_backward(transforms, vol, vol_mask, slices_mask, psf, grad_slices,
     return gvol, gtr
 
 
+def slice_acq_adjoint_backward(transforms, grad_vol, psf, slices, slices_mask, vol_mask, res_slice, interp_psf=False,
+                               equalize=False, vol=None, vol_weight=None, need_slices_grad=True, need_transforms_grad=True):
+    """Backward of `slice_acq_adjoint` in the CUDA semantics (fsg_slice_acq_adjoint_backward_f32): (D,H,W) grad_vol ->
+    (grad_slices (n,h,w) | None, grad_transforms (n,3,4) | None).  equalize: the backward of the equalised adjoint; `vol` is its
+    (equalised) output and `vol_weight` its weight (`return_weight=True`).  grad_vol is never written.  Both outputs are
+    gathered and reduced in a fixed order: bit-identical for the same inputs, each whether or not the other is requested."""
+    if not (need_slices_grad or need_transforms_grad):
+        return None, None
+    if equalize and (vol is None or vol_weight is None):
+        raise ValueError("equalize=True needs vol (the equalised output of the adjoint) and vol_weight")
+    n, (pd, ph, pw) = _sa_common(transforms, psf)
+    _need_gpu(grad_vol, slices)
+    D, H, W = _dims3(_f32(grad_vol, "grad_vol"))
+    _f32(slices, "slices")
+    if slices.dim() != 3 or int(slices.shape[0]) != n:
+        raise ValueError(f"slices must be (n,h,w) with n={n}, got {tuple(slices.shape)}")
+    h, w = int(slices.shape[1]), int(slices.shape[2])
+    vm, sm = _sa_mask(vol_mask, (D, H, W), "vol_mask"), _sa_mask(slices_mask, (n, h, w), "slices_mask")
+    if equalize:
+        _need_gpu(vol, vol_weight)
+        for t, name in ((vol, "vol"), (vol_weight, "vol_weight")):
+            if _dims3(_f32(t, name)) != (D, H, W):
+                raise ValueError(f"{name} shape {tuple(t.shape)} does not match grad_vol {(D, H, W)}")
+    else:
+        vol = vol_weight = None
+    gsl = torch.empty((n, h, w), dtype=F32, device=grad_vol.device) if need_slices_grad else None
+    gtr = torch.empty((n, 3, 4), dtype=F32, device=grad_vol.device) if need_transforms_grad else None
+    lib = _lib.load()
+    need = int(lib.fsg_slice_acq_adjoint_backward_ws_bytes(D, H, W, n, h, w, int(bool(equalize)), int(need_transforms_grad)))
+    ws = torch.empty((need + 7) // 8, dtype=torch.int64, device=grad_vol.device) if need else None
+    rc = lib.fsg_slice_acq_adjoint_backward_f32(_p(transforms), _p(grad_vol), _p(vol_weight), _p(vol), _p(vm), _p(psf), pd, ph,
+                                                pw, _p(slices), _p(sm), _p(gsl), _p(gtr), D, H, W, n, h, w, float(res_slice),
+                                                _sa_mode("cuda", interp_psf), int(bool(equalize)), _p(ws), need,
+                                                _stream(grad_vol))
+    _lib.check(rc, "fsg_slice_acq_adjoint_backward_f32")
+    return gsl, gtr
+
+
 def slice_acq_adjoint(transforms, psf, slices, slices_mask, vol_mask, vol_shape, res_slice, interp_psf=False,
                       equalize=False, semantics="cuda", return_weight=False, slice_ids=None, deterministic=False,
                       value_scale=1.0):

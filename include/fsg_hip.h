@@ -34,7 +34,8 @@ extern "C" {
                                  FSG_KEYED_I_OVERRIDES / BLOCK_BYTES;
                               6: fsg_voxel_pick_f32 / _u8, fsg_voxel_pick_ws_bytes;
                               7: fsg_slice_acq_adjoint_det_f32, fsg_slice_acq_adjoint_det_ws_bytes, FSG_SA_DET_FRAC_BITS / LIMB_BITS;
-                              8: fsg_slice_acq_backward_f32, fsg_slice_acq_backward_ws_bytes */
+                              8: fsg_slice_acq_backward_f32, fsg_slice_acq_backward_ws_bytes; still 8 with
+                                 fsg_slice_acq_adjoint_backward_f32 / _ws_bytes: two entries added, nothing older changed */
 
 #define FSG_E_BADARG (-1)   /* null pointer / non-positive size / bad enum */
 #define FSG_E_TOOBIG (-2)   /* size exceeds what the kernel indexes (2^31-1 voxels per volume) */
@@ -416,6 +417,55 @@ int fsg_slice_acq_backward_f32(const float* transforms, const float* vol, const 
                                int ph, int pw, const float* grad_slices, const uint8_t* slices_mask, float* grad_vol,
                                float* grad_transforms, int D, int H, int W, int n, int h, int w, float res_slice, int mode,
                                void* ws, size_t ws_bytes, void* stream);
+/* Backward of fsg_slice_acq_adjoint_f32 + fsg_equalize_f32 (fsg_slice_acq_adjoint_bwd.hip; reference
+ * SliceAcqAdjointFunction.backward, slice_acq_cuda_kernel.cu:695-950, host side :1079-1132): grad_slices (n,h,w) and
+ * grad_transforms (n,12) from grad_vol (D,H,W).  Either output may be NULL (not both: FSG_E_BADARG).  FSG_SA_LINEAR and
+ * FSG_SA_NEAREST_PSF; FSG_SA_TORCH is refused with FSG_E_BADARG.  PSF limits as the forward.  `equalize` != 0 is the backward
+ * of the equalised adjoint and needs vol_weight (the adjoint's weight output) and vol (its EQUALISED output), else
+ * FSG_E_BADARG; without it both are ignored and may be NULL.  The rule is the reference's, quirks included:
+ *   - equalisation of the gradient (:672-693, is_grad = true): g'[i] = grad_vol[i] / (w < 1e-3 ? 1e-3 : w) where
+ *     w = vol_weight[i] > 0, g'[i] = grad_vol[i] elsewhere; the comparison with and the division by the literal 1e-3 are done
+ *     in double, as the reference's promotion does, the division by w in fp32.  The reference overwrites the incoming gradient;
+ *     here one streaming pre-pass writes g' into ws and grad_vol is NEVER written.  Without equalize g' = grad_vol, no copy;
+ *   - a pixel outside slices_mask contributes nothing.  Otherwise ONE pass over the non-zero PSF taps whose position is inside
+ *     the volume (0 <= p < size - 1 per axis); geometry as fsg_slice_acq_adjoint_f32;
+ *   - LINEAR: val_ = sum over the unmasked corners of corner weight * g'[corner]; val += psf * val_; weight += psf -- the tap
+ *     counts whatever vol_mask says.  Transforms: per unmasked corner s = (equalize ? slices[p] - vol[corner] : slices[p]) *
+ *     g'[corner]; d = psf * sum of s * (derivative of the corner weight with respect to the position), in volume axes;
+ *     g_R[a][b] += d[a] * l[b] with the lever l = pixel + translation + tap offset in slice axes, g_t += R^T d;
+ *   - NEAREST_PSF: the voxel is the rounded position (half away from zero).  A voxel outside vol_mask skips the tap BEFORE it
+ *     is added to weight; then the PSF is re-interpolated at the rounded voxel, taps whose PSF coordinate leaves
+ *     [0, psf_size - 1) skipped; val += psf' * g'[voxel]; weight += psf'.  Transforms: d = (derivative of psf' with respect
+ *     to the PSF coordinate, from its 8 PSF neighbours) * s, s = (equalize ? slices[p] - vol[voxel] : slices[p]) * g'[voxel],
+ *     in PSF axes; g_R[a][b] += l[a] * d[b] with l = rounded voxel - volume centre, g_t -= d;
+ *   - end of pixel: weight > 0 gives grad_slices[p] = val / weight and the pixel's 12 sums divided by weight; otherwise
+ *     the pixel gives nothing.
+ *   Quirks kept: (1) the adjoint forward drops pixels with weight < 0.5, this backward tests weight > 0; (2) in NEAREST_PSF
+ *   with a vol_mask the forward's per-pixel weight counts masked voxels and this one does not; (3) the per-pixel weight is
+ *   treated as a constant in grad_transforms; (4) the 1e-3 floor.  So this is the derivative of the adjoint only where every
+ *   kept pixel has weight >= 0.5 and, in NEAREST_PSF, there is no vol_mask.
+ *   Arithmetic is fp32 in the reference's operation order except that the NEAREST_PSF lever products are formed in fp32
+ *   (the reference promotes them to double through a literal), as fsg_slice_acq_backward_f32.
+ * DETERMINISTIC, both outputs: the kernel only gathers.  grad_slices is one plain store per pixel; grad_transforms takes the
+ * reduction of fsg_slice_acq_backward_f32 (12 register sums, a fixed shuffle tree per wave, waves in order through LDS, one
+ * 12-float partial per workgroup in ws, a second launch adding a slice's tiles in index order).  No atomics.  The same bits on
+ * any stream, in any run, and for one output whether or not the other is requested.
+ *   ws   DEVICE; fsg_slice_acq_adjoint_backward_ws_bytes(D, H, W, n, h, w, equalize, want_transforms) = 48 bytes per 16x16
+ *        pixel tile of every slice if grad_transforms is requested, plus 4 * D*H*W if equalize.  If that is 0, ws is not
+ *        touched and may be NULL; otherwise it must be 8-byte aligned (else FSG_E_ALIGN) and large enough (else FSG_E_BADARG).
+ *        It needs no initialisation.
+ * Every refusal leaves grad_slices, grad_transforms and ws untouched; otherwise every element of each requested output is
+ * written: 0 outside slices_mask and where weight <= 0.  No allocation and no host synchronisation inside.  Every in-volume and
+ * in-PSF test accepts (`!(p >= 0 && p < size - 1)` skips), so a NaN or Inf in transforms or res_slice skips the tap and the
+ * pixel gives zeros: no address depends on a value that failed a range test.  Non-finite grad_vol, vol, vol_weight, psf or
+ * slices values give unspecified values where they reach and never a fault. */
+size_t fsg_slice_acq_adjoint_backward_ws_bytes(int D, int H, int W, int n, int h, int w, int equalize, int want_transforms);
+int fsg_slice_acq_adjoint_backward_f32(const float* transforms, const float* grad_vol, const float* vol_weight /*equalize*/,
+                                       const float* vol /*equalize: the equalised output of the forward*/,
+                                       const uint8_t* vol_mask, const float* psf, int pd, int ph, int pw, const float* slices,
+                                       const uint8_t* slices_mask, float* grad_slices /*may be NULL*/,
+                                       float* grad_transforms /*may be NULL; not both*/, int D, int H, int W, int n, int h,
+                                       int w, float res_slice, int mode, int equalize, void* ws, size_t ws_bytes, void* stream);
 
 /* ---- SR-artifact volumetric helpers, fsg_artifacts.hip ------------------------------------ */
 /* out = clamp(sum_g exp(-(((x-c0)/s0)^2 + ((y-c1)/s1)^2 + ((z-c2)/s2)^2) / 2), 0, 1) over a (D,H,W) grid with

@@ -2,12 +2,16 @@
 """Time the slice-acquisition kernels at BASELINE config 4 scale (384^3 volume at 0.5 mm, one stack of a
 3 mm-thick, 0.8 mm in-plane acquisition) with HIP events on the launch stream.  Prints one JSON line.
 
-    python tools/sr_bench.py [--size 384] [--slices 80] [--reps 5] [--deterministic] [--backward]
+    python tools/sr_bench.py [--size 384] [--slices 80] [--reps 5] [--deterministic] [--backward] [--adjoint-backward]
 
 --deterministic adds a leg for the adjoint timings: the fixed-point accumulation (fsg_slice_acq_adjoint_det_f32) timed right
 after the fp32-atomic entry on the same inputs (`*_det_ms`, the float figures are the yardstick), and its workspace size.
 --backward adds the backward of the forward operator (fsg_slice_acq_backward_f32) at the same size: `backward_<mode>_<leg>_ms`
 for grad_vol alone, grad_transforms alone and both, in both modes, beside the forward's and the float adjoint's times.
+--adjoint-backward adds the backward of the adjoint (fsg_slice_acq_adjoint_backward_f32) on the same problem:
+`adjoint_backward_<mode>[_eq]_<leg>_ms` for grad_slices alone, grad_transforms alone and both, in both modes, equalize off and
+on (the pre-pass over the gradient included), and its ratios to forward_<mode>_ms and, with --backward, to
+backward_<mode>_grad_transforms_ms of the same session.
 """
 import argparse
 import json
@@ -43,6 +47,7 @@ def main():
     ap.add_argument("--thick", type=float, default=3.0)
     ap.add_argument("--deterministic", action="store_true", help="also time the deterministic adjoint")
     ap.add_argument("--backward", action="store_true", help="also time the backward of the forward operator")
+    ap.add_argument("--adjoint-backward", action="store_true", help="also time the backward of the adjoint")
     a = ap.parse_args()
     dev, res = "cuda:0", 0.5
     vs = (a.size,) * 3
@@ -98,6 +103,28 @@ def main():
         out["backward_workspace_bytes"] = int(lib.fsg_slice_acq_backward_ws_bytes(a.slices, ss, ss))
         t1, t2 = (K.slice_acq_backward(tr, vol, None, None, psf, gs, rs, need_vol_grad=False)[1] for _ in range(2))
         out["backward_grad_transforms_twice_equal"] = bool(torch.equal(t1, t2))
+    if a.adjoint_backward:
+        # backward of the adjoint (fsg_slice_acq_adjoint_backward_f32): the slices of the forward, a random gradient on the
+        # volume; with equalize, the volume and weight of the equalised adjoint of the same mode
+        gv = torch.randn(vs, device=dev)
+        for mode, ipsf in (("linear", False), ("nearest_psf", True)):
+            ev, ew = K.slice_acq_adjoint(tr, psf, s, None, None, vs, rs, interp_psf=ipsf, equalize=True, return_weight=True)
+            for eq, tag in ((False, ""), (True, "_eq")):
+                st = dict(equalize=True, vol=ev, vol_weight=ew) if eq else {}
+                for leg, kw in (("grad_slices", dict(need_transforms_grad=False)), ("grad_transforms", dict(need_slices_grad=False)),
+                                ("both", {})):
+                    fn = lambda: K.slice_acq_adjoint_backward(tr, gv, psf, s, None, None, rs, interp_psf=ipsf, **st, **kw)  # noqa: E731
+                    out[f"adjoint_backward_{mode}{tag}_{leg}_ms"] = round(timed(fn, a.reps), 3)
+            for leg in ("grad_slices", "grad_transforms", "both"):
+                t = out[f"adjoint_backward_{mode}_{leg}_ms"]
+                out[f"adjoint_backward_{mode}_{leg}_over_forward"] = round(t / out[f"forward_{mode}_ms"], 2)
+            if a.backward:
+                out[f"adjoint_backward_{mode}_grad_transforms_over_backward"] = round(
+                    out[f"adjoint_backward_{mode}_grad_transforms_ms"] / out[f"backward_{mode}_grad_transforms_ms"], 2)
+        out["adjoint_backward_workspace_bytes"] = int(lib.fsg_slice_acq_adjoint_backward_ws_bytes(*vs, a.slices, ss, ss, 1, 1))
+        r1, r2 = (K.slice_acq_adjoint_backward(tr, gv, psf, s, None, None, rs, equalize=True, vol=ev, vol_weight=ew)
+                  for _ in range(2))
+        out["adjoint_backward_twice_equal"] = bool(torch.equal(r1[0], r2[0]) and torch.equal(r1[1], r2[1]))
     sweep = {}
     cfgs = ((4096, 0, 20), (3072, 0, 20), (6144, 0, 20), (4096, 3, 20), (4096, 2, 20), (6144, 1, 20), (4096, 0, 0), (4096, 0, 40))
     for ang in (0.3, 0.8, 1.5):
