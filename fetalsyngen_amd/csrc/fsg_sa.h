@@ -1,7 +1,9 @@
 // fsg_sa.h -- what the slice-acquisition translation units share (fsg_slice_acq.hip: forward and adjoint;
 // fsg_slice_acq_bwd.hip: backward of the forward; fsg_slice_acq_adjoint_bwd.hip: backward of the adjoint): the kernel-argument
-// block, the LDS image of the PSF and of the per-axis tap products, the pixel-centre arithmetic, the argument checks and the
-// fixed-order reduction of the 12 transform sums.  Internal linkage: each unit has its own copy.
+// block, the LDS image of the PSF and of the per-axis tap products and its fill for any workgroup shape, the pixel-centre
+// arithmetic, the trilinear cell (corner weights, the eight corners in their one order, sa_tri8, the PSF coordinate of a snapped
+// voxel), the lever arms and the fixed-order reduction of the 12 transform sums with the size of its partials, and the argument
+// checks.  Internal linkage: each unit has its own copy.  The SA_* corner macros stay defined for the including unit.
 #pragma once
 #include "fsg_common.h"
 
@@ -45,20 +47,23 @@ __device__ __forceinline__ SaLds sa_lds_layout(float* base, const SaParams& P) {
   return L;
 }
 
-__device__ __forceinline__ void sa_fill_lds(const SaLds& L, const SaParams& P, const float* __restrict__ T) {
-  const int tid = threadIdx.y * SA_TILE + threadIdx.x;
+// tid: the thread's linear id in its workgroup of `nthreads` (16x16 blocks: sa_tid(); the 256-thread adjoint: threadIdx.x)
+__device__ __forceinline__ int sa_tid() { return threadIdx.y * SA_TILE + threadIdx.x; }
+
+__device__ __forceinline__ void sa_fill_lds(const SaLds& L, const SaParams& P, const float* __restrict__ T, int tid,
+                                            int nthreads) {
   const int np = P.pd * P.ph * P.pw;
-  for (int e = tid; e < np; e += SA_TILE * SA_TILE) L.psf[e] = P.psf[e];
+  for (int e = tid; e < np; e += nthreads) L.psf[e] = P.psf[e];
   // float * int in the reference == float * (float)int
-  for (int e = tid; e < 3 * P.pw; e += SA_TILE * SA_TILE) {
+  for (int e = tid; e < 3 * P.pw; e += nthreads) {
     const int a = e / P.pw, i = e - a * P.pw;
     L.tx[e] = T[a * 4 + 0] * (float)(i - P.pw / 2);
   }
-  for (int e = tid; e < 3 * P.ph; e += SA_TILE * SA_TILE) {
+  for (int e = tid; e < 3 * P.ph; e += nthreads) {
     const int a = e / P.ph, i = e - a * P.ph;
     L.ty[e] = T[a * 4 + 1] * (float)(i - P.ph / 2);
   }
-  for (int e = tid; e < 3 * P.pd; e += SA_TILE * SA_TILE) {
+  for (int e = tid; e < 3 * P.pd; e += nthreads) {
     const int a = e / P.pd, i = e - a * P.pd;
     L.tz[e] = T[a * 4 + 2] * (float)(i - P.pd / 2);
   }
@@ -84,6 +89,77 @@ __device__ __forceinline__ void sa_centre(const SaParams& P, const float* __rest
   xc = (float)((double)xc + (P.W - 1) / 2.);
   yc = (float)((double)yc + (P.H - 1) / 2.);
   zc = (float)((double)zc + (P.D - 1) / 2.);
+}
+
+// (The triple loop over the PSF taps stays written out in every kernel: walked through one shared function template taking the
+// body as a lambda, the compiler allocates registers differently -- other VGPR counts and occupancies in the adjoint and both
+// backward kernels, scratch in the LDS adjoint -- and the forward's interp_psf kernel measured 0.5 % slower.)
+
+// ---- the trilinear cell: corner weights, the eight corners in their fixed order, the PSF re-interpolated at a voxel ----
+// Weight factors of corner (A,B,C) along x, y, z; `wx, wy, wz` are the caller's fractions.
+#define SA_FX(A) ((A) ? wx : (1 - wx))
+#define SA_FY(B) ((B) ? wy : (1 - wy))
+#define SA_FZ(C) ((C) ? wz : (1 - wz))
+// M(offset, A, B, C) for the eight corners of a cell with strides (1, SY, SZ).  The order is part of the bit contract with the
+// float64 / fp32 restatements: every sum over the corners is written through this list.
+#define SA_CORNERS8(M, SY, SZ) \
+  M(0, 0, 0, 0) M(1, 1, 0, 0) M(SY, 0, 1, 0) M(SZ, 0, 0, 1) M(1 + SY, 1, 1, 0) M(1 + SZ, 1, 0, 1) M(SY + SZ, 0, 1, 1) \
+  M(SY + SZ + 1, 1, 1, 1)
+// One corner's term of d(trilinear sum)/d(position): the caller's `dx, dy, dz` gain -/+ (the other two factors) * t.
+#define SA_DCORNER(TVAL, A, B, C)                                    \
+  t = (TVAL);                                                        \
+  dx = (A) ? dx + SA_FY(B) * SA_FZ(C) * t : dx - SA_FY(B) * SA_FZ(C) * t; \
+  dy = (B) ? dy + SA_FX(A) * SA_FZ(C) * t : dy - SA_FX(A) * SA_FZ(C) * t; \
+  dz = (C) ? dz + SA_FX(A) * SA_FY(B) * t : dz - SA_FX(A) * SA_FY(B) * t;
+
+// trilinear sum over the cell at q (strides 1, sy, sz), eight terms added to 0 in the list's order
+__device__ __forceinline__ float sa_tri8(const float* q, int sy, int sz, float wx, float wy, float wz) {
+  float v = 0.f;
+#define SA_TRI_TERM(OFF, A, B, C) v += SA_FX(A) * SA_FY(B) * SA_FZ(C) * q[(OFF)];
+  SA_CORNERS8(SA_TRI_TERM, sy, sz)
+#undef SA_TRI_TERM
+  return v;
+}
+
+// interp_psf (slice_acq_cuda_kernel.cu:79-101): the PSF coordinate of the offset (dx, dy, dz) of a snapped voxel from the pixel
+// centre (the literal `2.` promotes to double), and -- once the caller has found it inside the PSF grid -- its cell in the LDS
+// image of the PSF with the fractions in it.  The range test stays with the caller because its two forms are NOT the same: the
+// backward units accept (`!(xp >= 0 && ... && xp < pw - 1 ...)`: a NaN coordinate is outside), the forward and the adjoint reject
+// (`xp < 0 || ...`: the reference's form, NaN goes on).
+__device__ __forceinline__ void sa_psf_coord(const SaParams& P, const float* __restrict__ T, float dx, float dy, float dz,
+                                             float& xp, float& yp, float& zp) {
+  xp = (float)((double)(T[0] * dx + T[4] * dy + T[8] * dz) + (P.pw - 1) / 2.);
+  yp = (float)((double)(T[1] * dx + T[5] * dy + T[9] * dz) + (P.ph - 1) / 2.);
+  zp = (float)((double)(T[2] * dx + T[6] * dy + T[10] * dz) + (P.pd - 1) / 2.);
+}
+struct SaPsfCell {
+  const float* q;
+  float wx, wy, wz;
+};
+__device__ __forceinline__ SaPsfCell sa_psf_cell(const SaLds& L, const SaParams& P, float xp, float yp, float zp) {
+  const float xf = floorf(xp), yf = floorf(yp), zf = floorf(zp);
+  return SaPsfCell{L.psf + (int)zf * (P.pw * P.ph) + (int)yf * P.pw + (int)xf, xp - xf, yp - yf, zp - zf};
+}
+
+// ---- the lever arms of the 12 transform sums (both backward units) ----
+// NEAREST_PSF: (dx, dy, dz) = d psf' / d (PSF coordinate) times the tap's factor; l = the rounded voxel relative to the volume
+// centre.  The PSF moves under a fixed voxel: rotation columns gain d * l, the translation loses d.
+__device__ __forceinline__ void sa_lever_nn(float (&g)[12], float dx, float dy, float dz, float lx, float ly, float lz) {
+  g[0] += dx * lx; g[1] += dy * lx; g[2] += dz * lx;
+  g[4] += dx * ly; g[5] += dy * ly; g[6] += dz * ly;
+  g[8] += dx * lz; g[9] += dy * lz; g[10] += dz * lz;
+  g[3] -= dx; g[7] -= dy; g[11] -= dz;
+}
+// LINEAR: (dx, dy, dz) = d (trilinear sample) / d (sampling position) times the tap's factor; l = pixel + translation + tap
+// offset in slice axes.
+__device__ __forceinline__ void sa_lever_lin(float (&g)[12], const float* __restrict__ T, float dx, float dy, float dz, float lx,
+                                             float ly, float lz) {
+  g[0] += dx * lx; g[1] += dx * ly; g[2] += dx * lz;
+  g[4] += dy * lx; g[5] += dy * ly; g[6] += dy * lz;
+  g[8] += dz * lx; g[9] += dz * ly; g[10] += dz * lz;
+  g[3] += dx * T[0] + dy * T[4] + dz * T[8];
+  g[7] += dx * T[1] + dy * T[5] + dz * T[9];
+  g[11] += dx * T[2] + dy * T[6] + dz * T[10];
 }
 
 // ---- the fixed-order reduction of the 12 transform sums, shared by the two backward units ----
@@ -136,6 +212,13 @@ inline int sa_check(const SaParams& P, size_t& lds, bool torch_mode) {
 
 inline dim3 sa_grid(const SaParams& P) {
   return dim3((unsigned)((P.w + SA_TILE - 1) / SA_TILE), (unsigned)((P.h + SA_TILE - 1) / SA_TILE), (unsigned)P.n);
+}
+
+// bytes of the tile partials of sa_fold12, one 12-float partial per workgroup of sa_grid (a multiple of 48, so what follows
+// them in a workspace stays 16-byte aligned)
+inline size_t sa_partial_bytes(int n, int h, int w) {
+  const size_t tiles = (size_t)((w + SA_TILE - 1) / SA_TILE) * (size_t)((h + SA_TILE - 1) / SA_TILE);
+  return (size_t)n * tiles * 12 * sizeof(float);
 }
 
 }  // namespace

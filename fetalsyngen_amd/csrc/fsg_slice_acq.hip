@@ -34,25 +34,12 @@ __device__ __forceinline__ float sa_direct_cost(const float* T, float wy) { retu
 // interp_psf branch (:79-101): PSF value at the snapped voxel, trilinear in the PSF grid.  false = outside.
 __device__ __forceinline__ bool sa_psf_at(const SaLds& L, const SaParams& P, const float* __restrict__ T, float dx,
                                           float dy, float dz, float& val) {
-  const float xp = (float)((double)(T[0] * dx + T[4] * dy + T[8] * dz) + (P.pw - 1) / 2.);
-  const float yp = (float)((double)(T[1] * dx + T[5] * dy + T[9] * dz) + (P.ph - 1) / 2.);
-  const float zp = (float)((double)(T[2] * dx + T[6] * dy + T[10] * dz) + (P.pd - 1) / 2.);
+  float xp, yp, zp;
+  sa_psf_coord(P, T, dx, dy, dz, xp, yp, zp);
   if (xp < 0 || yp < 0 || zp < 0 || xp >= (float)(P.pw - 1) || yp >= (float)(P.ph - 1) || zp >= (float)(P.pd - 1))
     return false;
-  const float xf = floorf(xp), yf = floorf(yp), zf = floorf(zp);
-  const float wx = xp - xf, wy = yp - yf, wz = zp - zf;
-  const int sy = P.pw, sz = P.pw * P.ph;
-  const float* q = L.psf + (int)zf * sz + (int)yf * sy + (int)xf;
-  float v = 0.f;
-  v += (1 - wx) * (1 - wy) * (1 - wz) * q[0];
-  v += wx * (1 - wy) * (1 - wz) * q[1];
-  v += (1 - wx) * wy * (1 - wz) * q[sy];
-  v += (1 - wx) * (1 - wy) * wz * q[sz];
-  v += wx * wy * (1 - wz) * q[1 + sy];
-  v += wx * (1 - wy) * wz * q[1 + sz];
-  v += (1 - wx) * wy * wz * q[sy + sz];
-  v += wx * wy * wz * q[sy + sz + 1];
-  val = v;
+  const SaPsfCell c = sa_psf_cell(L, P, xp, yp, zp);
+  val = sa_tri8(c.q, P.pw, P.pw * P.ph, c.wx, c.wy, c.wz);
   return true;
 }
 
@@ -67,7 +54,7 @@ __global__ __launch_bounds__(SA_TILE* SA_TILE) void sa_forward_kernel(SaParams P
   const int in = blockIdx.z;
   const float* __restrict__ T = P.tr + (size_t)in * 12;
   const SaLds L = sa_lds_layout(smem, P);
-  sa_fill_lds(L, P, T);
+  sa_fill_lds(L, P, T, sa_tid(), SA_TILE * SA_TILE);
   __syncthreads();
   const int ix = blockIdx.x * SA_TILE + threadIdx.x, iy = blockIdx.y * SA_TILE + threadIdx.y;
   if (ix >= P.w || iy >= P.h) return;
@@ -107,20 +94,13 @@ __global__ __launch_bounds__(SA_TILE* SA_TILE) void sa_forward_kernel(SaParams P
           const int iv = (int)zf * Sz + (int)yf * Sy + (int)xf;
           const float* __restrict__ q = vol + iv;
           float pw_;
-#define SA_CORNER(OFF, WEXPR)                     \
+#define SA_CORNER(OFF, A, B, C)                   \
   if (!VM || P.vmask[iv + (OFF)]) {               \
-    pw_ = (WEXPR) * pv;                           \
+    pw_ = SA_FX(A) * SA_FY(B) * SA_FZ(C) * pv;    \
     val += pw_ * q[(OFF)];                        \
     weight += pw_;                                \
   }
-          SA_CORNER(0, (1 - wx) * (1 - wy) * (1 - wz))
-          SA_CORNER(1, wx * (1 - wy) * (1 - wz))
-          SA_CORNER(Sy, (1 - wx) * wy * (1 - wz))
-          SA_CORNER(Sz, (1 - wx) * (1 - wy) * wz)
-          SA_CORNER(1 + Sy, wx * wy * (1 - wz))
-          SA_CORNER(1 + Sz, wx * (1 - wy) * wz)
-          SA_CORNER(Sy + Sz, (1 - wx) * wy * wz)
-          SA_CORNER(Sy + Sz + 1, wx * wy * wz)
+          SA_CORNERS8(SA_CORNER, Sy, Sz)
 #undef SA_CORNER
         }
       }
@@ -449,112 +429,10 @@ __global__ __launch_bounds__(256) void sa_forward_plate_kernel(SaParams P, const
 }
 
 // ---------------------------------------------------------------------------------------------------------
-// adjoint, CUDA-kernel semantics (:472-670): pass 1 = pixel weight, pass 2 = scatter with fp32 atomics.
-// ---------------------------------------------------------------------------------------------------------
-template <bool NN, bool VM>
-__global__ __launch_bounds__(SA_TILE* SA_TILE) void sa_adjoint_kernel(SaParams P, const float* __restrict__ slices,
-                                                                      float* __restrict__ vol,
-                                                                      float* __restrict__ vol_weight) {
-  extern __shared__ float smem[];
-  const int in = blockIdx.z;
-  const float* __restrict__ T = P.tr + (size_t)in * 12;
-  const SaLds L = sa_lds_layout(smem, P);
-  sa_fill_lds(L, P, T);
-  __syncthreads();
-  const int ix = blockIdx.x * SA_TILE + threadIdx.x, iy = blockIdx.y * SA_TILE + threadIdx.y;
-  if (ix >= P.w || iy >= P.h) return;
-  const size_t idx = ((size_t)(P.sid ? P.sid[in] : in) * P.h + iy) * P.w + ix;
-  if (P.smask && !P.smask[idx]) return;
-  const float s = slices[idx];
-  float xc, yc, zc;
-  sa_centre(P, T, ix, iy, xc, yc, zc);
-  const int Sy = P.W, Sz = P.H * P.W;
-  const float hx = (float)(P.W - 1), hy = (float)(P.H - 1), hz = (float)(P.D - 1);
-
-  float weight = 0.f;
-  int ip = 0;
-  for (int kz = 0; kz < P.pd; ++kz) {
-    const float zx = L.tz[kz], zy = L.tz[P.pd + kz], zz = L.tz[2 * P.pd + kz];
-    for (int ky = 0; ky < P.ph; ++ky) {
-      const float yx = L.ty[ky], yy = L.ty[P.ph + ky], yz = L.ty[2 * P.ph + ky];
-      for (int kx = 0; kx < P.pw; ++kx, ++ip) {
-        float pv = L.psf[ip];
-        if (pv == 0.f) continue;
-        const float x = xc + L.tx[kx] + yx + zx;
-        const float y = yc + L.tx[P.pw + kx] + yy + zy;
-        const float z = zc + L.tx[2 * P.pw + kx] + yz + zz;
-        if (x < 0 || y < 0 || z < 0 || x >= hx || y >= hy || z >= hz) continue;
-        if (NN && !sa_psf_at(L, P, T, roundf(x) - xc, roundf(y) - yc, roundf(z) - zc, pv)) continue;
-        weight += pv;
-      }
-    }
-  }
-  if (weight < 0.5f) return;  // border
-
-  ip = 0;
-  for (int kz = 0; kz < P.pd; ++kz) {
-    const float zx = L.tz[kz], zy = L.tz[P.pd + kz], zz = L.tz[2 * P.pd + kz];
-    for (int ky = 0; ky < P.ph; ++ky) {
-      const float yx = L.ty[ky], yy = L.ty[P.ph + ky], yz = L.ty[2 * P.ph + ky];
-      for (int kx = 0; kx < P.pw; ++kx, ++ip) {
-        float pv = L.psf[ip];
-        if (pv == 0.f) continue;
-        const float x = xc + L.tx[kx] + yx + zx;
-        const float y = yc + L.tx[P.pw + kx] + yy + zy;
-        const float z = zc + L.tx[2 * P.pw + kx] + yz + zz;
-        if (x < 0 || y < 0 || z < 0 || x >= hx || y >= hy || z >= hz) continue;
-        if (NN) {
-          const float xr = roundf(x), yr = roundf(y), zr = roundf(z);
-          if (!sa_psf_at(L, P, T, xr - xc, yr - yc, zr - zc, pv)) continue;
-          pv /= weight;
-          const int iv = (int)zr * Sz + (int)yr * Sy + (int)xr;
-          if (VM && !P.vmask[iv]) continue;
-          unsafeAtomicAdd(vol + iv, pv * s);
-          if (vol_weight) unsafeAtomicAdd(vol_weight + iv, pv);
-        } else {
-          const float xf = floorf(x), yf = floorf(y), zf = floorf(z);
-          const float wx = x - xf, wy = y - yf, wz = z - zf;
-          const int iv = (int)zf * Sz + (int)yf * Sy + (int)xf;
-          pv /= weight;
-          float pw_;
-#define SA_CORNER(OFF, WEXPR)                                            \
-  if (!VM || P.vmask[iv + (OFF)]) {                                      \
-    pw_ = (WEXPR) * pv;                                                  \
-    unsafeAtomicAdd(vol + iv + (OFF), pw_ * s);                          \
-    if (vol_weight) unsafeAtomicAdd(vol_weight + iv + (OFF), pw_);       \
-  }
-          SA_CORNER(0, (1 - wx) * (1 - wy) * (1 - wz))
-          SA_CORNER(1, wx * (1 - wy) * (1 - wz))
-          SA_CORNER(Sy, (1 - wx) * wy * (1 - wz))
-          SA_CORNER(Sz, (1 - wx) * (1 - wy) * wz)
-          SA_CORNER(1 + Sy, wx * wy * (1 - wz))
-          SA_CORNER(1 + Sz, wx * (1 - wy) * wz)
-          SA_CORNER(Sy + Sz, (1 - wx) * wy * wz)
-          SA_CORNER(Sy + Sz + 1, wx * wy * wz)
-#undef SA_CORNER
-        }
-      }
-    }
-  }
-}
-
-
-// ---------------------------------------------------------------------------------------------------------
-// adjoint, interp_psf = true, with on-chip pre-summation.
-//
-// The scatter form issues two fp32 atomics per (pixel, tap): 7e9 of them for a 200-slice reconstruction at
-// 384^3, and global float atomics execute memory-side at a fixed byte rate (MI355X_MICROARCH.md, "Global float
-// atomics": ~1.3 TB/s for well-shaped wave instructions, 17x less for 64 lanes in 64 rows) -- the direct kernel
-// above spends 3/4 of its time there.  A tile of neighbouring pixels revisits the same voxels many times (taps
-// are 1 voxel apart, pixels 0.5-2 voxels apart), so this kernel sums a tile's contributions in LDS first:
-//   * workgroup = T x T pixel tile of one slice (T = 16: one pixel per thread; T = 8: wave g of the workgroup
-//     takes the PSF rows ky = g mod 4 of every pixel of the tile);
-//   * the PSF is walked in chunks of `zc` planes; per chunk the axis-aligned bounding box of the voxels the
-//     tile can reach is derived from the slice transform; if it fits the LDS accumulator (`cap` cells for
-//     value and weight) contributions go to LDS with ds_add_f32, and the box is flushed with one global
-//     atomic per touched cell in row order (contiguous x runs); otherwise the chunk falls back to direct
-//     global atomics.  A cell index outside the box (cannot happen by construction) also falls back.
-// Same sums as the direct kernel up to fp32 summation order (which is nondeterministic there as well).
+// adjoint, CUDA-kernel semantics (:472-670): pass 1 = pixel weight, pass 2 = scatter.  Two kernels -- the direct scatter
+// (sa_adjoint_kernel) and, for interp_psf, the one that sums a tile in LDS first (sa_adjoint_nn_lds_kernel) -- each written
+// once and instantiated with one of two accumulators, SaSumF32 (fp32 atomics: fsg_slice_acq_adjoint_f32) and SaSumFix (64-bit
+// fixed point: fsg_slice_acq_adjoint_det_f32).  First the pieces they are built from.
 // ---------------------------------------------------------------------------------------------------------
 // roundf(x) for 0 <= x < 2^23 in two instructions: floor(x + pred(0.5)).  Ties n + 0.5 still reach n + 1 (the sum rounds up to
 // the integer), and the one value below a tie, n + 0.5 - ulp, stays at n (with + 0.5 the sum for 0.5 - 2^-25 would round to 1).
@@ -582,215 +460,7 @@ __device__ __forceinline__ bool sa_psf_at_fast(const SaLds& L, const SaParams& P
   return true;
 }
 
-template <int T_, bool VM>
-__global__ __launch_bounds__(256) void sa_adjoint_nn_lds_kernel(SaParams P, const float* __restrict__ slices,
-                                                                float* __restrict__ vol, float* __restrict__ vol_weight,
-                                                                int zc, int cap) {
-  constexpr int NPIX = T_ * T_, G = 256 / NPIX;
-  extern __shared__ float smem[];
-  const int in = blockIdx.z;
-  const float* __restrict__ T = P.tr + (size_t)in * 12;
-  const SaLds L = sa_lds_layout(smem, P);
-  float* part = L.tz + 3 * P.pd;  // [256] partial pixel weights
-  float* accv = part + 256;
-  float* accw = accv + cap;
-  {
-    // sa_fill_lds with a 256-thread linear id
-    const int tid = threadIdx.x, np = P.pd * P.ph * P.pw;
-    for (int e = tid; e < np; e += 256) L.psf[e] = P.psf[e];
-    for (int e = tid; e < 3 * P.pw; e += 256) { const int a = e / P.pw, i = e - a * P.pw; L.tx[e] = T[a * 4 + 0] * (float)(i - P.pw / 2); }
-    for (int e = tid; e < 3 * P.ph; e += 256) { const int a = e / P.ph, i = e - a * P.ph; L.ty[e] = T[a * 4 + 1] * (float)(i - P.ph / 2); }
-    for (int e = tid; e < 3 * P.pd; e += 256) { const int a = e / P.pd, i = e - a * P.pd; L.tz[e] = T[a * 4 + 2] * (float)(i - P.pd / 2); }
-  }
-  __syncthreads();
-  const int tid = threadIdx.x;
-  const int p = tid % NPIX, g = tid / NPIX;
-  const int ix0 = blockIdx.x * T_, iy0 = blockIdx.y * T_;
-  const int ix = ix0 + p % T_, iy = iy0 + p / T_;
-  bool live = ix < P.w && iy < P.h;
-  const size_t idx = ((size_t)(P.sid ? P.sid[in] : in) * P.h + (live ? iy : 0)) * P.w + (live ? ix : 0);
-  if (live && P.smask && !P.smask[idx]) live = false;
-  const float s = live ? slices[idx] : 0.f;
-  float xc, yc, zc_;
-  sa_centre(P, T, ix, iy, xc, yc, zc_);
-  const int Sy = P.W, Sz = P.H * P.W;
-  const float hx = (float)(P.W - 1), hy = (float)(P.H - 1), hz = (float)(P.D - 1);
-
-  // tile extent in slice coordinates
-  const int ixl = ix0, ixh = min(ix0 + T_ - 1, P.w - 1), iyl = iy0, iyh = min(iy0 + T_ - 1, P.h - 1);
-  const float alo = ((float)ixl - (float)(P.w - 1) * 0.5f) * P.res + T[3] - (float)(P.pw / 2);
-  const float ahi = ((float)ixh - (float)(P.w - 1) * 0.5f) * P.res + T[3] + (float)(P.pw - 1 - P.pw / 2);
-  const float blo = ((float)iyl - (float)(P.h - 1) * 0.5f) * P.res + T[7] - (float)(P.ph / 2);
-  const float bhi = ((float)iyh - (float)(P.h - 1) * 0.5f) * P.res + T[7] + (float)(P.ph - 1 - P.ph / 2);
-  const int dimv[3] = {P.W, P.H, P.D};
-  // axis-aligned box of the positions the tile's pixels can reach through PSF planes [clo, chi] (slice coordinates), clipped to
-  // the volume: origin o, extent b; returns whether the unclipped box lies inside the volume by the fp32 slack of the position
-  // sums -- then no tap of the tile needs the per-tap inside test (uniform)
-  auto reach = [&](float clo, float chi, int* o, int* b) -> bool {
-    bool inside = true;
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-      const float r0 = T[a * 4], r1 = T[a * 4 + 1], r2 = T[a * 4 + 2];
-      const float off = (float)(dimv[a] - 1) * 0.5f;
-      const float mn = off + fminf(r0 * alo, r0 * ahi) + fminf(r1 * blo, r1 * bhi) + fminf(r2 * clo, r2 * chi);
-      const float mx = off + fmaxf(r0 * alo, r0 * ahi) + fmaxf(r1 * blo, r1 * bhi) + fmaxf(r2 * clo, r2 * chi);
-      // voxel = round(position): [floor(mn + .5), floor(mx + .5)], widened by the slack
-      const int lo = max((int)floorf(mn + 0.5f - 2e-3f), 0), hi = min((int)floorf(mx + 0.5f + 2e-3f), dimv[a] - 1);
-      o[a] = lo;
-      b[a] = hi - lo + 1;
-      inside = inside && mn - 2e-3f >= 0.f && mx + 2e-3f < (float)(dimv[a] - 1);
-    }
-    return inside;
-  };
-  int o_all[3], b_all[3];
-  const bool inside_all = reach(T[11] + (float)(0 - P.pd / 2), T[11] + (float)(P.pd - 1 - P.pd / 2), o_all, b_all);
-
-  // pass 1: pixel weight (slice_acq_cuda_kernel.cu:515-560), PSF rows split over the G waves of a pixel
-  float wsum = 0.f;
-  if (live) {
-    for (int kz = 0; kz < P.pd; ++kz) {
-      const float zx = L.tz[kz], zy = L.tz[P.pd + kz], zz = L.tz[2 * P.pd + kz];
-      for (int ky = g; ky < P.ph; ky += G) {
-        const float yx = L.ty[ky], yy = L.ty[P.ph + ky], yz = L.ty[2 * P.ph + ky];
-        const int ip0 = (kz * P.ph + ky) * P.pw;
-        for (int kx = 0; kx < P.pw; ++kx) {
-          float pv = L.psf[ip0 + kx];
-          if (pv == 0.f) continue;
-          const float x = xc + L.tx[kx] + yx + zx;
-          const float y = yc + L.tx[P.pw + kx] + yy + zy;
-          const float z = zc_ + L.tx[2 * P.pw + kx] + yz + zz;
-          if (!inside_all && (x < 0 || y < 0 || z < 0 || x >= hx || y >= hy || z >= hz)) continue;
-          if (!sa_psf_at_fast(L, P, T, sa_round_pos(x) - xc, sa_round_pos(y) - yc, sa_round_pos(z) - zc_, pv)) continue;
-          wsum += pv;
-        }
-      }
-    }
-  }
-  if (G > 1) {
-    part[tid] = wsum;
-    __syncthreads();
-    wsum = 0.f;
-#pragma unroll
-    for (int q = 0; q < G; ++q) wsum += part[q * NPIX + p];
-  }
-  if (wsum < 0.5f) live = false;
-  const float inv = live ? 1.f / wsum : 0.f;
-
-  // LDS cell layout: a chunk of PSF planes of a pixel tile is an oblique plate in the volume, whose axis-aligned
-  // bounding box can hold 10x more cells than the plate.  Cells are therefore indexed by the two volume axes (u, v)
-  // other than the one the slice normal leans on most (a), plus the offset k of the a-coordinate from the plate's
-  // mid-plane at (u, v): K = plate thickness along a, a few cells.  x is kept the fastest index for the flush.
-  const float n0 = T[2], n1 = T[6], n2 = T[10];  // slice normal in volume axes (x, y, z)
-  const int A = (fabsf(n0) >= fabsf(n1) && fabsf(n0) >= fabsf(n2)) ? 0 : (fabsf(n1) >= fabsf(n2) ? 1 : 2);
-  const int U = A == 0 ? 1 : 0, V = A == 2 ? 1 : 2;  // U < V, so x is U whenever x is not the lean axis
-  const float nA = A == 0 ? n0 : (A == 1 ? n1 : n2), nU = U == 0 ? n0 : n1, nV = V == 1 ? n1 : n2;
-  const float inv_na = 1.f / nA, slope = (fabsf(nU) + fabsf(nV)) * fabsf(inv_na);
-  // tile centre in slice coordinates -> a point of the mid-plane (per chunk: its z)
-  const float amid = 0.5f * (alo + ahi), bmid = 0.5f * (blo + bhi);
-
-  for (int kz0 = 0; kz0 < P.pd; kz0 += zc) {
-    const int kz1 = min(kz0 + zc, P.pd);
-    const float clo = T[11] + (float)(kz0 - P.pd / 2), chi = T[11] + (float)(kz1 - 1 - P.pd / 2);
-    int o[3], b[3];
-    const bool inside = reach(clo, chi, o, b);
-    if (b[0] <= 0 || b[1] <= 0 || b[2] <= 0) continue;  // the chunk cannot reach the volume (uniform)
-    const float cmid = 0.5f * (clo + chi);
-    float pm[3];  // mid-plane point in volume coordinates
-#pragma unroll
-    for (int a = 0; a < 3; ++a)
-      pm[a] = (float)(dimv[a] - 1) * 0.5f + T[a * 4] * amid + T[a * 4 + 1] * bmid + T[a * 4 + 2] * cmid;
-    // thickness of the plate along A: PSF planes (kz1-1-kz0) / |nA|, voxel rounding 1 + slope, plus one cell of slack
-    const int K = (int)ceilf(((float)(kz1 - 1 - kz0) + 1.f) * fabsf(inv_na) + slope + 1.f) + 1;
-    const float hb = 0.5f * (float)K;
-    const int bu = b[U], bv = b[V];
-    const long long cells = (long long)bu * bv * K;
-    const bool use_lds = cells <= (long long)cap;
-    // index = ((cv * K + k) * bu + cu) when x is U (x fastest); = ((cv * bu + cu) * K + k) when x is the lean axis
-    const bool xlean = A == 0;
-    if (use_lds) {
-      for (int c = tid; c < (int)cells; c += 256) { accv[c] = 0.f; accw[c] = 0.f; }
-      __syncthreads();
-    }
-    if (live) {
-      for (int kz = kz0; kz < kz1; ++kz) {
-        const float zx = L.tz[kz], zy = L.tz[P.pd + kz], zz = L.tz[2 * P.pd + kz];
-        for (int ky = g; ky < P.ph; ky += G) {
-          const float yx = L.ty[ky], yy = L.ty[P.ph + ky], yz = L.ty[2 * P.ph + ky];
-          const int ip0 = (kz * P.ph + ky) * P.pw;
-          for (int kx = 0; kx < P.pw; ++kx) {
-            float pv = L.psf[ip0 + kx];
-            if (pv == 0.f) continue;
-            const float x = xc + L.tx[kx] + yx + zx;
-            const float y = yc + L.tx[P.pw + kx] + yy + zy;
-            const float z = zc_ + L.tx[2 * P.pw + kx] + yz + zz;
-            if (!inside && (x < 0 || y < 0 || z < 0 || x >= hx || y >= hy || z >= hz)) continue;
-            const float xr = sa_round_pos(x), yr = sa_round_pos(y), zr = sa_round_pos(z);
-            if (!sa_psf_at_fast(L, P, T, xr - xc, yr - yc, zr - zc_, pv)) continue;
-            pv *= inv;
-            const int vv[3] = {(int)xr, (int)yr, (int)zr};
-            const int iv = vv[2] * Sz + vv[1] * Sy + vv[0];
-            if (VM && !P.vmask[iv]) continue;
-            bool done = false;
-            if (use_lds) {
-              const int cu = vv[U] - o[U], cv = vv[V] - o[V];
-              const float fu = (float)vv[U] - pm[U], fv = (float)vv[V] - pm[V];
-              const int base = (int)floorf(pm[A] - (nU * fu + nV * fv) * inv_na - hb);
-              const int k = vv[A] - base;
-              if ((unsigned)cu < (unsigned)bu && (unsigned)cv < (unsigned)bv && (unsigned)k < (unsigned)K) {
-                const int c = xlean ? (cv * bu + cu) * K + k : (cv * K + k) * bu + cu;
-                atomicAdd(&accv[c], pv * s);
-                atomicAdd(&accw[c], pv);
-                done = true;
-              }
-            }
-            if (!done) {
-              unsafeAtomicAdd(vol + iv, pv * s);
-              if (vol_weight) unsafeAtomicAdd(vol_weight + iv, pv);
-            }
-          }
-        }
-      }
-    }
-    if (use_lds) {
-      __syncthreads();
-      for (int c = tid; c < (int)cells; c += 256) {
-        const float wv = accw[c];
-        if (wv == 0.f) continue;
-        int cu, cv, k;
-        if (xlean) { k = c % K; const int r = c / K; cu = r % bu; cv = r / bu; }
-        else { cu = c % bu; const int r = c / bu; k = r % K; cv = r / K; }
-        int vv[3];
-        vv[U] = cu + o[U];
-        vv[V] = cv + o[V];
-        const float fu = (float)vv[U] - pm[U], fv = (float)vv[V] - pm[V];
-        vv[A] = (int)floorf(pm[A] - (nU * fu + nV * fv) * inv_na - hb) + k;
-        const int iv = vv[2] * Sz + vv[1] * Sy + vv[0];
-        unsafeAtomicAdd(vol + iv, accv[c]);
-        if (vol_weight) unsafeAtomicAdd(vol_weight + iv, wv);
-      }
-      __syncthreads();
-    }
-  }
-}
-
-// ---------------------------------------------------------------------------------------------------------
-// adjoint, CUDA-kernel semantics, deterministic accumulation (fsg_slice_acq_adjoint_det_f32; the rule is stated in
-// include/fsg_hip.h).  Sibling kernels of the two above, so that the fp32-atomic kernels stay what they are:
-//   * a contribution is formed by the same fp32 operations as in sa_adjoint_nn_lds_kernel (sa_round_pos,
-//     sa_psf_at_fast, pv * (1 / wsum)) in BOTH kernels here -- the float direct kernel's sa_psf_at / division differ
-//     from those in the last bit, which fp32 order noise hides there and nothing would hide here;
-//   * it is quantised once to a multiple of 2^-F, F = 72 (sa_fix2), and added as an integer of two 64-bit limbs, the high
-//     one counting 2^-32 and the low one 2^-72: ds_add_u64 in LDS, global_atomic_add_x2 in the workspace, each limb summed
-//     on its own and the carry resolved at the end.  Integer sums do not depend on their order, so tile size, chunking,
-//     the LDS / direct choice per chunk and the scheduling of workgroups all give the same accumulators.  (One limb at
-//     2^-32 is not enough: equalisation divides by weights that may be a few quanta, see DESIGN section 17.);
-//   * the per-pixel weight of pass 1 is summed in fixed point too (each tap's PSF value quantised to 2^-32, integer partials
-//     over the waves of an 8x8 tile, one conversion), so `wsum`, its 0.5 cut and 1 / wsum do not depend on the tile either;
-//   * sa_det_finalize_kernel converts every accumulator with one rounding.
-// Cells are 32 B (value and weight, two limbs each), so the LDS accumulator holds at most SA_DET_CAP_MAX cells; the dynamic
-// LDS prefix (PSF and tap products, an odd number of floats for some PSFs) is rounded up to 8 bytes before the 64-bit arrays.
-// No address depends on a slice value: a non-finite value gives an unspecified sum, never a fault.
-// ---------------------------------------------------------------------------------------------------------
+// ---- fixed point: the quantisers and the two-limb integer of the deterministic accumulator (SaSumFix below) ----
 typedef unsigned long long sa_u64;
 constexpr int SA_DET_CAP_MAX = 4096;  // 128 KiB of cells + <= 19 KiB of prefix and partials, inside the 160 KiB of a CU
 constexpr int SA_DET_HI_BITS = FSG_SA_DET_FRAC_BITS - FSG_SA_DET_LIMB_BITS;  // the high limb counts 2^-32
@@ -836,16 +506,132 @@ __device__ __forceinline__ float sa_unfix2(long long hi, long long lo, int ex) {
   return neg ? -f : f;
 }
 
-template <bool NN, bool VM>
-__global__ __launch_bounds__(SA_TILE* SA_TILE) void sa_adjoint_det_kernel(SaParams P, const float* __restrict__ slices,
-                                                                          sa_u64* __restrict__ acc, int limbs,
-                                                                          double kval) {
-  // acc: `limbs` (2: value only, 4: value and weight) 64-bit words per voxel
+// ---------------------------------------------------------------------------------------------------------
+// The accumulator policies.  A policy holds its own destination (a kernel builds it from its arguments, the host-side launch
+// from the entry point's) and states the five things in which the fp32-atomic adjoint and the deterministic one differ --
+// nothing else does:
+//   * the pixel weight of pass 1: its type `wacc`, how a tap's PSF value enters it (`wadd`) and how it becomes the fp32 wsum;
+//   * the LDS cell (`Cells`, `lds_part` / `lds_cells`: what follows the PSF and tap products in dynamic LDS);
+//   * the add: one contribution in the accumulator's own form (`term`, made once whether it then goes to LDS or to memory)
+//     and `lds_add` / `global_add`; * the test for a touched cell in the flush (`lds_touched`); * the destination (`flush`).
+// Two traits choose the arithmetic of the DIRECT kernel: FAST_PSF (sa_round_pos + sa_psf_at_fast, not roundf + sa_psf_at)
+// and MUL_INV (pv * (1 / weight), not pv / weight).  The LDS kernel uses the fast forms with either policy, as it always did.
+//
+// SaSumF32 is the arithmetic of the fp32 kernels as they were, untouched: ds_add_f32 into split value / weight arrays, a cell
+// flushed when its weight is not 0, unsafeAtomicAdd to the volume, and in the direct kernel the reference's roundf, the
+// double-promoting sa_psf_at and the division.  Those differ from the fast forms in the last bit, which fp32 order noise hides
+// there; so the float direct kernel is only within tolerance of the float LDS kernel, today as before.
+//
+// SaSumFix (fsg_slice_acq_adjoint_det_f32; the rule is stated in include/fsg_hip.h):
+//   * a contribution is formed by the same fp32 operations as in the LDS kernel (sa_round_pos, sa_psf_at_fast, pv * (1 / wsum))
+//     in BOTH kernels -- nothing would hide a last-bit difference here;
+//   * it is quantised once to a multiple of 2^-F, F = 72 (sa_fix2), and added as an integer of two 64-bit limbs, the high
+//     one counting 2^-32 and the low one 2^-72: ds_add_u64 in LDS, global_atomic_add_x2 in the workspace, each limb summed
+//     on its own and the carry resolved at the end.  Integer sums do not depend on their order, so tile size, chunking,
+//     the LDS / direct choice per chunk and the scheduling of workgroups all give the same accumulators.  (One limb at
+//     2^-32 is not enough: equalisation divides by weights that may be a few quanta, see DESIGN section 17.);
+//   * the per-pixel weight of pass 1 is summed in fixed point too (each tap's PSF value quantised to 2^-32, integer partials
+//     over the waves of an 8x8 tile, one conversion), so `wsum`, its 0.5 cut and 1 / wsum do not depend on the tile either;
+//   * sa_det_finalize_kernel converts every accumulator with one rounding.
+// Its cells are 32 B (value and weight, two limbs each), so the LDS accumulator holds at most SA_DET_CAP_MAX cells; the dynamic
+// LDS prefix (PSF and tap products, an odd number of floats for some PSFs) is rounded up to 8 bytes before the 64-bit arrays.
+// No address depends on a slice value: a non-finite value gives an unspecified sum, never a fault.
+// ---------------------------------------------------------------------------------------------------------
+constexpr int SA_CAP_TUNE_MAX = 18432;  // what fsg_slice_acq_set_tuning admits
+
+struct SaSumF32 {
+  float* __restrict__ vol;
+  float* __restrict__ vol_weight;  // or null
+  static constexpr bool FAST_PSF = false, MUL_INV = false;
+  static constexpr int CAP_MAX = SA_CAP_TUNE_MAX, CAP_GROW = 12288, CELL_WORDS = 2;
+  typedef float wacc;
+  static __device__ __forceinline__ void wadd(wacc& w, float pv) { w += pv; }
+  static __device__ __forceinline__ float wsum(wacc w) { return w; }
+  struct Cells { float *v, *w; };  // split arrays of `cap` floats
+  static __device__ __forceinline__ wacc* lds_part(float* smem, int npre) { return smem + npre; }
+  static __device__ __forceinline__ Cells lds_cells(wacc* part, int cap) { return Cells{part + 256, part + 256 + cap}; }
+  __device__ __forceinline__ void lds_zero(const Cells& a, int n, int tid) const {
+    for (int c = tid; c < n; c += 256) { a.v[c] = 0.f; a.w[c] = 0.f; }
+  }
+  struct Term { float v, w; };  // one contribution: value and weight
+  __device__ __forceinline__ Term term(float pv, float s) const { return Term{pv * s, pv}; }
+  __device__ __forceinline__ void lds_add(const Cells& a, int c, const Term& t) const {
+    atomicAdd(&a.v[c], t.v);
+    atomicAdd(&a.w[c], t.w);
+  }
+  __device__ __forceinline__ bool lds_touched(const Cells& a, int c) const { return !(a.w[c] == 0.f); }
+  __device__ __forceinline__ void flush(const Cells& a, int c, int iv) const {
+    unsafeAtomicAdd(vol + iv, a.v[c]);
+    if (vol_weight) unsafeAtomicAdd(vol_weight + iv, a.w[c]);
+  }
+  __device__ __forceinline__ void global_add(int iv, const Term& t) const {
+    unsafeAtomicAdd(vol + iv, t.v);
+    if (vol_weight) unsafeAtomicAdd(vol_weight + iv, t.w);
+  }
+};
+
+struct SaSumFix {
+  sa_u64* __restrict__ acc;  // `limbs` (2: value only, 4: value and weight) 64-bit words per voxel
+  int limbs;
+  double kval;
+  static constexpr bool FAST_PSF = true, MUL_INV = true;
+  static constexpr int CAP_MAX = SA_DET_CAP_MAX, CAP_GROW = SA_DET_CAP_MAX, CELL_WORDS = 4;
+  typedef long long wacc;  // counts 2^-32: the same integer for a pixel however its taps are split over waves
+  static __device__ __forceinline__ void wadd(wacc& w, float pv) { w += (long long)sa_fix(pv, SA_DET_ONE); }
+  static __device__ __forceinline__ float wsum(wacc w) { return sa_unfix(w, (float)(1.0 / SA_DET_ONE)); }
+  typedef sa_u64* Cells;  // [cap] cells of {value hi, value lo, weight hi, weight lo}
+  static __device__ __forceinline__ wacc* lds_part(float*, int npre) {
+    extern __shared__ __align__(16) sa_u64 smem64[];  // the same dynamic LDS; raises its alignment to that of the cells
+    return reinterpret_cast<wacc*>(smem64 + ((npre + 1) >> 1));  // the prefix in 8-byte units, rounded up
+  }
+  static __device__ __forceinline__ Cells lds_cells(wacc* part, int) { return reinterpret_cast<sa_u64*>(part) + 256; }
+  // (cap <= SA_DET_CAP_MAX: 4 * cells and the limb indices stay far inside int)
+  __device__ __forceinline__ void lds_zero(Cells a, int n, int tid) const {
+    for (int c = tid; c < 4 * n; c += 256) a[c] = 0;
+  }
+  struct Term { sa_q2 v, w; };  // one contribution, quantised once whichever way it goes
+  __device__ __forceinline__ Term term(float pv, float s) const {
+    return Term{sa_fix2(pv * s, kval), sa_fix2(pv, SA_DET_ONE)};
+  }
+  __device__ __forceinline__ void lds_add(Cells a, int c, const Term& t) const {
+    sa_add2(a + 4 * c, t.v);
+    sa_add2(a + 4 * c + 2, t.w);
+  }
+  // untouched, or sums of zero: nothing to add
+  __device__ __forceinline__ bool lds_touched(Cells a, int c) const {
+    return (a[4 * c] | a[4 * c + 1] | a[4 * c + 2] | a[4 * c + 3]) != 0;
+  }
+  __device__ __forceinline__ void flush(Cells a, int c, int iv) const {
+    sa_u64* cell = acc + (size_t)iv * limbs;
+    sa_add2(cell, sa_q2{a[4 * c], a[4 * c + 1]});
+    if (limbs == 4) sa_add2(cell + 2, sa_q2{a[4 * c + 2], a[4 * c + 3]});
+  }
+  __device__ __forceinline__ void global_add(int iv, const Term& t) const {
+    sa_u64* cell = acc + (size_t)iv * limbs;
+    sa_add2(cell, t.v);
+    if (limbs == 4) sa_add2(cell + 2, t.w);
+  }
+};
+
+template <bool FAST>
+__device__ __forceinline__ float sa_snap(float x) { return FAST ? sa_round_pos(x) : roundf(x); }
+template <bool FAST>
+__device__ __forceinline__ bool sa_psf_snapped(const SaLds& L, const SaParams& P, const float* __restrict__ T, float dx, float dy,
+                                               float dz, float& val) {
+  return FAST ? sa_psf_at_fast(L, P, T, dx, dy, dz, val) : sa_psf_at(L, P, T, dx, dy, dz, val);
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// adjoint, direct scatter: one global atomic (pair) per (pixel, tap) and corner.  NN = interp_psf.
+// ---------------------------------------------------------------------------------------------------------
+template <bool NN, bool VM, class Sum>
+__device__ __forceinline__ void sa_adjoint_body(const SaParams& P, const float* __restrict__ slices, const Sum sum) {
+  constexpr bool F = Sum::FAST_PSF;
   extern __shared__ float smem[];
   const int in = blockIdx.z;
   const float* __restrict__ T = P.tr + (size_t)in * 12;
   const SaLds L = sa_lds_layout(smem, P);
-  sa_fill_lds(L, P, T);
+  sa_fill_lds(L, P, T, sa_tid(), SA_TILE * SA_TILE);
   __syncthreads();
   const int ix = blockIdx.x * SA_TILE + threadIdx.x, iy = blockIdx.y * SA_TILE + threadIdx.y;
   if (ix >= P.w || iy >= P.h) return;
@@ -857,7 +643,7 @@ __global__ __launch_bounds__(SA_TILE* SA_TILE) void sa_adjoint_det_kernel(SaPara
   const int Sy = P.W, Sz = P.H * P.W;
   const float hx = (float)(P.W - 1), hy = (float)(P.H - 1), hz = (float)(P.D - 1);
 
-  long long wq = 0;
+  typename Sum::wacc wq = 0;
   int ip = 0;
   for (int kz = 0; kz < P.pd; ++kz) {
     const float zx = L.tz[kz], zy = L.tz[P.pd + kz], zz = L.tz[2 * P.pd + kz];
@@ -870,14 +656,14 @@ __global__ __launch_bounds__(SA_TILE* SA_TILE) void sa_adjoint_det_kernel(SaPara
         const float y = yc + L.tx[P.pw + kx] + yy + zy;
         const float z = zc + L.tx[2 * P.pw + kx] + yz + zz;
         if (x < 0 || y < 0 || z < 0 || x >= hx || y >= hy || z >= hz) continue;
-        if (NN && !sa_psf_at_fast(L, P, T, sa_round_pos(x) - xc, sa_round_pos(y) - yc, sa_round_pos(z) - zc, pv)) continue;
-        wq += (long long)sa_fix(pv, SA_DET_ONE);
+        if (NN && !sa_psf_snapped<F>(L, P, T, sa_snap<F>(x) - xc, sa_snap<F>(y) - yc, sa_snap<F>(z) - zc, pv)) continue;
+        Sum::wadd(wq, pv);
       }
     }
   }
-  const float weight = sa_unfix(wq, (float)(1.0 / SA_DET_ONE));
+  const float weight = Sum::wsum(wq);
   if (weight < 0.5f) return;  // border
-  const float inv = 1.f / weight;
+  const float norm = Sum::MUL_INV ? 1.f / weight : weight;
 
   ip = 0;
   for (int kz = 0; kz < P.pd; ++kz) {
@@ -892,35 +678,20 @@ __global__ __launch_bounds__(SA_TILE* SA_TILE) void sa_adjoint_det_kernel(SaPara
         const float z = zc + L.tx[2 * P.pw + kx] + yz + zz;
         if (x < 0 || y < 0 || z < 0 || x >= hx || y >= hy || z >= hz) continue;
         if (NN) {
-          const float xr = sa_round_pos(x), yr = sa_round_pos(y), zr = sa_round_pos(z);
-          if (!sa_psf_at_fast(L, P, T, xr - xc, yr - yc, zr - zc, pv)) continue;
-          pv *= inv;
+          const float xr = sa_snap<F>(x), yr = sa_snap<F>(y), zr = sa_snap<F>(z);
+          if (!sa_psf_snapped<F>(L, P, T, xr - xc, yr - yc, zr - zc, pv)) continue;
+          pv = Sum::MUL_INV ? pv * norm : pv / norm;
           const int iv = (int)zr * Sz + (int)yr * Sy + (int)xr;
           if (VM && !P.vmask[iv]) continue;
-          sa_u64* cell = acc + (size_t)iv * limbs;
-          sa_add2(cell, sa_fix2(pv * s, kval));
-          if (limbs == 4) sa_add2(cell + 2, sa_fix2(pv, SA_DET_ONE));
+          sum.global_add(iv, sum.term(pv, s));
         } else {
           const float xf = floorf(x), yf = floorf(y), zf = floorf(z);
           const float wx = x - xf, wy = y - yf, wz = z - zf;
           const int iv = (int)zf * Sz + (int)yf * Sy + (int)xf;
-          pv *= inv;
-          float pw_;
-#define SA_CORNER(OFF, WEXPR)                                                  \
-  if (!VM || P.vmask[iv + (OFF)]) {                                            \
-    pw_ = (WEXPR) * pv;                                                        \
-    sa_u64* cell = acc + (size_t)(iv + (OFF)) * limbs;                         \
-    sa_add2(cell, sa_fix2(pw_ * s, kval));                                     \
-    if (limbs == 4) sa_add2(cell + 2, sa_fix2(pw_, SA_DET_ONE));               \
-  }
-          SA_CORNER(0, (1 - wx) * (1 - wy) * (1 - wz))
-          SA_CORNER(1, wx * (1 - wy) * (1 - wz))
-          SA_CORNER(Sy, (1 - wx) * wy * (1 - wz))
-          SA_CORNER(Sz, (1 - wx) * (1 - wy) * wz)
-          SA_CORNER(1 + Sy, wx * wy * (1 - wz))
-          SA_CORNER(1 + Sz, wx * (1 - wy) * wz)
-          SA_CORNER(Sy + Sz, (1 - wx) * wy * wz)
-          SA_CORNER(Sy + Sz + 1, wx * wy * wz)
+          pv = Sum::MUL_INV ? pv * norm : pv / norm;
+#define SA_CORNER(OFF, A, B, C) \
+  if (!VM || P.vmask[iv + (OFF)]) sum.global_add(iv + (OFF), sum.term(SA_FX(A) * SA_FY(B) * SA_FZ(C) * pv, s));
+          SA_CORNERS8(SA_CORNER, Sy, Sz)
 #undef SA_CORNER
         }
       }
@@ -928,27 +699,35 @@ __global__ __launch_bounds__(SA_TILE* SA_TILE) void sa_adjoint_det_kernel(SaPara
   }
 }
 
-// sa_adjoint_nn_lds_kernel with 64-bit fixed-point cells: the tile / chunk / plate geometry is that kernel's, line by line.
-template <int T_, bool VM>
-__global__ __launch_bounds__(256) void sa_adjoint_nn_lds_det_kernel(SaParams P, const float* __restrict__ slices,
-                                                                    sa_u64* __restrict__ acc, int limbs, int zc, int cap,
-                                                                    double kval) {
+// ---------------------------------------------------------------------------------------------------------
+// adjoint, interp_psf = true, with on-chip pre-summation.
+//
+// The scatter form issues two fp32 atomics per (pixel, tap): 7e9 of them for a 200-slice reconstruction at
+// 384^3, and global float atomics execute memory-side at a fixed byte rate (MI355X_MICROARCH.md, "Global float
+// atomics": ~1.3 TB/s for well-shaped wave instructions, 17x less for 64 lanes in 64 rows) -- the direct kernel
+// above spends 3/4 of its time there.  A tile of neighbouring pixels revisits the same voxels many times (taps
+// are 1 voxel apart, pixels 0.5-2 voxels apart), so this kernel sums a tile's contributions in LDS first:
+//   * workgroup = T x T pixel tile of one slice (T = 16: one pixel per thread; T = 8: wave g of the workgroup
+//     takes the PSF rows ky = g mod 4 of every pixel of the tile);
+//   * the PSF is walked in chunks of `zc` planes; per chunk the axis-aligned bounding box of the voxels the
+//     tile can reach is derived from the slice transform; if it fits the LDS accumulator (`cap` cells for
+//     value and weight) contributions go to LDS (ds_add_f32 / ds_add_u64), and the box is flushed with one global
+//     atomic per touched cell in row order (contiguous x runs); otherwise the chunk falls back to direct
+//     global atomics.  A cell index outside the box (cannot happen by construction) also falls back.
+// With SaSumF32: the same sums as the direct kernel up to fp32 summation order (which is nondeterministic there as well).
+// With SaSumFix: the same accumulators as the direct kernel, whatever the tile, the chunks and the fallbacks.
+// ---------------------------------------------------------------------------------------------------------
+template <int T_, bool VM, class Sum>
+__device__ __forceinline__ void sa_adjoint_nn_lds_body(const SaParams& P, const float* __restrict__ slices, int zc, int cap,
+                                                       const Sum sum) {
   constexpr int NPIX = T_ * T_, G = 256 / NPIX;
   extern __shared__ float smem[];
-  extern __shared__ __align__(16) sa_u64 smem64[];  // the same dynamic LDS; raises its alignment to that of the cells
   const int in = blockIdx.z;
   const float* __restrict__ T = P.tr + (size_t)in * 12;
   const SaLds L = sa_lds_layout(smem, P);
-  const int pre = (P.pd * P.ph * P.pw + 3 * (P.pd + P.ph + P.pw) + 1) >> 1;  // prefix in 8-byte units, rounded up
-  long long* part = reinterpret_cast<long long*>(smem64 + pre);  // [256] partial pixel weights
-  sa_u64* cells_lds = smem64 + pre + 256;  // [cap] cells of {value hi, value lo, weight hi, weight lo}
-  {
-    const int tid = threadIdx.x, np = P.pd * P.ph * P.pw;
-    for (int e = tid; e < np; e += 256) L.psf[e] = P.psf[e];
-    for (int e = tid; e < 3 * P.pw; e += 256) { const int a = e / P.pw, i = e - a * P.pw; L.tx[e] = T[a * 4 + 0] * (float)(i - P.pw / 2); }
-    for (int e = tid; e < 3 * P.ph; e += 256) { const int a = e / P.ph, i = e - a * P.ph; L.ty[e] = T[a * 4 + 1] * (float)(i - P.ph / 2); }
-    for (int e = tid; e < 3 * P.pd; e += 256) { const int a = e / P.pd, i = e - a * P.pd; L.tz[e] = T[a * 4 + 2] * (float)(i - P.pd / 2); }
-  }
+  typename Sum::wacc* part = Sum::lds_part(smem, P.pd * P.ph * P.pw + 3 * (P.pd + P.ph + P.pw));  // [256] partial pixel weights
+  const typename Sum::Cells acc = Sum::lds_cells(part, cap);
+  sa_fill_lds(L, P, T, threadIdx.x, 256);
   __syncthreads();
   const int tid = threadIdx.x;
   const int p = tid % NPIX, g = tid / NPIX;
@@ -963,12 +742,16 @@ __global__ __launch_bounds__(256) void sa_adjoint_nn_lds_det_kernel(SaParams P, 
   const int Sy = P.W, Sz = P.H * P.W;
   const float hx = (float)(P.W - 1), hy = (float)(P.H - 1), hz = (float)(P.D - 1);
 
+  // tile extent in slice coordinates
   const int ixl = ix0, ixh = min(ix0 + T_ - 1, P.w - 1), iyl = iy0, iyh = min(iy0 + T_ - 1, P.h - 1);
   const float alo = ((float)ixl - (float)(P.w - 1) * 0.5f) * P.res + T[3] - (float)(P.pw / 2);
   const float ahi = ((float)ixh - (float)(P.w - 1) * 0.5f) * P.res + T[3] + (float)(P.pw - 1 - P.pw / 2);
   const float blo = ((float)iyl - (float)(P.h - 1) * 0.5f) * P.res + T[7] - (float)(P.ph / 2);
   const float bhi = ((float)iyh - (float)(P.h - 1) * 0.5f) * P.res + T[7] + (float)(P.ph - 1 - P.ph / 2);
   const int dimv[3] = {P.W, P.H, P.D};
+  // axis-aligned box of the positions the tile's pixels can reach through PSF planes [clo, chi] (slice coordinates), clipped to
+  // the volume: origin o, extent b; returns whether the unclipped box lies inside the volume by the fp32 slack of the position
+  // sums -- then no tap of the tile needs the per-tap inside test (uniform)
   auto reach = [&](float clo, float chi, int* o, int* b) -> bool {
     bool inside = true;
 #pragma unroll
@@ -977,6 +760,7 @@ __global__ __launch_bounds__(256) void sa_adjoint_nn_lds_det_kernel(SaParams P, 
       const float off = (float)(dimv[a] - 1) * 0.5f;
       const float mn = off + fminf(r0 * alo, r0 * ahi) + fminf(r1 * blo, r1 * bhi) + fminf(r2 * clo, r2 * chi);
       const float mx = off + fmaxf(r0 * alo, r0 * ahi) + fmaxf(r1 * blo, r1 * bhi) + fmaxf(r2 * clo, r2 * chi);
+      // voxel = round(position): [floor(mn + .5), floor(mx + .5)], widened by the slack
       const int lo = max((int)floorf(mn + 0.5f - 2e-3f), 0), hi = min((int)floorf(mx + 0.5f + 2e-3f), dimv[a] - 1);
       o[a] = lo;
       b[a] = hi - lo + 1;
@@ -987,8 +771,8 @@ __global__ __launch_bounds__(256) void sa_adjoint_nn_lds_det_kernel(SaParams P, 
   int o_all[3], b_all[3];
   const bool inside_all = reach(T[11] + (float)(0 - P.pd / 2), T[11] + (float)(P.pd - 1 - P.pd / 2), o_all, b_all);
 
-  // pass 1: pixel weight in fixed point -- the same integer for a pixel whatever G is
-  long long wq = 0;
+  // pass 1: pixel weight (slice_acq_cuda_kernel.cu:515-560), PSF rows split over the G waves of a pixel
+  typename Sum::wacc wq = 0;
   if (live) {
     for (int kz = 0; kz < P.pd; ++kz) {
       const float zx = L.tz[kz], zy = L.tz[P.pd + kz], zz = L.tz[2 * P.pd + kz];
@@ -1003,7 +787,7 @@ __global__ __launch_bounds__(256) void sa_adjoint_nn_lds_det_kernel(SaParams P, 
           const float z = zc_ + L.tx[2 * P.pw + kx] + yz + zz;
           if (!inside_all && (x < 0 || y < 0 || z < 0 || x >= hx || y >= hy || z >= hz)) continue;
           if (!sa_psf_at_fast(L, P, T, sa_round_pos(x) - xc, sa_round_pos(y) - yc, sa_round_pos(z) - zc_, pv)) continue;
-          wq += (long long)sa_fix(pv, SA_DET_ONE);
+          Sum::wadd(wq, pv);
         }
       }
     }
@@ -1015,15 +799,20 @@ __global__ __launch_bounds__(256) void sa_adjoint_nn_lds_det_kernel(SaParams P, 
 #pragma unroll
     for (int q = 0; q < G; ++q) wq += part[q * NPIX + p];
   }
-  const float wsum = sa_unfix(wq, (float)(1.0 / SA_DET_ONE));
+  const float wsum = Sum::wsum(wq);
   if (wsum < 0.5f) live = false;
   const float inv = live ? 1.f / wsum : 0.f;
 
-  const float n0 = T[2], n1 = T[6], n2 = T[10];
+  // LDS cell layout: a chunk of PSF planes of a pixel tile is an oblique plate in the volume, whose axis-aligned
+  // bounding box can hold 10x more cells than the plate.  Cells are therefore indexed by the two volume axes (u, v)
+  // other than the one the slice normal leans on most (a), plus the offset k of the a-coordinate from the plate's
+  // mid-plane at (u, v): K = plate thickness along a, a few cells.  x is kept the fastest index for the flush.
+  const float n0 = T[2], n1 = T[6], n2 = T[10];  // slice normal in volume axes (x, y, z)
   const int A = (fabsf(n0) >= fabsf(n1) && fabsf(n0) >= fabsf(n2)) ? 0 : (fabsf(n1) >= fabsf(n2) ? 1 : 2);
-  const int U = A == 0 ? 1 : 0, V = A == 2 ? 1 : 2;
+  const int U = A == 0 ? 1 : 0, V = A == 2 ? 1 : 2;  // U < V, so x is U whenever x is not the lean axis
   const float nA = A == 0 ? n0 : (A == 1 ? n1 : n2), nU = U == 0 ? n0 : n1, nV = V == 1 ? n1 : n2;
   const float inv_na = 1.f / nA, slope = (fabsf(nU) + fabsf(nV)) * fabsf(inv_na);
+  // tile centre in slice coordinates -> a point of the mid-plane (per chunk: its z)
   const float amid = 0.5f * (alo + ahi), bmid = 0.5f * (blo + bhi);
 
   for (int kz0 = 0; kz0 < P.pd; kz0 += zc) {
@@ -1031,20 +820,22 @@ __global__ __launch_bounds__(256) void sa_adjoint_nn_lds_det_kernel(SaParams P, 
     const float clo = T[11] + (float)(kz0 - P.pd / 2), chi = T[11] + (float)(kz1 - 1 - P.pd / 2);
     int o[3], b[3];
     const bool inside = reach(clo, chi, o, b);
-    if (b[0] <= 0 || b[1] <= 0 || b[2] <= 0) continue;
+    if (b[0] <= 0 || b[1] <= 0 || b[2] <= 0) continue;  // the chunk cannot reach the volume (uniform)
     const float cmid = 0.5f * (clo + chi);
-    float pm[3];
+    float pm[3];  // mid-plane point in volume coordinates
 #pragma unroll
     for (int a = 0; a < 3; ++a)
       pm[a] = (float)(dimv[a] - 1) * 0.5f + T[a * 4] * amid + T[a * 4 + 1] * bmid + T[a * 4 + 2] * cmid;
+    // thickness of the plate along A: PSF planes (kz1-1-kz0) / |nA|, voxel rounding 1 + slope, plus one cell of slack
     const int K = (int)ceilf(((float)(kz1 - 1 - kz0) + 1.f) * fabsf(inv_na) + slope + 1.f) + 1;
     const float hb = 0.5f * (float)K;
     const int bu = b[U], bv = b[V];
     const long long cells = (long long)bu * bv * K;
-    const bool use_lds = cells <= (long long)cap;  // cap <= SA_DET_CAP_MAX: 4 * cells and the limb indices stay far inside int
+    const bool use_lds = cells <= (long long)cap;
+    // index = ((cv * K + k) * bu + cu) when x is U (x fastest); = ((cv * bu + cu) * K + k) when x is the lean axis
     const bool xlean = A == 0;
     if (use_lds) {
-      for (int c = tid; c < 4 * (int)cells; c += 256) cells_lds[c] = 0;
+      sum.lds_zero(acc, (int)cells, tid);
       __syncthreads();
     }
     if (live) {
@@ -1066,7 +857,7 @@ __global__ __launch_bounds__(256) void sa_adjoint_nn_lds_det_kernel(SaParams P, 
             const int vv[3] = {(int)xr, (int)yr, (int)zr};
             const int iv = vv[2] * Sz + vv[1] * Sy + vv[0];
             if (VM && !P.vmask[iv]) continue;
-            const sa_q2 qv = sa_fix2(pv * s, kval), qw = sa_fix2(pv, SA_DET_ONE);
+            const typename Sum::Term t = sum.term(pv, s);
             bool done = false;
             if (use_lds) {
               const int cu = vv[U] - o[U], cv = vv[V] - o[V];
@@ -1075,16 +866,11 @@ __global__ __launch_bounds__(256) void sa_adjoint_nn_lds_det_kernel(SaParams P, 
               const int k = vv[A] - base;
               if ((unsigned)cu < (unsigned)bu && (unsigned)cv < (unsigned)bv && (unsigned)k < (unsigned)K) {
                 const int c = xlean ? (cv * bu + cu) * K + k : (cv * K + k) * bu + cu;
-                sa_add2(cells_lds + 4 * c, qv);
-                sa_add2(cells_lds + 4 * c + 2, qw);
+                sum.lds_add(acc, c, t);
                 done = true;
               }
             }
-            if (!done) {
-              sa_u64* cell = acc + (size_t)iv * limbs;
-              sa_add2(cell, qv);
-              if (limbs == 4) sa_add2(cell + 2, qw);
-            }
+            if (!done) sum.global_add(iv, t);
           }
         }
       }
@@ -1092,8 +878,7 @@ __global__ __launch_bounds__(256) void sa_adjoint_nn_lds_det_kernel(SaParams P, 
     if (use_lds) {
       __syncthreads();
       for (int c = tid; c < (int)cells; c += 256) {
-        const sa_q2 qv{cells_lds[4 * c], cells_lds[4 * c + 1]}, qw{cells_lds[4 * c + 2], cells_lds[4 * c + 3]};
-        if ((qv.hi | qv.lo | qw.hi | qw.lo) == 0) continue;  // untouched (or sums of zero: nothing to add)
+        if (!sum.lds_touched(acc, c)) continue;
         int cu, cv, k;
         if (xlean) { k = c % K; const int r = c / K; cu = r % bu; cv = r / bu; }
         else { cu = c % bu; const int r = c / bu; k = r % K; cv = r / K; }
@@ -1103,13 +888,39 @@ __global__ __launch_bounds__(256) void sa_adjoint_nn_lds_det_kernel(SaParams P, 
         const float fu = (float)vv[U] - pm[U], fv = (float)vv[V] - pm[V];
         vv[A] = (int)floorf(pm[A] - (nU * fu + nV * fv) * inv_na - hb) + k;
         const int iv = vv[2] * Sz + vv[1] * Sy + vv[0];
-        sa_u64* cell = acc + (size_t)iv * limbs;
-        sa_add2(cell, qv);
-        if (limbs == 4) sa_add2(cell + 2, qw);
+        sum.flush(acc, c, iv);
       }
       __syncthreads();
     }
   }
+}
+
+// The kernels: the two bodies above with each accumulator.  A kernel takes its destination as __restrict__ arguments of its
+// own and builds the policy from them: pointers that arrive inside a by-value struct lose `noalias`, and the compiler then
+// allocates registers differently (the same instructions, up to 3 more VGPRs: 6 waves per SIMD instead of 7 for some).
+template <bool NN, bool VM>
+__global__ __launch_bounds__(SA_TILE* SA_TILE) void sa_adjoint_kernel(SaParams P, const float* __restrict__ slices,
+                                                                      float* __restrict__ vol,
+                                                                      float* __restrict__ vol_weight) {
+  sa_adjoint_body<NN, VM>(P, slices, SaSumF32{vol, vol_weight});
+}
+template <bool NN, bool VM>
+__global__ __launch_bounds__(SA_TILE* SA_TILE) void sa_adjoint_det_kernel(SaParams P, const float* __restrict__ slices,
+                                                                          sa_u64* __restrict__ acc, int limbs,
+                                                                          double kval) {
+  sa_adjoint_body<NN, VM>(P, slices, SaSumFix{acc, limbs, kval});
+}
+template <int T_, bool VM>
+__global__ __launch_bounds__(256) void sa_adjoint_nn_lds_kernel(SaParams P, const float* __restrict__ slices,
+                                                                float* __restrict__ vol, float* __restrict__ vol_weight,
+                                                                int zc, int cap) {
+  sa_adjoint_nn_lds_body<T_, VM>(P, slices, zc, cap, SaSumF32{vol, vol_weight});
+}
+template <int T_, bool VM>
+__global__ __launch_bounds__(256) void sa_adjoint_nn_lds_det_kernel(SaParams P, const float* __restrict__ slices,
+                                                                    sa_u64* __restrict__ acc, int limbs, int zc, int cap,
+                                                                    double kval) {
+  sa_adjoint_nn_lds_body<T_, VM>(P, slices, zc, cap, SaSumFix{acc, limbs, kval});
 }
 
 // accumulators -> float32, one rounding each (sa_unfix2); every voxel is written, an untouched accumulator gives +0.
@@ -1236,6 +1047,80 @@ __global__ __launch_bounds__(256) void sa_equalize_kernel(float* __restrict__ vo
   }
 }
 
+// The LDS adjoint's launch shape.  tile: 16x16 pixels when their footprint (pixel pitch * 15 + PSF width) stays small, else
+// 8x8; PSF planes per chunk and accumulator size from the expected cell count of a chunk's plate, E^2 * K inflated for a typical
+// oblique orientation (each workgroup still decides per chunk whether ITS plate fits; if not it scatters directly -- the sums
+// are the same either way).  The accumulator's own limits: `cap_max` bounds the tuned capacity, `cap_grow` the capacity the
+// estimate may ask for; its LDS is the prefix rounded up to a `word`, 256 partial pixel weights of one word, `cell_words` per cell.
+struct SaLdsPlan {
+  int tile, zc, cap;
+  size_t lds2;
+};
+SaLdsPlan sa_lds_plan(const SaParams& P, size_t lds, int cap_max, int cap_grow, size_t word, int cell_words) {
+  const int ext = P.pw > P.ph ? P.pw : P.ph;
+  const bool t16 = P.res * 15.f + (float)ext <= (float)g_sa_t16_extent;
+  const int tile = t16 ? 16 : 8;
+  const float E = P.res * (float)(tile - 1) + (float)ext + 1.f;
+  auto est = [&](int z) { return 1.6f * E * E * (1.5f * (float)z + 3.f); };
+  int cap = g_sa_cap < cap_max ? g_sa_cap : cap_max, zc = g_sa_zc < P.pd ? g_sa_zc : P.pd;
+  if (g_sa_auto) {
+    zc = 1;
+    for (int z = 4; z >= 1; --z)
+      if (est(z) <= (float)cap) { zc = z; break; }
+    if (est(zc) > (float)cap) cap = (int)fminf(est(zc) * 1.25f, (float)cap_grow);
+    if (zc > P.pd) zc = P.pd;
+  }
+  return SaLdsPlan{tile, zc, cap, (lds + word - 1) / word * word + (256 + (size_t)cell_words * cap) * word};
+}
+
+// each accumulator's kernels with their argument lists
+template <bool NN, bool VM>
+void sa_launch_direct(const SaSumF32& d, const SaParams& P, const float* slices, size_t lds, hipStream_t st) {
+  hipLaunchKernelGGL((sa_adjoint_kernel<NN, VM>), sa_grid(P), dim3(SA_TILE, SA_TILE), lds, st, P, slices, d.vol, d.vol_weight);
+}
+template <bool NN, bool VM>
+void sa_launch_direct(const SaSumFix& d, const SaParams& P, const float* slices, size_t lds, hipStream_t st) {
+  hipLaunchKernelGGL((sa_adjoint_det_kernel<NN, VM>), sa_grid(P), dim3(SA_TILE, SA_TILE), lds, st, P, slices, d.acc, d.limbs,
+                     d.kval);
+}
+// (dynamic LDS above the default limit: the kernel has to be told)
+template <class Kernel, class... Args>
+int sa_launch_big_lds(Kernel kfn, dim3 grid, size_t lds2, hipStream_t st, Args... args) {
+  const hipError_t ea = hipFuncSetAttribute((const void*)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds2);
+  if (ea != hipSuccess) return (int)ea;
+  hipLaunchKernelGGL(kfn, grid, dim3(256), lds2, st, args...);
+  return 0;
+}
+template <int T_, bool VM>
+int sa_launch_lds(const SaSumF32& d, const SaParams& P, const float* slices, dim3 grid, const SaLdsPlan& pl, hipStream_t st) {
+  return sa_launch_big_lds(sa_adjoint_nn_lds_kernel<T_, VM>, grid, pl.lds2, st, P, slices, d.vol, d.vol_weight, pl.zc, pl.cap);
+}
+template <int T_, bool VM>
+int sa_launch_lds(const SaSumFix& d, const SaParams& P, const float* slices, dim3 grid, const SaLdsPlan& pl, hipStream_t st) {
+  return sa_launch_big_lds(sa_adjoint_nn_lds_det_kernel<T_, VM>, grid, pl.lds2, st, P, slices, d.acc, d.limbs, pl.zc, pl.cap,
+                           d.kval);
+}
+
+// LINEAR and, under FSG_TUNE_SA_DIRECT, NEAREST_PSF: the direct kernel; NEAREST_PSF otherwise: the LDS kernel.  0 or a HIP error.
+template <class Sum>
+int sa_adjoint_launch(const SaParams& P, const float* slices, size_t lds, bool nn, const Sum& sum, hipStream_t st) {
+  if (!nn) {
+    if (P.vmask) sa_launch_direct<false, true>(sum, P, slices, lds, st);
+    else sa_launch_direct<false, false>(sum, P, slices, lds, st);
+    return 0;
+  }
+  if (g_tuning_flags & FSG_TUNE_SA_DIRECT) {
+    if (P.vmask) sa_launch_direct<true, true>(sum, P, slices, lds, st);
+    else sa_launch_direct<true, false>(sum, P, slices, lds, st);
+    return 0;
+  }
+  const SaLdsPlan pl = sa_lds_plan(P, lds, Sum::CAP_MAX, Sum::CAP_GROW, sizeof(typename Sum::wacc), Sum::CELL_WORDS);
+  const dim3 grid((unsigned)((P.w + pl.tile - 1) / pl.tile), (unsigned)((P.h + pl.tile - 1) / pl.tile), (unsigned)P.n);
+  if (pl.tile == 16)
+    return P.vmask ? sa_launch_lds<16, true>(sum, P, slices, grid, pl, st) : sa_launch_lds<16, false>(sum, P, slices, grid, pl, st);
+  return P.vmask ? sa_launch_lds<8, true>(sum, P, slices, grid, pl, st) : sa_launch_lds<8, false>(sum, P, slices, grid, pl, st);
+}
+
 }  // namespace
 
 extern "C" {
@@ -1312,41 +1197,9 @@ int fsg_slice_acq_adjoint_f32(const float* transforms, const float* psf, int pd,
     // the fallback multiplies by vol_mask at the very end (fsg_equalize_f32), not per contribution
     hipLaunchKernelGGL((sa_torch_kernel<true, false>), grid, block, lds, st, P, (const float*)nullptr, const_cast<float*>(slices),
                        (float*)nullptr, vol, vol_weight);
-  } else if (mode == FSG_SA_LINEAR) {
-    if (vol_mask) hipLaunchKernelGGL((sa_adjoint_kernel<false, true>), grid, block, lds, st, P, slices, vol, vol_weight);
-    else hipLaunchKernelGGL((sa_adjoint_kernel<false, false>), grid, block, lds, st, P, slices, vol, vol_weight);
-  } else if (g_tuning_flags & FSG_TUNE_SA_DIRECT) {
-    if (vol_mask) hipLaunchKernelGGL((sa_adjoint_kernel<true, true>), grid, block, lds, st, P, slices, vol, vol_weight);
-    else hipLaunchKernelGGL((sa_adjoint_kernel<true, false>), grid, block, lds, st, P, slices, vol, vol_weight);
   } else {
-    // tile: 16x16 pixels when their footprint (pixel pitch * 15 + PSF width) stays small, else 8x8; PSF planes per
-    // chunk and accumulator size from the expected cell count of a chunk's plate, E^2 * K inflated for a typical
-    // oblique orientation (each workgroup still decides per chunk whether ITS plate fits; if not it scatters directly)
-    const int ext = pw > ph ? pw : ph;
-    const bool t16 = res_slice * 15.f + (float)ext <= (float)g_sa_t16_extent;
-    const int tile = t16 ? 16 : 8;
-    const float E = res_slice * (float)(tile - 1) + (float)ext + 1.f;
-    auto est = [&](int z) { return 1.6f * E * E * (1.5f * (float)z + 3.f); };
-    int cap = g_sa_cap, zc = g_sa_zc < pd ? g_sa_zc : pd;
-    if (g_sa_auto) {
-      zc = 1;
-      for (int z = 4; z >= 1; --z)
-        if (est(z) <= (float)g_sa_cap) { zc = z; break; }
-      if (est(zc) > (float)cap) cap = (int)fminf(est(zc) * 1.25f, 12288.f);
-      if (zc > pd) zc = pd;
-    }
-    const size_t lds2 = lds + (256 + 2 * (size_t)cap) * sizeof(float);
-    const dim3 grid2((unsigned)((w + tile - 1) / tile), (unsigned)((h + tile - 1) / tile), (unsigned)n);
-#define SA_LAUNCH_LDS(TT, VMM)                                                                                         \
-  do {                                                                                                                \
-    auto kfn = sa_adjoint_nn_lds_kernel<TT, VMM>;                                                                     \
-    hipError_t ea = hipFuncSetAttribute((const void*)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds2);     \
-    if (ea != hipSuccess) return (int)ea;                                                                             \
-    hipLaunchKernelGGL(kfn, grid2, dim3(256), lds2, st, P, slices, vol, vol_weight, zc, cap);                         \
-  } while (0)
-    if (t16) { if (vol_mask) SA_LAUNCH_LDS(16, true); else SA_LAUNCH_LDS(16, false); }
-    else { if (vol_mask) SA_LAUNCH_LDS(8, true); else SA_LAUNCH_LDS(8, false); }
-#undef SA_LAUNCH_LDS
+    const int rl = sa_adjoint_launch(P, slices, lds, mode == FSG_SA_NEAREST_PSF, SaSumF32{vol, vol_weight}, st);
+    if (rl) return rl;
   }
   FSG_RETURN_LAUNCH();
 }
@@ -1377,43 +1230,8 @@ int fsg_slice_acq_adjoint_det_f32(const float* transforms, const float* psf, int
   sa_u64* acc = static_cast<sa_u64*>(ws);
   const int limbs = vol_weight ? 4 : 2;
   const double kval = SA_DET_ONE / (double)value_scale;
-  const dim3 grid = sa_grid(P), block(SA_TILE, SA_TILE);
-  if (mode == FSG_SA_LINEAR) {
-    if (vol_mask) hipLaunchKernelGGL((sa_adjoint_det_kernel<false, true>), grid, block, lds, st, P, slices, acc, limbs, kval);
-    else hipLaunchKernelGGL((sa_adjoint_det_kernel<false, false>), grid, block, lds, st, P, slices, acc, limbs, kval);
-  } else if (g_tuning_flags & FSG_TUNE_SA_DIRECT) {
-    if (vol_mask) hipLaunchKernelGGL((sa_adjoint_det_kernel<true, true>), grid, block, lds, st, P, slices, acc, limbs, kval);
-    else hipLaunchKernelGGL((sa_adjoint_det_kernel<true, false>), grid, block, lds, st, P, slices, acc, limbs, kval);
-  } else {
-    // the float entry's chooser with this mode's own limit: 32-byte cells, at most SA_DET_CAP_MAX of them whatever
-    // fsg_slice_acq_set_tuning asks for (a chunk that does not fit scatters directly; the sums are the same either way)
-    const int ext = pw > ph ? pw : ph;
-    const bool t16 = res_slice * 15.f + (float)ext <= (float)g_sa_t16_extent;
-    const int tile = t16 ? 16 : 8;
-    const float E = res_slice * (float)(tile - 1) + (float)ext + 1.f;
-    auto est = [&](int z) { return 1.6f * E * E * (1.5f * (float)z + 3.f); };
-    int cap = g_sa_cap < SA_DET_CAP_MAX ? g_sa_cap : SA_DET_CAP_MAX, zc = g_sa_zc < pd ? g_sa_zc : pd;
-    if (g_sa_auto) {
-      zc = 1;
-      for (int z = 4; z >= 1; --z)
-        if (est(z) <= (float)cap) { zc = z; break; }
-      if (est(zc) > (float)cap) cap = (int)fminf(est(zc) * 1.25f, (float)SA_DET_CAP_MAX);
-      if (zc > pd) zc = pd;
-    }
-    // prefix rounded up to 8 bytes, 256 partial weights, cells of four limbs
-    const size_t lds2 = ((lds + 7) & ~(size_t)7) + (256 + 4 * (size_t)cap) * sizeof(sa_u64);
-    const dim3 grid2((unsigned)((w + tile - 1) / tile), (unsigned)((h + tile - 1) / tile), (unsigned)n);
-#define SA_LAUNCH_LDS_DET(TT, VMM)                                                                                     \
-  do {                                                                                                                \
-    auto kfn = sa_adjoint_nn_lds_det_kernel<TT, VMM>;                                                                 \
-    hipError_t ea = hipFuncSetAttribute((const void*)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds2);     \
-    if (ea != hipSuccess) return (int)ea;                                                                             \
-    hipLaunchKernelGGL(kfn, grid2, dim3(256), lds2, st, P, slices, acc, limbs, zc, cap, kval);                      \
-  } while (0)
-    if (t16) { if (vol_mask) SA_LAUNCH_LDS_DET(16, true); else SA_LAUNCH_LDS_DET(16, false); }
-    else { if (vol_mask) SA_LAUNCH_LDS_DET(8, true); else SA_LAUNCH_LDS_DET(8, false); }
-#undef SA_LAUNCH_LDS_DET
-  }
+  const int rl = sa_adjoint_launch(P, slices, lds, mode == FSG_SA_NEAREST_PSF, SaSumFix{acc, limbs, kval}, st);
+  if (rl) return rl;
   {
     hipError_t el = hipGetLastError();
     if (el != hipSuccess) return (int)el;
@@ -1426,7 +1244,7 @@ int fsg_slice_acq_adjoint_det_f32(const float* transforms, const float* psf, int
 }
 
 int fsg_slice_acq_set_tuning(int cap_cells, int z_chunk, int t16_extent) {
-  if (cap_cells < 256 || cap_cells > 18432 || z_chunk < 0 || t16_extent < 0) return FSG_E_BADARG;
+  if (cap_cells < 256 || cap_cells > SA_CAP_TUNE_MAX || z_chunk < 0 || t16_extent < 0) return FSG_E_BADARG;
   g_sa_cap = cap_cells; g_sa_zc = z_chunk; g_sa_t16_extent = t16_extent;
   g_sa_auto = z_chunk == 0;
   if (g_sa_auto) g_sa_zc = 3;

@@ -27,10 +27,6 @@
 
 namespace {
 
-#define SAA_FX(A) ((A) ? wx : (1 - wx))
-#define SAA_FY(B) ((B) ? wy : (1 - wy))
-#define SAA_FZ(C) ((C) ? wz : (1 - wz))
-
 // g' = grad_vol / max(vol_weight, 1e-3) where vol_weight > 0 (:672-693, is_grad = true).  The reference's `1e-3` is a double
 // literal: the comparison and the division by it are done in double, the division by the weight itself in fp32.
 __global__ __launch_bounds__(256) void saa_equalize_grad_kernel(const float* __restrict__ gvol, const float* __restrict__ vw,
@@ -55,7 +51,7 @@ __global__ __launch_bounds__(SA_TILE* SA_TILE) void sa_adjoint_backward_kernel(S
   const float* __restrict__ T = P.tr + (size_t)in * 12;
   const SaLds L = sa_lds_layout(smem, P);
   float* red = L.tz + 3 * P.pd;  // [SAB_WAVES][12]
-  sa_fill_lds(L, P, T);
+  sa_fill_lds(L, P, T, sa_tid(), SA_TILE * SA_TILE);
   __syncthreads();
   const int ix = blockIdx.x * SA_TILE + threadIdx.x, iy = blockIdx.y * SA_TILE + threadIdx.y;
   const bool inside = ix < P.w && iy < P.h;
@@ -93,49 +89,24 @@ __global__ __launch_bounds__(SA_TILE* SA_TILE) void sa_adjoint_backward_kernel(S
             const float xr = roundf(x), yr = roundf(y), zr = roundf(z);
             const int iv = (int)zr * Sz + (int)yr * Sy + (int)xr;
             if (VM && !P.vmask[iv]) continue;  // before the tap is counted: the forward's weight does count it
-            const float ex = xr - xc, ey = yr - yc, ez = zr - zc;
-            const float xp = (float)((double)(T[0] * ex + T[4] * ey + T[8] * ez) + (P.pw - 1) / 2.);
-            const float yp = (float)((double)(T[1] * ex + T[5] * ey + T[9] * ez) + (P.ph - 1) / 2.);
-            const float zp = (float)((double)(T[2] * ex + T[6] * ey + T[10] * ez) + (P.pd - 1) / 2.);
+            float xp, yp, zp;
+            sa_psf_coord(P, T, xr - xc, yr - yc, zr - zc, xp, yp, zp);
             if (!(xp >= 0 && yp >= 0 && zp >= 0 && xp < qx && yp < qy && zp < qz)) continue;
-            const float xf = floorf(xp), yf = floorf(yp), zf = floorf(zp);
-            const float wx = xp - xf, wy = yp - yf, wz = zp - zf;
-            const float* q = L.psf + (int)zf * sz + (int)yf * sy + (int)xf;
+            const SaPsfCell c = sa_psf_cell(L, P, xp, yp, zp);
+            const float* q = c.q;
+            const float wx = c.wx, wy = c.wy, wz = c.wz;
             val_ = G[iv];
-            pv = 0.f;
-            pv += (1 - wx) * (1 - wy) * (1 - wz) * q[0];
-            pv += wx * (1 - wy) * (1 - wz) * q[1];
-            pv += (1 - wx) * wy * (1 - wz) * q[sy];
-            pv += (1 - wx) * (1 - wy) * wz * q[sz];
-            pv += wx * wy * (1 - wz) * q[1 + sy];
-            pv += wx * (1 - wy) * wz * q[1 + sz];
-            pv += (1 - wx) * wy * wz * q[sy + sz];
-            pv += wx * wy * wz * q[sy + sz + 1];
+            pv = sa_tri8(q, sy, sz, wx, wy, wz);
             if (GT) {
               // d psf' / d (PSF coordinate), times s * g': the rounded voxel is fixed, the PSF moves under it
               float dx = 0.f, dy = 0.f, dz = 0.f, t;
-#define SAA_PSF_CORNER(OFF, A, B, C)                                          \
-  t = q[(OFF)];                                                               \
-  dx = (A) ? dx + SAA_FY(B) * SAA_FZ(C) * t : dx - SAA_FY(B) * SAA_FZ(C) * t; \
-  dy = (B) ? dy + SAA_FX(A) * SAA_FZ(C) * t : dy - SAA_FX(A) * SAA_FZ(C) * t; \
-  dz = (C) ? dz + SAA_FX(A) * SAA_FY(B) * t : dz - SAA_FX(A) * SAA_FY(B) * t;
-              SAA_PSF_CORNER(0, 0, 0, 0)
-              SAA_PSF_CORNER(1, 1, 0, 0)
-              SAA_PSF_CORNER(sy, 0, 1, 0)
-              SAA_PSF_CORNER(sz, 0, 0, 1)
-              SAA_PSF_CORNER(1 + sy, 1, 1, 0)
-              SAA_PSF_CORNER(1 + sz, 1, 0, 1)
-              SAA_PSF_CORNER(sy + sz, 0, 1, 1)
-              SAA_PSF_CORNER(sy + sz + 1, 1, 1, 1)
+#define SAA_PSF_CORNER(OFF, A, B, C) SA_DCORNER(q[(OFF)], A, B, C)
+              SA_CORNERS8(SAA_PSF_CORNER, sy, sz)
 #undef SAA_PSF_CORNER
               t = (EQ ? s - vol[iv] : s) * val_;
               dx *= t; dy *= t; dz *= t;
               // lever arm: the rounded voxel relative to the volume centre (exact in fp32: half-integers below 2^23)
-              const float lx = xr - hx * 0.5f, ly = yr - hy * 0.5f, lz = zr - hz * 0.5f;
-              g[0] += dx * lx; g[1] += dy * lx; g[2] += dz * lx;
-              g[4] += dx * ly; g[5] += dy * ly; g[6] += dz * ly;
-              g[8] += dx * lz; g[9] += dy * lz; g[10] += dz * lz;
-              g[3] -= dx; g[7] -= dy; g[11] -= dz;
+              sa_lever_nn(g, dx, dy, dz, xr - hx * 0.5f, yr - hy * 0.5f, zr - hz * 0.5f);
             }
           } else {
             const float xf = floorf(x), yf = floorf(y), zf = floorf(z);
@@ -143,45 +114,21 @@ __global__ __launch_bounds__(SA_TILE* SA_TILE) void sa_adjoint_backward_kernel(S
             const int iv = (int)zf * Sz + (int)yf * Sy + (int)xf;
             if (GS) {
 #define SAA_VAL_CORNER(OFF, A, B, C) \
-  if (!VM || P.vmask[iv + (OFF)]) val_ += SAA_FX(A) * SAA_FY(B) * SAA_FZ(C) * G[iv + (OFF)];
-              SAA_VAL_CORNER(0, 0, 0, 0)
-              SAA_VAL_CORNER(1, 1, 0, 0)
-              SAA_VAL_CORNER(Sy, 0, 1, 0)
-              SAA_VAL_CORNER(Sz, 0, 0, 1)
-              SAA_VAL_CORNER(1 + Sy, 1, 1, 0)
-              SAA_VAL_CORNER(1 + Sz, 1, 0, 1)
-              SAA_VAL_CORNER(Sy + Sz, 0, 1, 1)
-              SAA_VAL_CORNER(Sy + Sz + 1, 1, 1, 1)
+  if (!VM || P.vmask[iv + (OFF)]) val_ += SA_FX(A) * SA_FY(B) * SA_FZ(C) * G[iv + (OFF)];
+              SA_CORNERS8(SAA_VAL_CORNER, Sy, Sz)
 #undef SAA_VAL_CORNER
             }
             if (GT) {
               // d (trilinear sample of s * g') / d (sampling position) over the unmasked corners, times psf
               float dx = 0.f, dy = 0.f, dz = 0.f, t;
-#define SAA_LIN_CORNER(OFF, A, B, C)                                            \
-  if (!VM || P.vmask[iv + (OFF)]) {                                             \
-    t = (EQ ? s - vol[iv + (OFF)] : s) * G[iv + (OFF)];                         \
-    dx = (A) ? dx + SAA_FY(B) * SAA_FZ(C) * t : dx - SAA_FY(B) * SAA_FZ(C) * t; \
-    dy = (B) ? dy + SAA_FX(A) * SAA_FZ(C) * t : dy - SAA_FX(A) * SAA_FZ(C) * t; \
-    dz = (C) ? dz + SAA_FX(A) * SAA_FY(B) * t : dz - SAA_FX(A) * SAA_FY(B) * t; \
-  }
-              SAA_LIN_CORNER(0, 0, 0, 0)
-              SAA_LIN_CORNER(1, 1, 0, 0)
-              SAA_LIN_CORNER(Sy, 0, 1, 0)
-              SAA_LIN_CORNER(Sz, 0, 0, 1)
-              SAA_LIN_CORNER(1 + Sy, 1, 1, 0)
-              SAA_LIN_CORNER(1 + Sz, 1, 0, 1)
-              SAA_LIN_CORNER(Sy + Sz, 0, 1, 1)
-              SAA_LIN_CORNER(Sy + Sz + 1, 1, 1, 1)
+#define SAA_LIN_CORNER(OFF, A, B, C) \
+  if (!VM || P.vmask[iv + (OFF)]) { SA_DCORNER((EQ ? s - vol[iv + (OFF)] : s) * G[iv + (OFF)], A, B, C) }
+              SA_CORNERS8(SAA_LIN_CORNER, Sy, Sz)
 #undef SAA_LIN_CORNER
               dx *= pv; dy *= pv; dz *= pv;
               // lever arm: pixel + translation + tap offset, in slice axes
-              const float lx = _x + (float)(kx - P.pw / 2), ly = _y + (float)(ky - P.ph / 2), lz = _z + (float)(kz - P.pd / 2);
-              g[0] += dx * lx; g[1] += dx * ly; g[2] += dx * lz;
-              g[4] += dy * lx; g[5] += dy * ly; g[6] += dy * lz;
-              g[8] += dz * lx; g[9] += dz * ly; g[10] += dz * lz;
-              g[3] += dx * T[0] + dy * T[4] + dz * T[8];
-              g[7] += dx * T[1] + dy * T[5] + dz * T[9];
-              g[11] += dx * T[2] + dy * T[6] + dz * T[10];
+              sa_lever_lin(g, T, dx, dy, dz, _x + (float)(kx - P.pw / 2), _y + (float)(ky - P.ph / 2),
+                           _z + (float)(kz - P.pd / 2));
             }
           }
           if (GS) val += pv * val_;
@@ -200,10 +147,6 @@ __global__ __launch_bounds__(SA_TILE* SA_TILE) void sa_adjoint_backward_kernel(S
     sa_fold12(g, red, ws, in);
   }
 }
-
-#undef SAA_FX
-#undef SAA_FY
-#undef SAA_FZ
 
 template <bool NN, bool VM, bool EQ>
 void sa_adjoint_backward_launch(const SaParams& P, const float* G, const float* vol, const float* slices, float* gslices,
@@ -224,19 +167,13 @@ void sa_adjoint_backward_dispatch(const SaParams& P, bool eq, const float* G, co
   else sa_adjoint_backward_launch<NN, VM, false>(P, G, vol, slices, gslices, ws, gt, grid, lds, st);
 }
 
-// bytes of the tile partials: the first part of the workspace (a multiple of 48, so what follows stays 16-byte aligned)
-size_t saa_partial_bytes(int n, int h, int w) {
-  const size_t tiles = (size_t)((w + SA_TILE - 1) / SA_TILE) * (size_t)((h + SA_TILE - 1) / SA_TILE);
-  return (size_t)n * tiles * 12 * sizeof(float);
-}
-
 }  // namespace
 
 extern "C" {
 
 size_t fsg_slice_acq_adjoint_backward_ws_bytes(int D, int H, int W, int n, int h, int w, int equalize, int want_transforms) {
   if (D <= 0 || H <= 0 || W <= 0 || n <= 0 || h <= 0 || w <= 0) return 0;
-  return (want_transforms ? saa_partial_bytes(n, h, w) : 0) + (equalize ? (size_t)D * H * W * sizeof(float) : 0);
+  return (want_transforms ? sa_partial_bytes(n, h, w) : 0) + (equalize ? (size_t)D * H * W * sizeof(float) : 0);
 }
 
 int fsg_slice_acq_adjoint_backward_f32(const float* transforms, const float* grad_vol, const float* vol_weight, const float* vol,
@@ -262,7 +199,7 @@ int fsg_slice_acq_adjoint_backward_f32(const float* transforms, const float* gra
   float* partials = static_cast<float*>(ws);
   const float* G = grad_vol;
   if (eq) {
-    float* ge = reinterpret_cast<float*>(static_cast<char*>(ws) + (gt ? saa_partial_bytes(n, h, w) : 0));
+    float* ge = reinterpret_cast<float*>(static_cast<char*>(ws) + (gt ? sa_partial_bytes(n, h, w) : 0));
     const size_t nv = (size_t)D * H * W;
     size_t blocks = (nv + 255) / 256;
     if (blocks > 8192) blocks = 8192;

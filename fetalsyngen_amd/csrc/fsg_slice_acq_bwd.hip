@@ -24,11 +24,6 @@
 
 namespace {
 
-// Trilinear corner (A,B,C) of the cell at offset OFF: its weight factors along x, y, z.
-#define SAB_FX(A) ((A) ? wx : (1 - wx))
-#define SAB_FY(B) ((B) ? wy : (1 - wy))
-#define SAB_FZ(C) ((C) ? wz : (1 - wz))
-
 template <bool NN, bool VM, bool GV, bool GT>
 __global__ __launch_bounds__(SA_TILE* SA_TILE) void sa_backward_kernel(SaParams P, const float* __restrict__ vol,
                                                                        const float* __restrict__ gslices,
@@ -38,7 +33,7 @@ __global__ __launch_bounds__(SA_TILE* SA_TILE) void sa_backward_kernel(SaParams 
   const float* __restrict__ T = P.tr + (size_t)in * 12;
   const SaLds L = sa_lds_layout(smem, P);
   float* red = L.tz + 3 * P.pd;  // [SAB_WAVES][12]
-  sa_fill_lds(L, P, T);
+  sa_fill_lds(L, P, T, sa_tid(), SA_TILE * SA_TILE);
   __syncthreads();
   const int ix = blockIdx.x * SA_TILE + threadIdx.x, iy = blockIdx.y * SA_TILE + threadIdx.y;
   const bool inside = ix < P.w && iy < P.h;
@@ -73,23 +68,11 @@ __global__ __launch_bounds__(SA_TILE* SA_TILE) void sa_backward_kernel(SaParams 
           const float z = zc + L.tx[2 * P.pw + kx] + yz + zz;
           if (!(x >= 0 && y >= 0 && z >= 0 && x < hx && y < hy && z < hz)) continue;
           if (NN) {
-            const float dx = roundf(x) - xc, dy = roundf(y) - yc, dz = roundf(z) - zc;
-            const float xp = (float)((double)(T[0] * dx + T[4] * dy + T[8] * dz) + (P.pw - 1) / 2.);
-            const float yp = (float)((double)(T[1] * dx + T[5] * dy + T[9] * dz) + (P.ph - 1) / 2.);
-            const float zp = (float)((double)(T[2] * dx + T[6] * dy + T[10] * dz) + (P.pd - 1) / 2.);
+            float xp, yp, zp;
+            sa_psf_coord(P, T, roundf(x) - xc, roundf(y) - yc, roundf(z) - zc, xp, yp, zp);
             if (!(xp >= 0 && yp >= 0 && zp >= 0 && xp < qx && yp < qy && zp < qz)) continue;
-            const float xf = floorf(xp), yf = floorf(yp), zf = floorf(zp);
-            const float wx = xp - xf, wy = yp - yf, wz = zp - zf;
-            const float* q = L.psf + (int)zf * sz + (int)yf * sy + (int)xf;
-            pv = 0.f;
-            pv += (1 - wx) * (1 - wy) * (1 - wz) * q[0];
-            pv += wx * (1 - wy) * (1 - wz) * q[1];
-            pv += (1 - wx) * wy * (1 - wz) * q[sy];
-            pv += (1 - wx) * (1 - wy) * wz * q[sz];
-            pv += wx * wy * (1 - wz) * q[1 + sy];
-            pv += wx * (1 - wy) * wz * q[1 + sz];
-            pv += (1 - wx) * wy * wz * q[sy + sz];
-            pv += wx * wy * wz * q[sy + sz + 1];
+            const SaPsfCell c = sa_psf_cell(L, P, xp, yp, zp);
+            pv = sa_tri8(c.q, sy, sz, c.wx, c.wy, c.wz);
           }
           weight += pv;
         }
@@ -113,53 +96,25 @@ __global__ __launch_bounds__(SA_TILE* SA_TILE) void sa_backward_kernel(SaParams 
             if (!(x >= 0 && y >= 0 && z >= 0 && x < hx && y < hy && z < hz)) continue;
             if (NN) {
               const float xr = roundf(x), yr = roundf(y), zr = roundf(z);
-              const float ex = xr - xc, ey = yr - yc, ez = zr - zc;
-              const float xp = (float)((double)(T[0] * ex + T[4] * ey + T[8] * ez) + (P.pw - 1) / 2.);
-              const float yp = (float)((double)(T[1] * ex + T[5] * ey + T[9] * ez) + (P.ph - 1) / 2.);
-              const float zp = (float)((double)(T[2] * ex + T[6] * ey + T[10] * ez) + (P.pd - 1) / 2.);
+              float xp, yp, zp;
+              sa_psf_coord(P, T, xr - xc, yr - yc, zr - zc, xp, yp, zp);
               if (!(xp >= 0 && yp >= 0 && zp >= 0 && xp < qx && yp < qy && zp < qz)) continue;
-              const float xf = floorf(xp), yf = floorf(yp), zf = floorf(zp);
-              const float wx = xp - xf, wy = yp - yf, wz = zp - zf;
-              const float* q = L.psf + (int)zf * sz + (int)yf * sy + (int)xf;
+              const SaPsfCell c = sa_psf_cell(L, P, xp, yp, zp);
+              const float* q = c.q;
+              const float wx = c.wx, wy = c.wy, wz = c.wz;
               const int iv = (int)zr * Sz + (int)yr * Sy + (int)xr;
               if (VM && !P.vmask[iv]) continue;
-              if (GV) {
-                float pr = 0.f;
-                pr += (1 - wx) * (1 - wy) * (1 - wz) * q[0];
-                pr += wx * (1 - wy) * (1 - wz) * q[1];
-                pr += (1 - wx) * wy * (1 - wz) * q[sy];
-                pr += (1 - wx) * (1 - wy) * wz * q[sz];
-                pr += wx * wy * (1 - wz) * q[1 + sy];
-                pr += wx * (1 - wy) * wz * q[1 + sz];
-                pr += (1 - wx) * wy * wz * q[sy + sz];
-                pr += wx * wy * wz * q[sy + sz + 1];
-                unsafeAtomicAdd(gvol + iv, pr * gs);
-              }
+              if (GV) unsafeAtomicAdd(gvol + iv, sa_tri8(q, sy, sz, wx, wy, wz) * gs);
               if (GT) {
                 // d psf' / d (PSF coordinate), times gs * vol: the rounded voxel is fixed, the PSF moves under it
                 float dx = 0.f, dy = 0.f, dz = 0.f, t;
-#define SAB_PSF_CORNER(OFF, A, B, C)                                  \
-  t = q[(OFF)];                                                       \
-  dx = (A) ? dx + SAB_FY(B) * SAB_FZ(C) * t : dx - SAB_FY(B) * SAB_FZ(C) * t; \
-  dy = (B) ? dy + SAB_FX(A) * SAB_FZ(C) * t : dy - SAB_FX(A) * SAB_FZ(C) * t; \
-  dz = (C) ? dz + SAB_FX(A) * SAB_FY(B) * t : dz - SAB_FX(A) * SAB_FY(B) * t;
-                SAB_PSF_CORNER(0, 0, 0, 0)
-                SAB_PSF_CORNER(1, 1, 0, 0)
-                SAB_PSF_CORNER(sy, 0, 1, 0)
-                SAB_PSF_CORNER(sz, 0, 0, 1)
-                SAB_PSF_CORNER(1 + sy, 1, 1, 0)
-                SAB_PSF_CORNER(1 + sz, 1, 0, 1)
-                SAB_PSF_CORNER(sy + sz, 0, 1, 1)
-                SAB_PSF_CORNER(sy + sz + 1, 1, 1, 1)
+#define SAB_PSF_CORNER(OFF, A, B, C) SA_DCORNER(q[(OFF)], A, B, C)
+                SA_CORNERS8(SAB_PSF_CORNER, sy, sz)
 #undef SAB_PSF_CORNER
                 t = gs * vol[iv];
                 dx *= t; dy *= t; dz *= t;
                 // lever arm: the rounded voxel relative to the volume centre (exact in fp32: half-integers below 2^23)
-                const float lx = xr - hx * 0.5f, ly = yr - hy * 0.5f, lz = zr - hz * 0.5f;
-                g[0] += dx * lx; g[1] += dy * lx; g[2] += dz * lx;
-                g[4] += dx * ly; g[5] += dy * ly; g[6] += dz * ly;
-                g[8] += dx * lz; g[9] += dy * lz; g[10] += dz * lz;
-                g[3] -= dx; g[7] -= dy; g[11] -= dz;
+                sa_lever_nn(g, dx, dy, dz, xr - hx * 0.5f, yr - hy * 0.5f, zr - hz * 0.5f);
               }
             } else {
               const float xf = floorf(x), yf = floorf(y), zf = floorf(z);
@@ -168,44 +123,20 @@ __global__ __launch_bounds__(SA_TILE* SA_TILE) void sa_backward_kernel(SaParams 
               const float pg = pv * gs;
               if (GV) {
 #define SAB_VOL_CORNER(OFF, A, B, C) \
-  if (!VM || P.vmask[iv + (OFF)]) unsafeAtomicAdd(gvol + iv + (OFF), SAB_FX(A) * SAB_FY(B) * SAB_FZ(C) * pg);
-                SAB_VOL_CORNER(0, 0, 0, 0)
-                SAB_VOL_CORNER(1, 1, 0, 0)
-                SAB_VOL_CORNER(Sy, 0, 1, 0)
-                SAB_VOL_CORNER(Sz, 0, 0, 1)
-                SAB_VOL_CORNER(1 + Sy, 1, 1, 0)
-                SAB_VOL_CORNER(1 + Sz, 1, 0, 1)
-                SAB_VOL_CORNER(Sy + Sz, 0, 1, 1)
-                SAB_VOL_CORNER(Sy + Sz + 1, 1, 1, 1)
+  if (!VM || P.vmask[iv + (OFF)]) unsafeAtomicAdd(gvol + iv + (OFF), SA_FX(A) * SA_FY(B) * SA_FZ(C) * pg);
+                SA_CORNERS8(SAB_VOL_CORNER, Sy, Sz)
 #undef SAB_VOL_CORNER
               }
               if (GT) {
                 // d (trilinear sample) / d (sampling position), times gs * psf, over the unmasked corners
                 float dx = 0.f, dy = 0.f, dz = 0.f, t;
-#define SAB_LIN_CORNER(OFF, A, B, C)                                    \
-  if (!VM || P.vmask[iv + (OFF)]) {                                     \
-    t = pg * vol[iv + (OFF)];                                           \
-    dx = (A) ? dx + SAB_FY(B) * SAB_FZ(C) * t : dx - SAB_FY(B) * SAB_FZ(C) * t; \
-    dy = (B) ? dy + SAB_FX(A) * SAB_FZ(C) * t : dy - SAB_FX(A) * SAB_FZ(C) * t; \
-    dz = (C) ? dz + SAB_FX(A) * SAB_FY(B) * t : dz - SAB_FX(A) * SAB_FY(B) * t; \
-  }
-                SAB_LIN_CORNER(0, 0, 0, 0)
-                SAB_LIN_CORNER(1, 1, 0, 0)
-                SAB_LIN_CORNER(Sy, 0, 1, 0)
-                SAB_LIN_CORNER(Sz, 0, 0, 1)
-                SAB_LIN_CORNER(1 + Sy, 1, 1, 0)
-                SAB_LIN_CORNER(1 + Sz, 1, 0, 1)
-                SAB_LIN_CORNER(Sy + Sz, 0, 1, 1)
-                SAB_LIN_CORNER(Sy + Sz + 1, 1, 1, 1)
+#define SAB_LIN_CORNER(OFF, A, B, C) \
+  if (!VM || P.vmask[iv + (OFF)]) { SA_DCORNER(pg * vol[iv + (OFF)], A, B, C) }
+                SA_CORNERS8(SAB_LIN_CORNER, Sy, Sz)
 #undef SAB_LIN_CORNER
                 // lever arm: pixel + translation + tap offset, in slice axes
-                const float lx = _x + (float)(kx - P.pw / 2), ly = _y + (float)(ky - P.ph / 2), lz = _z + (float)(kz - P.pd / 2);
-                g[0] += dx * lx; g[1] += dx * ly; g[2] += dx * lz;
-                g[4] += dy * lx; g[5] += dy * ly; g[6] += dy * lz;
-                g[8] += dz * lx; g[9] += dz * ly; g[10] += dz * lz;
-                g[3] += dx * T[0] + dy * T[4] + dz * T[8];
-                g[7] += dx * T[1] + dy * T[5] + dz * T[9];
-                g[11] += dx * T[2] + dy * T[6] + dz * T[10];
+                sa_lever_lin(g, T, dx, dy, dz, _x + (float)(kx - P.pw / 2), _y + (float)(ky - P.ph / 2),
+                             _z + (float)(kz - P.pd / 2));
               }
             }
           }
@@ -217,10 +148,6 @@ __global__ __launch_bounds__(SA_TILE* SA_TILE) void sa_backward_kernel(SaParams 
   // the fold of fsg_sa.h: shuffle tree per wave, waves in order through LDS, one partial per workgroup
   if (GT) sa_fold12(g, red, ws, in);
 }
-
-#undef SAB_FX
-#undef SAB_FY
-#undef SAB_FZ
 
 template <bool NN, bool VM>
 void sa_backward_launch(const SaParams& P, const float* vol, const float* gslices, float* gvol, float* ws, bool gt, dim3 grid,
@@ -236,9 +163,7 @@ void sa_backward_launch(const SaParams& P, const float* vol, const float* gslice
 extern "C" {
 
 size_t fsg_slice_acq_backward_ws_bytes(int n, int h, int w) {
-  if (n <= 0 || h <= 0 || w <= 0) return 0;
-  const size_t tiles = (size_t)((w + SA_TILE - 1) / SA_TILE) * (size_t)((h + SA_TILE - 1) / SA_TILE);
-  return (size_t)n * tiles * 12 * sizeof(float);
+  return n <= 0 || h <= 0 || w <= 0 ? 0 : sa_partial_bytes(n, h, w);
 }
 
 int fsg_slice_acq_backward_f32(const float* transforms, const float* vol, const uint8_t* vol_mask, const float* psf, int pd,

@@ -198,6 +198,47 @@ def test_bit_for_bit_against_the_numpy_restatement(K, lib, which):
             assert not np.signbit(host(v)[want_w == 0]).any()  # untouched accumulators are +0
 
 
+@pytest.mark.parametrize("vs", [(9, 23, 19), (10, 24, 20)], ids=["odd", "even"])
+def test_float_lds_kernel_is_the_fixed_point_kernel_where_order_cannot_matter(K, lib, vs):
+    """The float and the fixed-point LDS adjoint are one kernel body with two accumulators, so where no sum has more than
+    one term they must agree in every bit.  Axis-aligned slices at a pitch of 4 voxels (wider than the 3 x 3 PSF), 3 voxels
+    apart in z (more than its 2 planes): no two (pixel, tap) pairs land on one voxel, which the single-pixel adjoints of the
+    numpy restatement confirm below.  PSF and slice values are multiples of 1/16, so the pixel weight is the same number
+    summed in fp32 in any order and in 2^-32 integers; a lone contribution fl32(pv / wsum * s) is far above 2^-48 and
+    passes the 2^-72 quantiser and the single rounding back unchanged.  Odd extents put the voxels on the grid, even ones
+    on rounding ties."""
+    rng = np.random.default_rng(41)
+    n, h, w, res = 3, 5, 4, 4.0
+    tr = _aligned(rng, n, 1, 0)
+    tr[:, 2, 3] = (-3, 0, 3)
+    psf = (rng.integers(4, 17, (2, 3, 3)) / 16.0).astype(np.float32)
+    s = (rng.integers(1, 33, (n, h, w)) * rng.choice([-1, 1], (n, h, w)) / 16.0).astype(np.float32)
+    sm = rng.uniform(size=(n, h, w)) > 0.1
+    vm = rng.uniform(size=vs) > 0.1
+    # CPU: every voxel receives at most one contribution -- the supports of the single-pixel adjoints are disjoint
+    hits = np.zeros(vs, np.int64)
+    for z in range(n):
+        for p in range(h * w):
+            one = np.zeros((1, h, w), bool)
+            one.reshape(-1)[p] = True
+            hits += X.adjoint_nearest_psf(tr[z:z + 1], psf, s[z:z + 1], vs, res, slices_mask=one)[1] != 0
+    assert hits.max() == 1
+    for masks in ((None, None), (sm, vm)):
+        want_v, want_w = X.adjoint_nearest_psf(tr, psf, s, vs, res, slices_mask=masks[0], vol_mask=masks[1])
+        assert np.count_nonzero(want_w) > 50
+        if masks[0] is None:
+            assert np.array_equal(want_w != 0, hits == 1)
+        args = (dev(tr), dev(psf), dev(s), dev(masks[0]), dev(masks[1]), vs, res)
+        for ctx in (tuned(lib), tuned(lib, tuning=(512, 1, 0)), tuned(lib, tuning=(16384, 64, 1000))):
+            with ctx:
+                f = K.slice_acq_adjoint(*args, interp_psf=True, return_weight=True)
+                d = K.slice_acq_adjoint(*args, interp_psf=True, return_weight=True, deterministic=True)
+            assert torch.equal(f[1], d[1]), f"weight: {float((f[1] - d[1]).abs().max())}"
+            assert torch.equal(f[0], d[0]), f"value: {float((f[0] - d[0]).abs().max())}"
+            assert np.array_equal(host(d[1]), want_w) and np.array_equal(host(d[0]), want_v)
+            assert np.array_equal(host(f[1]), want_w) and np.array_equal(host(f[0]), want_v)
+
+
 def test_value_scale_is_exact_and_bad_scales_are_refused_untouched(K, lib, case):
     a = det(K, case)
     b = det(K, case, s=case["s"] * 1024, value_scale=1024.0)
