@@ -460,51 +460,9 @@ __device__ __forceinline__ bool sa_psf_at_fast(const SaLds& L, const SaParams& P
   return true;
 }
 
-// ---- fixed point: the quantisers and the two-limb integer of the deterministic accumulator (SaSumFix below) ----
-typedef unsigned long long sa_u64;
+// (the quantisers, the two-limb add, sa_unfix2 and the finalising kernel of the deterministic accumulator are in fsg_sa.h: the
+// backward of the forward sums its grad_vol with them too)
 constexpr int SA_DET_CAP_MAX = 4096;  // 128 KiB of cells + <= 19 KiB of prefix and partials, inside the 160 KiB of a CU
-constexpr int SA_DET_HI_BITS = FSG_SA_DET_FRAC_BITS - FSG_SA_DET_LIMB_BITS;  // the high limb counts 2^-32
-constexpr double SA_DET_ONE = (double)(1ull << SA_DET_HI_BITS);
-constexpr double SA_DET_LIMB = (double)(1ull << FSG_SA_DET_LIMB_BITS);
-
-// round-half-even(c * k) for k a power of two: the product is exact in double, one rounding (the pixel weight's 2^-32)
-__device__ __forceinline__ sa_u64 sa_fix(float c, double k) { return (sa_u64)__double2ll_rn((double)c * k); }
-__device__ __forceinline__ float sa_unfix(long long q, float k) { return __ll2float_rn(q) * k; }
-// Q = round-half-even(c * k * 2^LIMB) as hi * 2^LIMB + lo: d = c * k is exact in double, d - rint(d) is exact (at most 1/2,
-// a multiple of ulp(d)), and rint(x + even integer) = rint(x) + that integer.  |lo| <= 2^(LIMB-1).  A contribution of
-// 2^-(F-24) and more (d >= 2^-16: ulp(d) >= 2^-LIMB) enters exactly.
-struct sa_q2 { sa_u64 hi, lo; };
-__device__ __forceinline__ sa_q2 sa_fix2(float c, double k) {
-  const double d = (double)c * k, h = rint(d);
-  return sa_q2{(sa_u64)(long long)h, (sa_u64)__double2ll_rn((d - h) * SA_DET_LIMB)};
-}
-// a cell is {value hi, value lo [, weight hi, weight lo]}; zero limbs are not sent
-__device__ __forceinline__ void sa_add2(sa_u64* cell, const sa_q2 q) {
-  if (q.hi) atomicAdd(cell, q.hi);
-  if (q.lo) atomicAdd(cell + 1, q.lo);
-}
-// hi * 2^LIMB + lo -> float32 with ONE rounding to nearest even, times 2^(ex - LIMB): the carry of lo goes into hi, the
-// magnitude is cut to 63 bits that keep a sticky bit far below the rounding position, one conversion rounds, ldexp is exact
-__device__ __forceinline__ float sa_unfix2(long long hi, long long lo, int ex) {
-  constexpr long long ONE = 1ll << FSG_SA_DET_LIMB_BITS;
-  const long long carry = lo >> FSG_SA_DET_LIMB_BITS;  // arithmetic shift: floor
-  hi += carry;
-  lo -= carry * ONE;  // 0 <= lo < ONE
-  const bool neg = hi < 0;
-  sa_u64 mh = (sa_u64)hi, ml = (sa_u64)lo;
-  if (neg) {  // -(hi * ONE + lo) = (-hi - 1) * ONE + (ONE - lo) for lo > 0
-    mh = lo ? (sa_u64)(-(hi + 1)) : (sa_u64)0 - (sa_u64)hi;
-    ml = lo ? (sa_u64)(ONE - lo) : 0;
-  }
-  int t = FSG_SA_DET_LIMB_BITS;
-  if (mh) t = min(t, __clzll((long long)mh) - 1);
-  t = max(t, 0);  // (mh = 2^63, the overflowed sum of an out-of-range input: any value will do)
-  const int down = FSG_SA_DET_LIMB_BITS - t;
-  sa_u64 x = (mh << t) | (ml >> down);
-  if (down && (ml & ((1ull << down) - 1))) x |= 1;  // sticky: x has its top bit at 62 here, rounding happens at bit 38
-  const float f = ldexpf(__ll2float_rn((long long)x), down + ex - FSG_SA_DET_LIMB_BITS);
-  return neg ? -f : f;
-}
 
 // ---------------------------------------------------------------------------------------------------------
 // The accumulator policies.  A policy holds its own destination (a kernel builds it from its arguments, the host-side launch
@@ -921,18 +879,6 @@ __global__ __launch_bounds__(256) void sa_adjoint_nn_lds_det_kernel(SaParams P, 
                                                                     sa_u64* __restrict__ acc, int limbs, int zc, int cap,
                                                                     double kval) {
   sa_adjoint_nn_lds_body<T_, VM>(P, slices, zc, cap, SaSumFix{acc, limbs, kval});
-}
-
-// accumulators -> float32, one rounding each (sa_unfix2); every voxel is written, an untouched accumulator gives +0.
-// ex_v = log2(value_scale) - 32, ex_w = -32: the exponent of the high limb's unit.
-__global__ __launch_bounds__(256) void sa_det_finalize_kernel(const long long* __restrict__ acc, int limbs,
-                                                              float* __restrict__ vol, float* __restrict__ vol_weight, int ex_v,
-                                                              int ex_w, size_t n) {
-  for (size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x; e < n; e += (size_t)gridDim.x * blockDim.x) {
-    const long long* cell = acc + e * limbs;
-    vol[e] = sa_unfix2(cell[0], cell[1], ex_v);
-    if (limbs == 4) vol_weight[e] = sa_unfix2(cell[2], cell[3], ex_w);
-  }
 }
 
 // ---------------------------------------------------------------------------------------------------------

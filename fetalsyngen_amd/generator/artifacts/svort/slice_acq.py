@@ -7,7 +7,8 @@ followed: "cuda" (default; what the reference computes on a GPU) or "torch" (its
 seed-matched comparison with a CPU run of the reference).  There is no CPU path here.
 
 `slice_acquisition` is differentiable in `transforms` and `vol` under "cuda" semantics, as the reference's SliceAcqFunction
-(fsg_slice_acq_bwd.hip).  `slice_acquisition_adjoint` is differentiable in `transforms` and `slices`, as
+(fsg_slice_acq_bwd.hip); with `deterministic=True` (the default inside a keyed scope) its `vol` gradient
+is summed in fixed point and is bit-identical from run to run as well.  `slice_acquisition_adjoint` is differentiable in `transforms` and `slices`, as
 the reference's SliceAcqAdjointFunction (fsg_slice_acq_adjoint_bwd.hip), with or without `equalize`; both
 of its gradients are bit-identical from run to run.  Neither has a backward under "torch" semantics, and the adjoint has none
 for a `slice_ids` subset: those calls raise NotImplementedError when a gradient is asked for.
@@ -42,30 +43,44 @@ def _dev(t, device):
 class SliceAcqFunction(torch.autograd.Function):
     """`slice_acquisition` with a backward, CUDA semantics (reference slice_acq.py:22-101): gradients with respect to
     `transforms` and `vol`; the masks, the PSF and the geometry get none, and the gradient that arrives for the weight
-    output is ignored, as in the reference."""
+    output is ignored, as in the reference.  `deterministic` and `grad_scale` are kept for the backward and change nothing
+    else: the forward is the same launch either way."""
 
     @staticmethod
-    def forward(ctx, transforms, vol, vol_mask, slices_mask, psf, slice_shape, res_slice, need_weight, interp_psf):
+    def forward(ctx, transforms, vol, vol_mask, slices_mask, psf, slice_shape, res_slice, need_weight, interp_psf,
+                deterministic=False, grad_scale=1.0):
         out = K.slice_acq_forward(transforms, vol, vol_mask, slices_mask, psf, slice_shape, res_slice,
                                   need_weight=need_weight, interp_psf=interp_psf, semantics="cuda")
         ctx.save_for_backward(transforms, vol, vol_mask, slices_mask, psf)
         ctx.res_slice, ctx.interp_psf = res_slice, interp_psf
+        ctx.deterministic, ctx.grad_scale = bool(deterministic), grad_scale
         return out
 
     @staticmethod
     def backward(ctx, grad_slices, *_grad_weight):
         transforms, vol, vol_mask, slices_mask, psf = ctx.saved_tensors
+        # a call that did not ask for the fixed-point grad_vol is the call it always was
+        det = dict(deterministic=True, grad_scale=ctx.grad_scale) if ctx.deterministic else {}
         grad_vol, grad_transforms = K.slice_acq_backward(
             transforms, vol, vol_mask, slices_mask, psf, grad_slices.contiguous(), ctx.res_slice, interp_psf=ctx.interp_psf,
-            need_vol_grad=ctx.needs_input_grad[1], need_transforms_grad=ctx.needs_input_grad[0])
-        return grad_transforms, grad_vol, None, None, None, None, None, None, None
+            need_vol_grad=ctx.needs_input_grad[1], need_transforms_grad=ctx.needs_input_grad[0], **det)
+        return grad_transforms, grad_vol, None, None, None, None, None, None, None, None, None
 
 
 def slice_acquisition(transforms, vol, vol_mask, slices_mask, psf, slice_shape, res_slice, need_weight, interp_psf,
-                      semantics=None):
+                      semantics=None, deterministic=None, grad_scale=1.0):
     """Differentiable in `transforms` and `vol` under `semantics="cuda"`: when either requires grad the call goes through
-    SliceAcqFunction (kernels.slice_acq_backward); otherwise it is the plain forward launch."""
+    SliceAcqFunction (kernels.slice_acq_backward); otherwise it is the plain forward launch.
+
+    deterministic: how the backward sums the gradient of `vol` -- None = in fixed point inside a keyed scope
+    (`rng.in_keyed_scope()`) under "cuda" semantics, as the adjoint's own rule; True / False force the fixed-point or the
+    fp32-atomic accumulation.  It changes the backward only.  True with `semantics="torch"` raises ValueError.  grad_scale: a
+    power of two in [2^-20, 2^20] the contributions are divided by before they are quantised (kernels.slice_acq_backward)."""
     sem = semantics or _SEMANTICS
+    if deterministic and sem == "torch":
+        raise ValueError("the deterministic grad_vol follows the CUDA semantics only (semantics='cuda')")
+    if deterministic is None:
+        deterministic = _rng.in_keyed_scope() and sem == "cuda"
     dev = vol.device
     if torch.is_grad_enabled() and (transforms.requires_grad or vol.requires_grad):
         if sem != "cuda":
@@ -76,7 +91,7 @@ def slice_acquisition(transforms, vol, vol_mask, slices_mask, psf, slice_shape, 
         vm = None if vol_mask is None or vol_mask.numel() == 0 else _dev(vol_mask, dev).reshape(v.shape)
         sm = None if slices_mask is None or slices_mask.numel() == 0 else _dev(slices_mask, dev).reshape(n, h, w)
         out = SliceAcqFunction.apply(_dev(transforms.float(), dev), v, vm, sm, _dev(psf.float(), dev), (h, w), res_slice,
-                                     need_weight, interp_psf)
+                                     need_weight, interp_psf, bool(deterministic), grad_scale)
         if need_weight:
             return out[0].view(n, 1, h, w), out[1].view(n, 1, h, w)
         return out.view(n, 1, h, w)

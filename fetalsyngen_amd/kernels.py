@@ -693,10 +693,18 @@ def slice_acq_forward(transforms, vol, vol_mask, slices_mask, psf, slice_shape, 
 
 
 def slice_acq_backward(transforms, vol, vol_mask, slices_mask, psf, grad_slices, res_slice, interp_psf=False,
-                       need_vol_grad=True, need_transforms_grad=True):
+                       need_vol_grad=True, need_transforms_grad=True, deterministic=False, grad_scale=1.0):
     """Backward of `slice_acq_forward` in the CUDA semantics (fsg_slice_acq_backward_f32): (n,h,w) grad_slices ->
-    (grad_vol (D,H,W) | None, grad_transforms (n,3,4) | None).  grad_vol is accumulated with fp32 atomics (its last bits change
-    from run to run); grad_transforms is reduced in a fixed order and is bit-identical for the same inputs."""
+    (grad_vol (D,H,W) | None, grad_transforms (n,3,4) | None).  grad_transforms is reduced in a fixed order and is bit-identical
+    for the same inputs.  grad_vol is accumulated with fp32 atomics (its last bits change from run to run) unless
+    deterministic: then every contribution is quantised once and summed in fixed point, two 64-bit limbs
+    (fsg_slice_acq_backward_det_f32), and grad_vol is a pure function of the inputs, whatever the run, the stream or the slice
+    order; grad_transforms has the same bits either way.  grad_scale: a power of two in [2^-20, 2^20] the contributions are
+    divided by before they are quantised (1 for gradients of about unit size)."""
+    if deterministic:
+        m, e = math.frexp(float(grad_scale))
+        if m != 0.5 or not -20 <= e - 1 <= 20:
+            raise ValueError(f"grad_scale must be a power of two in [2^-20, 2^20], got {grad_scale!r}")
     if not (need_vol_grad or need_transforms_grad):
         return None, None
     n, (pd, ph, pw) = _sa_common(transforms, psf)
@@ -712,6 +720,15 @@ def slice_acq_backward(transforms, vol, vol_mask, slices_mask, psf, grad_slices,
     lib = _lib.load()
     need = int(lib.fsg_slice_acq_backward_ws_bytes(n, h, w)) if need_transforms_grad else 0
     ws = torch.empty(need // 8, dtype=torch.int64, device=vol.device) if need else None  # 48 bytes per tile: a multiple of 8
+    if deterministic:
+        dneed = int(lib.fsg_slice_acq_backward_det_ws_bytes(D, H, W)) if need_vol_grad else 0
+        dws = torch.empty(dneed // 8, dtype=torch.int64, device=vol.device) if dneed else None  # zeroed by the call
+        rc = lib.fsg_slice_acq_backward_det_f32(_p(transforms), _p(vol), _p(vm), _p(psf), pd, ph, pw, _p(grad_slices), _p(sm),
+                                                _p(gvol), _p(gtr), D, H, W, n, h, w, float(res_slice),
+                                                _sa_mode("cuda", interp_psf), _p(ws), need, _p(dws), dneed, float(grad_scale),
+                                                _stream(vol))
+        _lib.check(rc, "fsg_slice_acq_backward_det_f32")
+        return gvol, gtr
     rc = lib.fsg_slice_acq_backward_f32(_p(transforms), _p(vol), _p(vm), _p(psf), pd, ph, pw, _p(grad_slices), _p(sm),
                                         _p(gvol), _p(gtr), D, H, W, n, h, w, float(res_slice),
                                         _sa_mode("cuda", interp_psf), _p(ws), need, _stream(vol))

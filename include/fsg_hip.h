@@ -35,7 +35,8 @@ extern "C" {
                               6: fsg_voxel_pick_f32 / _u8, fsg_voxel_pick_ws_bytes;
                               7: fsg_slice_acq_adjoint_det_f32, fsg_slice_acq_adjoint_det_ws_bytes, FSG_SA_DET_FRAC_BITS / LIMB_BITS;
                               8: fsg_slice_acq_backward_f32, fsg_slice_acq_backward_ws_bytes; still 8 with
-                                 fsg_slice_acq_adjoint_backward_f32 / _ws_bytes: two entries added, nothing older changed */
+                                 fsg_slice_acq_adjoint_backward_f32 / _ws_bytes and with fsg_slice_acq_backward_det_f32 /
+                                 _det_ws_bytes: entries added, nothing older changed */
 
 #define FSG_E_BADARG (-1)   /* null pointer / non-positive size / bad enum */
 #define FSG_E_TOOBIG (-2)   /* size exceeds what the kernel indexes (2^31-1 voxels per volume) */
@@ -400,7 +401,8 @@ int fsg_equalize_f32(float* vol, const float* vol_weight, const uint8_t* vol_mas
  * Accumulation:
  *   grad_vol         zeroed by the call on `stream`, then fp32 vector atomics, as the reference and fsg_slice_acq_adjoint_f32:
  *                    the order of the additions, and with it the last bits, change from run to run.  NOT deterministic
- *                    (bit-identical only where a voxel receives at most one contribution).
+ *                    (bit-identical only where a voxel receives at most one contribution).  fsg_slice_acq_backward_det_f32
+ *                    below sums the same contributions in fixed point and is deterministic.
  *   grad_transforms  DETERMINISTIC, no atomics: 12 sums per thread in registers, a fixed shuffle tree per wave, the waves of a
  *                    workgroup added in order through LDS, one 12-float partial per workgroup stored at ws[slice][tile], and a
  *                    second launch that adds a slice's tiles in index order.  The same bits on any stream, in any run, and
@@ -417,6 +419,41 @@ int fsg_slice_acq_backward_f32(const float* transforms, const float* vol, const 
                                int ph, int pw, const float* grad_slices, const uint8_t* slices_mask, float* grad_vol,
                                float* grad_transforms, int D, int H, int W, int n, int h, int w, float res_slice, int mode,
                                void* ws, size_t ws_bytes, void* stream);
+/* The same backward with a DETERMINISTIC grad_vol (FSG_SA_LINEAR and FSG_SA_NEAREST_PSF; FSG_SA_TORCH is refused with
+ * FSG_E_BADARG).  Only the accumulation of grad_vol differs from fsg_slice_acq_backward_f32.  The rule, with
+ * F = FSG_SA_DET_FRAC_BITS = 72 and L = FSG_SA_DET_LIMB_BITS = 40, as for fsg_slice_acq_adjoint_det_f32:
+ *   1. a contribution is the float32 value fsg_slice_acq_backward_f32 hands to its atomic, formed by the same fp32 operations
+ *      in the same order (no FMA contraction): FSG_SA_NEAREST_PSF c = fl32(psf' * gs), psf' the eight-term trilinear sum of
+ *      the PSF at the rounded voxel; FSG_SA_LINEAR c = fl32(fl32(fl32(fx * fy) * fz) * fl32(psf * gs)) per unmasked corner.
+ *      Pass 1, weight, the weight != 0 test, gs = grad_slices / weight, the masks and the accepting range tests are those
+ *      above, quirks included;
+ *   2. it is quantised ONCE, Q = rint_half_even(c * 2^F / grad_scale) (the scaling by a power of two is exact), carried as
+ *      two 64-bit limbs Q = hi * 2^L + lo, hi = rint_half_even(c * 2^(F-L) / grad_scale), |lo| <= 2^(L-1), and each limb is
+ *      added on its own with a 64-bit integer atomic into det_ws, 2 limbs per voxel (a limb that is zero is not sent).
+ *      Integer addition is associative, so the sums do not depend on the order.  A contribution of 2^-48 * grad_scale and
+ *      more enters exactly, a smaller one with an error of at most 2^-(F+1) * grad_scale;
+ *   3. a finalising pass forms sum(hi) * 2^L + sum(lo) exactly, rounds it ONCE to float32 (nearest even) and multiplies by
+ *      2^-F * grad_scale, which is exact.  It writes every voxel; an accumulator nothing was added to gives +0.0f;
+ *   4. grad_scale is a power of two in [2^-20, 2^20] (else FSG_E_BADARG), 1 for gradients of about unit size.  It is given
+ *      by the caller and never derived from the data: a data-derived scale would tie the bits of one voxel to every other
+ *      slice that is passed.  Range per voxel: |sum of contributions / grad_scale| < 2^(63-(F-L)) = 2^31 and fewer than
+ *      2^(63-L) = 2^23 contributions; beyond it the sums wrap (no fault);
+ *   5. grad_transforms is untouched: it has the bits of fsg_slice_acq_backward_f32, whether or not grad_vol is requested.
+ * grad_vol is therefore bit-identical for the same inputs in any run, on any stream, for any order of the slices (transforms,
+ * grad_slices and slices_mask permuted together) and with or without grad_transforms.
+ *   ws      as fsg_slice_acq_backward_f32: needed only when grad_transforms is requested.
+ *   det_ws  DEVICE; needed only when grad_vol is requested (else it may be NULL), and then 8-byte aligned (else FSG_E_ALIGN)
+ *           with det_ws_bytes >= fsg_slice_acq_backward_det_ws_bytes(D, H, W) = 16 bytes per voxel (else FSG_E_BADARG);
+ *           zeroed by the call on `stream`.
+ * Every refusal leaves grad_vol, grad_transforms, ws and det_ws untouched; otherwise every element of each requested output
+ * is written.  No allocation and no host synchronisation inside.  Non-finite grad_slices, vol or psf values give unspecified
+ * values where they reach and never a fault: no address depends on a value that did not pass a range test. */
+size_t fsg_slice_acq_backward_det_ws_bytes(int D, int H, int W);
+int fsg_slice_acq_backward_det_f32(const float* transforms, const float* vol, const uint8_t* vol_mask, const float* psf, int pd,
+                                   int ph, int pw, const float* grad_slices, const uint8_t* slices_mask, float* grad_vol,
+                                   float* grad_transforms, int D, int H, int W, int n, int h, int w, float res_slice, int mode,
+                                   void* ws, size_t ws_bytes, void* det_ws, size_t det_ws_bytes, float grad_scale,
+                                   void* stream);
 /* Backward of fsg_slice_acq_adjoint_f32 + fsg_equalize_f32 (fsg_slice_acq_adjoint_bwd.hip; reference
  * SliceAcqAdjointFunction.backward, slice_acq_cuda_kernel.cu:695-950, host side :1079-1132): grad_slices (n,h,w) and
  * grad_transforms (n,12) from grad_vol (D,H,W).  Either output may be NULL (not both: FSG_E_BADARG).  FSG_SA_LINEAR and

@@ -8,6 +8,8 @@
 after the fp32-atomic entry on the same inputs (`*_det_ms`, the float figures are the yardstick), and its workspace size.
 --backward adds the backward of the forward operator (fsg_slice_acq_backward_f32) at the same size: `backward_<mode>_<leg>_ms`
 for grad_vol alone, grad_transforms alone and both, in both modes, beside the forward's and the float adjoint's times.
+--backward --deterministic together add the fixed-point grad_vol (fsg_slice_acq_backward_det_f32) right after those float legs:
+`backward_<mode>_<leg>_det_ms` for grad_vol alone and both, their ratios to the float legs, and the workspace size.
 --adjoint-backward adds the backward of the adjoint (fsg_slice_acq_adjoint_backward_f32) on the same problem:
 `adjoint_backward_<mode>[_eq]_<leg>_ms` for grad_slices alone, grad_transforms alone and both, in both modes, equalize off and
 on (the pre-pass over the gradient included), and its ratios to forward_<mode>_ms and, with --backward, to
@@ -103,6 +105,21 @@ def main():
         out["backward_workspace_bytes"] = int(lib.fsg_slice_acq_backward_ws_bytes(a.slices, ss, ss))
         t1, t2 = (K.slice_acq_backward(tr, vol, None, None, psf, gs, rs, need_vol_grad=False)[1] for _ in range(2))
         out["backward_grad_transforms_twice_equal"] = bool(torch.equal(t1, t2))
+        if a.deterministic:
+            # the fixed-point grad_vol (fsg_slice_acq_backward_det_f32) on the same inputs, right after the float legs above,
+            # which are the yardstick: grad_vol alone and with grad_transforms, in both modes
+            for mode, ipsf in (("linear", False), ("nearest_psf", True)):
+                for leg, kw in (("grad_vol", dict(need_transforms_grad=False)), ("both", {})):
+                    fn = lambda: K.slice_acq_backward(tr, vol, None, None, psf, gs, rs, interp_psf=ipsf, deterministic=True, **kw)  # noqa: E731
+                    out[f"backward_{mode}_{leg}_det_ms"] = round(timed(fn, a.reps), 3)
+                    out[f"backward_{mode}_{leg}_det_over_float"] = round(
+                        out[f"backward_{mode}_{leg}_det_ms"] / out[f"backward_{mode}_{leg}_ms"], 2)
+            out["backward_det_workspace_bytes"] = int(lib.fsg_slice_acq_backward_det_ws_bytes(*vs))
+            bdet = lambda: K.slice_acq_backward(tr, vol, None, None, psf, gs, rs, need_transforms_grad=False, deterministic=True)[0]  # noqa: E731
+            d1 = bdet()
+            out["backward_det_twice_equal"] = bool(torch.equal(d1, bdet()))
+            out["backward_det_vs_float_max_abs"] = float(
+                (d1 - K.slice_acq_backward(tr, vol, None, None, psf, gs, rs, need_transforms_grad=False)[0]).abs().max())
     if a.adjoint_backward:
         # backward of the adjoint (fsg_slice_acq_adjoint_backward_f32): the slices of the forward, a random gradient on the
         # volume; with equalize, the volume and weight of the equalised adjoint of the same mode
