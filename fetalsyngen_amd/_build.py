@@ -26,7 +26,7 @@ def needs_build() -> bool:
     if not LIB.exists():
         return True
     t = LIB.stat().st_mtime
-    deps = [CSRC / s for s in SOURCES] + [CSRC / "fsg_common.h", CSRC / "fsg_sa.h", PKG.parent / "include" / "fsg_hip.h"]
+    deps = [CSRC / s for s in SOURCES] + [CSRC / "fsg_common.h", CSRC / "fsg_ride.h", CSRC / "fsg_sa.h", PKG.parent / "include" / "fsg_hip.h"]
     return any(d.stat().st_mtime > t for d in deps)
 
 
@@ -42,7 +42,7 @@ def build(force: bool = False, verbose: bool = False) -> Path:
         lang = ["-x", "hip"] if s.endswith(".cpp") else []
         cmd = [cc, *FLAGS, *EXTRA, *lang, "-c", str(CSRC / s), "-o", str(o)]
         objs.append(str(o))
-        deps = [CSRC / s, CSRC / "fsg_common.h", CSRC / "fsg_sa.h", PKG.parent / "include" / "fsg_hip.h", Path(__file__)]
+        deps = [CSRC / s, CSRC / "fsg_common.h", CSRC / "fsg_ride.h", CSRC / "fsg_sa.h", PKG.parent / "include" / "fsg_hip.h", Path(__file__)]
         if not force and not EXTRA and o.exists() and all(d.stat().st_mtime < o.stat().st_mtime for d in deps):
             continue  # object is newer than its source and the shared headers
         jobs.append(cmd)

@@ -370,9 +370,12 @@ struct HeadGmm {
 };
 
 // 8 waves/SIMD (<= 64 VGPRs) as the stand-alone GMM kernel has: the face job alone would take 73 and cap the launch at 6
+// HAS_DRAW: the NEXT sample's keyed draw job (fsg_ride.h; fsg_sample_plan::ride_draw) in workgroups [nfaces, nfaces + ndraw).
+// It touches nothing of this sample, borrows the GMM job's s_mu table (a workgroup does one job) and, like the faces, is a
+// dependent chain that should start before the bandwidth-bound jobs fill the machine.  ndraw == 0: no job, P is not read.
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))) void sample_head_kernel(HeadGmm G, FsgDeformK D, EpiK E, float* __restrict__ rows,
                                                           int stride, int rows_gx, int nrows, int nfaces,
-                                                          int32_t* __restrict__ mm3) {
+                                                          int32_t* __restrict__ mm3, int ndraw, const fsg_ride::DrawK P) {
   __shared__ float s_mu[256], s_sg[256];
   __shared__ float red[3][4];
   union HeadSmem {  // a workgroup does one job: the rows job's block and the codes mode's (mu, sigma) table share the space
@@ -381,12 +384,17 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))) voi
   };
   __shared__ HeadSmem U;
   RowsSmem& S = U.rows;
-  int b = blockIdx.x;  // workgroup-uniform branches: a workgroup does exactly one of the three jobs
+  int b = blockIdx.x;  // workgroup-uniform branches: a workgroup does exactly one of the jobs
   if (b < nfaces) {  // the longest dependent chain first
     coords_faces_min_body(D, mm3, red, b, nfaces);
     return;
   }
   b -= nfaces;
+  if (b < ndraw) {
+    fsg_ride::keyed_draw_body(P, b, s_mu);
+    return;
+  }
+  b -= ndraw;
   if (b < nrows) {
     deform_rows_block(D, E, rows, stride, b / rows_gx, (b % rows_gx) * RB_J, S);
     return;
@@ -394,7 +402,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))) voi
   b -= nrows;
   if (G.ntuples > 0) {  // codes mode (fsg_ride.h)
     const fsg_ride::GmmCodesK C{G.l0, G.l1, G.ntuples, G.stride, G.sel, G.n, G.mus, G.sigmas, G.ntab, G.seed, G.stream_id, G.out};
-    fsg_ride::gmm_codes_job(C, U.code_ms, (unsigned)b, gridDim.x - (unsigned)(nrows + nfaces));
+    fsg_ride::gmm_codes_job(C, U.code_ms, (unsigned)b, gridDim.x - (unsigned)(nrows + nfaces + ndraw));
     return;
   }
   for (int t = threadIdx.x; t < 256; t += blockDim.x) {
@@ -403,7 +411,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))) voi
   }
   __syncthreads();
   fsg_gmm_x4_loop(G.l0, G.l1, G.l2, G.l3, G.n, s_mu, s_sg, G.noise, G.seed, G.stream_id, G.out, (unsigned)b,
-                  gridDim.x - (unsigned)(nrows + nfaces));
+                  gridDim.x - (unsigned)(nrows + nfaces + ndraw));
 }
 
 constexpr int WARP_ROWS_PER_WAVE = 4;
@@ -712,15 +720,6 @@ __global__ __launch_bounds__(256) void coords_minmax_rows_kernel(FsgDeformK D, i
   coords_minmax_rows_body<MIN_ONLY>(D, mm6, rows_per_block, (int)blockIdx.x);
 }
 
-// The conditional floor(min) pass with the NEXT sample's keyed draw job beside it (fsg_sample_plan::ride_draw): both are a few
-// workgroups of latency, and as launches of their own each costs ~5 us of the step.  Workgroups [0, nrest): the pass;
-// [nrest, nrest + draw workgroups): the draw (fsg_ride.h), which touches nothing of this sample.
-__global__ __launch_bounds__(256) void floormin_ride_kernel(FsgDeformK D, int32_t* __restrict__ mm6, int rows_per_block, int nrest,
-                                                            const fsg_ride::DrawK P) {
-  if ((int)blockIdx.x < nrest) coords_minmax_rows_body<true>(D, mm6, rows_per_block, (int)blockIdx.x);
-  else fsg_ride::keyed_draw_body(P, (int)blockIdx.x - nrest);
-}
-
 template <bool MIN_ONLY>
 __device__ __forceinline__ void coords_minmax_rows_body(const FsgDeformK& D, int32_t* __restrict__ mm6, int rows_per_block, int blk) {
   if (MIN_ONLY) {  // floor(min) already known to be 0 on every axis: nothing to add (block-uniform exit)
@@ -1012,49 +1011,36 @@ int fsg_coords_floormin_rest_f32(const fsg_deform* d, int32_t* mm3, void* stream
 }
 
 static int launch_sample_head(const HeadGmm& G, size_t n, const fsg_deform* d, const fsg_epilogue* epi, float* rows,
-                              int row_stride, int32_t* mm3, void* stream);
+                              int row_stride, int32_t* mm3, const void* drawk, unsigned draw_blocks, void* stream);
 
-// ---- internal entry points of the look-ahead (fsg_pipeline.cpp; not part of include/fsg_hip.h) ------------------------------
-// the conditional floor(min) pass + the next sample's draw job (drawk: a fsg_ride::DrawK on the host)
-extern "C" int fsg_internal_floormin_rest_ride(const fsg_deform* d, int32_t* mm3, const void* drawk, unsigned draw_blocks, void* stream) {
-  FsgDeformK D;
-  int rc = fsg_fill_deform(d, D);
-  if (rc) return rc;
-  if (!mm3 || !drawk || draw_blocks == 0 || draw_blocks > 4096) return FSG_E_BADARG;
-  if ((D.field ? 3 * D.f2 : 0) > ROWCAP) return FSG_E_TOOBIG;
-  const int rows = D.n0 * D.n1;
-  int grid = (rows + 7) / 8 < 512 ? (rows + 7) / 8 : 512;
-  const int rpb = (rows + grid - 1) / grid;
-  grid = (rows + rpb - 1) / rpb;
-  hipLaunchKernelGGL(floormin_ride_kernel, dim3((unsigned)grid + draw_blocks), dim3(256), 0, fsg_stream(stream), D, mm3, rpb, grid,
-                     *reinterpret_cast<const fsg_ride::DrawK*>(drawk));
-  FSG_RETURN_LAUNCH();
-}
-
-// the one-launch head of a sample whose intensities are given (fsg_sample_image::prior_in): the rows and faces jobs, no GMM job
+// ---- internal entry points of fsg_pipeline.cpp (not part of include/fsg_hip.h) ------------------------------------------------
+// The one-launch head with the look-ahead's job beside it: drawk (a fsg_ride::DrawK on the host, NULL = none) is the NEXT
+// sample's keyed draw job of draw_blocks workgroups, 1 .. FSG_HEAD_DRAW_MAX (the caller launches a larger job on its own).
+// fsg_internal_head_no_gmm: a sample whose intensities are given (fsg_sample_image::prior_in) -- rows and faces jobs, no GMM job.
 extern "C" int fsg_internal_head_no_gmm(size_t n, const fsg_deform* d, const fsg_epilogue* epi, float* rows, int row_stride,
-                                        int32_t* mm3, void* stream) {
+                                        int32_t* mm3, const void* drawk, unsigned draw_blocks, void* stream) {
   if (n == 0 || !mm3) return FSG_E_BADARG;
   HeadGmm G{};  // G.out == nullptr: no workgroup is launched for the GMM job
   G.n = n;
-  return launch_sample_head(G, n, d, epi, rows, row_stride, mm3, stream);
+  return launch_sample_head(G, n, d, epi, rows, row_stride, mm3, drawk, draw_blocks, stream);
 }
 
-int fsg_sample_head_f32(const uint8_t* l0, const uint8_t* l1, const uint8_t* l2, const uint8_t* l3, size_t n,
-                        const float* mus, const float* sigmas, int ntab, const float* noise, uint64_t seed,
-                        uint64_t stream_id, float* out, const fsg_deform* d, const fsg_epilogue* epi, float* rows,
-                        int row_stride, int32_t* mm3, void* stream) {
+extern "C" int fsg_internal_head_f32(const uint8_t* l0, const uint8_t* l1, const uint8_t* l2, const uint8_t* l3, size_t n,
+                                     const float* mus, const float* sigmas, int ntab, const float* noise, uint64_t seed,
+                                     uint64_t stream_id, float* out, const fsg_deform* d, const fsg_epilogue* epi, float* rows,
+                                     int row_stride, int32_t* mm3, const void* drawk, unsigned draw_blocks, void* stream) {
   if (n == 0 || !l0 || !mus || !sigmas || !out || ntab <= 0 || ntab > 256 || !mm3) return FSG_E_BADARG;
   const uintptr_t al = (uintptr_t)l0 | (uintptr_t)l1 | (uintptr_t)l2 | (uintptr_t)l3;
   if ((al & 3) || ((uintptr_t)out & 15)) return FSG_E_ALIGN;
   HeadGmm G{l0, l1, l2, l3, n, mus, sigmas, ntab, noise, seed, stream_id, out, 0, 0, 0u};
-  return launch_sample_head(G, n, d, epi, rows, row_stride, mm3, stream);
+  return launch_sample_head(G, n, d, epi, rows, row_stride, mm3, drawk, draw_blocks, stream);
 }
 
-int fsg_sample_head_codes_f32(const uint16_t* codes, const uint8_t* tuples, int ntuples, int stride, const int32_t sel[4],
-                              size_t n, const float* mus, const float* sigmas, int ntab, uint64_t seed, uint64_t stream_id,
-                              float* out, const fsg_deform* d, const fsg_epilogue* epi, float* rows, int row_stride,
-                              int32_t* mm3, void* stream) {
+extern "C" int fsg_internal_head_codes_f32(const uint16_t* codes, const uint8_t* tuples, int ntuples, int stride,
+                                           const int32_t sel[4], size_t n, const float* mus, const float* sigmas, int ntab,
+                                           uint64_t seed, uint64_t stream_id, float* out, const fsg_deform* d,
+                                           const fsg_epilogue* epi, float* rows, int row_stride, int32_t* mm3, const void* drawk,
+                                           unsigned draw_blocks, void* stream) {
   if (n == 0 || !codes || !tuples || !sel || !mus || !sigmas || !out || ntab <= 0 || ntab > 256 || !mm3) return FSG_E_BADARG;
   if (ntuples <= 0 || stride <= 0 || stride > 256) return FSG_E_BADARG;
   for (int m = 0; m < 4; ++m)
@@ -1063,17 +1049,34 @@ int fsg_sample_head_codes_f32(const uint16_t* codes, const uint8_t* tuples, int 
   if ((n & 7) || ((uintptr_t)codes & 15) || ((uintptr_t)out & 15)) return FSG_E_ALIGN;
   HeadGmm G{reinterpret_cast<const uint8_t*>(codes), tuples, nullptr, nullptr, n, mus, sigmas, ntab, nullptr, seed, stream_id, out,
             ntuples, stride, (uint32_t)sel[0] | ((uint32_t)sel[1] << 8) | ((uint32_t)sel[2] << 16) | ((uint32_t)sel[3] << 24)};
-  return launch_sample_head(G, n, d, epi, rows, row_stride, mm3, stream);
+  return launch_sample_head(G, n, d, epi, rows, row_stride, mm3, drawk, draw_blocks, stream);
+}
+
+int fsg_sample_head_f32(const uint8_t* l0, const uint8_t* l1, const uint8_t* l2, const uint8_t* l3, size_t n,
+                        const float* mus, const float* sigmas, int ntab, const float* noise, uint64_t seed,
+                        uint64_t stream_id, float* out, const fsg_deform* d, const fsg_epilogue* epi, float* rows,
+                        int row_stride, int32_t* mm3, void* stream) {
+  return fsg_internal_head_f32(l0, l1, l2, l3, n, mus, sigmas, ntab, noise, seed, stream_id, out, d, epi, rows, row_stride, mm3,
+                               nullptr, 0u, stream);
+}
+
+int fsg_sample_head_codes_f32(const uint16_t* codes, const uint8_t* tuples, int ntuples, int stride, const int32_t sel[4],
+                              size_t n, const float* mus, const float* sigmas, int ntab, uint64_t seed, uint64_t stream_id,
+                              float* out, const fsg_deform* d, const fsg_epilogue* epi, float* rows, int row_stride,
+                              int32_t* mm3, void* stream) {
+  return fsg_internal_head_codes_f32(codes, tuples, ntuples, stride, sel, n, mus, sigmas, ntab, seed, stream_id, out, d, epi, rows,
+                                     row_stride, mm3, nullptr, 0u, stream);
 }
 
 static int launch_sample_head(const HeadGmm& G, size_t n, const fsg_deform* d, const fsg_epilogue* epi, float* rows,
-                              int row_stride, int32_t* mm3, void* stream) {
+                              int row_stride, int32_t* mm3, const void* drawk, unsigned draw_blocks, void* stream) {
   FsgDeformK D;
   int rc = fsg_fill_deform(d, D);
   if (rc) return rc;
   EpiK E;
   rc = fill_epilogue(epi, E);
   if (rc) return rc;
+  if (drawk ? (draw_blocks == 0 || draw_blocks > FSG_HEAD_DRAW_MAX) : draw_blocks != 0) return FSG_E_BADARG;
   const int need = (D.field ? 3 * D.f2 : 0) + (E.bias ? E.b2 : 0);
   if (need > 0 && (!rows || row_stride < need)) return FSG_E_BADARG;
   if ((size_t)D.n0 * D.n1 * D.n2 != n) return FSG_E_BADARG;
@@ -1089,8 +1092,10 @@ static int launch_sample_head(const HeadGmm& G, size_t n, const fsg_deform* d, c
   if (ngmm > 4096) ngmm = 4096;  // 4 groups per thread: 33.8 us (8 192: 34.8, 16 384: 39.0); codes mode, 2 x 8 voxels per thread: 30.5 us
                                  // (1 024: 34.7, 2 048: 37.0, 8 192: 33.6)
   if (nrows > 1000000) return FSG_E_TOOBIG;
-  hipLaunchKernelGGL(sample_head_kernel, dim3((unsigned)(nrows + nfaces + ngmm)), dim3(256), 0, fsg_stream(stream), G, D,
-                     E, rows, row_stride, rows_gx > 0 ? rows_gx : 1, (int)nrows, nfaces, mm3);
+  static const fsg_ride::DrawK no_draw = {};
+  hipLaunchKernelGGL(sample_head_kernel, dim3((unsigned)(nrows + nfaces + ngmm) + draw_blocks), dim3(256), 0, fsg_stream(stream), G,
+                     D, E, rows, row_stride, rows_gx > 0 ? rows_gx : 1, (int)nrows, nfaces, mm3, (int)draw_blocks,
+                     drawk ? *reinterpret_cast<const fsg_ride::DrawK*>(drawk) : no_draw);
   FSG_RETURN_LAUNCH();
 }
 

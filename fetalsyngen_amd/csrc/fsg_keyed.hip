@@ -241,7 +241,10 @@ int draw(const KeyedCtx& C, uint64_t key, const fsg_keyed_overrides* o, fsg_keye
 // ---- the draw kernel -------------------------------------------------------------------------------------------------------
 using fsg_ride::DrawK;
 
-__global__ __launch_bounds__(256) void keyed_draw_kernel(const DrawK P) { fsg_ride::keyed_draw_body(P, (int)blockIdx.x); }
+__global__ __launch_bounds__(256) void keyed_draw_kernel(const DrawK P) {
+  __shared__ float s_mu[256];
+  fsg_ride::keyed_draw_body(P, (int)blockIdx.x, s_mu);
+}
 
 // the draw job's argument block and its number of workgroups
 int fill_draw(const KeyedCtx& C, const fsg_keyed_draws& d, void* block_dev, DrawK& P, unsigned& grid) {
@@ -268,6 +271,90 @@ int fill_draw(const KeyedCtx& C, const fsg_keyed_draws& d, void* block_dev, Draw
   const int work = ((P.nbias + 3) >> 2) + ((P.nfield + 3) >> 2);
   grid = 1u + (unsigned)((work + 255) / 256);
   return 0;
+}
+
+// ---- host verdict: "floor(min) is settled" ---------------------------------------------------------------------------------
+// Element e of the coarse displacement grid as keyed_draw_body writes it (stream 3, four normals per Philox block, scaled by
+// the float32 std), in double: the device's v_log / v_sqrt / v_sin / v_cos Box-Muller differs from this by rounding only.
+double field_value_host(uint64_t key, float field_std, uint32_t e) {
+  const U4 r = philox_host(e >> 2, 0u, 3u, 0u, (uint32_t)key, (uint32_t)(key >> 32));
+  const double S = 5.9604644775390625e-08;  // 2^-24
+  const bool second = (e & 2u) != 0;
+  const double u = (double)(((second ? r.z : r.x) >> 8) + 1u) * S, t = (double)((second ? r.w : r.y) >> 8) * S;
+  const double rad = std::sqrt(-2.0 * std::log(u)), ang = 6.283185307179586476925286766559 * t;
+  return (double)field_std * (rad * ((e & 1u) ? std::sin(ang) : std::cos(ang)));
+}
+
+// True only when the faces job of the one-launch head (coords_faces_min_body, fsg_deform.hip) is PROVED to leave all three
+// floor(min) keys below key(1.0): the conditional full pass behind it would then return at once and need not be launched.
+// The eight corner voxels are among the faces job's voxels (first and last index of every axis).  For each, fsg_position's
+// value in double: p = index - centre + displacement, x = A p + c2, clamped to [0, n-1].  The displacement is a convex
+// combination (tap weights w_lo + w_hi = 1, both >= 0) of coarse nodes.  Which nodes and which weights is the device table's
+// business; what is used here holds for every table zoom_table builds for a coarse grid no finer than the volume: the first
+// voxel of an axis reads nodes {0, 1} at most, the last one {f-2, f-1}.  So each component lies in the interval spanned by the
+// <= 2x2x2 nodes of the corner's cell, re-drawn here with the draw job's own counters, and x is at most the sum of the
+// per-term maxima.  An axis is settled when some corner's upper bound is below 1 - margin; the clamp only lowers a value
+// below 1 further or leaves it.  margin = 0.25 voxel + 1e-4 of the summed magnitudes of the terms: fp32 evaluation of ~10
+// operations (<= 1e-6 relative) and the hardware transcendentals (|dz| <~ 1e-5 on |z| <= 5.8) stay two orders below it.
+// NaN or infinity anywhere fails every comparison: not settled.  Overrides are in `d` already (A, std, grid size).
+bool floormin_settled(const fsg_keyed_config& c, const fsg_keyed_draws& d) {
+  if (!d.deform_active) return false;
+  const bool field = d.nonlinear && d.field_dims[0] > 0 && d.field_dims[1] > 0 && d.field_dims[2] > 0;
+  if (d.nonlinear && !field) return false;
+  if (field)
+    for (int a = 0; a < 3; ++a)
+      if (d.field_dims[a] > c.shape[a]) return false;  // a grid finer than the volume: end voxels may read inner nodes
+  const float field_std = (float)d.nonlin_std;
+  bool settled[3] = {false, false, false};
+  for (int corner = 0; corner < 8 && !(settled[0] && settled[1] && settled[2]); ++corner) {
+    double p[3], lo[3] = {0, 0, 0}, hi[3] = {0, 0, 0};
+    int node0[3], nodes[3];
+    for (int a = 0; a < 3; ++a) {
+      const bool last = (corner >> a) & 1;
+      p[a] = (double)(last ? c.shape[a] - 1 : 0) - (double)(float)((c.size[a] - 1) / 2.0);
+      const int f = field ? d.field_dims[a] : 1;
+      nodes[a] = f < 2 ? f : 2;
+      node0[a] = last ? f - nodes[a] : 0;
+    }
+    // without the displacement first: a corner that settles nothing open even at the nodes' far end is not worth 48 draws
+    if (field) {
+      bool useful = false;
+      for (int a = 0; a < 3; ++a) {
+        const float* A = d.A + 3 * a;
+        const double x = (double)A[0] * p[0] + (double)A[1] * p[1] + (double)A[2] * p[2] + (double)(float)d.c2[a];
+        if (!settled[a] && x < 1.0) useful = true;
+      }
+      if (!useful) continue;
+      for (int ch = 0; ch < 3; ++ch) {
+        lo[ch] = INFINITY;
+        hi[ch] = -INFINITY;
+      }
+      for (int i = 0; i < nodes[0]; ++i)
+        for (int j = 0; j < nodes[1]; ++j)
+          for (int k = 0; k < nodes[2]; ++k) {
+            const uint32_t node = (uint32_t)(((node0[0] + i) * d.field_dims[1] + node0[1] + j) * d.field_dims[2] + node0[2] + k);
+            for (uint32_t ch = 0; ch < 3; ++ch) {
+              const double v = field_value_host(d.key, field_std, 3u * node + ch);
+              lo[ch] = std::fmin(lo[ch], v);
+              hi[ch] = std::fmax(hi[ch], v);
+              if (!(v == v)) lo[ch] = hi[ch] = NAN;
+            }
+          }
+    }
+    for (int a = 0; a < 3; ++a) {
+      if (settled[a]) continue;
+      const float* A = d.A + 3 * a;
+      double ub = (double)(float)d.c2[a], mag = std::fabs(ub);
+      for (int ch = 0; ch < 3; ++ch) {
+        const double w = (double)A[ch], t0 = w * (p[ch] + lo[ch]), t1 = w * (p[ch] + hi[ch]);
+        ub += std::fmax(t0, t1);
+        mag += std::fmax(std::fabs(t0), std::fabs(t1));
+        if (!(t0 == t0) || !(t1 == t1)) ub = NAN;
+      }
+      if (ub < 1.0 - (0.25 + 1e-4 * mag)) settled[a] = true;
+    }
+  }
+  return settled[0] && settled[1] && settled[2];
 }
 
 int launch_draw(const KeyedCtx& C, const fsg_keyed_draws& d, void* block_dev, void* stream) {
@@ -347,6 +434,20 @@ int fsg_keyed_draw_with(void* ctx, uint64_t key, const fsg_keyed_overrides* over
 int fsg_keyed_fill_block(void* ctx, const fsg_keyed_draws* d, void* block_dev, void* stream) {
   if (!ctx || !d) return FSG_E_BADARG;
   return launch_draw(*(KeyedCtx*)ctx, *d, block_dev, stream);
+}
+
+// fsg_pipeline.cpp: fsg_sample_run_image with the verdict above (not part of the public header)
+int fsg_internal_sample_run(const fsg_sample_plan* p, const fsg_sample_image* im, int floormin_settled, void* stream);
+
+// The verdict for (key, overrides) as fsg_keyed_sample_run reaches it: 1 settled, 0 not, < 0 an error of the draws.  Host only;
+// for the tests and for measuring the share of samples that go without the launch (not part of the public header).
+int fsg_internal_keyed_floormin_settled(void* ctx, uint64_t key, const fsg_keyed_overrides* overrides) {
+  if (!ctx) return FSG_E_BADARG;
+  const KeyedCtx& K = *(KeyedCtx*)ctx;
+  fsg_keyed_draws d;
+  const int rc = draw(K, key, overrides, d);
+  if (rc) return rc < 0 ? rc : -rc;
+  return floormin_settled(K.cfg, d) ? 1 : 0;
 }
 
 int fsg_keyed_sample_run(void* ctx, const int64_t* iv, int niv, fsg_keyed_draws* draws_out, void* stream) {
@@ -466,9 +567,9 @@ int fsg_keyed_sample_run(void* ctx, const int64_t* iv, int niv, fsg_keyed_draws*
   q.ev_blur_begin = (void*)(uintptr_t)iv[FSG_KEYED_I_EV_BLUR_BEGIN];
   q.ev_blur_end = (void*)(uintptr_t)iv[FSG_KEYED_I_EV_BLUR_END];
 
-  // ---- look-ahead: the caller names the next sample of this stream; its draw job rides in this sample's floor(min) launch -----
+  // ---- look-ahead: the caller names the next sample of this stream; its draw job rides in this sample's head launch -----------
   const int64_t flags = iv[FSG_KEYED_I_FLAGS];
-  // this sample's block was filled beside the previous sample's floor(min) pass (never one with overrides: a carried job drew every table)
+  // this sample's block was filled beside the previous sample's head (never one with overrides: a carried job drew every table)
   const bool draw_done = (flags & 1) != 0 && !ov;
   DrawK next_draw;
   int32_t rode = 0;
@@ -481,9 +582,11 @@ int fsg_keyed_sample_run(void* ctx, const int64_t* iv, int niv, fsg_keyed_draws*
     unsigned grid = 0;
     rc = fill_draw(*K, dn, nbase, next_draw, grid);
     if (rc) return rc;
-    q.ride_draw = &next_draw;
-    q.ride_draw_blocks = grid;
-    q.rode = &rode;
+    if (grid <= FSG_HEAD_DRAW_MAX) {  // (a larger job is not carried: the next call finds rode = 0 and launches it itself)
+      q.ride_draw = &next_draw;
+      q.ride_draw_blocks = grid;
+      q.rode = &rode;
+    }
   }
 
   if (!draw_done && q.trace_events && q.trace_ids && q.trace_cap > 1) {  // stage trace: an event before the draw kernel, the next one behind it
@@ -498,7 +601,7 @@ int fsg_keyed_sample_run(void* ctx, const int64_t* iv, int niv, fsg_keyed_draws*
     rc = launch_draw(*K, d, base, stream);
     if (rc) return rc;
   }
-  rc = fsg_sample_run_image(&q, &im, stream);
+  rc = fsg_internal_sample_run(&q, &im, floormin_settled(c, d) ? 1 : 0, stream);
   if (draws_out) draws_out->rode = rode;
   return rc;
 }

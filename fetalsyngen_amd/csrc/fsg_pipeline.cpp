@@ -9,11 +9,19 @@
 #include <cstddef>
 #include "../../include/fsg_hip.h"
 
-// look-ahead launches (fsg_deform.hip, fsg_zoom.hip): not part of the public header
-extern "C" int fsg_internal_floormin_rest_ride(const fsg_deform* d, int32_t* mm3, const void* drawk, unsigned draw_blocks, void* stream);
-// the one-launch head without its GMM job (fsg_deform.hip; fsg_sample_image::prior_in)
+// The one-launch head with the look-ahead's draw job beside it (fsg_deform.hip; not part of the public header): the public
+// fsg_sample_head_* entry points plus (drawk, draw_blocks), and the form without a GMM job (fsg_sample_image::prior_in).
 extern "C" int fsg_internal_head_no_gmm(size_t n, const fsg_deform* d, const fsg_epilogue* epi, float* rows, int row_stride,
-                                        int32_t* mm3, void* stream);
+                                        int32_t* mm3, const void* drawk, unsigned draw_blocks, void* stream);
+extern "C" int fsg_internal_head_f32(const uint8_t* l0, const uint8_t* l1, const uint8_t* l2, const uint8_t* l3, size_t n,
+                                     const float* mus, const float* sigmas, int ntab, const float* noise, uint64_t seed,
+                                     uint64_t stream_id, float* out, const fsg_deform* d, const fsg_epilogue* epi, float* rows,
+                                     int row_stride, int32_t* mm3, const void* drawk, unsigned draw_blocks, void* stream);
+extern "C" int fsg_internal_head_codes_f32(const uint16_t* codes, const uint8_t* tuples, int ntuples, int stride,
+                                           const int32_t sel[4], size_t n, const float* mus, const float* sigmas, int ntab,
+                                           uint64_t seed, uint64_t stream_id, float* out, const fsg_deform* d,
+                                           const fsg_epilogue* epi, float* rows, int row_stride, int32_t* mm3, const void* drawk,
+                                           unsigned draw_blocks, void* stream);
 
 
 extern int g_tuning_flags;
@@ -34,7 +42,15 @@ extern "C" int fsg_pipeline_teardown(void) { return 0; }
 
 extern "C" int fsg_sample_run(const fsg_sample_plan* p, void* stream) { return fsg_sample_run_image(p, nullptr, stream); }
 
+extern "C" int fsg_internal_sample_run(const fsg_sample_plan* p, const fsg_sample_image* im, int floormin_settled, void* stream);
 extern "C" int fsg_sample_run_image(const fsg_sample_plan* p, const fsg_sample_image* im, void* stream) {
+  return fsg_internal_sample_run(p, im, 0, stream);
+}
+
+// floormin_settled (fsg_keyed_sample_run's host verdict, fsg_keyed.hip): the caller has PROVED that the faces job of the fused
+// head leaves every floor(min) key below key(1.0), so the conditional full pass behind it would return at once -- it is not
+// launched (FSG_TUNE_NO_FLOORMIN_SKIP: launched all the same).  0: no such proof, the pass runs as ever.
+extern "C" int fsg_internal_sample_run(const fsg_sample_plan* p, const fsg_sample_image* im, int floormin_settled, void* stream) {
   if (!p || !p->out || !p->ws0 || !p->ws1 || !p->mm8) return FSG_E_BADARG;
   const int n0 = p->shape[0], n1 = p->shape[1], n2 = p->shape[2];
   if (n0 <= 0 || n1 <= 0 || n2 <= 0) return FSG_E_BADARG;
@@ -72,22 +88,25 @@ extern "C" int fsg_sample_run_image(const fsg_sample_plan* p, const fsg_sample_i
     FSG_TRY(mark(FSG_ST_UPLOAD));
   }
   int head_rc = 0;
+  const void* const ride = p->ride_draw && p->ride_draw_blocks ? p->ride_draw : nullptr;  // + the next sample's draw job
+  const unsigned ride_blocks = ride ? p->ride_draw_blocks : 0u;
   if (fused_head) {
     // K1 + per-row coarse values + six-face minimum in one launch (keys arrive initialised with the parameters)
     dh.rows = nullptr;
     dh.row_stride = 0;
     head_rc = FSG_E_ALIGN;
     if (prior)  // rows + faces; the GMM job has nothing to draw
-      head_rc = fsg_internal_head_no_gmm(n, &dh, &p->epi, p->ws_rows, p->row_stride, p->mm8, stream);
+      head_rc = fsg_internal_head_no_gmm(n, &dh, &p->epi, p->ws_rows, p->row_stride, p->mm8, ride, ride_blocks, stream);
     else if (p->label_codes && p->code_tuples && !p->gmm_noise && !(g_tuning_flags & FSG_TUNE_NO_SEED_CODES))  // 6 instead of 8 B/voxel
-      head_rc = fsg_sample_head_codes_f32(p->label_codes, p->code_tuples, p->code_ntuples, p->code_stride, p->code_sel, n, p->mus,
-                                          p->sigmas, p->ntab, p->gmm_seed, p->gmm_stream, p->ws0, &dh, &p->epi, p->ws_rows,
-                                          p->row_stride, p->mm8, stream);
+      head_rc = fsg_internal_head_codes_f32(p->label_codes, p->code_tuples, p->code_ntuples, p->code_stride, p->code_sel, n, p->mus,
+                                            p->sigmas, p->ntab, p->gmm_seed, p->gmm_stream, p->ws0, &dh, &p->epi, p->ws_rows,
+                                            p->row_stride, p->mm8, ride, ride_blocks, stream);
     if (!prior && (head_rc == FSG_E_ALIGN || head_rc == FSG_E_TOOBIG))  // no codes, or outside their domain: the four label volumes
-      head_rc = fsg_sample_head_f32(p->label_parts[0], p->label_parts[1], p->label_parts[2], p->label_parts[3], n, p->mus,
-                                    p->sigmas, p->ntab, p->gmm_noise, p->gmm_seed, p->gmm_stream, p->ws0, &dh, &p->epi,
-                                    p->ws_rows, p->row_stride, p->mm8, stream);
+      head_rc = fsg_internal_head_f32(p->label_parts[0], p->label_parts[1], p->label_parts[2], p->label_parts[3], n, p->mus,
+                                      p->sigmas, p->ntab, p->gmm_noise, p->gmm_seed, p->gmm_stream, p->ws0, &dh, &p->epi,
+                                      p->ws_rows, p->row_stride, p->mm8, ride, ride_blocks, stream);
     if (head_rc == 0) head_done = true;
+    if (head_done && ride) rode |= 1;
     if (head_done) FSG_TRY(mark(FSG_ST_HEAD));
   }
   if (head_rc != 0 && head_rc != FSG_E_TOOBIG && head_rc != FSG_E_ALIGN) return head_rc;
@@ -118,13 +137,10 @@ extern "C" int fsg_sample_run_image(const fsg_sample_plan* p, const fsg_sample_i
     if (head_done) {
       d.rows = p->ws_rows;
       d.row_stride = p->row_stride;
-      if (p->ride_draw && p->ride_draw_blocks) {  // + the next sample's draw job (fsg_sample_plan::ride_draw)
-        FSG_TRY(fsg_internal_floormin_rest_ride(&d, p->mm8, p->ride_draw, p->ride_draw_blocks, stream));
-        rode |= 1;
-      } else {
+      if (!floormin_settled || (g_tuning_flags & FSG_TUNE_NO_FLOORMIN_SKIP)) {
         FSG_TRY(fsg_coords_floormin_rest_f32(&d, p->mm8, stream));
+        FSG_TRY(mark(FSG_ST_FLOORMIN));
       }
-      FSG_TRY(mark(FSG_ST_FLOORMIN));
     } else {
       if (p->ws_rows && need > 0 && need <= p->row_stride) {
         d.rows = nullptr;

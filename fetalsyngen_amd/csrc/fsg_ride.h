@@ -1,11 +1,13 @@
-// Device jobs that more than one launch carries: the keyed draw job (its own kernel in fsg_keyed.hip; beside the floor(min)
-// pass in fsg_deform.hip when the caller named the next sample: fsg_sample_plan::ride_draw) and the code-volume GMM job of the
+// Device jobs that more than one launch carries: the keyed draw job (its own kernel in fsg_keyed.hip; beside the head
+// launch in fsg_deform.hip when the caller named the next sample: fsg_sample_plan::ride_draw) and the code-volume GMM job of the
 // head kernel.  (The GMM job of the NEXT sample beside the zoom-back launches was built and measured in r03 -- K9b 27 -> 52-61 us,
 // K9a 18 -> 45-55 us for a job that costs ~21 us in the head kernel: the two slow each other down -- and removed again.)
 #pragma once
 #include "fsg_common.h"
 
 #define FSG_MM_NSLOTS 64      // slots of the sharded K9 keys (generator/model.py: MM_NSLOTS; fsg_zoom3d_minmax_sharded_f32: 2..64)
+
+#define FSG_HEAD_DRAW_MAX 4096u // most workgroups of a keyed draw job the head launch carries; a larger job is a launch of its own
 
 namespace fsg_ride {
 
@@ -39,7 +41,8 @@ __device__ __forceinline__ float keyed_uniform(uint64_t key, uint64_t stream, ui
 // entry is read before the barrier and stored after the last one, so it may be the block's own table --, the tie step and
 // the stores are the same).  Workgroups >= 1: one Philox block (4 normals) per thread of
 // the bias grid (stream 4, synthseg.py:172-176) and the coarse displacement grid (stream 3, affine_nonrigid.py:318).
-__device__ __forceinline__ void keyed_draw_body(const DrawK& P, const int blk) {
+// s_mu: 256 floats of LDS (the caller's, so that a carrying kernel can lend space it already has).
+__device__ __forceinline__ void keyed_draw_body(const DrawK& P, const int blk, float* s_mu) {
   const int tid = threadIdx.x;
   if (blk == 0) {
     if (tid < 8) P.mm8[tid] = tid < 4 ? KEY_POS_INF : KEY_NEG_INF;
@@ -47,7 +50,6 @@ __device__ __forceinline__ void keyed_draw_body(const DrawK& P, const int blk) {
       const int f = q % FSG_MM_SLOT_STRIDE;
       P.slots[q] = f == 0 ? KEY_POS_INF : (f == 1 ? KEY_NEG_INF : 0);
     }
-    __shared__ float s_mu[256];
     float sg = 0.f;
     if (tid < P.nlabels) {
       s_mu[tid] = P.mus_in ? P.mus_in[tid] : 25.f + 200.f * keyed_uniform(P.key, 5, (uint32_t)tid);

@@ -417,7 +417,7 @@ class KeyedContext:
         (draws, parameter block, whether that block was carried, image, labels), or None outside the fused kernels' domain.
         workspace(shape, rows): the caller's scratch entry; out, seg_out: the caller's output tensors, None: made here, behind
         the workspace (the order the memory pool has always seen).  next_key: the key this context will be asked for NEXT on this
-        stream; its draw job rides in this sample's floor(min) launch and the block it fills waits in `_carried` (a call for
+        stream; its draw job rides in this sample's head launch and the block it fills waits in `_carried` (a call for
         another key drops it).  genparams (validated): the values the caller fixed (`overrides_of`); such a sample uses no
         carried block (that one holds the key's own tables) and sizes its block, row workspace and low-res scratch itself."""
         ov = overrides_of(genparams, self.cfg, dev) if genparams else None

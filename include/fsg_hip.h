@@ -93,6 +93,8 @@ const char* fsg_error_string(int code);
 #define FSG_TUNE_SA_FWD_DIRECT 131072 /* slice-acquisition forward (linear PSF, no volume mask): direct global gathers for every slice */
 #define FSG_TUNE_SA_FWD_PLATE 262144  /* ... the LDS plate kernel for every slice (default: chosen per slice by its orientation) */
 #define FSG_TUNE_NO_BLUR_RS 16384 /* fsg_sample_run: blur x3 + K7 as separate launches instead of the fused blur+resample pair */
+#define FSG_TUNE_NO_FLOORMIN_SKIP 524288 /* A/B: fsg_keyed_sample_run launches the conditional floor(min) pass even when the host has
+                                          * proved it a no-op (same keys, same volumes) */
 /* Bits 16, 64 and 32768 are retired (kernel variants measured slower and removed): ignored by fsg_set_tuning, never reuse them. */
 int fsg_set_tuning(int flags);
 /* Lockstep pacing of the lean warp kernel (speed only, results identical): 0 = chosen per launch, 5 = no barrier,
@@ -718,8 +720,8 @@ typedef struct fsg_sample_plan {
   int32_t code_ntuples, code_stride;
   int32_t code_sel[4];
   /* Look-ahead (ABI 3; set by fsg_keyed_sample_run when the caller names the next sample, zero otherwise): the keyed draw job
-   * of the NEXT sample -- it depends on nothing of this one -- goes out beside this sample's conditional floor(min) pass
-   * instead of as a launch of its own.  ride_draw: host pointer to a library-internal argument block, valid for the call.
+   * of the NEXT sample -- it depends on nothing of this one -- goes out beside this sample's one-launch head
+   * instead of as a launch of its own (a job of more than 4096 workgroups is not carried).  ride_draw: host pointer to a library-internal argument block, valid for the call.
    * *rode (may be NULL) receives 1 when the job really went out. */
   const void* ride_draw;
   uint32_t ride_draw_blocks;
@@ -954,8 +956,8 @@ enum {
   FSG_KEYED_I_CODES = 16 + 66, FSG_KEYED_I_CODE_TUPLES = 16 + 67, FSG_KEYED_I_CODE_NTUPLES = 16 + 68, FSG_KEYED_I_CODE_STRIDE = 16 + 69,
   /* look-ahead (optional).  FLAGS bit 0 (FSG_KEYED_FLAG_BLOCK_FILLED): the block of THIS sample is already filled (the previous
    * call carried its draw job); bit 2 (FSG_KEYED_FLAG_NEXT_NAMED): NEXT_KEY / NEXT_BLOCK name the sample the caller will run next
-   * on this stream -- its draw job then rides in this sample's floor(min) launch (fsg_keyed_draws::rode says whether it did: not
-   * when the deformation gate is off).  A caller that then runs something else simply does not set bit 0.  (r03: the next sample's GMM draw beside the zoom-back launches was built
+   * on this stream -- its draw job then rides in this sample's head launch (fsg_keyed_draws::rode says whether it did: not
+   * when the deformation gate is off, nor when the job is too large to be carried).  A caller that then runs something else simply does not set bit 0.  (r03: the next sample's GMM draw beside the zoom-back launches was built
    * and measured too -- 224 -> 230-244 us per step, the two jobs slow each other down -- and removed.) */
   FSG_KEYED_I_FLAGS = 16 + 70, FSG_KEYED_I_NEXT_KEY = 16 + 71, FSG_KEYED_I_NEXT_BLOCK = 16 + 72,
   /* real-image samples (optional, 0 = none): fsg_sample_image::image_in / image_out / prior_in.  With PRIOR_IN the BANK and CODES
