@@ -828,6 +828,62 @@ def slice_acq_adjoint(transforms, psf, slices, slices_mask, vol_mask, vol_shape,
     return (vol, wgt) if return_weight else vol
 
 
+# ---- pose conversions (fsg_transform_convert.hip) ----------------------------------------------------------
+def _tc_rows(t, name, shape):
+    """`t` is a contiguous fp32 device tensor (n, *shape); returns n."""
+    _need_gpu(t)
+    _f32(t, name)
+    if t.dim() != 1 + len(shape) or tuple(t.shape[1:]) != shape:
+        raise ValueError(f"{name} must be (n,{','.join(map(str, shape))}), got {tuple(t.shape)}")
+    return int(t.shape[0])
+
+
+def _tc_same(n, m, a, b, ta, tb):
+    """both tensors of a backward call: as many rows, and on ONE device (the output and the stream follow the second)"""
+    if n != m:
+        raise ValueError(f"{a} has {n} rows, {b} has {m}")
+    if ta.device != tb.device:
+        raise ValueError(f"{a} is on {ta.device}, {b} on {tb.device}")
+
+
+def axisangle2mat(axisangle) -> torch.Tensor:
+    """(n,6) [rotation vector | translation] -> (n,3,4) [R | t]  (fsg_axisangle2mat_f32)."""
+    n = _tc_rows(axisangle, "axisangle", (6,))
+    mat = torch.empty((n, 3, 4), dtype=F32, device=axisangle.device)
+    _lib.check(_lib.load().fsg_axisangle2mat_f32(_p(axisangle), _p(mat), n, _stream(axisangle)), "fsg_axisangle2mat_f32")
+    return mat
+
+
+def axisangle2mat_backward(grad_mat, axisangle) -> torch.Tensor:
+    """(n,3,4) grad_mat at the (n,6) axisangle -> (n,6) grad_axisangle  (fsg_axisangle2mat_backward_f32)."""
+    n = _tc_rows(axisangle, "axisangle", (6,))
+    _tc_same(_tc_rows(grad_mat, "grad_mat", (3, 4)), n, "grad_mat", "axisangle", grad_mat, axisangle)
+    out = torch.empty((n, 6), dtype=F32, device=axisangle.device)
+    _lib.check(_lib.load().fsg_axisangle2mat_backward_f32(_p(grad_mat), _p(axisangle), _p(out), n, _stream(axisangle)),
+               "fsg_axisangle2mat_backward_f32")
+    return out
+
+
+def mat2axisangle(mat) -> torch.Tensor:
+    """(n,3,4) [R | t] -> (n,6) [rotation vector | translation]  (fsg_mat2axisangle_f32)."""
+    n = _tc_rows(mat, "mat", (3, 4))
+    ax = torch.empty((n, 6), dtype=F32, device=mat.device)
+    _lib.check(_lib.load().fsg_mat2axisangle_f32(_p(mat), _p(ax), n, _stream(mat)), "fsg_mat2axisangle_f32")
+    return ax
+
+
+def mat2axisangle_backward(mat, grad_axisangle) -> torch.Tensor:
+    """(n,6) grad_axisangle at the (n,3,4) mat -> (n,3,4) grad_mat, all 12 entries of a row free
+    (fsg_mat2axisangle_backward_f32; the reference's rule, not the derivative for rotations of 2e-3 rad or less: DESIGN.md
+    section 21)."""
+    n = _tc_rows(mat, "mat", (3, 4))
+    _tc_same(_tc_rows(grad_axisangle, "grad_axisangle", (6,)), n, "grad_axisangle", "mat", grad_axisangle, mat)
+    out = torch.empty((n, 3, 4), dtype=F32, device=mat.device)
+    _lib.check(_lib.load().fsg_mat2axisangle_backward_f32(_p(mat), _p(grad_axisangle), _p(out), n, _stream(mat)),
+               "fsg_mat2axisangle_backward_f32")
+    return out
+
+
 # ---- SR-artifact volumetric helpers (fsg_artifacts.hip) ----------------------------------------------------
 def _upload(host: torch.Tensor, device):
     """Small host tensor -> device through a pinned staging copy (async on the current stream)."""

@@ -36,7 +36,8 @@ extern "C" {
                               7: fsg_slice_acq_adjoint_det_f32, fsg_slice_acq_adjoint_det_ws_bytes, FSG_SA_DET_FRAC_BITS / LIMB_BITS;
                               8: fsg_slice_acq_backward_f32, fsg_slice_acq_backward_ws_bytes; still 8 with
                                  fsg_slice_acq_adjoint_backward_f32 / _ws_bytes and with fsg_slice_acq_backward_det_f32 /
-                                 _det_ws_bytes: entries added, nothing older changed */
+                                 _det_ws_bytes, and with fsg_axisangle2mat_f32 / fsg_mat2axisangle_f32 and their _backward_f32:
+                                 entries added, nothing older changed */
 
 #define FSG_E_BADARG (-1)   /* null pointer / non-positive size / bad enum */
 #define FSG_E_TOOBIG (-2)   /* size exceeds what the kernel indexes (2^31-1 voxels per volume) */
@@ -505,6 +506,34 @@ int fsg_slice_acq_adjoint_backward_f32(const float* transforms, const float* gra
                                        const uint8_t* slices_mask, float* grad_slices /*may be NULL*/,
                                        float* grad_transforms /*may be NULL; not both*/, int D, int H, int W, int n, int h,
                                        int w, float res_slice, int mode, int equalize, void* ws, size_t ws_bytes, void* stream);
+
+/* ---- pose conversions (fsg_transform_convert.hip; reference svort/transform/transform_convert_cuda.cpp and
+ * transform_convert_cuda_kernel.cu:14-440) ------------------------------------------------------
+ * axisangle rows are [rotation vector (3) | translation (3)], mat rows the 12 entries of [R | t] in row-major order; both
+ * fp32, C-contiguous, n rows.  One thread per row, 256 per workgroup; fp32 in the reference's operation order.
+ *   fsg_axisangle2mat_f32           Rodrigues' formula for |rotation vector|^2 > 1e-6, else the first-order matrix I + [a]x.
+ *   fsg_axisangle2mat_backward_f32  its derivative in both branches (small branch: the antisymmetric differences of grad_mat).
+ *   fsg_mat2axisangle_f32           the quaternion by one of four formulas (chosen by r22 < 1e-6, r00 > r11, r00 < -r11), its
+ *                                   sign flipped where w < 0, then the rotation vector (x,y,z) * fac with fac = theta / sin for
+ *                                   x^2 + y^2 + z^2 > 1e-6, else 2 / w.
+ *   fsg_mat2axisangle_backward_f32  the chain rule through that, all 12 entries of a row free.  QUIRK kept from the reference:
+ *                                   for x^2 + y^2 + z^2 <= 1e-6 it differentiates fac as in the other branch with sin floored
+ *                                   by 1e-6 (in double), which is NOT the derivative of 2 / w; elsewhere it is the derivative.
+ * The comparisons with 1e-6 are float-with-double as in the reference.  No float lies between float(1e-6) and 1e-6, so they
+ * agree with the float32 comparisons against float(1e-6) for every float32 value, except `r22 < 1e-6` at r22 == float(1e-6).
+ * n == 0: returns 0 without a launch.  n < 0 or a null pointer with n > 0: FSG_E_BADARG.  12 * n > 2^31 - 1: FSG_E_TOOBIG.
+ * An output that shares a byte with an input: FSG_E_BADARG (the kernels take their pointers __restrict__).  Every refusal
+ * comes before any launch and leaves the output untouched; otherwise EVERY element of the output is written (the translation
+ * column or elements copied bit for bit), so it needs no initialisation.  No address depends on a value: a NaN or Inf in a row
+ * gives NaN or Inf in that row's output and nothing else (but a NaN pose given to fsg_axisangle2mat_backward_f32 compares
+ * false, takes the small branch, which reads grad_mat alone, and leaves a finite row, as in the reference).  Deterministic: a
+ * row's output is a function of that row alone. */
+int fsg_axisangle2mat_f32(const float* axisangle /*(n,6)*/, float* mat /*(n,12)*/, int n, void* stream);
+int fsg_axisangle2mat_backward_f32(const float* grad_mat /*(n,12)*/, const float* axisangle /*(n,6)*/,
+                                   float* grad_axisangle /*(n,6)*/, int n, void* stream);
+int fsg_mat2axisangle_f32(const float* mat /*(n,12)*/, float* axisangle /*(n,6)*/, int n, void* stream);
+int fsg_mat2axisangle_backward_f32(const float* mat /*(n,12)*/, const float* grad_axisangle /*(n,6)*/,
+                                   float* grad_mat /*(n,12)*/, int n, void* stream);
 
 /* ---- SR-artifact volumetric helpers, fsg_artifacts.hip ------------------------------------ */
 /* out = clamp(sum_g exp(-(((x-c0)/s0)^2 + ((y-c1)/s1)^2 + ((z-c2)/s2)^2) / 2), 0, 1) over a (D,H,W) grid with

@@ -14,10 +14,13 @@ for grad_vol alone, grad_transforms alone and both, in both modes, beside the fo
 `adjoint_backward_<mode>[_eq]_<leg>_ms` for grad_slices alone, grad_transforms alone and both, in both modes, equalize off and
 on (the pre-pass over the gradient included), and its ratios to forward_<mode>_ms and, with --backward, to
 backward_<mode>_grad_transforms_ms of the same session.
+--pose-chain runs INSTEAD of the legs above, on the same problem: the pose conversions of fsg_transform_convert.hip beside
+`axisangle2mat_autograd`, alone and inside one iteration of a pose fit, at n = 80 and 250, by the host clock (pose_chain below).
 """
 import argparse
 import json
 import sys
+import time
 from pathlib import Path
 
 import numpy as np
@@ -40,6 +43,67 @@ def timed(fn, reps):
     return e0.elapsed_time(e1) / reps
 
 
+def host_timed(fn, iters, warmup=20):
+    """ms per call by the host clock around `iters` calls ended by a device synchronise, after a warm-up: for chains that are
+    bound by host dispatch, where device events around single calls would time the wrong thing."""
+    for _ in range(warmup):
+        fn()
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for _ in range(iters):
+        fn()
+    torch.cuda.synchronize()
+    return (time.perf_counter() - t0) * 1e3 / iters
+
+
+def pose_chain(a, dev, vs, ss, psf, vol, res):
+    """--pose-chain: (n,6) poses on the device through the conversions and back, n = 80 and 250.
+    (a) axisangle2mat_autograd(ax).backward(g)     the torch-operation route, the yardstick
+    (b) transform_convert.axisangle2mat(ax).backward(g)
+    (c) mat2axisangle(axisangle2mat(ax)).backward(g)
+    (d), (e) one iteration of a pose fit on this bench's problem: poses -> matrices -> slice_acquisition (LINEAR, gradient of
+    the transforms only) -> sum().backward(), with (a)'s and with (b)'s conversion.
+    (a)/(b) and (d)/(e) are alternated three times; every repeat is reported."""
+    from fetalsyngen_amd.generator.artifacts.svort import axisangle2mat_autograd, rigid, slice_acquisition
+    from fetalsyngen_amd.generator.artifacts.svort import transform_convert as tc
+
+    out = {"volume": vs, "psf": list(psf.shape), "iters": a.chain_iters, "clock": "host, synchronised at both ends"}
+    rs = a.res_slice / res
+    v5 = vol.reshape(1, 1, *vs)
+    for n in (80, 250):
+        np.random.seed(0)
+        tr = random_stack(n, gap=a.size * res / n / res, max_angle=0.3)
+        ax = rigid.mat2axisangle(tr).to(dev).requires_grad_()
+        g12, g6 = torch.randn(n, 3, 4, device=dev), torch.randn(n, 6, device=dev)
+
+        def conv(f, g):
+            def run():
+                ax.grad = None
+                f(ax).backward(g)
+            return run
+
+        def fit(f):
+            def run():
+                ax.grad = None
+                slice_acquisition(f(ax), v5, None, None, psf, (ss, ss), rs, False, False).sum().backward()
+            return run
+
+        legs = {"a_autograd": conv(axisangle2mat_autograd, g12), "b_kernel": conv(tc.axisangle2mat, g12),
+                "c_roundtrip_kernel": conv(lambda x: tc.mat2axisangle(tc.axisangle2mat(x)), g6),
+                "d_fit_autograd": fit(axisangle2mat_autograd), "e_fit_kernel": fit(tc.axisangle2mat)}
+        row = {k: [] for k in legs}
+        for _ in range(3):
+            for k in ("a_autograd", "b_kernel"):
+                row[k].append(round(host_timed(legs[k], a.chain_iters, warmup=200), 4))  # (20 calls left (b)'s first repeat 2.5x slow)
+        row["c_roundtrip_kernel"].append(round(host_timed(legs["c_roundtrip_kernel"], a.chain_iters, warmup=200), 4))
+        for _ in range(3):
+            for k in ("d_fit_autograd", "e_fit_kernel"):
+                row[k].append(round(host_timed(legs[k], a.chain_iters, warmup=5), 4))
+        row["slices"] = [n, ss, ss]
+        out[f"n{n}_ms"] = row
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--size", type=int, default=384)
@@ -50,12 +114,17 @@ def main():
     ap.add_argument("--deterministic", action="store_true", help="also time the deterministic adjoint")
     ap.add_argument("--backward", action="store_true", help="also time the backward of the forward operator")
     ap.add_argument("--adjoint-backward", action="store_true", help="also time the backward of the adjoint")
+    ap.add_argument("--pose-chain", action="store_true", help="time the pose conversions and a pose-fit iteration instead")
+    ap.add_argument("--chain-iters", type=int, default=200, help="iterations per --pose-chain timing (host clock)")
     a = ap.parse_args()
     dev, res = "cuda:0", 0.5
     vs = (a.size,) * 3
     ss = int(np.sqrt(3 * a.size**2 / 2.0) * res / a.res_slice)
     ss = int(np.ceil(ss / 32.0) * 32)
     psf = get_PSF(res_ratio=(a.res_slice / res, a.res_slice / res, a.thick / res)).to(dev)
+    if a.pose_chain:
+        print(json.dumps(pose_chain(a, dev, vs, ss, psf, torch.rand(vs, device=dev), res)))
+        return
     delta = get_PSF(0).to(dev)
     np.random.seed(0)
     tr = random_stack(a.slices, gap=a.size * res / a.slices / res, max_angle=0.3).to(dev)
