@@ -31,7 +31,7 @@ from ... import rng as _rng
 from ... import tables as T
 from .svort import (RigidTransform, get_PSF, interleave_index, mat_update_resolution, random_angle,
                     random_init_stack_transforms, reset_transform, sample_motion, slice_acquisition,
-                    slice_acquisition_adjoint)
+                    slice_acquisition_adjoint, srr)
 from .utils import ReconMergeParams, fractal_noise_plan, mog_3d_tensor
 
 
@@ -41,6 +41,15 @@ def PSFreconstruction(transforms, slices, slices_mask, vol_mask, params, slice_i
     return slice_acquisition_adjoint(transforms, params["psf"], slices, slices_mask, vol_mask, params["volume_shape"],
                                      params["res_s"] / params["res_r"], params["interp_psf"], True, slice_ids=slice_ids,
                                      deterministic=deterministic)
+
+
+def SRRreconstruction(transforms, slices, slices_mask, vol_mask, params, n_iter, mu=0.0, x0=None, deterministic=None):
+    """`n_iter` conjugate-gradient iterations on (A^T P A + mu I) x = A^T P y + mu x0 with the reconstruction PSF, from `x0`
+    (svort.srr; not in the reference).  x0 is the start and the Tikhonov target: usually the PSFreconstruction of the same
+    slices.  deterministic: as PSFreconstruction."""
+    return srr(transforms, slices, params["psf"], params["volume_shape"], params["res_s"] / params["res_r"],
+               interp_psf=params["interp_psf"], slices_mask=slices_mask, vol_mask=vol_mask, x0=x0, mu=mu, z=x0, n_iter=n_iter,
+               deterministic=deterministic)
 
 
 def _axis_resample_tables(n_src, res, res_r, nearest):
@@ -273,9 +282,14 @@ class PSFReconstructor:
 
     def __init__(self, prob_misreg_slice: float, slices_misreg_ratio: float, prob_misreg_stack: float, txy: float,
                  prob_merge: float, merge_params: ReconMergeParams, prob_smooth: float, prob_rm_slices: float,
-                 rm_slices_min: float, rm_slices_max: float, deterministic: bool | None = None):
+                 rm_slices_min: float, rm_slices_max: float, deterministic: bool | None = None, srr_iterations: int = 0,
+                 srr_mu: float = 0.0):
         # None: the reconstruction accumulates deterministically inside a keyed scope and with fp32 atomics outside it
         self.deterministic = deterministic
+        # > 0: that many CG iterations (SRRreconstruction) refine the PSF reconstruction before it is smoothed; 0: as the reference
+        self.srr_iterations, self.srr_mu = int(srr_iterations), float(srr_mu)
+        if self.srr_iterations < 0:
+            raise ValueError(f"srr_iterations must be >= 0, got {srr_iterations}")
         self.prob_misreg_slice = prob_misreg_slice
         self.slices_misreg_ratio = slices_misreg_ratio
         self.prob_misreg_stack = prob_misreg_stack
@@ -319,6 +333,8 @@ class PSFReconstructor:
             "misreg_slice_on": self._misreg_slice_on,
             "merge_volume_on": self._merge_volume_on,
         }
+        if self.srr_iterations:
+            seeds["srr_iterations"] = self.srr_iterations
         if self.merge_params.merge_type == "gaussian":
             seeds["merge_type"] = "gaussian"
             seeds["ngaussians_merge"] = self._ngaussians_merge
@@ -428,9 +444,13 @@ class PSFReconstructor:
         # a keyed sample is a function of its key: inside a keyed scope the scatter accumulates in fixed point
         det = _rng.in_keyed_scope() if self.deterministic is None else bool(self.deterministic)
         rec = partial(PSFreconstruction, slices_mask=None, vol_mask=None, params=params, deterministic=det)
-        return self.__recon_volume(data, rec, want_weight)
+        refine = None
+        if self.srr_iterations > 0:
+            refine = partial(SRRreconstruction, slices_mask=None, vol_mask=None, params=params, n_iter=self.srr_iterations,
+                             mu=self.srr_mu, deterministic=det)
+        return self.__recon_volume(data, rec, want_weight, refine)
 
-    def __recon_volume(self, data, rec, want_weight=True):
+    def __recon_volume(self, data, rec, want_weight=True, refine=None):
         self.sample_seeds()
         self.device = data["stacks"].device
         trf = self.misregister_slices(data["transforms_angle"], data["transforms_gt_angle"])
@@ -438,6 +458,9 @@ class PSFReconstructor:
         kept_idx = self.kept_slices_idx(data["stacks"].shape[0])
         mats = K._upload(trf.matrix()[kept_idx].contiguous(), self.device)
         volume = rec(mats, data["stacks"], slice_ids=kept_idx)  # the kept slices are addressed in place, not gathered
+        if refine is not None:  # the solve applies the forward too, which has no slice_ids: gather the kept slices on the device
+            kept = data["stacks"].index_select(0, K._upload(kept_idx.to(torch.int64).contiguous(), self.device))
+            volume = refine(mats, kept, x0=volume)
         volume = self.smooth_volume(volume)
         # the reference forms `mask = seg_gt > 0` here (:772); only the Gaussian merge reads it, and the
         # voxel-selection kernels apply the `> 0` test to the label map directly

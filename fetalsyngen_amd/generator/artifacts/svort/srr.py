@@ -1,0 +1,110 @@
+"""`srr`: slice-to-volume reconstruction by conjugate gradients on the normal equations
+
+    (A^T P W A + mu I) x = A^T P W y + mu z        restricted to the voxels of `vol_mask`
+
+with A = `slice_acquisition` and A^T = `slice_acquisition_adjoint` (not equalised) in the CUDA semantics, P the pixels the
+adjoint keeps (PSF weight inside the volume >= 0.5) and W = diag(slices_weight).  The reference's svort/ was vendored without
+this solve; it is the volume update of the SVoRT / NeSVoR family.
+
+The loop is a fixed sequence of launches on torch's current stream: per iteration the forward, (the weight,) the adjoint and
+the three vector kernels of fsg_cg.hip.  alpha, beta, the dot products and the stopping decision live on the device
+(kernels.CGWorkspace): nothing is read back, so the call never synchronises with the host.  With
+`deterministic=True` (the default inside a keyed scope) the adjoint is the fixed-point one and the whole solve is a pure
+function of its inputs: bit-identical from run to run, on any stream and for any order of the slices.
+
+`vol_mask` is NOT passed to the operators (their per-pixel weights treat masked voxels differently: the forward leaves them
+out of its weight, the adjoint does not, and A^T would stop being the transpose of A); it is applied around them as the 0/1
+projection V by the vector kernels.  Not differentiable.
+"""
+from __future__ import annotations
+
+import torch
+
+from .... import kernels as K
+from .... import rng as _rng
+
+
+def _no_grad_inputs(**tensors):
+    if not torch.is_grad_enabled():
+        return
+    for name, t in tensors.items():
+        if isinstance(t, torch.Tensor) and t.requires_grad:
+            raise NotImplementedError(f"srr is not differentiable: `{name}` requires grad.  Detach it, or call under "
+                                      "torch.no_grad(); gradients through the solve are not implemented")
+
+
+def srr(transforms, slices, psf, vol_shape, res_slice, *, interp_psf=False, slices_mask=None, vol_mask=None,
+        slices_weight=None, x0=None, mu=0.0, z=None, n_iter=10, tol=0.0, output_relu=True, deterministic=None,
+        value_scale=1.0, return_info=False):
+    """transforms (n,3,4), slices (n,1,h,w) or (n,h,w), psf (pd,ph,pw) -> volume (1,1,D,H,W) after `n_iter` CG iterations.
+
+    slices_mask (n,[1,]h,w) bool: pixels that take part.  vol_mask (D,H,W)-shaped bool: the voxels solved for, the rest is 0.
+    slices_weight: non-negative per-pixel weights.  x0: the start (default 0), z / mu: the Tikhonov term mu |x - z|^2.
+    tol: the solve stops changing x once <r,r> <= tol (on the device; the launches still run and do nothing).
+    output_relu: x = max(x, 0) at the end.  deterministic: None = inside a keyed scope; value_scale: as
+    kernels.slice_acq_adjoint.  return_info: also a dict of the device histories rr, pq (float64), alpha, beta (float32) and
+    frozen (int32), n_iter + 1 slots each, slot k for iteration k."""
+    _no_grad_inputs(transforms=transforms, slices=slices, psf=psf, slices_weight=slices_weight, x0=x0, z=z)
+    if deterministic is None:
+        deterministic = _rng.in_keyed_scope()
+    det = bool(deterministic)
+    n_iter = int(n_iter)
+    dev = slices.device
+    h, w = (int(v) for v in slices.shape[-2:])
+    D, H, W = (int(v) for v in vol_shape)
+    n = int(transforms.shape[0])
+    nvox = D * H * W
+
+    def prep(t, shape, dtype=torch.float32):
+        if t is None or t.numel() == 0:
+            return None
+        return t.detach().to(device=dev, dtype=dtype).reshape(shape).contiguous()
+
+    tr = prep(transforms, (n, 3, 4))
+    ps = prep(psf, tuple(psf.shape))
+    y = prep(slices, (n, h, w))
+    sm = prep(slices_mask, (n, h, w), torch.bool)
+    vm = prep(vol_mask, (D, H, W), torch.bool)
+    wt = prep(slices_weight, (n, h, w))
+    zz = prep(z, (D, H, W))
+    xs = prep(x0, (D, H, W))
+
+    def normal(v):
+        """A^T P W A v"""
+        s = K.slice_acq_forward(tr, v, None, sm, ps, (h, w), res_slice, interp_psf=interp_psf, semantics="cuda")
+        if wt is not None:
+            s = K.mul(s, wt)
+        return K.slice_acq_adjoint(tr, ps, s, sm, None, (D, H, W), res_slice, interp_psf=interp_psf, semantics="cuda",
+                                   deterministic=det, value_scale=value_scale)
+
+    ws = K.cg_workspace(nvox, n_iter, dev)
+    b = K.slice_acq_adjoint(tr, ps, y if wt is None else K.mul(y, wt), sm, None, (D, H, W), res_slice, interp_psf=interp_psf,
+                            semantics="cuda", deterministic=det, value_scale=value_scale)
+    t0 = None
+    if xs is not None:
+        if vm is not None:
+            xs = torch.where(vm, xs, torch.zeros((), dtype=xs.dtype, device=dev))  # A sees V x0
+        t0 = normal(xs)
+    r, p, x = (torch.empty((D, H, W), dtype=torch.float32, device=dev) for _ in range(3))
+    K.cg_init(ws, b, r, p, x, mask=vm, mu=mu, z=zz, x0=xs, t0=t0)
+    for k in range(1, n_iter + 1):
+        q = normal(p)
+        K.cg_q(ws, k, p, q, mask=vm, mu=mu, tol=tol)
+        K.cg_step(ws, k, p, q, x, r, relu=bool(output_relu))
+        K.cg_dir(ws, k, r, p, tol=tol)
+    out = x.view(1, 1, D, H, W)
+    return (out, ws.info()) if return_info else out
+
+
+class SRR:
+    """`srr` behind the call shape of `PSFreconstruction`: `params` carries psf, interp_psf, res_s, res_r, s_thick and
+    volume_shape."""
+
+    def __init__(self, n_iter=10, tol=0.0, output_relu=True):
+        self.n_iter, self.tol, self.output_relu = n_iter, tol, output_relu
+
+    def __call__(self, transforms, slices, volume, params, p=None, mu=0, z=None, vol_mask=None, slices_mask=None):
+        vol_shape = params["volume_shape"] if volume is None else volume.shape[-3:]
+        return srr(transforms, slices, params["psf"], vol_shape, params["res_s"] / params["res_r"],
+                   interp_psf=params.get("interp_psf", False), slices_mask=slices_mask, vol_mask=vol_mask, slices_weight=p,
+                   x0=volume, mu=mu, z=z, n_iter=self.n_iter, tol=self.tol, output_relu=self.output_relu)

@@ -204,9 +204,11 @@ class SimulateMotion(RandTransform):
     """Acquire motion-corrupted low-resolution slice stacks of the image and reconstruct it from them (ref :345-425)."""
 
     def __init__(self, prob: float, scanner_params: ScannerParams, recon_params: ReconParams,
-                 deterministic: bool | None = None):
+                 deterministic: bool | None = None, srr_iterations: int = 0, srr_mu: float = 0.0):
         # None: the reconstruction is deterministic inside a keyed scope only; True / False force either accumulation
         self.deterministic = deterministic
+        # > 0: refine the PSF reconstruction by that many CG iterations (PSFReconstructor); 0, the default: as the reference
+        self.srr_iterations, self.srr_mu = srr_iterations, srr_mu
         self.scanner_args = scanner_params
         self.recon_args = recon_params
         self.prob = prob
@@ -230,8 +232,9 @@ class SimulateMotion(RandTransform):
             self.scanner_args.resolution_recon = res_
             scanner = Scanner(**asdict(self.scanner_args))
             d_scan = scanner.scan(d)
+            refine = dict(srr_iterations=self.srr_iterations, srr_mu=self.srr_mu) if self.srr_iterations else {}
             recon = PSFReconstructor(**{f.name: getattr(self.recon_args, f.name) for f in fields(self.recon_args)},
-                                     deterministic=self.deterministic)
+                                     deterministic=self.deterministic, **refine)
             output, _ = recon.recon_psf(d_scan, want_weight=False)
             metadata = {
                 "resolution_recon": d_scan["resolution_recon"],

@@ -884,6 +884,101 @@ def mat2axisangle_backward(mat, grad_axisangle) -> torch.Tensor:
     return out
 
 
+# ---- conjugate gradients around the slice-acquisition operators (fsg_cg.hip) ------------------------------------
+CG_RELU = _lib.CG_RELU
+CG_MAX_ITER = 4096
+
+
+class CGWorkspace:
+    """The device block of a solve's scalars (include/fsg_hip.h, fsg_cg_*): `buf` (int64) and, as views of it, the histories
+    rr, pq (float64), alpha, beta (float32), frozen (int32), each of n_iter + 1 slots indexed by iteration."""
+
+    def __init__(self, n: int, n_iter: int, device):
+        n, n_iter = int(n), int(n_iter)
+        if not 1 <= n_iter <= CG_MAX_ITER:
+            raise ValueError(f"n_iter must be in 1..{CG_MAX_ITER}, got {n_iter}")
+        self.n, self.n_iter = n, n_iter
+        self.nbytes = int(_lib.load().fsg_cg_ws_bytes(n, n_iter))
+        self.buf = torch.empty(self.nbytes // 8, dtype=torch.int64, device=device)
+        s, b = n_iter + 1, min(max((n + 1023) // 1024, 1), 1024)
+        raw, off = self.buf.view(torch.uint8), 0
+        for name, dtype, count in (("rr", torch.float64, s), ("pq", torch.float64, s), ("partial_rr", torch.float64, b),
+                                   ("partial_pq", torch.float64, b), ("alpha", F32, s), ("beta", F32, s),
+                                   ("frozen", torch.int32, s)):
+            size = count * torch.empty((), dtype=dtype).element_size()
+            setattr(self, name, raw[off:off + size].view(dtype))
+            off += size
+        if (off + 7) // 8 * 8 != self.nbytes:
+            raise RuntimeError(f"fsg_cg_ws_bytes({n}, {n_iter}) = {self.nbytes}, the layout of fsg_hip.h needs {off}")
+
+    def info(self):
+        return {k: getattr(self, k) for k in ("rr", "pq", "alpha", "beta", "frozen")}
+
+
+def cg_workspace(n: int, n_iter: int, device) -> CGWorkspace:
+    return CGWorkspace(n, n_iter, device)
+
+
+def _cg_vectors(ws, *named):
+    """fp32 contiguous device vectors of ws.n elements each (None allowed where the entry allows it), on ws's device"""
+    for name, t in named:
+        if t is None:
+            continue
+        _need_gpu(t)
+        _f32(t, name)
+        if t.numel() != ws.n:
+            raise ValueError(f"{name} has {t.numel()} elements, the workspace was made for {ws.n}")
+        if t.device != ws.buf.device:
+            raise ValueError(f"{name} is on {t.device}, the workspace on {ws.buf.device}")
+
+
+def _cg_mask(ws, mask):
+    if mask is None:
+        return None
+    _need_gpu(mask)
+    if mask.dtype not in (torch.bool, torch.uint8):
+        raise TypeError(f"mask must be bool/uint8, got {mask.dtype}")
+    if mask.numel() != ws.n or mask.device != ws.buf.device:
+        raise ValueError(f"mask must have {ws.n} elements on {ws.buf.device}")
+    return mask
+
+
+def cg_init(ws: CGWorkspace, b, r, p, x, mask=None, mu=0.0, z=None, x0=None, t0=None):
+    """r = V(b + mu z) - V(t0 + mu x0), p = r, x = V x0 or 0, partials of <r,r>  (fsg_cg_init_f32); writes r, p, x."""
+    if (x0 is None) != (t0 is None):
+        raise ValueError("x0 and t0 = A^T P W A x0 are given together")
+    _cg_vectors(ws, ("b", b), ("r", r), ("p", p), ("x", x), ("z", z), ("x0", x0), ("t0", t0))
+    mask = _cg_mask(ws, mask)
+    rc = _lib.load().fsg_cg_init_f32(_p(b), _p(z), _p(t0), _p(x0), _p(mask), float(mu), ws.n, ws.n_iter, _p(r), _p(p), _p(x),
+                                     _p(ws.buf), ws.nbytes, _stream(b))
+    _lib.check(rc, "fsg_cg_init_f32")
+
+
+def cg_q(ws: CGWorkspace, k: int, p, t, mask=None, mu=0.0, tol=0.0):
+    """q = V(t + mu p) over t, partials of <p,q>  (fsg_cg_q_f32)."""
+    _cg_vectors(ws, ("p", p), ("t", t))
+    mask = _cg_mask(ws, mask)
+    rc = _lib.load().fsg_cg_q_f32(_p(p), _p(t), _p(mask), float(mu), float(tol), ws.n, int(k), ws.n_iter, _p(ws.buf), ws.nbytes,
+                                  _stream(p))
+    _lib.check(rc, "fsg_cg_q_f32")
+
+
+def cg_step(ws: CGWorkspace, k: int, p, q, x, r, relu=False):
+    """alpha[k]; x += alpha p; r -= alpha q; partials of the new <r,r>; relu: x = max(x, 0) when k is the last iteration
+    (fsg_cg_step_f32)."""
+    _cg_vectors(ws, ("p", p), ("q", q), ("x", x), ("r", r))
+    rc = _lib.load().fsg_cg_step_f32(_p(p), _p(q), _p(x), _p(r), ws.n, int(k), ws.n_iter, CG_RELU if relu else 0, _p(ws.buf),
+                                     ws.nbytes, _stream(p))
+    _lib.check(rc, "fsg_cg_step_f32")
+
+
+def cg_dir(ws: CGWorkspace, k: int, r, p, tol=0.0):
+    """rr[k], beta[k], frozen[k]; p = r + beta p  (fsg_cg_dir_f32)."""
+    _cg_vectors(ws, ("r", r), ("p", p))
+    rc = _lib.load().fsg_cg_dir_f32(_p(r), _p(p), float(tol), ws.n, int(k), ws.n_iter, _p(ws.buf), ws.nbytes, _stream(p))
+    _lib.check(rc, "fsg_cg_dir_f32")
+
+
 # ---- SR-artifact volumetric helpers (fsg_artifacts.hip) ----------------------------------------------------
 def _upload(host: torch.Tensor, device):
     """Small host tensor -> device through a pinned staging copy (async on the current stream)."""

@@ -36,7 +36,8 @@ extern "C" {
                               7: fsg_slice_acq_adjoint_det_f32, fsg_slice_acq_adjoint_det_ws_bytes, FSG_SA_DET_FRAC_BITS / LIMB_BITS;
                               8: fsg_slice_acq_backward_f32, fsg_slice_acq_backward_ws_bytes; still 8 with
                                  fsg_slice_acq_adjoint_backward_f32 / _ws_bytes and with fsg_slice_acq_backward_det_f32 /
-                                 _det_ws_bytes, and with fsg_axisangle2mat_f32 / fsg_mat2axisangle_f32 and their _backward_f32:
+                                 _det_ws_bytes, and with fsg_axisangle2mat_f32 / fsg_mat2axisangle_f32 and their _backward_f32,
+                                 and with fsg_cg_ws_bytes / fsg_cg_init_f32 / _q_f32 / _step_f32 / _dir_f32:
                                  entries added, nothing older changed */
 
 #define FSG_E_BADARG (-1)   /* null pointer / non-positive size / bad enum */
@@ -534,6 +535,52 @@ int fsg_axisangle2mat_backward_f32(const float* grad_mat /*(n,12)*/, const float
 int fsg_mat2axisangle_f32(const float* mat /*(n,12)*/, float* axisangle /*(n,6)*/, int n, void* stream);
 int fsg_mat2axisangle_backward_f32(const float* mat /*(n,12)*/, const float* grad_axisangle /*(n,6)*/,
                                    float* grad_mat /*(n,12)*/, int n, void* stream);
+
+/* ---- conjugate gradients between two applications of the slice-acquisition operators (fsg_cg.hip) ----
+ * The vector half of K = n_iter iterations of CG on M x = rhs, M p = V (A^T P W A (V p) + mu p), rhs = V (b + mu z):
+ * the caller applies A and A^T (fsg_slice_acq_forward_f32, fsg_ewise_f32 op 3, fsg_slice_acq_adjoint[_det]_f32) and hands the
+ * result `t` to these entries.  All vectors are fp32 with n elements; `mask` is V, one byte per voxel (non-zero keeps), or NULL.
+ * One solve is the launch sequence
+ *     init;  for k = 1..K:  t = A^T P W A p;  q(k);  step(k);  dir(k)
+ * and it is the same sequence whatever the data: nothing returns early, nothing is read back.
+ *   init     r = V(b + mu z) - V(t0 + mu x0) (second term only with x0; t0 = A^T P W A x0), p = r, x = V x0 or 0.  z may be NULL.
+ *   q(k)     q = V(t + mu p), written over t.
+ *   step(k)  alpha[k] = (float)(rr[k-1] / pq[k]);  x = x + alpha p;  r = r - alpha q (r is not stored when k == K).
+ *   dir(k)   beta[k] = (float)(rr[k] / rr[k-1]);  p = r + beta p (p is not touched when k == K).
+ * Element-wise arithmetic is fp32, one rounding per operation (no contraction); V is a selection (a masked element is +0).
+ * Scalars: ws holds, 8-byte aligned and in this order, with s = K + 1 and B = clamp(ceil(n / 1024), 1, 1024):
+ *     double rr[s], double pq[s], double partial_rr[B], double partial_pq[B], float alpha[s], float beta[s], int32 frozen[s]
+ * = fsg_cg_ws_bytes(n, K) bytes (rounded up to 8; 0 for K outside 1..4096).  Slot k belongs to iteration k (slot 0 of pq, alpha,
+ * beta is 0).  It needs no initialisation: q(1) writes rr[0], frozen[0] and the zero slots, step(k) writes pq[k] and alpha[k], dir(k) writes
+ * rr[k], beta[k] and frozen[k], each from workgroup 0; a launch reads only slots and partials that an EARLIER launch wrote.
+ * Dot products <r,r> and <p,q>: every launch has B workgroups of 256 threads.  Elements are dealt in groups of four: group
+ * g = e / 4 belongs to thread g mod (256 B) (thread id = 256 workgroup + thread), whether it is loaded as one 16-byte word or
+ * as scalars.  A thread adds (double)a[e] * (double)b[e] (exact) over its elements in increasing e, from +0.0; the 64 lanes of a
+ * wave fold by the butterfly v[i] = v[i] + v[i ^ o] for o = 32, 16, 8, 4, 2, 1; thread 0 adds the 4 waves as ((w0 + w1) + w2) + w3
+ * and stores one double per workgroup.  The NEXT launch that needs the sum adds the B partials in index order from +0.0, in
+ * every workgroup alike.  No atomics, no second launch, no grid barrier: the sum is a function of the two arrays alone.
+ * Freeze instead of early return: frozen[0] = rr[0] <= tol, frozen[k] = frozen[k-1] || !(pq[k] > 0) || rr[k] <= tol.
+ *   - frozen[k-1]: q(k), step(k), dir(k) write no vector; pq[k] = 0, alpha[k] = beta[k] = 0, rr[k] = rr[k-1].
+ *   - !(pq[k] > 0) (a NaN, or a direction M maps to 0): step(k) and dir(k) write no vector; x is what it was after k - 1 steps.
+ *   - rr[k] <= tol: step(k) has updated x and r; dir(k) leaves p.
+ *   x therefore holds exactly what a loop with `return` at those points returns, and a NaN never reaches another voxel.
+ * FSG_CG_RELU in `flags` of step(K), the LAST iteration and only there: x = max(x, 0) once, in the same pass as the update, or
+ * as the only thing the launch does when the solve is frozen by then.  For k < K the flag is ignored.
+ * Loads and stores are 16 bytes per lane when every float pointer of the call is 16-byte aligned and mask is 4-byte aligned;
+ * otherwise scalars, same values and same sums.
+ * Refusals, all before any launch and with nothing written: K outside 1..4096 or k outside 1..K (FSG_E_BADARG); n == 0 is
+ * success without a launch; a null vector or ws with n > 0, x0 without t0, ws_bytes < fsg_cg_ws_bytes(n, K), an unknown flag
+ * (FSG_E_BADARG); ws not 8-byte aligned (FSG_E_ALIGN); an output that shares a byte with an input, another output or ws
+ * (FSG_E_BADARG; q over t is the one in-place pair). */
+#define FSG_CG_RELU 1
+size_t fsg_cg_ws_bytes(size_t n, int n_iter);
+int fsg_cg_init_f32(const float* b, const float* z, const float* t0, const float* x0, const uint8_t* mask, float mu, size_t n,
+                    int n_iter, float* r, float* p, float* x, void* ws, size_t ws_bytes, void* stream);
+int fsg_cg_q_f32(const float* p, float* t, const uint8_t* mask, float mu, double tol, size_t n, int k, int n_iter, void* ws,
+                 size_t ws_bytes, void* stream);
+int fsg_cg_step_f32(const float* p, const float* q, float* x, float* r, size_t n, int k, int n_iter, int flags, void* ws,
+                    size_t ws_bytes, void* stream);
+int fsg_cg_dir_f32(const float* r, float* p, double tol, size_t n, int k, int n_iter, void* ws, size_t ws_bytes, void* stream);
 
 /* ---- SR-artifact volumetric helpers, fsg_artifacts.hip ------------------------------------ */
 /* out = clamp(sum_g exp(-(((x-c0)/s0)^2 + ((y-c1)/s1)^2 + ((z-c2)/s2)^2) / 2), 0, 1) over a (D,H,W) grid with

@@ -16,6 +16,9 @@ on (the pre-pass over the gradient included), and its ratios to forward_<mode>_m
 backward_<mode>_grad_transforms_ms of the same session.
 --pose-chain runs INSTEAD of the legs above, on the same problem: the pose conversions of fsg_transform_convert.hip beside
 `axisangle2mat_autograd`, alone and inside one iteration of a pose fit, at n = 80 and 250, by the host clock (pose_chain below).
+--srr runs INSTEAD of the legs above, on the same problem: `svort.srr` (--srr-iters iterations) beside the same conjugate gradients
+written in torch operations around slice_acquisition / slice_acquisition_adjoint, float and deterministic, and the three vector
+launches of an iteration alone (srr_bench below).
 """
 import argparse
 import json
@@ -104,6 +107,96 @@ def pose_chain(a, dev, vs, ss, psf, vol, res):
     return out
 
 
+def torch_cg(tr, y, psf, vs, rs, n_iter, mu, deterministic, interp_psf=True):
+    """The route without fsg_cg.hip: CG on (A^T P A + mu I) x = A^T P y from x = 0 in torch operations, alpha and beta as 0-dim
+    tensors (no host synchronisation either), relu at the end.  What a user of the two operators writes."""
+    from fetalsyngen_amd.generator.artifacts.svort import slice_acquisition, slice_acquisition_adjoint
+
+    h, w = y.shape[-2:]
+
+    def normal(v):
+        s = slice_acquisition(tr, v, None, None, psf, (h, w), rs, False, interp_psf)
+        return slice_acquisition_adjoint(tr, psf, s, None, None, vs, rs, interp_psf, False, deterministic=deterministic)
+
+    r = slice_acquisition_adjoint(tr, psf, y, None, None, vs, rs, interp_psf, False, deterministic=deterministic)
+    x = torch.zeros_like(r)
+    p = r.clone()
+    rr = (r * r).sum()
+    for _ in range(n_iter):
+        q = normal(p) + mu * p
+        alpha = rr / (p * q).sum()
+        x = x + alpha * p
+        r = r - alpha * q
+        rr_new = (r * r).sum()
+        p = r + (rr_new / rr) * p
+        rr = rr_new
+    return torch.relu(x)
+
+
+def srr_bench(a, dev, vs, ss, psf, vol, tr, res):
+    """--srr.  Per setting (float / deterministic adjoint): ms per iteration of svort.srr and of torch_cg, the legs alternated
+    three times after a warm-up, host clock around one solve ended by a synchronise, divided by the iterations (the set-up,
+    one adjoint, is in both).  Then the three vector launches of an iteration alone: a loop of `t = d * p` (torch, standing in
+    for the operator: M = diag(d), d > 0, never converged, so no launch is a frozen one) + q + step + dir, minus the same loop
+    with the multiplication only; their bytes come from the shapes: 12 volume-sized array passes per iteration (q: 2 reads + 1
+    write, step: 4 + 2, dir: 2 + 1)."""
+    from fetalsyngen_amd.generator.artifacts.svort import srr
+
+    n_iter, mu, rs = a.srr_iters, 0.1, a.res_slice / res
+    y = K.slice_acq_forward(tr, vol, None, None, psf, (ss, ss), rs, interp_psf=True)[:, None]
+    out = {"volume": vs, "slices": [a.slices, ss, ss], "psf": list(psf.shape), "psf_taps": int((psf > 0).sum()), "iters": n_iter,
+           "mu": mu, "interp_psf": True, "clock": "host, one solve per timing, synchronised at both ends"}
+
+    def once(fn):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        fn()
+        torch.cuda.synchronize()
+        return round((time.perf_counter() - t0) * 1e3 / n_iter, 3)
+
+    for tag, det in (("float", False), ("det", True)):
+        legs = {"srr": lambda: srr(tr, y, psf, vs, rs, interp_psf=True, mu=mu, n_iter=n_iter, deterministic=det),
+                "torch": lambda: torch_cg(tr, y, psf, vs, rs, n_iter, mu, det)}
+        xs = {k: fn() for k, fn in legs.items()}  # warm-up, and the two routes solve the same problem
+        out[f"{tag}_srr_vs_torch_max_abs_over_max"] = float((xs["srr"] - xs["torch"]).abs().max() / xs["torch"].abs().max())
+        del xs
+        row = {k: [] for k in legs}
+        for _ in range(3):
+            for k, fn in legs.items():
+                row[k].append(once(fn))
+        out[f"{tag}_ms_per_iter"] = row
+        out[f"{tag}_torch_over_srr"] = round(min(row["torch"]) / min(row["srr"]), 3)
+    # the vector launches alone
+    n = int(np.prod(vs))
+    g = lambda: torch.rand(vs, device=dev)  # noqa: E731
+    d, b, t = g() + 0.5, g() - 0.5, g()
+    r, p, x = torch.empty_like(b), torch.empty_like(b), torch.empty_like(b)
+    ws = K.cg_workspace(n, n_iter, dev)
+
+    def loop(vector):
+        K.cg_init(ws, b, r, p, x)
+        for k in range(1, n_iter + 1):
+            torch.mul(d, p, out=t)
+            if vector:
+                K.cg_q(ws, k, p, t, mu=mu)
+                K.cg_step(ws, k, p, t, x, r, relu=True)
+                K.cg_dir(ws, k, r, p)
+
+    loop(True), loop(False)
+    with_v, without = [once(lambda: loop(True)) for _ in range(3)], [once(lambda: loop(False)) for _ in range(3)]
+    loop(True)
+    out["vector_loop_ms_per_iter"], out["mul_only_loop_ms_per_iter"] = with_v, without
+    out["vector_frozen_at_end"] = int(ws.frozen[-1].item())
+    vec = min(with_v) - min(without)
+    nbytes = 12 * n * 4 - 2 * n * 4 / n_iter  # the last iteration stores no r and touches no p in dir: 9 passes
+    out["vector_ms_per_iter"] = round(vec, 3)
+    out["vector_bytes_per_iter"] = int(12 * n * 4)
+    out["vector_GB_per_s"] = round(nbytes / vec / 1e6, 1)
+    out["vector_share_of_float_iter"] = round(vec / min(out["float_ms_per_iter"]["srr"]), 4)
+    out["vector_share_of_det_iter"] = round(vec / min(out["det_ms_per_iter"]["srr"]), 4)
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--size", type=int, default=384)
@@ -116,6 +209,8 @@ def main():
     ap.add_argument("--adjoint-backward", action="store_true", help="also time the backward of the adjoint")
     ap.add_argument("--pose-chain", action="store_true", help="time the pose conversions and a pose-fit iteration instead")
     ap.add_argument("--chain-iters", type=int, default=200, help="iterations per --pose-chain timing (host clock)")
+    ap.add_argument("--srr", action="store_true", help="time svort.srr against the same CG in torch operations instead")
+    ap.add_argument("--srr-iters", type=int, default=6, help="CG iterations per --srr solve")
     a = ap.parse_args()
     dev, res = "cuda:0", 0.5
     vs = (a.size,) * 3
@@ -129,6 +224,9 @@ def main():
     np.random.seed(0)
     tr = random_stack(a.slices, gap=a.size * res / a.slices / res, max_angle=0.3).to(dev)
     vol = torch.rand(vs, device=dev)
+    if a.srr:
+        print(json.dumps(srr_bench(a, dev, vs, ss, psf, vol, tr, res)))
+        return
     out = {"volume": vs, "slices": [a.slices, ss, ss], "psf": list(psf.shape), "psf_taps": int((psf > 0).sum())}
     rs = a.res_slice / res
     s = K.slice_acq_forward(tr, vol, None, None, psf, (ss, ss), rs)
