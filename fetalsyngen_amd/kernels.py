@@ -979,6 +979,112 @@ def cg_dir(ws: CGWorkspace, k: int, r, p, tol=0.0):
     _lib.check(rc, "fsg_cg_dir_f32")
 
 
+# ---- per-slice Levenberg-Marquardt slice-to-volume registration (fsg_svr.hip) -----------------------------------
+SVR_MAX_ITER = 4096
+SVR_SLOTS = 32  # doubles per slice in `stats`: H (21, upper triangle), g (6), sum w e^2, sum w, m, two zeros
+
+
+def svr_ws_bytes(n: int, h: int, w: int) -> int:
+    return int(_lib.load().fsg_svr_ws_bytes(int(n), int(h), int(w)))
+
+
+def svr_normal(transforms, jac, vol, psf, slices, slices_mask, slices_weight, res_slice, min_weight=0.5, out=None, ws=None):
+    """Per-slice normal equations of e = slice_acq_forward(vol) - slices in the LINEAR geometry (fsg_svr_normal_f32):
+    transforms (n,3,4), jac (n,12,6) = d transforms / d pose -> stats (n,32) float64: H = sum w J J^T (upper triangle, 21),
+    g = sum w e J (6), sum w e^2, sum w, the pixel count m, two zeros.  Reduced in a fixed order without atomics: a slice's row is
+    a pure function of that slice's inputs.  `out` (n,32) float64 and `ws` (int64, svr_ws_bytes(n,h,w) bytes) may be passed to
+    keep a loop free of allocations."""
+    n, (pd, ph, pw) = _sa_common(transforms, psf)
+    _need_gpu(jac, vol, slices, slices_weight, out, ws)
+    D, H, W = _dims3(_f32(vol, "vol"))
+    _f32(jac, "jac"), _f32(slices, "slices")
+    if tuple(jac.shape) != (n, 12, 6):
+        raise ValueError(f"jac must be (n,12,6) with n={n}, got {tuple(jac.shape)}")
+    if slices.dim() != 3 or int(slices.shape[0]) != n:
+        raise ValueError(f"slices must be (n,h,w) with n={n}, got {tuple(slices.shape)}")
+    h, w = int(slices.shape[1]), int(slices.shape[2])
+    sm = _sa_mask(slices_mask, (n, h, w), "slices_mask")
+    if slices_weight is not None:
+        _f32(slices_weight, "slices_weight")
+        if tuple(slices_weight.shape) != (n, h, w):
+            raise ValueError(f"slices_weight shape {tuple(slices_weight.shape)} does not match {(n, h, w)}")
+    if not float(min_weight) >= 0.0:
+        raise ValueError(f"min_weight must be >= 0, got {min_weight!r}")
+    for t, name in ((jac, "jac"), (slices, "slices"), (psf, "psf"), (transforms, "transforms"), (sm, "slices_mask"),
+                    (slices_weight, "slices_weight"), (out, "out"), (ws, "ws")):
+        if t is not None and t.device != vol.device:
+            raise ValueError(f"{name} is on {t.device}, vol on {vol.device}")
+    need = svr_ws_bytes(n, h, w)
+    if ws is None:
+        ws = torch.empty(need // 8, dtype=torch.int64, device=vol.device)  # 128 bytes per tile
+    elif ws.dtype != torch.int64 or ws.numel() * 8 < need:
+        raise ValueError(f"ws must be int64 with at least {need // 8} elements")
+    if out is None:
+        out = torch.empty((n, SVR_SLOTS), dtype=torch.float64, device=vol.device)
+    elif out.dtype != torch.float64 or tuple(out.shape) != (n, SVR_SLOTS):
+        raise ValueError(f"out must be float64 ({n},{SVR_SLOTS}), got {out.dtype} {tuple(out.shape)}")
+    rc = _lib.load().fsg_svr_normal_f32(_p(transforms), _p(jac), _p(vol), _p(psf), pd, ph, pw, _p(slices), _p(sm),
+                                        _p(slices_weight), _p(out), D, H, W, n, h, w, float(res_slice), float(min_weight),
+                                        SA_MODES["linear"], _p(ws), ws.numel() * 8, _stream(vol))
+    _lib.check(rc, "fsg_svr_normal_f32")
+    return out
+
+
+class SVRState:
+    """The device block of a registration's per-slice state (include/fsg_hip.h, fsg_svr_update_f32): `buf` (int64) and, as views
+    of it, stats_cur (n,32), lam (n), m0 (n) float64, theta_cur (n,6) float32, frozen_now (n) int32 and the histories cost,
+    lambda (float64), accepted, frozen (int32), each (n_iter + 1, n), row k for iteration slot k."""
+
+    def __init__(self, n: int, n_iter: int, device):
+        n, n_iter = int(n), int(n_iter)
+        if n < 1:
+            raise ValueError(f"n must be at least 1, got {n}")
+        if not 1 <= n_iter <= SVR_MAX_ITER:
+            raise ValueError(f"n_iter must be in 1..{SVR_MAX_ITER}, got {n_iter}")
+        self.n, self.n_iter = n, n_iter
+        self.nbytes = int(_lib.load().fsg_svr_state_bytes(n, n_iter))
+        self.buf = torch.empty(self.nbytes // 8, dtype=torch.int64, device=device)
+        s = n_iter + 1
+        raw, off = self.buf.view(torch.uint8), 0
+        for name, dtype, shape in (("stats_cur", torch.float64, (n, SVR_SLOTS)), ("lam", torch.float64, (n,)),
+                                   ("m0", torch.float64, (n,)), ("cost", torch.float64, (s, n)),
+                                   ("lambda_hist", torch.float64, (s, n)), ("theta_cur", F32, (n, 6)),
+                                   ("frozen_now", torch.int32, (n,)), ("accepted", torch.int32, (s, n)),
+                                   ("frozen", torch.int32, (s, n))):
+            size = int(np.prod(shape)) * torch.empty((), dtype=dtype).element_size()
+            setattr(self, name, raw[off:off + size].view(dtype).view(shape))
+            off += size
+        if (off + 7) // 8 * 8 != self.nbytes:
+            raise RuntimeError(f"fsg_svr_state_bytes({n}, {n_iter}) = {self.nbytes}, the layout of fsg_hip.h needs {off}")
+
+    def info(self):
+        return {"cost": self.cost, "lambda": self.lambda_hist, "accepted": self.accepted, "frozen": self.frozen}
+
+
+def svr_state(n: int, n_iter: int, device) -> SVRState:
+    return SVRState(n, n_iter, device)
+
+
+def svr_update(state: SVRState, k: int, stats_trial, theta_trial, lambda0=1e-3, factor=10.0, lambda_min=1e-9, lambda_max=1e10,
+               min_overlap=0.5, tol=0.0):
+    """Slot k of a registration (fsg_svr_update_f32): accept or reject the trial whose normal equations are `stats_trial`
+    (n,32) float64, adapt lambda, and overwrite theta_trial (n,6) with the next trial (the current pose for a frozen slice and
+    for k == n_iter)."""
+    _need_gpu(stats_trial, theta_trial)
+    _f32(theta_trial, "theta_trial")
+    if stats_trial.dtype != torch.float64 or tuple(stats_trial.shape) != (state.n, SVR_SLOTS):
+        raise ValueError(f"stats_trial must be float64 ({state.n},{SVR_SLOTS}), got {stats_trial.dtype} {tuple(stats_trial.shape)}")
+    if tuple(theta_trial.shape) != (state.n, 6):
+        raise ValueError(f"theta_trial must be ({state.n},6), got {tuple(theta_trial.shape)}")
+    for t, name in ((stats_trial, "stats_trial"), (theta_trial, "theta_trial")):
+        if t.device != state.buf.device:
+            raise ValueError(f"{name} is on {t.device}, the state on {state.buf.device}")
+    rc = _lib.load().fsg_svr_update_f32(_p(stats_trial), _p(theta_trial), _p(state.buf), state.nbytes, state.n, int(k),
+                                        state.n_iter, float(lambda0), float(factor), float(lambda_min), float(lambda_max),
+                                        float(min_overlap), float(tol), _stream(theta_trial))
+    _lib.check(rc, "fsg_svr_update_f32")
+
+
 # ---- SR-artifact volumetric helpers (fsg_artifacts.hip) ----------------------------------------------------
 def _upload(host: torch.Tensor, device):
     """Small host tensor -> device through a pinned staging copy (async on the current stream)."""

@@ -37,7 +37,8 @@ extern "C" {
                               8: fsg_slice_acq_backward_f32, fsg_slice_acq_backward_ws_bytes; still 8 with
                                  fsg_slice_acq_adjoint_backward_f32 / _ws_bytes and with fsg_slice_acq_backward_det_f32 /
                                  _det_ws_bytes, and with fsg_axisangle2mat_f32 / fsg_mat2axisangle_f32 and their _backward_f32,
-                                 and with fsg_cg_ws_bytes / fsg_cg_init_f32 / _q_f32 / _step_f32 / _dir_f32:
+                                 and with fsg_cg_ws_bytes / fsg_cg_init_f32 / _q_f32 / _step_f32 / _dir_f32, and with
+                                 fsg_svr_ws_bytes / fsg_svr_normal_f32 / fsg_svr_state_bytes / fsg_svr_update_f32:
                                  entries added, nothing older changed */
 
 #define FSG_E_BADARG (-1)   /* null pointer / non-positive size / bad enum */
@@ -581,6 +582,76 @@ int fsg_cg_q_f32(const float* p, float* t, const uint8_t* mask, float mu, double
 int fsg_cg_step_f32(const float* p, const float* q, float* x, float* r, size_t n, int k, int n_iter, int flags, void* ws,
                     size_t ws_bytes, void* stream);
 int fsg_cg_dir_f32(const float* r, float* p, double tol, size_t n, int k, int n_iter, void* ws, size_t ws_bytes, void* stream);
+
+/* ---- per-slice Levenberg-Marquardt slice-to-volume registration (fsg_svr.hip) ----------------------
+ * One solve is the launch sequence, for k = 0..K (K = n_iter), all on one stream:
+ *     transforms = axisangle2mat(theta_trial);  jac = d transforms / d theta at theta_trial;  normal;  update(k)
+ * and it is the same sequence whatever the data: nothing returns early, nothing is read back.
+ *
+ * fsg_svr_normal_f32: the per-slice normal equations of the residual e = s - y, s the slice fsg_slice_acq_forward_f32 simulates
+ * in FSG_SA_LINEAR without a vol_mask (any other `mode`: FSG_E_BADARG; there is no vol_mask parameter because the forward and
+ * its backward treat one differently, so a Jacobian under a mask would not be the derivative of the residual).
+ *   transforms (n,12), jac (n,12,6): row k of a slice = the derivative of transform entry k with respect to the 6 pose
+ *   parameters; vol (D,H,W); psf (pd,ph,pw), limits as the forward; slices (n,h,w) = y; slices_mask (n,h,w) bytes or NULL;
+ *   slices_weight (n,h,w) non-negative or NULL (w = 1); min_weight >= 0 (negative or NaN: FSG_E_BADARG).
+ *   stats (n,32) DOUBLE, 8-byte aligned: [0..20] H = sum w J J^T, upper triangle row-major (00 01 .. 05 11 12 .. 55);
+ *   [21..26] g = sum w e J; [27] sum w e^2; [28] sum w; [29] m, the number of pixels that took part; [30], [31] = 0.
+ * Per pixel inside slices_mask:
+ *   pass 1  weight = the raw PSF sum over the non-zero taps with 0 <= p < size - 1 on every axis, exactly as
+ *           fsg_slice_acq_backward_f32 in LINEAR.  The pixel takes part iff weight > 0 && weight >= min_weight.
+ *   pass 2  over the same taps: tri = the eight-term trilinear sample of vol (corner order of the family, added to 0),
+ *           val += psf * tri; and the twelve sums J12[k] that fsg_slice_acq_backward_f32 forms for grad_slices = 1, i.e.
+ *           gs = 1 / weight, pg = psf * gs, per corner the derivative terms of pg * vol[corner], then the LINEAR lever arms:
+ *           the same fp32 operations in the same order, the weight held constant.
+ *   then    s = val / weight; e = s - y; J6[a] = sum_k jac[k][a] * J12[k], k increasing, from +0; we = w * e; the 30 fp32
+ *           terms fl(fl(w * J6[a]) * J6[b]) (a <= b), we * J6[a], we * e, w, 1.  A pixel that takes no part carries 30 zeros.
+ * Reduction, no atomics: the 64 lanes of a wave fold each term by v[i] += v[i + o], o = 32..1 (shuffle-down; lane 0 holds the
+ * sum); the four waves of the 16x16 workgroup are added in wave order; the workgroup stores one 32-float partial (128 bytes)
+ * at ws[slice][tile], tile = tile_y * tiles_x + tile_x; a second launch adds a slice's partials in DOUBLE in tile-index order
+ * from +0.0 and writes all 32 slots.  stats of a slice is a pure function of that slice's inputs: the same bits in any run, on
+ * any stream, for any order or number of the other slices.
+ *   ws  DEVICE, 8-byte aligned (else FSG_E_ALIGN), ws_bytes >= fsg_svr_ws_bytes(n, h, w) = 128 bytes per 16x16 tile of every
+ *       slice (else FSG_E_BADARG).  It needs no initialisation.
+ * Every refusal (null pointer, bad size, PSF limits, mode, min_weight, alignment, short workspace) comes before the first
+ * write and leaves stats and ws untouched.  No allocation and no host synchronisation inside.  Range tests accept, so a NaN or
+ * Inf in transforms or res_slice skips the tap; non-finite vol, psf, jac, slices or weights give unspecified sums and never
+ * an address.
+ *
+ * fsg_svr_update_f32: the damped step and the accept / reject decision for slot k of 0..K, one thread per slice, double
+ * arithmetic with + - * / only and no contraction.  `state` is a DEVICE block of fsg_svr_state_bytes(n, K) bytes (0 for n < 1
+ * or K outside 1..4096), 8-byte aligned, in this order with s = K + 1:
+ *     double stats_cur[n][32], double lambda[n], double m0[n], double cost[s][n], double lambda_hist[s][n],
+ *     float theta_cur[n][6], int32 frozen[n], int32 accepted[s][n], int32 frozen_hist[s][n]
+ * rounded up to 8 bytes.  It needs no initialisation: update(0) writes every per-slice field, update(k) row k of the histories.
+ * stats_trial (n,32) are the normal equations at theta_trial (n,6), which the call overwrites with the next trial.
+ *   cost of a block of sums = [27] / [28].
+ *   k = 0   cur <- trial, theta_cur <- theta_trial, m0 = m, lambda = lambda0.  The slice freezes if !(m >= 1), !(sum w > 0)
+ *           or any of the 30 sums is not finite.
+ *   k >= 1  not frozen: accept iff the 30 trial sums are finite && m_t >= min_overlap * m0 && cost_t < cost_cur.  On accept
+ *           cur <- trial, theta_cur <- theta_trial, lambda = max(lambda / factor, lambda_min), and the slice freezes if
+ *           cost_old - cost_t <= tol * cost_old.  Otherwise lambda *= factor and the slice freezes once lambda > lambda_max.
+ *           A NaN fails every comparison and is rejected.  A frozen slice changes nothing.
+ *   next    for k < K and a slice not frozen: A = H + lambda diag(H) from cur (Marquardt's scaling); a parameter with
+ *           H_aa == 0 is taken out (unit row and column, g_a = 0, so delta_a = 0); A = L D L^T, Cholesky's factorisation in
+ *           its square-root-free form, d_j = A_jj - sum_p (L_jp * L_jp) * d_p, L_rj = (A_rj - sum_p (L_rp * L_jp) * d_p) / d_j,
+ *           p increasing; a pivot d_j that is not > 0 freezes the slice; L z = g, z_r /= d_r, L^T x = z, delta = -x;
+ *           theta_trial = (float)((double)theta_cur + delta).
+ *           A frozen slice, or k = K: theta_trial = theta_cur, so every later launch runs on valid data.
+ *   histories, row k: cost[k] = the cost of cur after the decision, lambda_hist[k], accepted[k] (0 for k = 0), frozen_hist[k]
+ *           (after the pivot test).
+ * Refusals, before any launch and with nothing written: n < 1, K outside 1..4096, k outside 0..K, a null pointer, a short
+ * state, !(lambda0 > 0), !(factor > 1), !(lambda_min > 0), !(lambda_max >= lambda_min), !(min_overlap >= 0), !(tol >= 0)
+ * (FSG_E_BADARG); state or stats_trial not 8-byte aligned, theta_trial not 4-byte aligned (FSG_E_ALIGN); state, stats_trial
+ * and theta_trial sharing a byte (FSG_E_BADARG). */
+size_t fsg_svr_ws_bytes(int n, int h, int w);
+int fsg_svr_normal_f32(const float* transforms, const float* jac, const float* vol, const float* psf, int pd, int ph, int pw,
+                       const float* slices, const uint8_t* slices_mask, const float* slices_weight, double* stats, int D, int H,
+                       int W, int n, int h, int w, float res_slice, float min_weight, int mode, void* ws, size_t ws_bytes,
+                       void* stream);
+size_t fsg_svr_state_bytes(int n, int n_iter);
+int fsg_svr_update_f32(const double* stats_trial, float* theta_trial, void* state, size_t state_bytes, int n, int k, int n_iter,
+                       double lambda0, double factor, double lambda_min, double lambda_max, double min_overlap, double tol,
+                       void* stream);
 
 /* ---- SR-artifact volumetric helpers, fsg_artifacts.hip ------------------------------------ */
 /* out = clamp(sum_g exp(-(((x-c0)/s0)^2 + ((y-c1)/s1)^2 + ((z-c2)/s2)^2) / 2), 0, 1) over a (D,H,W) grid with

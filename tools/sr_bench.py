@@ -19,6 +19,8 @@ backward_<mode>_grad_transforms_ms of the same session.
 --srr runs INSTEAD of the legs above, on the same problem: `svort.srr` (--srr-iters iterations) beside the same conjugate gradients
 written in torch operations around slice_acquisition / slice_acquisition_adjoint, float and deterministic, and the three vector
 launches of an iteration alone (srr_bench below).
+--svr runs INSTEAD of the legs above, on the same problem: a round of `svort.svr` beside a pose-fit iteration through autograd and
+beside the forward plus the grad_transforms-only backward, at n = 80 and 250 (svr_bench below).
 """
 import argparse
 import json
@@ -197,6 +199,72 @@ def srr_bench(a, dev, vs, ss, psf, vol, tr, res):
     return out
 
 
+def svr_bench(a, dev, vs, ss, psf, vol, res):
+    """--svr, n = 80 and 250.  Per round of svort.svr (axisangle2mat, the Jacobian, fsg_svr_normal_f32, fsg_svr_update_f32):
+    host clock around one solve of --svr-iters iterations ended by a synchronise, divided by its iters + 1 rounds.  Beside it,
+    in the same session and alternated three times after a warm-up: (e) one pose-fit iteration through autograd as --pose-chain
+    times it (conversion kernel, forward, backward of the transforms, conversion backward), by the host clock over
+    --chain-iters iterations; and the forward (LINEAR) plus the grad_transforms-only backward, and fsg_svr_normal_f32 alone, by
+    device events.  The launches of a round do not depend on the data (a frozen slice is still evaluated), so the poses need
+    not converge for the timing to stand."""
+    from fetalsyngen_amd.generator.artifacts.svort import rigid, slice_acquisition, svr
+    from fetalsyngen_amd.generator.artifacts.svort import transform_convert as tc
+
+    rs, n_iter = a.res_slice / res, a.svr_iters
+    out = {"volume": vs, "psf": list(psf.shape), "psf_taps": int((psf > 0).sum()), "iters": n_iter, "rounds": n_iter + 1,
+           "clock": "svr and fit: host, synchronised at both ends; forward/backward/normal: device events"}
+    v5 = vol.reshape(1, 1, *vs)
+    for n in (80, 250):
+        np.random.seed(0)
+        tr = random_stack(n, gap=a.size * res / n / res, max_angle=0.3)
+        ax = rigid.mat2axisangle(tr).to(dev).float().contiguous()
+        trd = K.axisangle2mat(ax)
+        y = K.slice_acq_forward(trd, vol, None, None, psf, (ss, ss), rs)
+        start = (ax + 0.01 * torch.randn_like(ax)).contiguous()
+        axg = start.clone().requires_grad_()
+        gs = torch.randn_like(y)
+        onehot = torch.eye(12, device=dev).repeat(n, 1).view(12 * n, 3, 4)
+        jac = K.axisangle2mat_backward(onehot, start.repeat_interleave(12, 0).contiguous()).view(n, 12, 6)
+
+        def solve():
+            return svr(start, y, vol, psf, rs, n_iter=n_iter)
+
+        def once():
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            solve()
+            torch.cuda.synchronize()
+            return round((time.perf_counter() - t0) * 1e3 / (n_iter + 1), 3)
+
+        def fit():
+            axg.grad = None
+            slice_acquisition(tc.axisangle2mat(axg), v5, None, None, psf, (ss, ss), rs, False, False).sum().backward()
+
+        legs = {
+            "svr_round": once,
+            "fit_iteration_autograd": lambda: round(host_timed(fit, a.chain_iters, warmup=5), 3),
+            "forward_linear": lambda: round(timed(lambda: K.slice_acq_forward(trd, vol, None, None, psf, (ss, ss), rs), a.reps), 3),
+            "backward_grad_transforms": lambda: round(timed(
+                lambda: K.slice_acq_backward(trd, vol, None, None, psf, gs, rs, need_vol_grad=False), a.reps), 3),
+            "svr_normal": lambda: round(timed(lambda: K.svr_normal(trd, jac, vol, psf, y, None, None, rs), a.reps), 3),
+        }
+        solve(), fit()  # warm-up
+        row = {k: [] for k in legs}
+        for _ in range(3):
+            for k, fn in legs.items():
+                row[k].append(fn())
+        best = {k: min(v) for k, v in row.items()}
+        row["slices"] = [n, ss, ss]
+        row["svr_round_over_fit_iteration"] = round(best["svr_round"] / best["fit_iteration_autograd"], 3)
+        row["svr_normal_over_backward"] = round(best["svr_normal"] / best["backward_grad_transforms"], 3)
+        row["svr_normal_over_forward_plus_backward"] = round(
+            best["svr_normal"] / (best["forward_linear"] + best["backward_grad_transforms"]), 3)
+        p1, p2 = solve(), solve()
+        row["poses_twice_equal"] = bool(torch.equal(p1, p2))
+        out[f"n{n}_ms"] = row
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--size", type=int, default=384)
@@ -211,6 +279,8 @@ def main():
     ap.add_argument("--chain-iters", type=int, default=200, help="iterations per --pose-chain timing (host clock)")
     ap.add_argument("--srr", action="store_true", help="time svort.srr against the same CG in torch operations instead")
     ap.add_argument("--srr-iters", type=int, default=6, help="CG iterations per --srr solve")
+    ap.add_argument("--svr", action="store_true", help="time a round of svort.svr against a pose-fit iteration through autograd instead")
+    ap.add_argument("--svr-iters", type=int, default=5, help="iterations per --svr solve (iters + 1 rounds)")
     a = ap.parse_args()
     dev, res = "cuda:0", 0.5
     vs = (a.size,) * 3
@@ -219,6 +289,9 @@ def main():
     psf = get_PSF(res_ratio=(a.res_slice / res, a.res_slice / res, a.thick / res)).to(dev)
     if a.pose_chain:
         print(json.dumps(pose_chain(a, dev, vs, ss, psf, torch.rand(vs, device=dev), res)))
+        return
+    if a.svr:
+        print(json.dumps(svr_bench(a, dev, vs, ss, psf, torch.rand(vs, device=dev), res)))
         return
     delta = get_PSF(0).to(dev)
     np.random.seed(0)
