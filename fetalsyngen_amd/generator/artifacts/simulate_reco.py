@@ -46,10 +46,12 @@ def PSFreconstruction(transforms, slices, slices_mask, vol_mask, params, slice_i
 def SRRreconstruction(transforms, slices, slices_mask, vol_mask, params, n_iter, mu=0.0, x0=None, deterministic=None):
     """`n_iter` conjugate-gradient iterations on (A^T P A + mu I) x = A^T P y + mu x0 with the reconstruction PSF, from `x0`
     (svort.srr; not in the reference).  x0 is the start and the Tikhonov target: usually the PSFreconstruction of the same
-    slices.  deterministic: as PSFreconstruction."""
+    slices.  deterministic: as PSFreconstruction.  The first-order regulariser of svort.srr travels in `params`, as the optional
+    entries "lam", "huber_delta" and "n_outer" (this function's own parameter list is fixed); what is absent is not handed on."""
+    reg = {k: params[k] for k in ("lam", "huber_delta", "n_outer") if k in params}
     return srr(transforms, slices, params["psf"], params["volume_shape"], params["res_s"] / params["res_r"],
                interp_psf=params["interp_psf"], slices_mask=slices_mask, vol_mask=vol_mask, x0=x0, mu=mu, z=x0, n_iter=n_iter,
-               deterministic=deterministic)
+               deterministic=deterministic, **reg)
 
 
 def _axis_resample_tables(n_src, res, res_r, nearest):
@@ -283,13 +285,18 @@ class PSFReconstructor:
     def __init__(self, prob_misreg_slice: float, slices_misreg_ratio: float, prob_misreg_stack: float, txy: float,
                  prob_merge: float, merge_params: ReconMergeParams, prob_smooth: float, prob_rm_slices: float,
                  rm_slices_min: float, rm_slices_max: float, deterministic: bool | None = None, srr_iterations: int = 0,
-                 srr_mu: float = 0.0):
+                 srr_mu: float = 0.0, srr_lambda: float = 0.0, srr_huber_delta: float | None = None, srr_outer: int = 1):
         # None: the reconstruction accumulates deterministically inside a keyed scope and with fp32 atomics outside it
         self.deterministic = deterministic
         # > 0: that many CG iterations (SRRreconstruction) refine the PSF reconstruction before it is smoothed; 0: as the reference
         self.srr_iterations, self.srr_mu = int(srr_iterations), float(srr_mu)
         if self.srr_iterations < 0:
             raise ValueError(f"srr_iterations must be >= 0, got {srr_iterations}")
+        # the first-order regulariser of that solve (svort.srr: lam, huber_delta, n_outer); only what is set is handed on
+        self.srr_reg = {k: v for k, v, unset in (("srr_lambda", srr_lambda, 0.0), ("srr_huber_delta", srr_huber_delta, None),
+                                                 ("srr_outer", srr_outer, 1)) if v != unset}
+        if self.srr_reg and not self.srr_iterations:
+            raise ValueError("srr_lambda, srr_huber_delta and srr_outer belong to the srr solve: set srr_iterations > 0")
         self.prob_misreg_slice = prob_misreg_slice
         self.slices_misreg_ratio = slices_misreg_ratio
         self.prob_misreg_stack = prob_misreg_stack
@@ -335,6 +342,7 @@ class PSFReconstructor:
         }
         if self.srr_iterations:
             seeds["srr_iterations"] = self.srr_iterations
+            seeds.update(self.srr_reg)
         if self.merge_params.merge_type == "gaussian":
             seeds["merge_type"] = "gaussian"
             seeds["ngaussians_merge"] = self._ngaussians_merge
@@ -446,6 +454,8 @@ class PSFReconstructor:
         rec = partial(PSFreconstruction, slices_mask=None, vol_mask=None, params=params, deterministic=det)
         refine = None
         if self.srr_iterations > 0:
+            names = {"srr_lambda": "lam", "srr_huber_delta": "huber_delta", "srr_outer": "n_outer"}
+            params.update({names[k]: v for k, v in self.srr_reg.items()})
             refine = partial(SRRreconstruction, slices_mask=None, vol_mask=None, params=params, n_iter=self.srr_iterations,
                              mu=self.srr_mu, deterministic=det)
         return self.__recon_volume(data, rec, want_weight, refine)

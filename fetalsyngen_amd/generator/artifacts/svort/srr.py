@@ -15,8 +15,16 @@ function of its inputs: bit-identical from run to run, on any stream and for any
 `vol_mask` is NOT passed to the operators (their per-pixel weights treat masked voxels differently: the forward leaves them
 out of its weight, the adjoint does not, and A^T would stop being the transpose of A); it is applied around them as the 0/1
 projection V by the vector kernels.  Not differentiable.
+
+With `lam > 0` the operator gains the first-order regulariser of DESIGN.md section 24: M + lam L, L the graph Laplacian of the
+6-neighbour grid inside V (kernels.tk1_apply, one launch after every application of A^T P W A; the cg kernels are untouched).
+`huber_delta` and `n_outer` make it edge preserving by reweighting: `n_outer` complete solves, each guided by the x of the one
+before, whose edges steeper than `huber_delta` are weighted down by Huber's rule.  With `lam == 0`, the default, the launch
+sequence is the one above and tk1_apply is never called.
 """
 from __future__ import annotations
+
+import math
 
 import torch
 
@@ -35,7 +43,7 @@ def _no_grad_inputs(**tensors):
 
 def srr(transforms, slices, psf, vol_shape, res_slice, *, interp_psf=False, slices_mask=None, vol_mask=None,
         slices_weight=None, x0=None, mu=0.0, z=None, n_iter=10, tol=0.0, output_relu=True, deterministic=None,
-        value_scale=1.0, return_info=False):
+        value_scale=1.0, return_info=False, lam=0.0, huber_delta=None, n_outer=1, guide=None):
     """transforms (n,3,4), slices (n,1,h,w) or (n,h,w), psf (pd,ph,pw) -> volume (1,1,D,H,W) after `n_iter` CG iterations.
 
     slices_mask (n,[1,]h,w) bool: pixels that take part.  vol_mask (D,H,W)-shaped bool: the voxels solved for, the rest is 0.
@@ -43,8 +51,25 @@ def srr(transforms, slices, psf, vol_shape, res_slice, *, interp_psf=False, slic
     tol: the solve stops changing x once <r,r> <= tol (on the device; the launches still run and do nothing).
     output_relu: x = max(x, 0) at the end.  deterministic: None = inside a keyed scope; value_scale: as
     kernels.slice_acq_adjoint.  return_info: also a dict of the device histories rr, pq (float64), alpha, beta (float32) and
-    frozen (int32), n_iter + 1 slots each, slot k for iteration k."""
-    _no_grad_inputs(transforms=transforms, slices=slices, psf=psf, slices_weight=slices_weight, x0=x0, z=z)
+    frozen (int32), n_iter + 1 slots each, slot k for iteration k; with lam > 0 they are the last round's and "rounds" lists every round's dict.
+    lam: the weight of the first-order regulariser lam * sum over the grid edges inside vol_mask of c |x_i - x_j|^2 (0 = none).
+    huber_delta: with a guide, c = min(1, huber_delta / |g_i - g_j|) instead of 1.  n_outer: that many complete solves of
+    `n_iter` iterations; round 0 is guided by `guide` (None: c = 1), every later round starts from the x of the round before
+    and is guided by it.  The relu is applied in the last round only."""
+    _no_grad_inputs(transforms=transforms, slices=slices, psf=psf, slices_weight=slices_weight, x0=x0, z=z, guide=guide)
+    lam, n_outer = float(lam), int(n_outer)
+    if not (math.isfinite(lam) and lam >= 0):
+        raise ValueError(f"lam must be finite and >= 0, got {lam}")
+    if huber_delta is not None:
+        huber_delta = float(huber_delta)
+        if not lam > 0:
+            raise ValueError("huber_delta weights the regulariser: it needs lam > 0")
+        if not (math.isfinite(huber_delta) and huber_delta > 0):
+            raise ValueError(f"huber_delta must be finite and > 0, got {huber_delta}")
+    if n_outer < 1:
+        raise ValueError(f"n_outer must be >= 1, got {n_outer}")
+    if huber_delta is None and (n_outer > 1 or guide is not None):
+        raise ValueError("n_outer > 1 and guide reweight the edges by huber_delta: give it")
     if deterministic is None:
         deterministic = _rng.in_keyed_scope()
     det = bool(deterministic)
@@ -68,6 +93,7 @@ def srr(transforms, slices, psf, vol_shape, res_slice, *, interp_psf=False, slic
     wt = prep(slices_weight, (n, h, w))
     zz = prep(z, (D, H, W))
     xs = prep(x0, (D, H, W))
+    gd = prep(guide, (D, H, W))
 
     def normal(v):
         """A^T P W A v"""
@@ -77,34 +103,51 @@ def srr(transforms, slices, psf, vol_shape, res_slice, *, interp_psf=False, slic
         return K.slice_acq_adjoint(tr, ps, s, sm, None, (D, H, W), res_slice, interp_psf=interp_psf, semantics="cuda",
                                    deterministic=det, value_scale=value_scale)
 
-    ws = K.cg_workspace(nvox, n_iter, dev)
-    b = K.slice_acq_adjoint(tr, ps, y if wt is None else K.mul(y, wt), sm, None, (D, H, W), res_slice, interp_psf=interp_psf,
-                            semantics="cuda", deterministic=det, value_scale=value_scale)
-    t0 = None
-    if xs is not None:
-        if vm is not None:
-            xs = torch.where(vm, xs, torch.zeros((), dtype=xs.dtype, device=dev))  # A sees V x0
-        t0 = normal(xs)
-    r, p, x = (torch.empty((D, H, W), dtype=torch.float32, device=dev) for _ in range(3))
-    K.cg_init(ws, b, r, p, x, mask=vm, mu=mu, z=zz, x0=xs, t0=t0)
-    for k in range(1, n_iter + 1):
-        q = normal(p)
-        K.cg_q(ws, k, p, q, mask=vm, mu=mu, tol=tol)
-        K.cg_step(ws, k, p, q, x, r, relu=bool(output_relu))
-        K.cg_dir(ws, k, r, p, tol=tol)
+    def apply(v, g):
+        """(A^T P W A + lam L_g) v"""
+        t = normal(v)
+        if lam > 0:
+            K.tk1_apply(v, t, (D, H, W), lam, mask=vm, guide=g, delta=None if g is None else huber_delta, out=t)
+        return t
+
+    rounds = []
+    for o in range(n_outer):
+        ws = K.cg_workspace(nvox, n_iter, dev)
+        if o == 0:
+            b = K.slice_acq_adjoint(tr, ps, y if wt is None else K.mul(y, wt), sm, None, (D, H, W), res_slice,
+                                    interp_psf=interp_psf, semantics="cuda", deterministic=det, value_scale=value_scale)
+            if xs is not None and vm is not None:
+                xs = torch.where(vm, xs, torch.zeros((), dtype=xs.dtype, device=dev))  # A sees V x0
+        else:
+            xs = gd = x  # the round before: already inside V
+        t0 = None if xs is None else apply(xs, gd)
+        r, p, x = (torch.empty((D, H, W), dtype=torch.float32, device=dev) for _ in range(3))
+        K.cg_init(ws, b, r, p, x, mask=vm, mu=mu, z=zz, x0=xs, t0=t0)
+        relu = bool(output_relu) and o == n_outer - 1
+        for k in range(1, n_iter + 1):
+            q = apply(p, gd)
+            K.cg_q(ws, k, p, q, mask=vm, mu=mu, tol=tol)
+            K.cg_step(ws, k, p, q, x, r, relu=relu)
+            K.cg_dir(ws, k, r, p, tol=tol)
+        rounds.append(ws.info())
     out = x.view(1, 1, D, H, W)
-    return (out, ws.info()) if return_info else out
+    if not return_info:
+        return out
+    return out, (dict(rounds[-1], rounds=rounds) if lam > 0 else rounds[-1])  # lam == 0: the dict it has always been
 
 
 class SRR:
     """`srr` behind the call shape of `PSFreconstruction`: `params` carries psf, interp_psf, res_s, res_r, s_thick and
     volume_shape."""
 
-    def __init__(self, n_iter=10, tol=0.0, output_relu=True):
+    def __init__(self, n_iter=10, tol=0.0, output_relu=True, lam=0.0, huber_delta=None, n_outer=1):
         self.n_iter, self.tol, self.output_relu = n_iter, tol, output_relu
+        # the regulariser of `srr`, handed on only when set
+        self.reg = {k: v for k, v, unset in (("lam", lam, 0.0), ("huber_delta", huber_delta, None), ("n_outer", n_outer, 1))
+                    if v != unset}
 
     def __call__(self, transforms, slices, volume, params, p=None, mu=0, z=None, vol_mask=None, slices_mask=None):
         vol_shape = params["volume_shape"] if volume is None else volume.shape[-3:]
         return srr(transforms, slices, params["psf"], vol_shape, params["res_s"] / params["res_r"],
                    interp_psf=params.get("interp_psf", False), slices_mask=slices_mask, vol_mask=vol_mask, slices_weight=p,
-                   x0=volume, mu=mu, z=z, n_iter=self.n_iter, tol=self.tol, output_relu=self.output_relu)
+                   x0=volume, mu=mu, z=z, n_iter=self.n_iter, tol=self.tol, output_relu=self.output_relu, **self.reg)

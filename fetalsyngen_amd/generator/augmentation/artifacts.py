@@ -204,11 +204,15 @@ class SimulateMotion(RandTransform):
     """Acquire motion-corrupted low-resolution slice stacks of the image and reconstruct it from them (ref :345-425)."""
 
     def __init__(self, prob: float, scanner_params: ScannerParams, recon_params: ReconParams,
-                 deterministic: bool | None = None, srr_iterations: int = 0, srr_mu: float = 0.0):
+                 deterministic: bool | None = None, srr_iterations: int = 0, srr_mu: float = 0.0, srr_lambda: float = 0.0,
+                 srr_huber_delta: float | None = None, srr_outer: int = 1):
         # None: the reconstruction is deterministic inside a keyed scope only; True / False force either accumulation
         self.deterministic = deterministic
         # > 0: refine the PSF reconstruction by that many CG iterations (PSFReconstructor); 0, the default: as the reference
         self.srr_iterations, self.srr_mu = srr_iterations, srr_mu
+        # the first-order regulariser of that solve (PSFReconstructor); handed on only when set
+        self.srr_reg = {k: v for k, v, unset in (("srr_lambda", srr_lambda, 0.0), ("srr_huber_delta", srr_huber_delta, None),
+                                                 ("srr_outer", srr_outer, 1)) if v != unset}
         self.scanner_args = scanner_params
         self.recon_args = recon_params
         self.prob = prob
@@ -233,6 +237,7 @@ class SimulateMotion(RandTransform):
             scanner = Scanner(**asdict(self.scanner_args))
             d_scan = scanner.scan(d)
             refine = dict(srr_iterations=self.srr_iterations, srr_mu=self.srr_mu) if self.srr_iterations else {}
+            refine.update(self.srr_reg)
             recon = PSFReconstructor(**{f.name: getattr(self.recon_args, f.name) for f in fields(self.recon_args)},
                                      deterministic=self.deterministic, **refine)
             output, _ = recon.recon_psf(d_scan, want_weight=False)

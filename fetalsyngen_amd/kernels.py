@@ -979,6 +979,37 @@ def cg_dir(ws: CGWorkspace, k: int, r, p, tol=0.0):
     _lib.check(rc, "fsg_cg_dir_f32")
 
 
+def tk1_apply(p, t, shape, lam, mask=None, guide=None, delta=None, out=None):
+    """out = t + lam * L p over (D,H,W) = `shape` volumes (fsg_tk1_apply_f32): L the graph Laplacian of the 6-neighbour grid
+    inside `mask`, its edges weighted by Huber's min(1, delta / |g_i - g_j|) with a `guide` g.  `out` may be `t` (in place);
+    default: a new tensor.  Returns out."""
+    D, H, W = (int(v) for v in shape)
+    n = D * H * W
+    if out is None:
+        out = torch.empty_like(t)
+    for name, v in (("p", p), ("t", t), ("guide", guide), ("out", out)):
+        if v is None:
+            continue
+        _need_gpu(v)
+        _f32(v, name)
+        if v.numel() != n:
+            raise ValueError(f"{name} has {v.numel()} elements, shape {(D, H, W)} has {n}")
+        if v.device != p.device:
+            raise ValueError(f"{name} is on {v.device}, p on {p.device}")
+    if mask is not None:
+        _need_gpu(mask)
+        if mask.dtype not in (torch.bool, torch.uint8):
+            raise TypeError(f"mask must be bool/uint8, got {mask.dtype}")
+        if mask.numel() != n or mask.device != p.device or not mask.is_contiguous():
+            raise ValueError(f"mask must be contiguous with {n} elements on {p.device}")
+    if (guide is None) != (delta is None):
+        raise ValueError("guide and delta are given together")
+    rc = _lib.load().fsg_tk1_apply_f32(_p(p), _p(t), _p(mask), _p(guide), 0.0 if delta is None else float(delta), float(lam),
+                                       D, H, W, _p(out), _stream(p))
+    _lib.check(rc, "fsg_tk1_apply_f32")
+    return out
+
+
 # ---- per-slice Levenberg-Marquardt slice-to-volume registration (fsg_svr.hip) -----------------------------------
 SVR_MAX_ITER = 4096
 SVR_SLOTS = 32  # doubles per slice in `stats`: H (21, upper triangle), g (6), sum w e^2, sum w, m, two zeros

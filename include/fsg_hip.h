@@ -38,8 +38,8 @@ extern "C" {
                                  fsg_slice_acq_adjoint_backward_f32 / _ws_bytes and with fsg_slice_acq_backward_det_f32 /
                                  _det_ws_bytes, and with fsg_axisangle2mat_f32 / fsg_mat2axisangle_f32 and their _backward_f32,
                                  and with fsg_cg_ws_bytes / fsg_cg_init_f32 / _q_f32 / _step_f32 / _dir_f32, and with
-                                 fsg_svr_ws_bytes / fsg_svr_normal_f32 / fsg_svr_state_bytes / fsg_svr_update_f32:
-                                 entries added, nothing older changed */
+                                 fsg_svr_ws_bytes / fsg_svr_normal_f32 / fsg_svr_state_bytes / fsg_svr_update_f32, and with
+                                 fsg_tk1_apply_f32: entries added, nothing older changed */
 
 #define FSG_E_BADARG (-1)   /* null pointer / non-positive size / bad enum */
 #define FSG_E_TOOBIG (-2)   /* size exceeds what the kernel indexes (2^31-1 voxels per volume) */
@@ -582,6 +582,25 @@ int fsg_cg_q_f32(const float* p, float* t, const uint8_t* mask, float mu, double
 int fsg_cg_step_f32(const float* p, const float* q, float* x, float* r, size_t n, int k, int n_iter, int flags, void* ws,
                     size_t ws_bytes, void* stream);
 int fsg_cg_dir_f32(const float* r, float* p, double tol, size_t n, int k, int n_iter, void* ws, size_t ws_bytes, void* stream);
+
+/* ---- first-order regulariser of the solve above (fsg_tk1.hip) ---------------------------------------
+ *     out = t + lam * L p        over (D,H,W) fp32 volumes, W fastest
+ * L = D^T C D is the weighted graph Laplacian of the 6-neighbour grid.  An edge (i, j) takes part iff both ends are inside the
+ * volume and, with `mask` (V, one byte per voxel, non-zero keeps; NULL = all), both ends are in V: the free boundary follows the
+ * mask.  Edge weight c = 1 without `guide`; with `guide` g and delta > 0 it is Huber's, a = |fl(g_i - g_j)|,
+ * c = (a <= delta) ? 1 : fl(delta / a).  a has the same bits from either end of an edge, so L is symmetric entry for entry.
+ * Per voxel i, fp32 with one rounding per operation (no contraction; the division is correctly rounded):
+ *     acc = +0;  for the neighbours j in the order x-, x+, y-, y+, z-, z+ (x along W, z along D) that take part (the others
+ *     are skipped, they do not contribute a zero):  d = fl(p_i - p_j);  with a guide d = fl(c * d);  acc = fl(acc + d);
+ *     out_i = fl(t_i + fl(lam * acc)).
+ * A voxel outside V gets out_i = t_i (fsg_cg_q_f32 / fsg_cg_init_f32 apply V afterwards).  A gather in a fixed order: the same
+ * bits in any run and on any stream.  Four consecutive voxels per thread; 16-byte loads and stores when every float pointer of
+ * the call is 16-byte aligned and mask 4-byte aligned (the neighbour rows too when W % 4 == 0), scalars otherwise, same values.
+ * `out` may be `t` itself (in place).  Refusals, before any launch and with nothing written: a null p, t or out; D, H or W < 1;
+ * lam not finite or < 0; with a guide, delta not finite or <= 0 (without one delta is ignored); out sharing a byte with p,
+ * guide or mask, or overlapping t other than out == t (FSG_E_BADARG); D * H * W > 2^31 - 1 (FSG_E_TOOBIG). */
+int fsg_tk1_apply_f32(const float* p, const float* t, const uint8_t* mask, const float* guide, float delta, float lam, int D,
+                      int H, int W, float* out, void* stream);
 
 /* ---- per-slice Levenberg-Marquardt slice-to-volume registration (fsg_svr.hip) ----------------------
  * One solve is the launch sequence, for k = 0..K (K = n_iter), all on one stream:

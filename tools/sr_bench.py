@@ -18,7 +18,9 @@ backward_<mode>_grad_transforms_ms of the same session.
 `axisangle2mat_autograd`, alone and inside one iteration of a pose fit, at n = 80 and 250, by the host clock (pose_chain below).
 --srr runs INSTEAD of the legs above, on the same problem: `svort.srr` (--srr-iters iterations) beside the same conjugate gradients
 written in torch operations around slice_acquisition / slice_acquisition_adjoint, float and deterministic, and the three vector
-launches of an iteration alone (srr_bench below).
+launches of an iteration alone (srr_bench below).  --srr-lambda L > 0 adds the same solve with the first-order regulariser
+(`srr_lam`; with --srr-huber-delta also `srr_lam_huber`, guided from round 0 on, --srr-outer rounds) to the alternated legs, and
+`kernels.tk1_apply` alone against a streaming pass of the same bytes (tk1_bench below).
 --svr runs INSTEAD of the legs above, on the same problem: a round of `svort.svr` beside a pose-fit iteration through autograd and
 beside the forward plus the grad_transforms-only backward, at n = 80 and 250 (svr_bench below).
 """
@@ -135,6 +137,37 @@ def torch_cg(tr, y, psf, vs, rs, n_iter, mu, deterministic, interp_psf=True):
     return torch.relu(x)
 
 
+def tk1_bench(a, dev, vs):
+    """kernels.tk1_apply alone (--srr with --srr-lambda > 0), by device events over --reps launches, alternated three times with a
+    streaming pass of the same bytes (torch.mul by 1 into another tensor: 16-byte loads and stores, half the bytes read, half
+    written).  Bytes from the shapes: p, t and out once each (the neighbours are re-reads of p that the caches serve), the guide
+    once, the mask a quarter of a float volume."""
+    n = int(np.prod(vs))
+    g = lambda: torch.rand(vs, device=dev)  # noqa: E731
+    p, t, guide, o = g(), g(), g(), torch.empty(vs, device=dev)
+    mask = torch.rand(vs, device=dev) < 0.9
+    lam, delta = a.srr_lambda, a.srr_huber_delta if a.srr_huber_delta is not None else 0.05
+    legs = {"tk1": (12 * n, lambda: K.tk1_apply(p, t, vs, lam, out=o)),
+            "tk1_mask": (13 * n, lambda: K.tk1_apply(p, t, vs, lam, mask=mask, out=o)),
+            "tk1_mask_inplace": (13 * n, lambda: K.tk1_apply(p, t, vs, lam, mask=mask, out=t)),
+            "tk1_mask_huber": (17 * n, lambda: K.tk1_apply(p, t, vs, lam, mask=mask, guide=guide, delta=delta, out=o))}
+    out = {"tk1_clock": f"device events around {a.reps} launches, alternated three times with the copy of the same bytes"}
+    for name, (nbytes, fn) in legs.items():
+        half = nbytes // 8 * 4  # bytes read = bytes written
+        src = torch.rand(half // 4, device=dev)
+        dst = torch.empty_like(src)
+        copy = lambda: torch.mul(src, 1.0, out=dst)  # noqa: E731
+        rows = {"kernel": [], "copy": []}
+        for _ in range(3):
+            rows["kernel"].append(round(timed(fn, a.reps), 4))
+            rows["copy"].append(round(timed(copy, a.reps), 4))
+        out[f"{name}_ms"], out[f"{name}_copy_ms"], out[f"{name}_bytes"] = rows["kernel"], rows["copy"], nbytes
+        out[f"{name}_GB_per_s"] = round(nbytes / min(rows["kernel"]) / 1e6, 1)
+        out[f"{name}_copy_GB_per_s"] = round(2 * half / min(rows["copy"]) / 1e6, 1)
+        del src, dst
+    return out
+
+
 def srr_bench(a, dev, vs, ss, psf, vol, tr, res):
     """--srr.  Per setting (float / deterministic adjoint): ms per iteration of svort.srr and of torch_cg, the legs alternated
     three times after a warm-up, host clock around one solve ended by a synchronise, divided by the iterations (the set-up,
@@ -149,25 +182,34 @@ def srr_bench(a, dev, vs, ss, psf, vol, tr, res):
     out = {"volume": vs, "slices": [a.slices, ss, ss], "psf": list(psf.shape), "psf_taps": int((psf > 0).sum()), "iters": n_iter,
            "mu": mu, "interp_psf": True, "clock": "host, one solve per timing, synchronised at both ends"}
 
-    def once(fn):
+    def once(fn, iters=n_iter):
         torch.cuda.synchronize()
         t0 = time.perf_counter()
         fn()
         torch.cuda.synchronize()
-        return round((time.perf_counter() - t0) * 1e3 / n_iter, 3)
+        return round((time.perf_counter() - t0) * 1e3 / iters, 3)
 
+    lam, delta, outer = a.srr_lambda, a.srr_huber_delta, a.srr_outer
     for tag, det in (("float", False), ("det", True)):
-        legs = {"srr": lambda: srr(tr, y, psf, vs, rs, interp_psf=True, mu=mu, n_iter=n_iter, deterministic=det),
-                "torch": lambda: torch_cg(tr, y, psf, vs, rs, n_iter, mu, det)}
+        solve = lambda **kw: srr(tr, y, psf, vs, rs, interp_psf=True, mu=mu, n_iter=n_iter, deterministic=det, **kw)  # noqa: E731
+        legs = {"srr": solve, "torch": lambda: torch_cg(tr, y, psf, vs, rs, n_iter, mu, det)}
+        iters = {"srr": n_iter, "torch": n_iter}
+        if lam > 0:  # the same solve with the first-order regulariser: unguided, and guided from round 0 on (by the truth)
+            legs["srr_lam"], iters["srr_lam"] = (lambda: solve(lam=lam)), n_iter
+            if delta is not None:
+                legs["srr_lam_huber"] = lambda: solve(lam=lam, huber_delta=delta, n_outer=outer, guide=vol)
+                iters["srr_lam_huber"] = n_iter * outer
         xs = {k: fn() for k, fn in legs.items()}  # warm-up, and the two routes solve the same problem
         out[f"{tag}_srr_vs_torch_max_abs_over_max"] = float((xs["srr"] - xs["torch"]).abs().max() / xs["torch"].abs().max())
         del xs
         row = {k: [] for k in legs}
         for _ in range(3):
             for k, fn in legs.items():
-                row[k].append(once(fn))
+                row[k].append(once(fn, iters[k]))
         out[f"{tag}_ms_per_iter"] = row
         out[f"{tag}_torch_over_srr"] = round(min(row["torch"]) / min(row["srr"]), 3)
+    if lam > 0:
+        out.update(tk1_bench(a, dev, vs))
     # the vector launches alone
     n = int(np.prod(vs))
     g = lambda: torch.rand(vs, device=dev)  # noqa: E731
@@ -279,6 +321,9 @@ def main():
     ap.add_argument("--chain-iters", type=int, default=200, help="iterations per --pose-chain timing (host clock)")
     ap.add_argument("--srr", action="store_true", help="time svort.srr against the same CG in torch operations instead")
     ap.add_argument("--srr-iters", type=int, default=6, help="CG iterations per --srr solve")
+    ap.add_argument("--srr-lambda", type=float, default=0.0, help="> 0: also time --srr with the first-order regulariser, and tk1_apply alone")
+    ap.add_argument("--srr-huber-delta", type=float, default=None, help="with --srr-lambda: also the guided (Huber-weighted) solve")
+    ap.add_argument("--srr-outer", type=int, default=1, help="rounds of the guided solve (n_outer)")
     ap.add_argument("--svr", action="store_true", help="time a round of svort.svr against a pose-fit iteration through autograd instead")
     ap.add_argument("--svr-iters", type=int, default=5, help="iterations per --svr solve (iters + 1 rounds)")
     a = ap.parse_args()
