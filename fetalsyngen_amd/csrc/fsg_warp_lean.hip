@@ -255,19 +255,53 @@ __global__ __launch_bounds__(1024, 8) void warp_lean_kernel(FsgDeformK D, const 
     if (HAS_NN && live && (ABL != 1 || P.bx == 1.2345e30f)) lean_store_label(r_onn, oelem, (DT)P.lab);
   };
 
-  // the barrier only paces the 16 waves (same z slab -> the brick's source block is what L1 holds); nothing is
-  // exchanged through memory inside the loop, so no fence: loads of the next step stay in flight across it
+  // The loop.  Every trip issues the same vector-memory operations in the same order and no issue() sits under a
+  // branch: the compiler's s_waitcnt vmcnt(N) in front of a blend then counts exactly the operations that are younger than
+  // the step's own gathers, and the next step's gathers stay in flight across the blend.  (With `if (more) issue(..)`
+  // inside the loop the wait has to hold on the path where the branch is not taken as well, and becomes vmcnt(0): every
+  // blend then waited for the gathers issued just before it -- profiles/r13_a_warp_in_flight.txt.)  The one or two steps
+  // of a row that have nothing left to issue therefore run after the loop, as straight-line code.
+  // The barrier only paces the 16 waves (same z slab -> the brick's source block is what L1 holds); nothing is
+  // exchanged through memory inside the loop, so no fence: loads of the next step stay in flight across it.
+  const int nsteps = (D.n2 + KZ - 1) / KZ;
+  auto paced = [&](int s) {
+    if (pace == 1 || (pace == 2 && (s & 1))) __builtin_amdgcn_s_barrier();
+  };
   Pend A, B;
   issue(0, A);
-  for (int kb = 0; kb < D.n2; kb += 2 * KZ) {
-    const bool more1 = kb + KZ < D.n2;
-    if (more1) issue(kb + KZ, B);
-    finish(kb, A);
-    if (pace == 1) __builtin_amdgcn_s_barrier();
-    if (more1) {
-      if (kb + 2 * KZ < D.n2) issue(kb + 2 * KZ, A);
-      finish(kb + KZ, B);
-      if (pace) __builtin_amdgcn_s_barrier();
+  if constexpr (HAS_IMG) {
+    // The dual-source kernels keep the loop with the issue() under a branch: their second set of corners leaves no
+    // registers for the straight-line tail below (it spills 12 bytes per lane), and their blends wait as before.
+    for (int kb = 0; kb < D.n2; kb += 2 * KZ) {
+      const bool more1 = kb + KZ < D.n2;
+      if (more1) issue(kb + KZ, B);
+      finish(kb, A);
+      paced(kb / KZ);
+      if (more1) {
+        if (kb + 2 * KZ < D.n2) issue(kb + 2 * KZ, A);
+        finish(kb + KZ, B);
+        paced(kb / KZ + 1);
+      }
+    }
+  } else {
+    int s = 0;
+    for (; s + 2 < nsteps; s += 2) {
+      issue((s + 1) * KZ, B);
+      finish(s * KZ, A);
+      paced(s);
+      issue((s + 2) * KZ, A);
+      finish((s + 1) * KZ, B);
+      paced(s + 1);
+    }
+    if (s + 2 == nsteps) {
+      issue((s + 1) * KZ, B);
+      finish(s * KZ, A);
+      paced(s);
+      finish((s + 1) * KZ, B);
+      paced(s + 1);
+    } else {
+      finish(s * KZ, A);
+      paced(s);
     }
   }
 }
@@ -278,12 +312,15 @@ int launch_lean(const FsgDeformK& D, const EpiK& E, const int32_t* mm6, const fl
   constexpr int KZ = 32, WI = 8;
   constexpr int PI = WI, PJ = (16 / WI) * (64 / KZ);
   const dim3 grid((unsigned)(((D.n0 + PI - 1) / PI) * ((D.n1 + PJ - 1) / PJ))), block(1024);
-  // Pacing.  The barrier keeps the 16 waves on one z slab so that L1 holds the source block they share.  With a small
-  // slope of the source position along the output row (|dx/dk|, |dy/dk| -- the affine's third column) a slab's block is
-  // small and stays resident across two steps, and a barrier every second step is 4-5 us faster at 256^3; beyond
-  // ~16 degrees the every-step barrier wins (gpurun_out r4d, profiles/r02_f_warp_pace.txt).
+  // Pacing.  The barrier keeps the 16 waves on one z slab so that L1 holds the source block they share.  While every blend
+  // waited for the gathers issued just before it (see the loop), a barrier every second step was faster below ~16 degrees
+  // and the period followed the affine's third column (profiles/r02_f_warp_pace.txt).  With the next step's gathers in
+  // flight a wave no longer stands at the barrier with nothing requested, and the barrier every step is the fastest or
+  // within 1 us of it at 0, 12 and 20 degrees (256^3: 72.4 / 89.0 / 110.5 us against 75.6 / 94.3 / 120.9 every second step
+  // and 72.2 / 99.3 / 141.7 without: profiles/r13_a_warp_in_flight.txt).  The dual-source kernels, whose loop is the
+  // earlier one, keep the earlier rule.
   const float slope = fmaxf(fabsf(D.A[2]), fabsf(D.A[5]));
-  const int pace = g_lean_pace >= 0 ? g_lean_pace : (slope < 0.27f ? 2 : 1);
+  const int pace = g_lean_pace >= 0 ? g_lean_pace : (src_img && slope < 0.27f ? 2 : 1);
 #define FSG_LEAN(L, N, F) \
   hipLaunchKernelGGL((warp_lean_kernel<ST, DT, L, N, F, KZ, WI>), grid, block, 0, st, D, mm6, src_lin, out_lin, src_nn, out_nn, E, \
                      pace, LeanImg<false>{})
