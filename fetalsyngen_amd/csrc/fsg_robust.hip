@@ -1,0 +1,461 @@
+// fsg_robust.hip -- outlier weights for srr / svr: the robust-statistics EM of the slice-to-volume family (DESIGN.md section
+// 25; the contract, the rule and the layout of the state block are in include/fsg_hip.h, fsg_robust_*).
+//
+//   fsg_robust_estep_f32    one streaming pass over y and s = A x: per pixel the inlier posterior p, per workgroup one partial
+//                           of the six per-slice sums (count, sum p, sum p e^2, sum (1-p)^2, min y, max y).
+//   fsg_robust_update_f32   one workgroup: folds a slice's partials in double, then the pixel parameters (sigma, c), one sweep
+//                           of the two-class slice EM, and the two floats (kappa, inv2var) the next estep reads.
+//   fsg_robust_weights_f32  the last pass: out = ws_k (* p) on the pixels that take part, 0 elsewhere.
+//
+// MI355X shape of the work: the passes are pure streaming (9 to 13 bytes a pixel, no reuse), so the workgroup is 256 threads
+// that each own FOUR consecutive pixels of one slice, 1024 pixels a workgroup: with 16-byte alignment every lane issues one
+// 16-byte load per array and a wave reads 1 KiB contiguously.  No LDS beyond the 4 x 8 floats where the waves meet, about 30
+// VGPRs: occupancy is not the limit, HBM is.  No atomics: fixed shuffle tree per wave, waves in order, one 8-float partial per
+// workgroup in a workspace that needs no zeroing, a slice's partials added in double in index order by the update.
+#include "fsg_common.h"
+#include <math.h>
+
+namespace {
+
+constexpr int RB_THREADS = 256;
+constexpr int RB_CHUNK = 4 * RB_THREADS;  // pixels of one slice per workgroup
+constexpr int RB_SLOTS = 8;               // floats of a partial: N, sum p, sum p e^2, sum (1-p)^2, min y, max y, 0, 0
+constexpr int RB_ROW = 6;                 // doubles of a slice's row
+constexpr int RB_MAX_EM = 4096;
+constexpr float RB_FLT_MAX = 3.402823466e+38f;
+
+struct RbState {  // pointers into the state block for (n, T); layout in fsg_hip.h
+  double* consts;   // [4] R, m, sigma_min, 0
+  double* rows;     // [n][6]
+  double* u;        // [n]
+  double* sigma;    // [s]
+  double* c;        // [s]
+  double* mu1;      // [s]
+  double* mu2;      // [s]
+  double* ws;       // [s][n]
+  float* scal;      // [2] kappa, inv2var
+  int32_t* frozen;  // [s]
+};
+
+__host__ __device__ inline size_t rb_state_bytes(size_t n, int T) {
+  const size_t s = (size_t)T + 1;
+  return (8 * (4 + RB_ROW * n + n + 4 * s + s * n) + 4 * (2 + s) + 7) & ~(size_t)7;
+}
+
+__host__ __device__ inline RbState rb_state(void* p, size_t n, int T) {
+  const size_t s = (size_t)T + 1;
+  RbState S;
+  S.consts = (double*)p;
+  S.rows = S.consts + 4;
+  S.u = S.rows + RB_ROW * n;
+  S.sigma = S.u + n;
+  S.c = S.sigma + s;
+  S.mu1 = S.c + s;
+  S.mu2 = S.mu1 + s;
+  S.ws = S.mu2 + s;
+  S.scal = (float*)(S.ws + s * n);
+  S.frozen = (int32_t*)(S.scal + 2);
+  return S;
+}
+
+inline int rb_chunks(int h, int w) { return (int)(((size_t)h * (size_t)w + RB_CHUNK - 1) / RB_CHUNK); }
+
+struct RbIn {
+  const float* y;
+  const float* s;
+  const uint8_t* mask;
+  const float* sw;
+  float min_weight;
+  int hw;
+};
+
+// The four pixels of a thread: e = fl(y - s), `part` = the pixel is in Omega.  A pixel past the end of the slice takes no part
+// and no address is formed for it.
+template <bool VEC>
+__device__ __forceinline__ void rb_load(const RbIn& I, size_t base, int e0, float (&y)[4], float (&e)[4], bool (&part)[4]) {
+  const int cnt = I.hw - e0 < 4 ? I.hw - e0 : 4;  // >= 1 for a thread that is called
+  float s[4], wg[4];
+  uint32_t mk = 0x01010101u;
+  if (VEC) {  // hw % 4 == 0, so cnt == 4
+    const float4 ty = *reinterpret_cast<const float4*>(I.y + base + e0);
+    const float4 ts = *reinterpret_cast<const float4*>(I.s + base + e0);
+    y[0] = ty.x; y[1] = ty.y; y[2] = ty.z; y[3] = ty.w;
+    s[0] = ts.x; s[1] = ts.y; s[2] = ts.z; s[3] = ts.w;
+    if (I.mask) mk = *reinterpret_cast<const uint32_t*>(I.mask + base + e0);
+    if (I.sw) {
+      const float4 tw = *reinterpret_cast<const float4*>(I.sw + base + e0);
+      wg[0] = tw.x; wg[1] = tw.y; wg[2] = tw.z; wg[3] = tw.w;
+    }
+  } else {
+    mk = 0;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const bool in = j < cnt;
+      const size_t a = base + e0 + (in ? j : 0);
+      y[j] = in ? I.y[a] : 0.f;
+      s[j] = in ? I.s[a] : 0.f;
+      wg[j] = (in && I.sw) ? I.sw[a] : 0.f;
+      const uint32_t b = !in ? 0u : (I.mask ? (I.mask[a] != 0 ? 1u : 0u) : 1u);
+      mk |= b << (8 * j);
+    }
+  }
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    e[j] = y[j] - s[j];
+    bool ok = j < cnt && ((mk >> (8 * j)) & 255u) != 0;
+    if (I.sw) ok = ok && wg[j] > 0.f && wg[j] >= I.min_weight;  // a NaN weight takes no part
+    part[j] = ok && fabsf(e[j]) <= RB_FLT_MAX;                  // NaN and Inf fail
+  }
+}
+
+// p = 1 / (1 + kappa * expf(e^2 * inv2var)), one rounding per operation; an overflowing expf gives 0
+__device__ __forceinline__ float rb_posterior(float e2, float kappa, float inv2var) {
+  const float x = expf(e2 * inv2var);
+  return x <= RB_FLT_MAX ? 1.f / (1.f + kappa * x) : 0.f;
+}
+
+template <bool VEC>
+__global__ __launch_bounds__(RB_THREADS) void rb_estep_kernel(RbIn I, int n, int T, int first, const void* state,
+                                                              float* __restrict__ ws) {
+  __shared__ float red[RB_THREADS / FSG_WAVE][RB_SLOTS];
+  const int k = blockIdx.y, tid = threadIdx.x, lane = tid & (FSG_WAVE - 1), wave = tid / FSG_WAVE;
+  const int e0 = (blockIdx.x * RB_THREADS + tid) * 4;
+  float v[4] = {0.f, 0.f, 0.f, 0.f};
+  float mn = INFINITY, mx = -INFINITY;
+  // no thread leaves before the fold
+  if (e0 < I.hw) {
+    const RbState S = rb_state(const_cast<void*>(state), (size_t)n, T);
+    const float kappa = first ? 0.f : S.scal[0], inv2var = first ? 0.f : S.scal[1];
+    float y[4], e[4];
+    bool part[4];
+    rb_load<VEC>(I, (size_t)k * I.hw, e0, y, e, part);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      if (!part[j]) continue;
+      const float e2 = e[j] * e[j];
+      const float p = first ? 1.f : rb_posterior(e2, kappa, inv2var);
+      const float q = 1.f - p;
+      v[0] += 1.f;
+      v[1] += p;
+      v[2] += p * e2;
+      v[3] += q * q;
+      mn = fminf(mn, y[j]);
+      mx = fmaxf(mx, y[j]);
+    }
+  }
+#pragma unroll
+  for (int o = FSG_WAVE / 2; o > 0; o >>= 1) {
+#pragma unroll
+    for (int j = 0; j < 4; ++j) v[j] += __shfl_down(v[j], o, FSG_WAVE);
+    mn = fminf(mn, __shfl_down(mn, o, FSG_WAVE));
+    mx = fmaxf(mx, __shfl_down(mx, o, FSG_WAVE));
+  }
+  if (lane == 0) {
+#pragma unroll
+    for (int j = 0; j < 4; ++j) red[wave][j] = v[j];
+    red[wave][4] = mn;
+    red[wave][5] = mx;
+  }
+  __syncthreads();
+  if (tid < RB_SLOTS) {
+    float s = 0.f;
+    if (tid < RB_ROW) {
+      s = red[0][tid];
+#pragma unroll
+      for (int q = 1; q < RB_THREADS / FSG_WAVE; ++q)
+        s = tid < 4 ? s + red[q][tid] : (tid == 4 ? fminf(s, red[q][tid]) : fmaxf(s, red[q][tid]));
+    }
+    ws[((size_t)k * gridDim.x + blockIdx.x) * RB_SLOTS + tid] = s;  // all 8 slots: the workspace needs no zeroing
+  }
+}
+
+struct RbOpts {
+  double c0, sigma_floor, slice_floor;
+  int min_pixels;
+};
+
+__device__ __forceinline__ bool rb_finite(double x) { return fabs(x) <= 1.7976931348623157e308; }  // NaN fails
+
+__device__ __forceinline__ double rb_normal_pdf(double u, double mu, double v) {
+  const double d = u - mu;
+  return exp(-(d * d) / (2.0 * v)) / sqrt(6.283185307179586 * v);
+}
+
+// One workgroup.  Phase A, a thread per slice: the row and u.  Phase B, wave 0: every sum over the slices, in slice-index
+// order.  Phase C, a thread per slice: the new slice weight.
+__global__ __launch_bounds__(RB_THREADS) void rb_update_kernel(void* state, const float* __restrict__ ws, int chunks, int n, int t,
+                                                               int T, RbOpts O) {
+  __shared__ double sh[6];  // frozen, mu1, mu2, v1, v2, mix
+  const RbState S = rb_state(state, (size_t)n, T);
+  const int tid = threadIdx.x;
+  const double* wold = t > 0 ? S.ws + (size_t)(t - 1) * n : nullptr;
+  double* wnew = S.ws + (size_t)t * n;
+  for (int k = tid; k < n; k += RB_THREADS) {
+    const float* p = ws + (size_t)k * chunks * RB_SLOTS;
+    double r[4] = {0.0, 0.0, 0.0, 0.0}, mn = INFINITY, mx = -INFINITY;
+    for (int b = 0; b < chunks; ++b) {
+#pragma unroll
+      for (int j = 0; j < 4; ++j) r[j] = r[j] + (double)p[(size_t)b * RB_SLOTS + j];
+      mn = fmin(mn, (double)p[(size_t)b * RB_SLOTS + 4]);
+      mx = fmax(mx, (double)p[(size_t)b * RB_SLOTS + 5]);
+    }
+    const bool any = r[0] > 0.0;  // a slice without a pixel stores no Inf
+    double* row = S.rows + (size_t)k * RB_ROW;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) row[j] = r[j];
+    row[4] = any ? mn : 0.0;
+    row[5] = any ? mx : 0.0;
+    const bool ok = r[0] >= (double)O.min_pixels && any;
+    S.u[k] = ok ? sqrt(r[3] / r[0]) : 0.0;
+  }
+  __syncthreads();
+  // Wave 0, all 64 lanes in step: a lane loads the figures of ONE slice (64 slices per trip, one memory latency), then the
+  // wave walks the 64 in index order, every lane adding the broadcast values: the sums of a serial loop over the slices, in
+  // its order, without its one memory latency per slice.  Every lane holds the same scalars; lane 0 stores them.
+  if (tid < FSG_WAVE) {
+    bool frozen = t > 0 && S.frozen[t - 1] != 0;
+    double m, smin;
+    if (t == 0) {
+      double mn = INFINITY, mx = -INFINITY;  // min and max do not depend on the order
+      for (int k = tid; k < n; k += FSG_WAVE) {
+        const double* row = S.rows + (size_t)k * RB_ROW;
+        if (row[0] > 0.0) { mn = fmin(mn, row[4]); mx = fmax(mx, row[5]); }
+      }
+#pragma unroll
+      for (int o = FSG_WAVE / 2; o > 0; o >>= 1) {
+        mn = fmin(mn, __shfl_xor(mn, o, FSG_WAVE));
+        mx = fmax(mx, __shfl_xor(mx, o, FSG_WAVE));
+      }
+      const double R = mx - mn;
+      const bool good = rb_finite(R) && R > 0.0 && rb_finite(1.0 / R);
+      if (tid == 0) {
+        S.consts[0] = good ? R : 0.0;
+        S.consts[1] = good ? 1.0 / R : 0.0;
+        S.consts[2] = good ? O.sigma_floor * R : 0.0;
+        S.consts[3] = 0.0;
+      }
+      m = good ? 1.0 / R : 0.0;
+      smin = good ? O.sigma_floor * R : 0.0;
+      frozen = !good;
+    } else {
+      m = S.consts[1];
+      smin = S.consts[2];
+    }
+    double S0 = 0.0, S2 = 0.0, Nw = 0.0;
+    double sw = 0.0, swu = 0.0, so = 0.0, sou = 0.0, umax = 0.0, nok = 0.0;
+    for (int base = 0; base < n; base += FSG_WAVE) {
+      const int k = base + tid, cnt = n - base < FSG_WAVE ? n - base : FSG_WAVE;
+      const bool in = k < n;
+      const double* row = S.rows + (size_t)(in ? k : 0) * RB_ROW;
+      const double lN = in ? row[0] : 0.0, lp = in ? row[1] : 0.0, le = in ? row[2] : 0.0, lu = in ? S.u[k] : 0.0;
+      const double lw = !in ? 0.0 : (wold ? wold[k] : 1.0);
+      for (int j = 0; j < cnt; ++j) {
+        const double N = __shfl(lN, j, FSG_WAVE), sp = __shfl(lp, j, FSG_WAVE), se = __shfl(le, j, FSG_WAVE);
+        const double u = __shfl(lu, j, FSG_WAVE), wj = __shfl(lw, j, FSG_WAVE);
+        const bool ok = N >= (double)O.min_pixels && N > 0.0;
+        const double w = ok ? wj : 0.0;
+        S0 = S0 + w * sp;
+        S2 = S2 + w * se;
+        Nw = Nw + w * N;
+        if (ok) {  // the slice mixture's moments under the old weights (used for t >= 1)
+          sw = sw + wj;
+          swu = swu + wj * u;
+          so = so + (1.0 - wj);
+          sou = sou + (1.0 - wj) * u;
+          umax = fmax(umax, u);
+          nok = nok + 1.0;
+        }
+      }
+    }
+    const double var = fmax(S2 / S0, smin * smin);
+    const double c = t == 0 ? O.c0 : S0 / Nw;
+    const double kappa = ((1.0 - c) / c) * m * sqrt(6.283185307179586 * var), inv2var = 1.0 / (2.0 * var);
+    const float kf = (float)kappa, vf = (float)inv2var;
+    frozen = frozen || !(Nw > 0.0) || !(S0 > 0.0) || !rb_finite(S2) || !rb_finite(var) || !(var > 0.0) || !rb_finite(c) ||
+             !(fabsf(kf) <= RB_FLT_MAX) || !(fabsf(vf) <= RB_FLT_MAX) || !(kf >= 0.f);
+    double mu1 = 0.0, mu2 = 0.0, v1 = 0.0, v2 = 0.0, mix = 1.0;
+    if (t > 0 && !frozen) {  // wave-uniform
+      const double fl2 = O.slice_floor * O.slice_floor;
+      mu1 = swu / sw;
+      mu2 = so > 0.0 ? sou / so : (umax + mu1) / 2.0;
+      double a1 = 0.0, a2 = 0.0;
+      for (int base = 0; base < n; base += FSG_WAVE) {
+        const int k = base + tid, cnt = n - base < FSG_WAVE ? n - base : FSG_WAVE;
+        const bool in = k < n;
+        const double lN = in ? S.rows[(size_t)k * RB_ROW] : 0.0, lu = in ? S.u[k] : 0.0, lw = in ? wold[k] : 0.0;
+        for (int j = 0; j < cnt; ++j) {
+          const double N = __shfl(lN, j, FSG_WAVE), u = __shfl(lu, j, FSG_WAVE), w = __shfl(lw, j, FSG_WAVE);
+          if (!(N >= (double)O.min_pixels && N > 0.0)) continue;
+          a1 = a1 + w * ((u - mu1) * (u - mu1));
+          a2 = a2 + (1.0 - w) * ((u - mu2) * (u - mu2));
+        }
+      }
+      v1 = fmax(a1 / sw, fl2);
+      v2 = so > 0.0 ? a2 / so : 0.0;
+      if (!(v2 > 0.0)) v2 = ((mu2 - mu1) * (mu2 - mu1)) / 4.0;
+      v2 = fmax(v2, fl2);
+      mix = sw / nok;
+      frozen = !rb_finite(mu1) || !rb_finite(mu2) || !rb_finite(v1) || !rb_finite(v2) || !rb_finite(mix);
+    }
+    if (tid == 0) {
+      S.sigma[t] = frozen ? 0.0 : sqrt(var);
+      S.c[t] = frozen ? 0.0 : c;
+      S.mu1[t] = frozen ? 0.0 : mu1;
+      S.mu2[t] = frozen ? 0.0 : mu2;
+      S.frozen[t] = frozen ? 1 : 0;
+      S.scal[0] = frozen ? 0.f : kf;
+      S.scal[1] = frozen ? 0.f : vf;
+      sh[0] = frozen ? 1.0 : 0.0;
+      sh[1] = mu1; sh[2] = mu2; sh[3] = v1; sh[4] = v2; sh[5] = mix;
+    }
+  }
+  __syncthreads();
+  const bool frozen = sh[0] != 0.0;
+  const double mu1 = sh[1], mu2 = sh[2], v1 = sh[3], v2 = sh[4], mix = sh[5];
+  for (int k = tid; k < n; k += RB_THREADS) {
+    const double N = S.rows[(size_t)k * RB_ROW];
+    const bool ok = N >= (double)O.min_pixels && N > 0.0;
+    double w = ok ? 1.0 : 0.0;
+    if (ok && t > 0 && !frozen) {
+      const double u = S.u[k];
+      if (u < mu1) w = 1.0;
+      else if (u > mu2) w = 0.0;
+      else {
+        const double g1 = rb_normal_pdf(u, mu1, v1) * mix, g2 = rb_normal_pdf(u, mu2, v2) * (1.0 - mix);
+        const double den = g1 + g2;
+        // both densities underflowed, or a zero variance: the class of the nearer mean
+        w = (den > 0.0 && rb_finite(den) && rb_finite(g1)) ? g1 / den : (fabs(u - mu1) <= fabs(u - mu2) ? 1.0 : 0.0);
+      }
+    }
+    wnew[k] = w;
+  }
+}
+
+template <bool VEC>
+__global__ __launch_bounds__(RB_THREADS) void rb_weights_kernel(RbIn I, int n, int T, int both, const void* state,
+                                                                float* __restrict__ out) {
+  const int k = blockIdx.y;
+  const int e0 = (blockIdx.x * RB_THREADS + threadIdx.x) * 4;
+  if (e0 >= I.hw) return;
+  const RbState S = rb_state(const_cast<void*>(state), (size_t)n, T);
+  const float wk = (float)S.ws[(size_t)T * n + k], kappa = S.scal[0], inv2var = S.scal[1];
+  float y[4], e[4], o[4];
+  bool part[4];
+  const size_t base = (size_t)k * I.hw;
+  rb_load<VEC>(I, base, e0, y, e, part);
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    float v = 0.f;
+    if (part[j]) v = both ? wk * rb_posterior(e[j] * e[j], kappa, inv2var) : wk;
+    o[j] = v;
+  }
+  if (VEC) {
+    *reinterpret_cast<float4*>(out + base + e0) = make_float4(o[0], o[1], o[2], o[3]);
+  } else {
+    const int cnt = I.hw - e0 < 4 ? I.hw - e0 : 4;
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+      if (j < cnt) out[base + e0 + j] = o[j];
+  }
+}
+
+bool rb_overlap(const void* p, size_t bytes, const void* q, size_t qbytes) {
+  if (!p || !q) return false;
+  const uintptr_t a = (uintptr_t)p, b = (uintptr_t)q;
+  return a < b + qbytes && b < a + bytes;
+}
+
+// what estep and weights share: sizes, pointers, options, the state and its alignment
+int rb_check_pixels(const float* y, const float* s, const float* sw, float min_weight, int n, int h, int w, int n_em,
+                    const void* state, size_t state_bytes) {
+  if (n <= 0 || h <= 0 || w <= 0 || n_em < 1 || n_em > RB_MAX_EM) return FSG_E_BADARG;
+  if (!y || !s || !state) return FSG_E_BADARG;
+  if (!(min_weight >= 0.f)) return FSG_E_BADARG;  // negative or NaN
+  if (n > 65535 || (size_t)n * (size_t)h * (size_t)w > (size_t)0x7FFFFFFF) return FSG_E_TOOBIG;
+  if (state_bytes < rb_state_bytes((size_t)n, n_em)) return FSG_E_BADARG;
+  if (((uintptr_t)y & 3) || ((uintptr_t)s & 3) || ((uintptr_t)sw & 3)) return FSG_E_ALIGN;
+  if ((uintptr_t)state & 7) return FSG_E_ALIGN;
+  return 0;
+}
+
+bool rb_vec(const RbIn& I, const float* out) {
+  return I.hw % 4 == 0 && !((uintptr_t)I.y & 15) && !((uintptr_t)I.s & 15) && !((uintptr_t)I.sw & 15) && !((uintptr_t)I.mask & 3) &&
+         !((uintptr_t)out & 15);
+}
+
+}  // namespace
+
+extern "C" {
+
+size_t fsg_robust_ws_bytes(int n, int h, int w) {
+  if (n <= 0 || h <= 0 || w <= 0 || (size_t)n * (size_t)h * (size_t)w > (size_t)0x7FFFFFFF) return 0;
+  return (size_t)n * (size_t)rb_chunks(h, w) * RB_SLOTS * sizeof(float);
+}
+
+size_t fsg_robust_state_bytes(int n, int n_em) {
+  if (n <= 0 || n_em < 1 || n_em > RB_MAX_EM) return 0;
+  return rb_state_bytes((size_t)n, n_em);
+}
+
+int fsg_robust_estep_f32(const float* y, const float* s, const uint8_t* slices_mask, const float* sim_weight, float min_weight,
+                         int n, int h, int w, int t, int n_em, const void* state, size_t state_bytes, void* ws, size_t ws_bytes,
+                         void* stream) {
+  // every refusal comes before the first write
+  const int rc = rb_check_pixels(y, s, sim_weight, min_weight, n, h, w, n_em, state, state_bytes);
+  if (rc) return rc;
+  if (t < 0 || t > n_em) return FSG_E_BADARG;
+  if (!ws || ws_bytes < fsg_robust_ws_bytes(n, h, w)) return FSG_E_BADARG;
+  if ((uintptr_t)ws & 7) return FSG_E_ALIGN;
+  const size_t pix = (size_t)n * h * w, wsb = fsg_robust_ws_bytes(n, h, w), stb = rb_state_bytes((size_t)n, n_em);
+  if (rb_overlap(ws, wsb, y, pix * 4) || rb_overlap(ws, wsb, s, pix * 4) || rb_overlap(ws, wsb, sim_weight, pix * 4) ||
+      rb_overlap(ws, wsb, slices_mask, pix) || rb_overlap(ws, wsb, state, stb))
+    return FSG_E_BADARG;
+  const RbIn I{y, s, slices_mask, sim_weight, min_weight, h * w};
+  const dim3 grid((unsigned)rb_chunks(h, w), (unsigned)n);
+  hipStream_t st = fsg_stream(stream);
+  if (rb_vec(I, nullptr))
+    hipLaunchKernelGGL(rb_estep_kernel<true>, grid, dim3(RB_THREADS), 0, st, I, n, n_em, t == 0 ? 1 : 0, state, (float*)ws);
+  else
+    hipLaunchKernelGGL(rb_estep_kernel<false>, grid, dim3(RB_THREADS), 0, st, I, n, n_em, t == 0 ? 1 : 0, state, (float*)ws);
+  FSG_RETURN_LAUNCH();
+}
+
+int fsg_robust_update_f32(void* state, size_t state_bytes, const void* ws, size_t ws_bytes, int n, int h, int w, int t, int n_em,
+                          double c0, double sigma_floor, double slice_floor, int min_pixels, void* stream) {
+  if (n <= 0 || h <= 0 || w <= 0 || n_em < 1 || n_em > RB_MAX_EM || t < 0 || t > n_em) return FSG_E_BADARG;
+  if (n > 65535 || (size_t)n * (size_t)h * (size_t)w > (size_t)0x7FFFFFFF) return FSG_E_TOOBIG;
+  if (!state || !ws || state_bytes < rb_state_bytes((size_t)n, n_em) || ws_bytes < fsg_robust_ws_bytes(n, h, w)) return FSG_E_BADARG;
+  if (!(c0 > 0.0 && c0 <= 1.0) || !(sigma_floor >= 0.0 && sigma_floor <= 1.7976931348623157e308) ||
+      !(slice_floor >= 0.0 && slice_floor <= 1.7976931348623157e308) || min_pixels < 0)
+    return FSG_E_BADARG;
+  if (((uintptr_t)state & 7) || ((uintptr_t)ws & 7)) return FSG_E_ALIGN;
+  if (rb_overlap(state, rb_state_bytes((size_t)n, n_em), ws, fsg_robust_ws_bytes(n, h, w))) return FSG_E_BADARG;
+  const RbOpts O{c0, sigma_floor, slice_floor, min_pixels};
+  hipLaunchKernelGGL(rb_update_kernel, dim3(1), dim3(RB_THREADS), 0, fsg_stream(stream), state, (const float*)ws, rb_chunks(h, w),
+                     n, t, n_em, O);
+  FSG_RETURN_LAUNCH();
+}
+
+int fsg_robust_weights_f32(const float* y, const float* s, const uint8_t* slices_mask, const float* sim_weight, float min_weight,
+                           int n, int h, int w, int n_em, int level, const void* state, size_t state_bytes, float* out,
+                           void* stream) {
+  const int rc = rb_check_pixels(y, s, sim_weight, min_weight, n, h, w, n_em, state, state_bytes);
+  if (rc) return rc;
+  if (!out || (level != FSG_ROBUST_SLICE && level != FSG_ROBUST_BOTH)) return FSG_E_BADARG;
+  if ((uintptr_t)out & 3) return FSG_E_ALIGN;
+  const size_t pix = (size_t)n * h * w, stb = rb_state_bytes((size_t)n, n_em);
+  if (rb_overlap(out, pix * 4, y, pix * 4) || rb_overlap(out, pix * 4, s, pix * 4) || rb_overlap(out, pix * 4, sim_weight, pix * 4) ||
+      rb_overlap(out, pix * 4, slices_mask, pix) || rb_overlap(out, pix * 4, state, stb))
+    return FSG_E_BADARG;
+  const RbIn I{y, s, slices_mask, sim_weight, min_weight, h * w};
+  const dim3 grid((unsigned)rb_chunks(h, w), (unsigned)n);
+  hipStream_t st = fsg_stream(stream);
+  if (rb_vec(I, out))
+    hipLaunchKernelGGL(rb_weights_kernel<true>, grid, dim3(RB_THREADS), 0, st, I, n, n_em, level == FSG_ROBUST_BOTH ? 1 : 0, state, out);
+  else
+    hipLaunchKernelGGL(rb_weights_kernel<false>, grid, dim3(RB_THREADS), 0, st, I, n, n_em, level == FSG_ROBUST_BOTH ? 1 : 0, state,
+                       out);
+  FSG_RETURN_LAUNCH();
+}
+
+}  // extern "C"

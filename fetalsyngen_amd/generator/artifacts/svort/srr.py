@@ -21,6 +21,11 @@ With `lam > 0` the operator gains the first-order regulariser of DESIGN.md secti
 `huber_delta` and `n_outer` make it edge preserving by reweighting: `n_outer` complete solves, each guided by the x of the one
 before, whose edges steeper than `huber_delta` are weighted down by Huber's rule.  With `lam == 0`, the default, the launch
 sequence is the one above and tk1_apply is never called.
+
+With `n_robust > 0` the solve rejects outliers: after the complete solve the slices are simulated from
+its x, `outlier.robust_weights` turns the residual into per-pixel weights, they multiply the caller's `slices_weight`, the
+right-hand side is rebuilt and the whole solve runs again from `x0` as given, `n_robust` times.  With `n_robust == 0`, the
+default, none of this is launched.
 """
 from __future__ import annotations
 
@@ -30,6 +35,7 @@ import torch
 
 from .... import kernels as K
 from .... import rng as _rng
+from .outlier import check_options as _robust_options, robust_weights
 
 
 def _no_grad_inputs(**tensors):
@@ -43,7 +49,8 @@ def _no_grad_inputs(**tensors):
 
 def srr(transforms, slices, psf, vol_shape, res_slice, *, interp_psf=False, slices_mask=None, vol_mask=None,
         slices_weight=None, x0=None, mu=0.0, z=None, n_iter=10, tol=0.0, output_relu=True, deterministic=None,
-        value_scale=1.0, return_info=False, lam=0.0, huber_delta=None, n_outer=1, guide=None):
+        value_scale=1.0, return_info=False, lam=0.0, huber_delta=None, n_outer=1, guide=None,
+        n_robust=0, robust=None):
     """transforms (n,3,4), slices (n,1,h,w) or (n,h,w), psf (pd,ph,pw) -> volume (1,1,D,H,W) after `n_iter` CG iterations.
 
     slices_mask (n,[1,]h,w) bool: pixels that take part.  vol_mask (D,H,W)-shaped bool: the voxels solved for, the rest is 0.
@@ -55,7 +62,11 @@ def srr(transforms, slices, psf, vol_shape, res_slice, *, interp_psf=False, slic
     lam: the weight of the first-order regulariser lam * sum over the grid edges inside vol_mask of c |x_i - x_j|^2 (0 = none).
     huber_delta: with a guide, c = min(1, huber_delta / |g_i - g_j|) instead of 1.  n_outer: that many complete solves of
     `n_iter` iterations; round 0 is guided by `guide` (None: c = 1), every later round starts from the x of the round before
-    and is guided by it.  The relu is applied in the last round only."""
+    and is guided by it.  The relu is applied in the last round only.
+    n_robust: that many outlier-rejection rounds: weights from `robust_weights(slices, A x, ...)` times `slices_weight`, then
+    the complete solve (all `n_outer` rounds) again from `x0`; the relu is applied in the very last solve only.  robust: a
+    dict of `robust_weights`' options (n_em, c0, sigma_floor, slice_floor, min_pixels, level, min_weight).  With n_robust > 0
+    the info dict gains "robust": the list of the EM histories, one dict per rejection round."""
     _no_grad_inputs(transforms=transforms, slices=slices, psf=psf, slices_weight=slices_weight, x0=x0, z=z, guide=guide)
     lam, n_outer = float(lam), int(n_outer)
     if not (math.isfinite(lam) and lam >= 0):
@@ -70,6 +81,12 @@ def srr(transforms, slices, psf, vol_shape, res_slice, *, interp_psf=False, slic
         raise ValueError(f"n_outer must be >= 1, got {n_outer}")
     if huber_delta is None and (n_outer > 1 or guide is not None):
         raise ValueError("n_outer > 1 and guide reweight the edges by huber_delta: give it")
+    n_robust = int(n_robust)
+    if n_robust < 0:
+        raise ValueError(f"n_robust must be >= 0, got {n_robust}")
+    if robust is not None and n_robust == 0:
+        raise ValueError("robust sets the options of the outlier rejection: it needs n_robust > 0")
+    ropts = {k: v for k, v in _robust_options(dict(robust or {})).items() if robust and k in robust}
     if deterministic is None:
         deterministic = _rng.in_keyed_scope()
     det = bool(deterministic)
@@ -90,7 +107,7 @@ def srr(transforms, slices, psf, vol_shape, res_slice, *, interp_psf=False, slic
     y = prep(slices, (n, h, w))
     sm = prep(slices_mask, (n, h, w), torch.bool)
     vm = prep(vol_mask, (D, H, W), torch.bool)
-    wt = prep(slices_weight, (n, h, w))
+    wt = wt_given = prep(slices_weight, (n, h, w))
     zz = prep(z, (D, H, W))
     xs = prep(x0, (D, H, W))
     gd = prep(guide, (D, H, W))
@@ -110,40 +127,52 @@ def srr(transforms, slices, psf, vol_shape, res_slice, *, interp_psf=False, slic
             K.tk1_apply(v, t, (D, H, W), lam, mask=vm, guide=g, delta=None if g is None else huber_delta, out=t)
         return t
 
-    rounds = []
-    for o in range(n_outer):
-        ws = K.cg_workspace(nvox, n_iter, dev)
-        if o == 0:
-            b = K.slice_acq_adjoint(tr, ps, y if wt is None else K.mul(y, wt), sm, None, (D, H, W), res_slice,
-                                    interp_psf=interp_psf, semantics="cuda", deterministic=det, value_scale=value_scale)
-            if xs is not None and vm is not None:
-                xs = torch.where(vm, xs, torch.zeros((), dtype=xs.dtype, device=dev))  # A sees V x0
-        else:
-            xs = gd = x  # the round before: already inside V
-        t0 = None if xs is None else apply(xs, gd)
-        r, p, x = (torch.empty((D, H, W), dtype=torch.float32, device=dev) for _ in range(3))
-        K.cg_init(ws, b, r, p, x, mask=vm, mu=mu, z=zz, x0=xs, t0=t0)
-        relu = bool(output_relu) and o == n_outer - 1
-        for k in range(1, n_iter + 1):
-            q = apply(p, gd)
-            K.cg_q(ws, k, p, q, mask=vm, mu=mu, tol=tol)
-            K.cg_step(ws, k, p, q, x, r, relu=relu)
-            K.cg_dir(ws, k, r, p, tol=tol)
-        rounds.append(ws.info())
+    robust_info = []
+    xs0, gd0 = xs, gd
+    for rb in range(n_robust + 1):
+        xs, gd = xs0, gd0  # every robust round solves from x0 as given: a warm start keeps the outliers' imprint
+        rounds = []
+        for o in range(n_outer):
+            ws = K.cg_workspace(nvox, n_iter, dev)
+            if o == 0:
+                b = K.slice_acq_adjoint(tr, ps, y if wt is None else K.mul(y, wt), sm, None, (D, H, W), res_slice,
+                                        interp_psf=interp_psf, semantics="cuda", deterministic=det, value_scale=value_scale)
+                if rb == 0 and xs is not None and vm is not None:
+                    xs = xs0 = torch.where(vm, xs, torch.zeros((), dtype=xs.dtype, device=dev))  # A sees V x0
+            else:
+                xs = gd = x  # the round before: already inside V
+            t0 = None if xs is None else apply(xs, gd)
+            r, p, x = (torch.empty((D, H, W), dtype=torch.float32, device=dev) for _ in range(3))
+            K.cg_init(ws, b, r, p, x, mask=vm, mu=mu, z=zz, x0=xs, t0=t0)
+            relu = bool(output_relu) and o == n_outer - 1 and rb == n_robust
+            for k in range(1, n_iter + 1):
+                q = apply(p, gd)
+                K.cg_q(ws, k, p, q, mask=vm, mu=mu, tol=tol)
+                K.cg_step(ws, k, p, q, x, r, relu=relu)
+                K.cg_dir(ws, k, r, p, tol=tol)
+            rounds.append(ws.info())
+        if rb < n_robust:
+            s, wgt = K.slice_acq_forward(tr, x, None, sm, ps, (h, w), res_slice, need_weight=True, interp_psf=interp_psf,
+                                         semantics="cuda")
+            rw = robust_weights(y, s, slices_mask=sm, sim_weight=wgt, return_info=True, **ropts)
+            robust_info.append(rw[1])
+            wt = rw[0] if wt_given is None else K.mul(rw[0], wt_given)
     out = x.view(1, 1, D, H, W)
     if not return_info:
         return out
-    return out, (dict(rounds[-1], rounds=rounds) if lam > 0 else rounds[-1])  # lam == 0: the dict it has always been
+    info = dict(rounds[-1], rounds=rounds) if lam > 0 else rounds[-1]  # lam == 0: the dict it has always been
+    return out, (dict(info, robust=robust_info) if n_robust > 0 else info)
 
 
 class SRR:
     """`srr` behind the call shape of `PSFreconstruction`: `params` carries psf, interp_psf, res_s, res_r, s_thick and
     volume_shape."""
 
-    def __init__(self, n_iter=10, tol=0.0, output_relu=True, lam=0.0, huber_delta=None, n_outer=1):
+    def __init__(self, n_iter=10, tol=0.0, output_relu=True, lam=0.0, huber_delta=None, n_outer=1, n_robust=0, robust=None):
         self.n_iter, self.tol, self.output_relu = n_iter, tol, output_relu
-        # the regulariser of `srr`, handed on only when set
-        self.reg = {k: v for k, v, unset in (("lam", lam, 0.0), ("huber_delta", huber_delta, None), ("n_outer", n_outer, 1))
+        # the regulariser and the outlier rejection of `srr`, handed on only when set
+        self.reg = {k: v for k, v, unset in (("lam", lam, 0.0), ("huber_delta", huber_delta, None), ("n_outer", n_outer, 1),
+                                             ("n_robust", n_robust, 0), ("robust", robust, None))
                     if v != unset}
 
     def __call__(self, transforms, slices, volume, params, p=None, mu=0, z=None, vol_mask=None, slices_mask=None):

@@ -40,7 +40,10 @@ def svr(poses, slices, vol, psf, res_slice, *, slices_mask=None, slices_weight=N
     """poses (n,6) [rotation vector | translation], slices (n,1,h,w) or (n,h,w), vol (..,D,H,W), psf (pd,ph,pw) -> (n,6) poses
     after `n_iter` damped Gauss-Newton steps per slice.
 
-    slices_mask (n,[1,]h,w) bool: pixels that take part.  slices_weight: non-negative per-pixel weights.  lambda0, factor,
+    slices_mask (n,[1,]h,w) bool: pixels that take part.  slices_weight: non-negative per-pixel weights; to reject outliers
+    (signal voids, slices that do not fit the volume) pass `outlier.robust_weights(slices, simulated, sim_weight=...)`, with
+    `simulated` and its weight from `kernels.slice_acq_forward(..., need_weight=True)` at the poses the call starts from
+    (DESIGN.md section 25).  lambda0, factor,
     lambda_min, lambda_max: the damping starts at lambda0, is divided by `factor` after an accepted step (not below lambda_min)
     and multiplied after a rejected one; a slice whose lambda passes lambda_max stops.  min_weight: a pixel takes part when the
     PSF weight it finds inside the volume is at least this.  min_overlap: a trial that keeps fewer than min_overlap times the

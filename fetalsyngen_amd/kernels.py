@@ -1116,6 +1116,119 @@ def svr_update(state: SVRState, k: int, stats_trial, theta_trial, lambda0=1e-3, 
     _lib.check(rc, "fsg_svr_update_f32")
 
 
+# ---- outlier weights: robust-statistics EM over the residual of a reconstruction (fsg_robust.hip) -----------------
+ROBUST_MAX_EM = 4096
+ROBUST_LEVELS = {"slice": _lib.ROBUST_SLICE, "both": _lib.ROBUST_BOTH}
+ROBUST_ROW = 6  # doubles of a slice's row: N, sum p, sum p e^2, sum (1-p)^2, min y, max y
+
+
+class RobustState:
+    """The device blocks of one EM (include/fsg_hip.h, fsg_robust_*): `buf` (int64), the state, and as views of it consts (4:
+    R, m, sigma_min, 0), rows (n,6), u (n), the histories sigma, c, mu1, mu2 (float64), frozen (int32), each of n_em + 1 slots,
+    ws (n_em + 1, n) float64 and scal (2 float32: kappa, inv2var); `part` (int64) is the workspace of the per-workgroup
+    partials for (h, w) slices."""
+
+    def __init__(self, n: int, n_em: int, device, slice_shape=None):
+        n, n_em = int(n), int(n_em)
+        if n < 1:
+            raise ValueError(f"n must be at least 1, got {n}")
+        if not 1 <= n_em <= ROBUST_MAX_EM:
+            raise ValueError(f"n_em must be in 1..{ROBUST_MAX_EM}, got {n_em}")
+        self.n, self.n_em = n, n_em
+        self.nbytes = int(_lib.load().fsg_robust_state_bytes(n, n_em))
+        self.buf = torch.empty(self.nbytes // 8, dtype=torch.int64, device=device)
+        s = n_em + 1
+        raw, off = self.buf.view(torch.uint8), 0
+        for name, dtype, shape in (("consts", torch.float64, (4,)), ("rows", torch.float64, (n, ROBUST_ROW)),
+                                   ("u", torch.float64, (n,)), ("sigma", torch.float64, (s,)), ("c", torch.float64, (s,)),
+                                   ("mu1", torch.float64, (s,)), ("mu2", torch.float64, (s,)), ("ws", torch.float64, (s, n)),
+                                   ("scal", F32, (2,)), ("frozen", torch.int32, (s,))):
+            size = int(np.prod(shape)) * torch.empty((), dtype=dtype).element_size()
+            setattr(self, name, raw[off:off + size].view(dtype).view(shape))
+            off += size
+        if (off + 7) // 8 * 8 != self.nbytes:
+            raise RuntimeError(f"fsg_robust_state_bytes({n}, {n_em}) = {self.nbytes}, the layout of fsg_hip.h needs {off}")
+        self.part, self.slice_shape = None, None
+        if slice_shape is not None:
+            self.reserve(slice_shape)
+
+    def reserve(self, slice_shape):
+        """the workspace for (h, w) slices"""
+        h, w = (int(v) for v in slice_shape)
+        if self.slice_shape != (h, w):
+            need = int(_lib.load().fsg_robust_ws_bytes(self.n, h, w))
+            if need == 0:
+                raise ValueError(f"no workspace for {self.n} slices of {(h, w)}")
+            self.part = torch.empty(need // 8, dtype=torch.int64, device=self.buf.device)
+            self.slice_shape = (h, w)
+        return self.part
+
+    def info(self):
+        return {k: getattr(self, k) for k in ("sigma", "c", "mu1", "mu2", "frozen", "ws", "u")}
+
+
+def robust_state(n: int, n_em: int, device, slice_shape=None) -> RobustState:
+    return RobustState(n, n_em, device, slice_shape)
+
+
+def _robust_pixels(state, y, s, slices_mask, sim_weight, min_weight, out=None):
+    """(n,h,w) fp32 contiguous device arrays on the state's device -> (h, w, mask as bytes)"""
+    _need_gpu(y, s, slices_mask, sim_weight, out)
+    if y.dim() != 3 or int(y.shape[0]) != state.n:
+        raise ValueError(f"slices must be (n,h,w) with n={state.n}, got {tuple(y.shape)}")
+    shape = tuple(int(v) for v in y.shape)
+    for name, v in (("slices", y), ("simulated", s), ("sim_weight", sim_weight), ("out", out)):
+        if v is None:
+            continue
+        _f32(v, name)
+        if tuple(v.shape) != shape:
+            raise ValueError(f"{name} shape {tuple(v.shape)} does not match {shape}")
+        if v.device != state.buf.device:
+            raise ValueError(f"{name} is on {v.device}, the state on {state.buf.device}")
+    sm = _sa_mask(slices_mask, shape, "slices_mask")
+    if sm is not None and sm.device != state.buf.device:
+        raise ValueError(f"slices_mask is on {sm.device}, the state on {state.buf.device}")
+    if not float(min_weight) >= 0.0:
+        raise ValueError(f"min_weight must be >= 0, got {min_weight!r}")
+    return shape[1], shape[2], sm
+
+
+def robust_estep(state: RobustState, t: int, y, s, slices_mask=None, sim_weight=None, min_weight=0.5):
+    """Slot t of the EM, the pixel pass (fsg_robust_estep_f32): the posteriors p of e = y - s under the scalars update(t - 1)
+    stored (p = 1 at t == 0) and one partial of the per-slice sums per workgroup, into state.part."""
+    h, w, sm = _robust_pixels(state, y, s, slices_mask, sim_weight, min_weight)
+    part = state.reserve((h, w))
+    rc = _lib.load().fsg_robust_estep_f32(_p(y), _p(s), _p(sm), _p(sim_weight), float(min_weight), state.n, h, w, int(t),
+                                          state.n_em, _p(state.buf), state.nbytes, _p(part), part.numel() * 8, _stream(y))
+    _lib.check(rc, "fsg_robust_estep_f32")
+
+
+def robust_update(state: RobustState, t: int, c0=0.9, sigma_floor=0.04, slice_floor=0.025, min_pixels=4):
+    """Slot t of the EM, the scalar pass (fsg_robust_update_f32): the slices' rows, sigma, c, one sweep of the slice mixture,
+    ws[t], and the kappa and inv2var of the next pixel pass.  After robust_estep(state, t, ...), on the same stream."""
+    if state.part is None:
+        raise ValueError("robust_update follows robust_estep: the state has no partials yet")
+    h, w = state.slice_shape
+    rc = _lib.load().fsg_robust_update_f32(_p(state.buf), state.nbytes, _p(state.part), state.part.numel() * 8, state.n, h, w,
+                                           int(t), state.n_em, float(c0), float(sigma_floor), float(slice_floor),
+                                           int(min_pixels), _stream(state.buf))
+    _lib.check(rc, "fsg_robust_update_f32")
+
+
+def robust_weights(state: RobustState, y, s, slices_mask=None, sim_weight=None, min_weight=0.5, level="slice", out=None):
+    """out (n,h,w) fp32 = ws[n_em][k] on the pixels that take part, 0 elsewhere; level "both": times the pixel posterior
+    under the last scalars (fsg_robust_weights_f32)."""
+    if level not in ROBUST_LEVELS:
+        raise ValueError(f"level must be one of {sorted(ROBUST_LEVELS)}, got {level!r}")
+    if out is None and isinstance(y, torch.Tensor):
+        out = torch.empty_like(y)
+    h, w, sm = _robust_pixels(state, y, s, slices_mask, sim_weight, min_weight, out)
+    rc = _lib.load().fsg_robust_weights_f32(_p(y), _p(s), _p(sm), _p(sim_weight), float(min_weight), state.n, h, w, state.n_em,
+                                            ROBUST_LEVELS[level], _p(state.buf), state.nbytes, _p(out), _stream(y))
+    _lib.check(rc, "fsg_robust_weights_f32")
+    return out
+
+
 # ---- SR-artifact volumetric helpers (fsg_artifacts.hip) ----------------------------------------------------
 def _upload(host: torch.Tensor, device):
     """Small host tensor -> device through a pinned staging copy (async on the current stream)."""

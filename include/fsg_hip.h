@@ -39,7 +39,8 @@ extern "C" {
                                  _det_ws_bytes, and with fsg_axisangle2mat_f32 / fsg_mat2axisangle_f32 and their _backward_f32,
                                  and with fsg_cg_ws_bytes / fsg_cg_init_f32 / _q_f32 / _step_f32 / _dir_f32, and with
                                  fsg_svr_ws_bytes / fsg_svr_normal_f32 / fsg_svr_state_bytes / fsg_svr_update_f32, and with
-                                 fsg_tk1_apply_f32: entries added, nothing older changed */
+                                 fsg_tk1_apply_f32, and with fsg_robust_ws_bytes / _state_bytes / _estep_f32 / _update_f32 /
+                                 _weights_f32: entries added, nothing older changed */
 
 #define FSG_E_BADARG (-1)   /* null pointer / non-positive size / bad enum */
 #define FSG_E_TOOBIG (-2)   /* size exceeds what the kernel indexes (2^31-1 voxels per volume) */
@@ -671,6 +672,78 @@ size_t fsg_svr_state_bytes(int n, int n_iter);
 int fsg_svr_update_f32(const double* stats_trial, float* theta_trial, void* state, size_t state_bytes, int n, int k, int n_iter,
                        double lambda0, double factor, double lambda_min, double lambda_max, double min_overlap, double tol,
                        void* stream);
+
+/* ---- outlier weights for the two solves above: robust-statistics EM (fsg_robust.hip) ----------------
+ * The W of fsg_cg_* / fsg_svr_normal_f32 from the residual of a reconstruction (Kuklisova-Murgasova et al. 2012): per pixel a
+ * Gaussian inlier / uniform outlier posterior p, per slice a two-class mixture over the slice's potential u.  One solve is the
+ * launch sequence, T = n_em, all on one stream:
+ *     for t = 0..T:  estep(t);  update(t)        then  weights
+ * and it is the same sequence whatever the data: nothing returns early, nothing is read back.
+ *   y (n,h,w) the acquired slices, s (n,h,w) the simulated ones (A x), fp32; slices_mask (n,h,w) bytes or NULL; sim_weight
+ *   (n,h,w) fp32 or NULL, the weight fsg_slice_acq_forward_f32 returns, with min_weight >= 0.
+ * Omega: a pixel takes part iff it is inside slices_mask, (with sim_weight) weight > 0 && weight >= min_weight, and
+ * e = fl(y - s) is finite.  A NaN or Inf in y, s or the weight therefore leaves the pixel out and reaches no sum.
+ *
+ * fsg_robust_estep_f32, slot t.  Per pixel of Omega, fp32 with one rounding per operation (no contraction), expf the library's:
+ *     e2 = e * e;  x = expf(e2 * inv2var);  p = 1 / (1 + kappa * x), and p = 0 when x overflowed to Inf;  q = 1 - p
+ * kappa and inv2var are the two floats update(t - 1) stored; at t == 0, p = 1 and the state is not read.  Per-slice sums: N (the
+ * count), sum p, sum p * e2, sum q * q, and min y, max y.  Reduction, no atomics: pixel i of a slice (row-major) belongs to
+ * thread (i / 4) mod 256 of workgroup i / 1024 of that slice; a thread adds its four pixels in increasing i from +0; the 64
+ * lanes of a wave fold by v[i] += v[i + o], o = 32..1 (shuffle-down; lane 0 holds the sum; min / max by fminf / fmaxf from
+ * +Inf / -Inf); the four waves are added in wave order; the workgroup stores one partial of 8 floats (N, sum p, sum p e2,
+ * sum q^2, min, max, 0, 0) at ws[slice][workgroup].  ws: DEVICE, 8-byte aligned, fsg_robust_ws_bytes(n, h, w) = 32 bytes per
+ * 1024 pixels (rounded up) of every slice; it needs no initialisation.  Loads are 16 bytes per lane when h * w is a multiple
+ * of 4, every float pointer is 16-byte aligned and slices_mask 4-byte aligned; scalars otherwise, same values and same sums.
+ *
+ * fsg_robust_update_f32, slot t: one workgroup, double arithmetic.  A slice's row = its partials added in DOUBLE in workgroup
+ * order from +0.0 (min / max by fmin / fmax; a slice without a pixel stores min = max = 0).  Given kappa and inv2var a row is a
+ * pure function of that slice's data.  ok_k = N_k >= min_pixels && N_k > 0; a slice that is not ok has ws = 0 in every slot.
+ *   t == 0     R = max y - min y over Omega, m = 1 / R, sigma_min = sigma_floor * R: the constants of the solve.
+ *   pixels     w_k = ws[t-1][k] (1 at t == 0; 0 for a slice not ok); over the slices in index order from +0.0:
+ *              S0 = sum w_k * sum p, S2 = sum w_k * sum p e2, Nw = sum w_k * N_k;
+ *              var = max(S2 / S0, sigma_min^2);  c = S0 / Nw, and c = c0 at t == 0;
+ *              kappa = (float)(((1 - c) / c) * m * sqrt(2 pi var));  inv2var = (float)(1 / (2 var)).
+ *   slices     t >= 1, one sweep over u_k = sqrt(sum q^2 / N_k) of the ok slices, sums in index order, w the OLD weights:
+ *              sw = sum w, mu1 = sum w u / sw, v1 = max(sum w (u - mu1)^2 / sw, slice_floor^2);  so = sum (1 - w);
+ *              so > 0: mu2 = sum (1 - w) u / so, v2 = sum (1 - w)(u - mu2)^2 / so;  else mu2 = (max u + mu1) / 2, v2 = 0;
+ *              !(v2 > 0): v2 = (mu2 - mu1)^2 / 4;  v2 = max(v2, slice_floor^2);  mix = sw / n_ok;
+ *              ws[t][k] = 1 if u < mu1, 0 if u > mu2, else g1 mix / (g1 mix + g2 (1 - mix)), g the normal densities of u under
+ *              (mu1, v1) and (mu2, v2); where that quotient is not a number (both densities underflowed, a zero variance) the
+ *              class of the nearer mean.  At t == 0, ws[0][k] = 1.
+ *   freeze     R == 0 or not finite, Nw == 0, S0 == 0, var == 0 or any scalar above not finite: the solve is frozen from this
+ *              slot on.  Frozen: ws[t][k] = 1 for every ok slice, kappa = inv2var = 0 (so p = 1), sigma, c, mu1, mu2 of the
+ *              slot are 0, frozen[t] = 1, and every later slot repeats this.  No NaN is ever stored.
+ * state: one DEVICE block of fsg_robust_state_bytes(n, T) bytes (0 for n < 1 or T outside 1..4096), 8-byte aligned, in this
+ * order with s = T + 1:
+ *     double consts[4] (R, m, sigma_min, 0), double rows[n][6] (N, sum p, sum p e2, sum q^2, min y, max y: the LAST estep's),
+ *     double u[n], double sigma[s], double c[s], double mu1[s], double mu2[s], double ws[s][n], float kappa, float inv2var,
+ *     int32 frozen[s]
+ * rounded up to 8 bytes.  It needs no initialisation: update(0) writes the constants, update(t) every per-slice field and
+ * slot t of the histories; a launch reads only what an EARLIER launch wrote.
+ *
+ * fsg_robust_weights_f32: out (n,h,w) fp32 = (float)ws[T][k] on Omega and 0 elsewhere (FSG_ROBUST_SLICE), or
+ * fl((float)ws[T][k] * p) with p under the kappa and inv2var update(T) stored (FSG_ROBUST_BOTH).
+ *
+ * Determinism: no atomics and every order fixed, so the same bits in any run and on any stream.  sigma and c are GLOBAL sums
+ * in slice-index order, so permuting the slices permutes the result only up to rounding (unlike fsg_svr_normal_f32, whose
+ * rows do not see the other slices).
+ * Refusals, all before any launch and with nothing written: n, h or w < 1, T outside 1..4096, t outside 0..T, a null y, s,
+ * state, ws or out, a short state or ws, min_weight negative or NaN, c0 outside (0, 1] or NaN, sigma_floor or slice_floor
+ * negative, NaN or Inf, min_pixels < 0, an unknown level (FSG_E_BADARG); n > 65535 or n * h * w > 2^31 - 1 (FSG_E_TOOBIG);
+ * state or ws not 8-byte aligned, a float pointer not 4-byte aligned (FSG_E_ALIGN); ws sharing a byte with an input or the
+ * state, out sharing a byte with an input or the state (FSG_E_BADARG). */
+#define FSG_ROBUST_SLICE 0
+#define FSG_ROBUST_BOTH 1
+size_t fsg_robust_ws_bytes(int n, int h, int w);
+size_t fsg_robust_state_bytes(int n, int n_em);
+int fsg_robust_estep_f32(const float* y, const float* s, const uint8_t* slices_mask, const float* sim_weight, float min_weight,
+                         int n, int h, int w, int t, int n_em, const void* state, size_t state_bytes, void* ws, size_t ws_bytes,
+                         void* stream);
+int fsg_robust_update_f32(void* state, size_t state_bytes, const void* ws, size_t ws_bytes, int n, int h, int w, int t, int n_em,
+                          double c0, double sigma_floor, double slice_floor, int min_pixels, void* stream);
+int fsg_robust_weights_f32(const float* y, const float* s, const uint8_t* slices_mask, const float* sim_weight, float min_weight,
+                           int n, int h, int w, int n_em, int level, const void* state, size_t state_bytes, float* out,
+                           void* stream);
 
 /* ---- SR-artifact volumetric helpers, fsg_artifacts.hip ------------------------------------ */
 /* out = clamp(sum_g exp(-(((x-c0)/s0)^2 + ((y-c1)/s1)^2 + ((z-c2)/s2)^2) / 2), 0, 1) over a (D,H,W) grid with

@@ -23,6 +23,8 @@ launches of an iteration alone (srr_bench below).  --srr-lambda L > 0 adds the s
 `kernels.tk1_apply` alone against a streaming pass of the same bytes (tk1_bench below).
 --svr runs INSTEAD of the legs above, on the same problem: a round of `svort.svr` beside a pose-fit iteration through autograd and
 beside the forward plus the grad_transforms-only backward, at n = 80 and 250 (svr_bench below).
+--robust runs INSTEAD of the legs above, on the same problem: one `svort.robust_weights` call (--robust-em EM iterations) beside
+one CG iteration of `svort.srr`, and its three kernels alone, at n = 80 and 250 (robust_bench below).
 """
 import argparse
 import json
@@ -307,6 +309,69 @@ def svr_bench(a, dev, vs, ss, psf, vol, res):
     return out
 
 
+def robust_bench(a, dev, vs, ss, psf, vol, res):
+    """--robust, n = 80 and 250.  One `svort.robust_weights` call (T = --robust-em: T + 1 pixel passes, T + 1 scalar passes, the
+    weights) beside ONE iteration of the conjugate gradients of `svort.srr` (A, A^T in the float adjoint, q, step, dir), both by
+    device events over --reps calls, the legs alternated three times after a warm-up.  Then the three kernels alone, with their
+    bytes from the shapes: y, s and the forward's weight read once per pixel pass (12 bytes a pixel), the weights pass writes 4
+    more.  No threshold is asserted: the figures are for DESIGN.md section 25."""
+    from fetalsyngen_amd.generator.artifacts.svort import robust_weights
+
+    rs, T = a.res_slice / res, a.robust_em
+    out = {"volume": vs, "psf": list(psf.shape), "psf_taps": int((psf > 0).sum()), "n_em": T,
+           "clock": f"device events around {a.reps} calls, legs alternated three times"}
+    nvox = int(np.prod(vs))
+    for n in (80, 250):
+        np.random.seed(0)
+        tr = random_stack(n, gap=a.size * res / n / res, max_angle=0.3).to(dev)
+        y = K.slice_acq_forward(tr, vol, None, None, psf, (ss, ss), rs, interp_psf=True)
+        y = y + 0.02 * torch.randn_like(y)
+        y[n // 3] *= 0.2  # a slice to reject
+        s, wgt = K.slice_acq_forward(tr, 0.95 * vol, None, None, psf, (ss, ss), rs, need_weight=True, interp_psf=True)
+        ws = K.cg_workspace(nvox, 1, dev)
+        b = torch.rand(vs, device=dev)
+        r, p, x = torch.empty_like(b), torch.empty_like(b), torch.empty_like(b)
+
+        def cg_iteration():
+            K.cg_init(ws, b, r, p, x)
+            t = K.slice_acq_forward(tr, p, None, None, psf, (ss, ss), rs, interp_psf=True)
+            q = K.slice_acq_adjoint(tr, psf, t, None, None, vs, rs, interp_psf=True)
+            K.cg_q(ws, 1, p, q)
+            K.cg_step(ws, 1, p, q, x, r)
+            K.cg_dir(ws, 1, r, p)
+
+        st = K.robust_state(n, T, dev, (ss, ss))
+        o = torch.empty_like(y)
+        legs = {"robust_weights": lambda: robust_weights(y, s, sim_weight=wgt, n_em=T), "cg_iteration": cg_iteration,
+                "cg_init_alone": lambda: K.cg_init(ws, b, r, p, x)}
+        for fn in legs.values():
+            fn()
+        row = {k: [] for k in legs}
+        for _ in range(3):
+            for k, fn in legs.items():
+                row[k].append(round(timed(fn, a.reps), 4))
+        K.robust_estep(st, 0, y, s, None, wgt), K.robust_update(st, 0)
+        alone = {"estep": lambda: K.robust_estep(st, 1, y, s, None, wgt), "update": lambda: K.robust_update(st, 1),
+                 "weights_slice": lambda: K.robust_weights(st, y, s, None, wgt, out=o),
+                 "weights_both": lambda: K.robust_weights(st, y, s, None, wgt, level="both", out=o)}
+        for k, fn in alone.items():
+            row[k] = [round(timed(fn, a.reps), 4) for _ in range(3)]
+        npix = n * ss * ss
+        row["estep_GB_per_s"] = round(12 * npix / min(row["estep"]) / 1e6, 1)
+        row["weights_GB_per_s"] = round(16 * npix / min(row["weights_both"]) / 1e6, 1)
+        it = min(row["cg_iteration"]) - min(row["cg_init_alone"])
+        row["cg_iteration_without_init"] = round(it, 4)
+        row["robust_over_cg_iteration"] = round(min(row["robust_weights"]) / it, 4)
+        row["slices"] = [n, ss, ss]
+        w1, i1 = robust_weights(y, s, sim_weight=wgt, n_em=T, return_info=True)
+        w2 = robust_weights(y, s, sim_weight=wgt, n_em=T)
+        row["weights_twice_equal"] = bool(torch.equal(w1, w2))
+        row["rejected_slices"] = int((i1["ws"][-1] < 0.5).sum().item())
+        out[f"n{n}_ms"] = row
+        del y, s, wgt, o, st
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--size", type=int, default=384)
@@ -326,6 +391,8 @@ def main():
     ap.add_argument("--srr-outer", type=int, default=1, help="rounds of the guided solve (n_outer)")
     ap.add_argument("--svr", action="store_true", help="time a round of svort.svr against a pose-fit iteration through autograd instead")
     ap.add_argument("--svr-iters", type=int, default=5, help="iterations per --svr solve (iters + 1 rounds)")
+    ap.add_argument("--robust", action="store_true", help="time svort.robust_weights beside one CG iteration instead")
+    ap.add_argument("--robust-em", type=int, default=5, help="EM iterations per --robust call (n_em)")
     a = ap.parse_args()
     dev, res = "cuda:0", 0.5
     vs = (a.size,) * 3
@@ -337,6 +404,9 @@ def main():
         return
     if a.svr:
         print(json.dumps(svr_bench(a, dev, vs, ss, psf, torch.rand(vs, device=dev), res)))
+        return
+    if a.robust:
+        print(json.dumps(robust_bench(a, dev, vs, ss, psf, torch.rand(vs, device=dev), res)))
         return
     delta = get_PSF(0).to(dev)
     np.random.seed(0)
