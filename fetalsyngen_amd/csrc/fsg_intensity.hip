@@ -35,8 +35,9 @@ __global__ __launch_bounds__(256) void gmm_kernel(const LT* __restrict__ labels,
     float v[4];
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
-      int l = (e + q < n) ? (int)labels[e + q] : 0;
-      l = min(max(l, 0), 255);
+      // clamp at the label's own width, then narrow: an int64 label beyond 2^31 must not wrap into the table
+      const long long lw = (e + q < n) ? (long long)labels[e + q] : 0;
+      const int l = (int)(lw < 0 ? 0 : (lw > 255 ? 255 : lw));
       const float t = s_mu[l] + s_sg[l] * z[q];
       v[q] = t < 0.f ? 0.f : t;
     }
@@ -184,8 +185,8 @@ int launch_gmm(const LT* labels, size_t n, const float* mus, const float* sigmas
 extern "C" {
 
 int fsg_randn_f32(float* out, size_t n, uint64_t seed, uint64_t stream_id, void* stream) {
+  if (n == 0) return 0;  // empty: nothing to do, pointers may be null (as launch_gmm)
   if (!out) return FSG_E_BADARG;
-  if (n == 0) return 0;
   hipLaunchKernelGGL(randn_kernel, dim3(grid_for((n + 3) / 4, 8192)), dim3(256), 0, fsg_stream(stream), out, n, seed,
                      stream_id);
   FSG_RETURN_LAUNCH();
@@ -207,7 +208,7 @@ int fsg_gmm_sample_u8x4_mm(const uint8_t* l0, const uint8_t* l1, const uint8_t* 
                            const float* mus, const float* sigmas, int ntab, const float* noise, uint64_t seed,
                            uint64_t stream_id, float* out, int32_t* mm, int nmin, int nmax, void* stream) {
   if (mm && (nmin < 0 || nmax < 0 || nmin + nmax > 64)) return FSG_E_BADARG;
-  if (n == 0) return mm ? fsg_minmax_init(mm, nmin, nmax, stream) : 0;
+  if (n == 0) return (mm && nmin + nmax > 0) ? fsg_minmax_init(mm, nmin, nmax, stream) : 0;  // no keys to reset: as with n > 0
   if (!l0 || !mus || !sigmas || !out || ntab <= 0 || ntab > 256) return FSG_E_BADARG;
   const uintptr_t al = (uintptr_t)l0 | (uintptr_t)l1 | (uintptr_t)l2 | (uintptr_t)l3;
   if ((al & 3) || ((uintptr_t)out & 15)) return FSG_E_ALIGN;
@@ -223,8 +224,8 @@ int fsg_gmm_sample_i64(const int64_t* labels, size_t n, const float* mus, const 
 
 int fsg_label_stats_u8(const uint8_t* labels, const float* values, size_t n, int nlabels, unsigned long long* count,
                        double* sum, double* sumsq, void* stream) {
-  if (!labels || !values || !count || !sum || !sumsq || nlabels <= 0 || nlabels > 256) return FSG_E_BADARG;
   if (n == 0) return 0;
+  if (!labels || !values || !count || !sum || !sumsq || nlabels <= 0 || nlabels > 256) return FSG_E_BADARG;
   const size_t blocks = (n + 4095) / 4096;
   if (blocks > 0x7FFFFFFF) return FSG_E_TOOBIG;
   hipLaunchKernelGGL(label_stats_kernel, dim3((unsigned)blocks), dim3(256), 0, fsg_stream(stream), labels, values, n,
@@ -233,8 +234,8 @@ int fsg_label_stats_u8(const uint8_t* labels, const float* values, size_t n, int
 }
 
 int fsg_gamma_f32(const float* x, size_t n, float gamma, float* out, void* stream) {
-  if (!x || !out) return FSG_E_BADARG;
   if (n == 0) return 0;
+  if (!x || !out) return FSG_E_BADARG;
   hipLaunchKernelGGL(gamma_kernel, dim3(grid_for(n, 8192)), dim3(256), 0, fsg_stream(stream), x, n, gamma, out);
   FSG_RETURN_LAUNCH();
 }
@@ -250,8 +251,8 @@ int fsg_bias_mul_f32(const float* x, int nx, int ny, int nz, const float* bias, 
 
 int fsg_add_noise_f32(const float* x, size_t n, const float* noise, uint64_t seed, uint64_t stream_id,
                       float noise_std, float* out, void* stream) {
-  if (!x || !out) return FSG_E_BADARG;
   if (n == 0) return 0;
+  if (!x || !out) return FSG_E_BADARG;
   hipLaunchKernelGGL(add_noise_kernel, dim3(grid_for(n, 8192)), dim3(256), 0, fsg_stream(stream), x, n, noise, seed,
                      stream_id, noise_std, out);
   FSG_RETURN_LAUNCH();

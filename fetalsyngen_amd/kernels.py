@@ -181,11 +181,21 @@ def gmm_sample(labels, mus, sigmas, noise=None, seed=0, stream_id=0) -> torch.Te
     return out
 
 
+def _gmm_tables(mus, sigmas) -> int:
+    """The table length the kernels are told: they read `ntab` entries of BOTH tables, so the two must agree (host check, before
+    anything could be launched)."""
+    ntab = int(mus.numel())
+    if sigmas.numel() != ntab or not (0 < ntab <= 256):
+        raise ValueError("mus/sigmas must have the same length in 1..256")
+    return ntab
+
+
 def gmm_sample_parts(parts, mus, sigmas, noise=None, seed=0, stream_id=0) -> torch.Tensor:
     """GMM draw from the per-meta-label seed volumes (uint8, disjoint supports) without summing them."""
     parts = [p for p in parts if p is not None]
     if not 1 <= len(parts) <= 4:
         raise ValueError("1..4 label volumes expected")
+    _gmm_tables(mus, sigmas)
     _need_gpu(*parts, mus, sigmas, noise)
     for p in parts:
         if p.dtype != torch.uint8 or p.shape != parts[0].shape:
@@ -210,6 +220,7 @@ def sample_head(parts, mus, sigmas, spec: "DeformSpec", bias=None, bias_tabs=Non
     parts = [p for p in parts if p is not None]
     if not 1 <= len(parts) <= 4:
         raise ValueError("1..4 label volumes expected")
+    _gmm_tables(mus, sigmas)
     _need_gpu(*parts, mus, sigmas, noise)
     out = torch.empty(parts[0].shape, dtype=F32, device=parts[0].device)
     if mm3 is None:

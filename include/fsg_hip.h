@@ -277,8 +277,7 @@ int fsg_add_noise_f32(const float* x, size_t n, const float* noise, uint64_t see
 /* ---- K9/K10 stand-alone reductions / scaling --------------------------------------------------- */
 /* Empty inputs: in the entry points whose work is one flat range of `size_t n` elements, n == 0 is success with no launch
  * and outputs are not touched (one exception: fsg_gmm_sample_u8x4_mm with mm given still resets mm to its identities).
- * In fsg_artifacts.hip and fsg_reduce.hip the n == 0 test comes first, so pointers may then be null; fsg_randn_f32,
- * fsg_label_stats_*, fsg_gamma_f32 and fsg_add_noise_f32 check their pointers first and refuse null ones even then.
+ * The n == 0 test comes first in every one of them, so pointers (and nlabels / ntab) are not looked at and may be null.
  * The calls that follow the rule are the K1/K5/K8/K9/K10 element-wise calls of this header
  * (fsg_gmm_sample_*, fsg_randn_f32, fsg_label_stats_*, fsg_gamma_f32, fsg_add_noise_f32, fsg_reduce_minmax_f32,
  * fsg_scale_f32, fsg_cast_f32_to_f16) and, of the artifact helpers, fsg_blend_f32, fsg_slice_noise_f32,
