@@ -12,6 +12,8 @@ LIB = PKG / "libfsg_hip.so"
 SOURCES = ["fsg_deform.hip", "fsg_warp_lean.hip", "fsg_zoom.hip", "fsg_intensity.hip", "fsg_blur.hip", "fsg_blur_rs.hip", "fsg_reduce.hip", "fsg_slice_acq.hip", "fsg_slice_acq_bwd.hip", "fsg_slice_acq_adjoint_bwd.hip", "fsg_transform_convert.hip", "fsg_cg.hip", "fsg_tk1.hip", "fsg_svr.hip", "fsg_robust.hip", "fsg_artifacts.hip", "fsg_keyed.hip", "fsg_codes.hip", "fsg_seedgen.hip",
            "fsg_regrid.hip", "fsg_pick.hip", "fsg_pipeline.cpp"]
 EXTRA = os.environ.get("FSG_EXTRA_FLAGS", "").split()
+# every header a translation unit may include: all of csrc/ (one added there cannot be missed) and the public one
+HEADERS = sorted(CSRC.glob("*.h")) + [PKG.parent / "include" / "fsg_hip.h"]
 FLAGS = ["-O3", "--offload-arch=gfx950", "-ffp-contract=off", "-fPIC", "-std=c++17", "-Wall", "-Wno-unused-function"]
 
 
@@ -26,7 +28,7 @@ def needs_build() -> bool:
     if not LIB.exists():
         return True
     t = LIB.stat().st_mtime
-    deps = [CSRC / s for s in SOURCES] + [CSRC / "fsg_common.h", CSRC / "fsg_ride.h", CSRC / "fsg_sa.h", PKG.parent / "include" / "fsg_hip.h"]
+    deps = [CSRC / s for s in SOURCES] + HEADERS
     return any(d.stat().st_mtime > t for d in deps)
 
 
@@ -42,7 +44,7 @@ def build(force: bool = False, verbose: bool = False) -> Path:
         lang = ["-x", "hip"] if s.endswith(".cpp") else []
         cmd = [cc, *FLAGS, *EXTRA, *lang, "-c", str(CSRC / s), "-o", str(o)]
         objs.append(str(o))
-        deps = [CSRC / s, CSRC / "fsg_common.h", CSRC / "fsg_ride.h", CSRC / "fsg_sa.h", PKG.parent / "include" / "fsg_hip.h", Path(__file__)]
+        deps = [CSRC / s, *HEADERS, Path(__file__)]
         if not force and not EXTRA and o.exists() and all(d.stat().st_mtime < o.stat().st_mtime for d in deps):
             continue  # object is newer than its source and the shared headers
         jobs.append(cmd)

@@ -7,15 +7,15 @@
 //
 // Element-wise arithmetic is fp32 with contraction off (the library's flag and fsg_common.h's pragma); dot products are
 // summed in double from exact products.  No atomics, no grid barrier, no allocation, no host synchronisation.
+// The iteration cap is the header's FSG_SOLVER_MAX_ITER; the overlap test and the measuring of `ws` are fsg_common.h's.
 #include "fsg_common.h"
 #include <initializer_list>
 
 namespace {
 
 constexpr int CG_THREADS = 256;
-constexpr int CG_MAX_ITER = 4096;
 
-struct CgWs {  // pointers into `ws` for (blocks, K)
+struct CgWs {  // pointers into `ws` for (blocks, K); cg_ws is the one statement of the layout here, cg_ws_bytes measures it
   double* rr;
   double* pq;
   double* part_rr;
@@ -23,6 +23,7 @@ struct CgWs {  // pointers into `ws` for (blocks, K)
   float* alpha;
   float* beta;
   int32_t* frozen;
+  void* end;  // one past frozen
 };
 
 __host__ __device__ inline unsigned cg_blocks(size_t n) {
@@ -30,11 +31,6 @@ __host__ __device__ inline unsigned cg_blocks(size_t n) {
   if (b < 1) b = 1;
   if (b > 1024) b = 1024;
   return (unsigned)b;
-}
-
-__host__ __device__ inline size_t cg_ws_bytes(size_t n, int K) {
-  const size_t s = (size_t)K + 1, b = cg_blocks(n);
-  return (16 * s + 16 * b + 12 * s + 7) & ~(size_t)7;
 }
 
 __host__ __device__ inline CgWs cg_ws(void* ws, size_t n, int K) {
@@ -47,8 +43,11 @@ __host__ __device__ inline CgWs cg_ws(void* ws, size_t n, int K) {
   w.alpha = (float*)(w.part_pq + b);
   w.beta = w.alpha + s;
   w.frozen = (int32_t*)(w.beta + s);
+  w.end = w.frozen + s;
   return w;
 }
+
+inline size_t cg_ws_bytes(size_t n, int K) { return fsg_carved_bytes(fsg_origin, cg_ws(fsg_origin, n, K).end); }
 
 // ---- the dot-product order (a function of n alone) ------------------------------------------------------------------------
 // Elements are dealt in groups of four: group g = e / 4 belongs to thread g % T of the launch (T = blocks * 256, thread id =
@@ -278,15 +277,9 @@ __global__ __launch_bounds__(CG_THREADS) void cg_dir_kernel(const float* __restr
   }
 }
 
-bool cg_overlap(const void* p, size_t bytes, const void* q, size_t qbytes) {
-  if (!p || !q) return false;
-  const uintptr_t a = (uintptr_t)p, b = (uintptr_t)q;
-  return a < b + qbytes && b < a + bytes;
-}
-
 // 0 = go on, 1 = nothing to do, < 0 = the refusal
 int cg_check(size_t n, int k, int K, const void* ws, size_t ws_bytes) {
-  if (K < 1 || K > CG_MAX_ITER || k < 1 || k > K) return FSG_E_BADARG;
+  if (K < 1 || K > FSG_SOLVER_MAX_ITER || k < 1 || k > K) return FSG_E_BADARG;
   if (n == 0) return 1;
   if (!ws || ws_bytes < cg_ws_bytes(n, K)) return FSG_E_BADARG;
   if ((uintptr_t)ws & 7) return FSG_E_ALIGN;
@@ -304,7 +297,7 @@ bool cg_vec(std::initializer_list<const void*> f32s, const void* mask) {
 extern "C" {
 
 size_t fsg_cg_ws_bytes(size_t n, int n_iter) {
-  if (n_iter < 1 || n_iter > CG_MAX_ITER) return 0;
+  if (n_iter < 1 || n_iter > FSG_SOLVER_MAX_ITER) return 0;
   return cg_ws_bytes(n, n_iter);
 }
 
@@ -319,10 +312,10 @@ int fsg_cg_init_f32(const float* b, const float* z, const float* t0, const float
   float* outs[3] = {r, p, x};
   for (int o = 0; o < 3; ++o) {
     for (int i = 0; i < 5; ++i)
-      if (cg_overlap(outs[o], nb, ins[i], i == 4 ? n : nb)) return FSG_E_BADARG;
+      if (fsg_overlap(outs[o], nb, ins[i], i == 4 ? n : nb)) return FSG_E_BADARG;
     for (int o2 = o + 1; o2 < 3; ++o2)
-      if (cg_overlap(outs[o], nb, outs[o2], nb)) return FSG_E_BADARG;
-    if (cg_overlap(outs[o], nb, ws, ws_bytes)) return FSG_E_BADARG;
+      if (fsg_overlap(outs[o], nb, outs[o2], nb)) return FSG_E_BADARG;
+    if (fsg_overlap(outs[o], nb, ws, ws_bytes)) return FSG_E_BADARG;
   }
   const dim3 grid(cg_blocks(n)), block(CG_THREADS);
   if (cg_vec({b, z, t0, x0, r, p, x}, mask))
@@ -338,7 +331,7 @@ int fsg_cg_q_f32(const float* p, float* t, const uint8_t* mask, float mu, double
   if (c) return c < 0 ? c : 0;
   if (!p || !t) return FSG_E_BADARG;
   const size_t nb = n * sizeof(float);
-  if (cg_overlap(t, nb, p, nb) || cg_overlap(t, nb, mask, n) || cg_overlap(t, nb, ws, ws_bytes)) return FSG_E_BADARG;
+  if (fsg_overlap(t, nb, p, nb) || fsg_overlap(t, nb, mask, n) || fsg_overlap(t, nb, ws, ws_bytes)) return FSG_E_BADARG;
   const dim3 grid(cg_blocks(n)), block(CG_THREADS);
   if (cg_vec({p, t}, mask))
     hipLaunchKernelGGL(cg_q_kernel<true>, grid, block, 0, fsg_stream(stream), p, t, mask, mu, tol, n, k, n_iter, ws);
@@ -355,9 +348,9 @@ int fsg_cg_step_f32(const float* p, const float* q, float* x, float* r, size_t n
   const size_t nb = n * sizeof(float);
   float* outs[2] = {x, r};
   for (int o = 0; o < 2; ++o)
-    if (cg_overlap(outs[o], nb, p, nb) || cg_overlap(outs[o], nb, q, nb) || cg_overlap(outs[o], nb, ws, ws_bytes))
+    if (fsg_overlap(outs[o], nb, p, nb) || fsg_overlap(outs[o], nb, q, nb) || fsg_overlap(outs[o], nb, ws, ws_bytes))
       return FSG_E_BADARG;
-  if (cg_overlap(x, nb, r, nb)) return FSG_E_BADARG;
+  if (fsg_overlap(x, nb, r, nb)) return FSG_E_BADARG;
   const dim3 grid(cg_blocks(n)), block(CG_THREADS);
   if (cg_vec({p, q, x, r}, nullptr))
     hipLaunchKernelGGL(cg_step_kernel<true>, grid, block, 0, fsg_stream(stream), p, q, x, r, n, k, n_iter, flags, ws);
@@ -371,7 +364,7 @@ int fsg_cg_dir_f32(const float* r, float* p, double tol, size_t n, int k, int n_
   if (c) return c < 0 ? c : 0;
   if (!r || !p) return FSG_E_BADARG;
   const size_t nb = n * sizeof(float);
-  if (cg_overlap(p, nb, r, nb) || cg_overlap(p, nb, ws, ws_bytes)) return FSG_E_BADARG;
+  if (fsg_overlap(p, nb, r, nb) || fsg_overlap(p, nb, ws, ws_bytes)) return FSG_E_BADARG;
   const dim3 grid(cg_blocks(n)), block(CG_THREADS);
   if (cg_vec({r, p}, nullptr))
     hipLaunchKernelGGL(cg_dir_kernel<true>, grid, block, 0, fsg_stream(stream), r, p, tol, n, k, n_iter, ws);

@@ -22,6 +22,26 @@ extern int g_tuning_flags;
 
 static inline hipStream_t fsg_stream(void* s) { return (hipStream_t)s; }
 
+// [p, p + bytes) and [q, q + qbytes) share a byte; an absent (null) array shares none.  The one overlap test of the library:
+// it stands in front of every kernel whose arguments are declared __restrict__ or whose state block must not be an operand.
+static inline bool fsg_overlap(const void* p, size_t bytes, const void* q, size_t qbytes) {
+  if (!p || !q) return false;
+  const uintptr_t a = (uintptr_t)p, b = (uintptr_t)q;
+  return a < b + qbytes && b < a + bytes;
+}
+
+// finite in double; NaN fails (the comparison is in accepting form)
+__device__ __forceinline__ bool fsg_finite(double x) { return fabs(x) <= 1.7976931348623157e308; }
+
+// Size of a device state block whose fields are carved from `base` by a typed pointer chain (cg_ws, svr_state, rb_state) that
+// also yields the end of its last field: the bytes up to that end, rounded up to 8.  The chain is the one statement of the
+// layout; sizes are measured on it and never written a second time.  fsg_origin is the 8-byte aligned base to measure from
+// when there is no block yet (fsg_*_bytes): the chain only counts from it, nothing is read or written through it.
+alignas(8) inline char fsg_origin[8];
+static inline size_t fsg_carved_bytes(const void* base, const void* end) {
+  return ((size_t)((const char*)end - (const char*)base) + 7) & ~(size_t)7;
+}
+
 // ---------------------------------------------------------------------------------------------
 // order-preserving float <-> int32 keys (so integer atomicMin/atomicMax reduce floats, -0 < +0)
 // ---------------------------------------------------------------------------------------------

@@ -12,6 +12,8 @@
 // 16-byte load per array and a wave reads 1 KiB contiguously.  No LDS beyond the 4 x 8 floats where the waves meet, about 30
 // VGPRs: occupancy is not the limit, HBM is.  No atomics: fixed shuffle tree per wave, waves in order, one 8-float partial per
 // workgroup in a workspace that needs no zeroing, a slice's partials added in double in index order by the update.
+// The iteration cap and the width of a slice's row are the header's (FSG_SOLVER_MAX_ITER, FSG_ROBUST_ROW); the overlap and
+// finite tests and the measuring of the state block are fsg_common.h's.
 #include "fsg_common.h"
 #include <math.h>
 
@@ -20,11 +22,9 @@ namespace {
 constexpr int RB_THREADS = 256;
 constexpr int RB_CHUNK = 4 * RB_THREADS;  // pixels of one slice per workgroup
 constexpr int RB_SLOTS = 8;               // floats of a partial: N, sum p, sum p e^2, sum (1-p)^2, min y, max y, 0, 0
-constexpr int RB_ROW = 6;                 // doubles of a slice's row
-constexpr int RB_MAX_EM = 4096;
 constexpr float RB_FLT_MAX = 3.402823466e+38f;
 
-struct RbState {  // pointers into the state block for (n, T); layout in fsg_hip.h
+struct RbState {  // pointers into the state block for (n, T); layout in fsg_hip.h, stated here once by rb_state and measured by rb_state_bytes
   double* consts;   // [4] R, m, sigma_min, 0
   double* rows;     // [n][6]
   double* u;        // [n]
@@ -35,19 +35,15 @@ struct RbState {  // pointers into the state block for (n, T); layout in fsg_hip
   double* ws;       // [s][n]
   float* scal;      // [2] kappa, inv2var
   int32_t* frozen;  // [s]
+  void* end;        // one past frozen
 };
-
-__host__ __device__ inline size_t rb_state_bytes(size_t n, int T) {
-  const size_t s = (size_t)T + 1;
-  return (8 * (4 + RB_ROW * n + n + 4 * s + s * n) + 4 * (2 + s) + 7) & ~(size_t)7;
-}
 
 __host__ __device__ inline RbState rb_state(void* p, size_t n, int T) {
   const size_t s = (size_t)T + 1;
   RbState S;
   S.consts = (double*)p;
   S.rows = S.consts + 4;
-  S.u = S.rows + RB_ROW * n;
+  S.u = S.rows + FSG_ROBUST_ROW * n;
   S.sigma = S.u + n;
   S.c = S.sigma + s;
   S.mu1 = S.c + s;
@@ -55,8 +51,11 @@ __host__ __device__ inline RbState rb_state(void* p, size_t n, int T) {
   S.ws = S.mu2 + s;
   S.scal = (float*)(S.ws + s * n);
   S.frozen = (int32_t*)(S.scal + 2);
+  S.end = S.frozen + s;
   return S;
 }
+
+inline size_t rb_state_bytes(size_t n, int T) { return fsg_carved_bytes(fsg_origin, rb_state(fsg_origin, n, T).end); }
 
 inline int rb_chunks(int h, int w) { return (int)(((size_t)h * (size_t)w + RB_CHUNK - 1) / RB_CHUNK); }
 
@@ -159,7 +158,7 @@ __global__ __launch_bounds__(RB_THREADS) void rb_estep_kernel(RbIn I, int n, int
   __syncthreads();
   if (tid < RB_SLOTS) {
     float s = 0.f;
-    if (tid < RB_ROW) {
+    if (tid < FSG_ROBUST_ROW) {
       s = red[0][tid];
 #pragma unroll
       for (int q = 1; q < RB_THREADS / FSG_WAVE; ++q)
@@ -173,8 +172,6 @@ struct RbOpts {
   double c0, sigma_floor, slice_floor;
   int min_pixels;
 };
-
-__device__ __forceinline__ bool rb_finite(double x) { return fabs(x) <= 1.7976931348623157e308; }  // NaN fails
 
 __device__ __forceinline__ double rb_normal_pdf(double u, double mu, double v) {
   const double d = u - mu;
@@ -200,7 +197,7 @@ __global__ __launch_bounds__(RB_THREADS) void rb_update_kernel(void* state, cons
       mx = fmax(mx, (double)p[(size_t)b * RB_SLOTS + 5]);
     }
     const bool any = r[0] > 0.0;  // a slice without a pixel stores no Inf
-    double* row = S.rows + (size_t)k * RB_ROW;
+    double* row = S.rows + (size_t)k * FSG_ROBUST_ROW;
 #pragma unroll
     for (int j = 0; j < 4; ++j) row[j] = r[j];
     row[4] = any ? mn : 0.0;
@@ -218,7 +215,7 @@ __global__ __launch_bounds__(RB_THREADS) void rb_update_kernel(void* state, cons
     if (t == 0) {
       double mn = INFINITY, mx = -INFINITY;  // min and max do not depend on the order
       for (int k = tid; k < n; k += FSG_WAVE) {
-        const double* row = S.rows + (size_t)k * RB_ROW;
+        const double* row = S.rows + (size_t)k * FSG_ROBUST_ROW;
         if (row[0] > 0.0) { mn = fmin(mn, row[4]); mx = fmax(mx, row[5]); }
       }
 #pragma unroll
@@ -227,7 +224,7 @@ __global__ __launch_bounds__(RB_THREADS) void rb_update_kernel(void* state, cons
         mx = fmax(mx, __shfl_xor(mx, o, FSG_WAVE));
       }
       const double R = mx - mn;
-      const bool good = rb_finite(R) && R > 0.0 && rb_finite(1.0 / R);
+      const bool good = fsg_finite(R) && R > 0.0 && fsg_finite(1.0 / R);
       if (tid == 0) {
         S.consts[0] = good ? R : 0.0;
         S.consts[1] = good ? 1.0 / R : 0.0;
@@ -246,7 +243,7 @@ __global__ __launch_bounds__(RB_THREADS) void rb_update_kernel(void* state, cons
     for (int base = 0; base < n; base += FSG_WAVE) {
       const int k = base + tid, cnt = n - base < FSG_WAVE ? n - base : FSG_WAVE;
       const bool in = k < n;
-      const double* row = S.rows + (size_t)(in ? k : 0) * RB_ROW;
+      const double* row = S.rows + (size_t)(in ? k : 0) * FSG_ROBUST_ROW;
       const double lN = in ? row[0] : 0.0, lp = in ? row[1] : 0.0, le = in ? row[2] : 0.0, lu = in ? S.u[k] : 0.0;
       const double lw = !in ? 0.0 : (wold ? wold[k] : 1.0);
       for (int j = 0; j < cnt; ++j) {
@@ -271,7 +268,7 @@ __global__ __launch_bounds__(RB_THREADS) void rb_update_kernel(void* state, cons
     const double c = t == 0 ? O.c0 : S0 / Nw;
     const double kappa = ((1.0 - c) / c) * m * sqrt(6.283185307179586 * var), inv2var = 1.0 / (2.0 * var);
     const float kf = (float)kappa, vf = (float)inv2var;
-    frozen = frozen || !(Nw > 0.0) || !(S0 > 0.0) || !rb_finite(S2) || !rb_finite(var) || !(var > 0.0) || !rb_finite(c) ||
+    frozen = frozen || !(Nw > 0.0) || !(S0 > 0.0) || !fsg_finite(S2) || !fsg_finite(var) || !(var > 0.0) || !fsg_finite(c) ||
              !(fabsf(kf) <= RB_FLT_MAX) || !(fabsf(vf) <= RB_FLT_MAX) || !(kf >= 0.f);
     double mu1 = 0.0, mu2 = 0.0, v1 = 0.0, v2 = 0.0, mix = 1.0;
     if (t > 0 && !frozen) {  // wave-uniform
@@ -282,7 +279,7 @@ __global__ __launch_bounds__(RB_THREADS) void rb_update_kernel(void* state, cons
       for (int base = 0; base < n; base += FSG_WAVE) {
         const int k = base + tid, cnt = n - base < FSG_WAVE ? n - base : FSG_WAVE;
         const bool in = k < n;
-        const double lN = in ? S.rows[(size_t)k * RB_ROW] : 0.0, lu = in ? S.u[k] : 0.0, lw = in ? wold[k] : 0.0;
+        const double lN = in ? S.rows[(size_t)k * FSG_ROBUST_ROW] : 0.0, lu = in ? S.u[k] : 0.0, lw = in ? wold[k] : 0.0;
         for (int j = 0; j < cnt; ++j) {
           const double N = __shfl(lN, j, FSG_WAVE), u = __shfl(lu, j, FSG_WAVE), w = __shfl(lw, j, FSG_WAVE);
           if (!(N >= (double)O.min_pixels && N > 0.0)) continue;
@@ -295,7 +292,7 @@ __global__ __launch_bounds__(RB_THREADS) void rb_update_kernel(void* state, cons
       if (!(v2 > 0.0)) v2 = ((mu2 - mu1) * (mu2 - mu1)) / 4.0;
       v2 = fmax(v2, fl2);
       mix = sw / nok;
-      frozen = !rb_finite(mu1) || !rb_finite(mu2) || !rb_finite(v1) || !rb_finite(v2) || !rb_finite(mix);
+      frozen = !fsg_finite(mu1) || !fsg_finite(mu2) || !fsg_finite(v1) || !fsg_finite(v2) || !fsg_finite(mix);
     }
     if (tid == 0) {
       S.sigma[t] = frozen ? 0.0 : sqrt(var);
@@ -313,7 +310,7 @@ __global__ __launch_bounds__(RB_THREADS) void rb_update_kernel(void* state, cons
   const bool frozen = sh[0] != 0.0;
   const double mu1 = sh[1], mu2 = sh[2], v1 = sh[3], v2 = sh[4], mix = sh[5];
   for (int k = tid; k < n; k += RB_THREADS) {
-    const double N = S.rows[(size_t)k * RB_ROW];
+    const double N = S.rows[(size_t)k * FSG_ROBUST_ROW];
     const bool ok = N >= (double)O.min_pixels && N > 0.0;
     double w = ok ? 1.0 : 0.0;
     if (ok && t > 0 && !frozen) {
@@ -324,7 +321,7 @@ __global__ __launch_bounds__(RB_THREADS) void rb_update_kernel(void* state, cons
         const double g1 = rb_normal_pdf(u, mu1, v1) * mix, g2 = rb_normal_pdf(u, mu2, v2) * (1.0 - mix);
         const double den = g1 + g2;
         // both densities underflowed, or a zero variance: the class of the nearer mean
-        w = (den > 0.0 && rb_finite(den) && rb_finite(g1)) ? g1 / den : (fabs(u - mu1) <= fabs(u - mu2) ? 1.0 : 0.0);
+        w = (den > 0.0 && fsg_finite(den) && fsg_finite(g1)) ? g1 / den : (fabs(u - mu1) <= fabs(u - mu2) ? 1.0 : 0.0);
       }
     }
     wnew[k] = w;
@@ -359,16 +356,10 @@ __global__ __launch_bounds__(RB_THREADS) void rb_weights_kernel(RbIn I, int n, i
   }
 }
 
-bool rb_overlap(const void* p, size_t bytes, const void* q, size_t qbytes) {
-  if (!p || !q) return false;
-  const uintptr_t a = (uintptr_t)p, b = (uintptr_t)q;
-  return a < b + qbytes && b < a + bytes;
-}
-
 // what estep and weights share: sizes, pointers, options, the state and its alignment
 int rb_check_pixels(const float* y, const float* s, const float* sw, float min_weight, int n, int h, int w, int n_em,
                     const void* state, size_t state_bytes) {
-  if (n <= 0 || h <= 0 || w <= 0 || n_em < 1 || n_em > RB_MAX_EM) return FSG_E_BADARG;
+  if (n <= 0 || h <= 0 || w <= 0 || n_em < 1 || n_em > FSG_SOLVER_MAX_ITER) return FSG_E_BADARG;
   if (!y || !s || !state) return FSG_E_BADARG;
   if (!(min_weight >= 0.f)) return FSG_E_BADARG;  // negative or NaN
   if (n > 65535 || (size_t)n * (size_t)h * (size_t)w > (size_t)0x7FFFFFFF) return FSG_E_TOOBIG;
@@ -393,7 +384,7 @@ size_t fsg_robust_ws_bytes(int n, int h, int w) {
 }
 
 size_t fsg_robust_state_bytes(int n, int n_em) {
-  if (n <= 0 || n_em < 1 || n_em > RB_MAX_EM) return 0;
+  if (n <= 0 || n_em < 1 || n_em > FSG_SOLVER_MAX_ITER) return 0;
   return rb_state_bytes((size_t)n, n_em);
 }
 
@@ -407,8 +398,8 @@ int fsg_robust_estep_f32(const float* y, const float* s, const uint8_t* slices_m
   if (!ws || ws_bytes < fsg_robust_ws_bytes(n, h, w)) return FSG_E_BADARG;
   if ((uintptr_t)ws & 7) return FSG_E_ALIGN;
   const size_t pix = (size_t)n * h * w, wsb = fsg_robust_ws_bytes(n, h, w), stb = rb_state_bytes((size_t)n, n_em);
-  if (rb_overlap(ws, wsb, y, pix * 4) || rb_overlap(ws, wsb, s, pix * 4) || rb_overlap(ws, wsb, sim_weight, pix * 4) ||
-      rb_overlap(ws, wsb, slices_mask, pix) || rb_overlap(ws, wsb, state, stb))
+  if (fsg_overlap(ws, wsb, y, pix * 4) || fsg_overlap(ws, wsb, s, pix * 4) || fsg_overlap(ws, wsb, sim_weight, pix * 4) ||
+      fsg_overlap(ws, wsb, slices_mask, pix) || fsg_overlap(ws, wsb, state, stb))
     return FSG_E_BADARG;
   const RbIn I{y, s, slices_mask, sim_weight, min_weight, h * w};
   const dim3 grid((unsigned)rb_chunks(h, w), (unsigned)n);
@@ -422,14 +413,14 @@ int fsg_robust_estep_f32(const float* y, const float* s, const uint8_t* slices_m
 
 int fsg_robust_update_f32(void* state, size_t state_bytes, const void* ws, size_t ws_bytes, int n, int h, int w, int t, int n_em,
                           double c0, double sigma_floor, double slice_floor, int min_pixels, void* stream) {
-  if (n <= 0 || h <= 0 || w <= 0 || n_em < 1 || n_em > RB_MAX_EM || t < 0 || t > n_em) return FSG_E_BADARG;
+  if (n <= 0 || h <= 0 || w <= 0 || n_em < 1 || n_em > FSG_SOLVER_MAX_ITER || t < 0 || t > n_em) return FSG_E_BADARG;
   if (n > 65535 || (size_t)n * (size_t)h * (size_t)w > (size_t)0x7FFFFFFF) return FSG_E_TOOBIG;
   if (!state || !ws || state_bytes < rb_state_bytes((size_t)n, n_em) || ws_bytes < fsg_robust_ws_bytes(n, h, w)) return FSG_E_BADARG;
   if (!(c0 > 0.0 && c0 <= 1.0) || !(sigma_floor >= 0.0 && sigma_floor <= 1.7976931348623157e308) ||
       !(slice_floor >= 0.0 && slice_floor <= 1.7976931348623157e308) || min_pixels < 0)
     return FSG_E_BADARG;
   if (((uintptr_t)state & 7) || ((uintptr_t)ws & 7)) return FSG_E_ALIGN;
-  if (rb_overlap(state, rb_state_bytes((size_t)n, n_em), ws, fsg_robust_ws_bytes(n, h, w))) return FSG_E_BADARG;
+  if (fsg_overlap(state, rb_state_bytes((size_t)n, n_em), ws, fsg_robust_ws_bytes(n, h, w))) return FSG_E_BADARG;
   const RbOpts O{c0, sigma_floor, slice_floor, min_pixels};
   hipLaunchKernelGGL(rb_update_kernel, dim3(1), dim3(RB_THREADS), 0, fsg_stream(stream), state, (const float*)ws, rb_chunks(h, w),
                      n, t, n_em, O);
@@ -444,8 +435,8 @@ int fsg_robust_weights_f32(const float* y, const float* s, const uint8_t* slices
   if (!out || (level != FSG_ROBUST_SLICE && level != FSG_ROBUST_BOTH)) return FSG_E_BADARG;
   if ((uintptr_t)out & 3) return FSG_E_ALIGN;
   const size_t pix = (size_t)n * h * w, stb = rb_state_bytes((size_t)n, n_em);
-  if (rb_overlap(out, pix * 4, y, pix * 4) || rb_overlap(out, pix * 4, s, pix * 4) || rb_overlap(out, pix * 4, sim_weight, pix * 4) ||
-      rb_overlap(out, pix * 4, slices_mask, pix) || rb_overlap(out, pix * 4, state, stb))
+  if (fsg_overlap(out, pix * 4, y, pix * 4) || fsg_overlap(out, pix * 4, s, pix * 4) || fsg_overlap(out, pix * 4, sim_weight, pix * 4) ||
+      fsg_overlap(out, pix * 4, slices_mask, pix) || fsg_overlap(out, pix * 4, state, stb))
     return FSG_E_BADARG;
   const RbIn I{y, s, slices_mask, sim_weight, min_weight, h * w};
   const dim3 grid((unsigned)rb_chunks(h, w), (unsigned)n);

@@ -2,8 +2,9 @@
 // fsg_slice_acq_bwd.hip: backward of the forward; fsg_slice_acq_adjoint_bwd.hip: backward of the adjoint): the kernel-argument
 // block, the LDS image of the PSF and of the per-axis tap products and its fill for any workgroup shape, the pixel-centre
 // arithmetic, the trilinear cell (corner weights, the eight corners in their one order, sa_tri8, the PSF coordinate of a snapped
-// voxel), the lever arms and the fixed-order reduction of the 12 transform sums with the size of its partials, the fixed-point
-// quantisers with their finalising kernel, and the argument checks.  Internal linkage: each unit has its own copy.  The SA_* corner macros stay defined for the including unit.
+// voxel), the lever arms, the fixed-order workgroup fold sa_fold<TERMS, SLOTS> (the 12 transform sums of the two backward units,
+// the 30 sums of fsg_svr.hip) with the size of its partials, the fixed-point quantisers with their finalising kernel, and the
+// argument checks.  Internal linkage: each unit has its own copy.  The SA_* corner macros stay defined for the including unit.
 #pragma once
 #include "fsg_common.h"
 
@@ -162,28 +163,33 @@ __device__ __forceinline__ void sa_lever_lin(float (&g)[12], const float* __rest
   g[11] += dx * T[2] + dy * T[6] + dz * T[10];
 }
 
-// ---- the fixed-order reduction of the 12 transform sums, shared by the two backward units ----
+// ---- the fixed-order fold of a workgroup's per-lane sums: the 12 transform sums of the two backward units (sa_fold<12>), the
+// 30 sums of fsg_svr.hip (sa_fold<30, 32>) ----
 constexpr int SAB_WAVES = SA_TILE * SA_TILE / FSG_WAVE;
 
-// Every thread of the workgroup calls this with its 12 sums (a pixel without a contribution carries twelve zeros).  Lanes of a
-// wave: a fixed shuffle tree; waves of the workgroup: LDS (`red`, [SAB_WAVES][12]), added in wave order; one 12-float partial
-// per workgroup at ws[slice][tile].
-__device__ __forceinline__ void sa_fold12(const float (&g)[12], float* red, float* __restrict__ ws, int in) {
-  const int tid = threadIdx.y * SA_TILE + threadIdx.x, lane = tid & (FSG_WAVE - 1), wave = tid / FSG_WAVE;
+// Every thread of the 16x16 workgroup calls this with its TERMS sums (a pixel without a contribution carries zeros).  Lanes of a
+// wave: a fixed shuffle tree; waves of the workgroup: LDS (`red`, [SAB_WAVES][SLOTS]), added in wave order; one partial of
+// SLOTS floats per workgroup at ws[slice][tile].  All SLOTS are stored, zeros from TERMS on: the workspace needs no zeroing.
+template <int TERMS, int SLOTS = TERMS>
+__device__ __forceinline__ void sa_fold(const float (&v)[TERMS], float* red, float* __restrict__ ws, int in) {
+  const int tid = sa_tid(), lane = tid & (FSG_WAVE - 1), wave = tid / FSG_WAVE;
 #pragma unroll
-  for (int k = 0; k < 12; ++k) {
-    float v = g[k];
+  for (int k = 0; k < TERMS; ++k) {
+    float s = v[k];
 #pragma unroll
-    for (int o = FSG_WAVE / 2; o > 0; o >>= 1) v += __shfl_down(v, o, FSG_WAVE);
-    if (lane == 0) red[wave * 12 + k] = v;
+    for (int o = FSG_WAVE / 2; o > 0; o >>= 1) s += __shfl_down(s, o, FSG_WAVE);
+    if (lane == 0) red[wave * SLOTS + k] = s;
   }
   __syncthreads();
-  if (tid < 12) {
-    float v = red[tid];
+  if (tid < SLOTS) {
+    float s = 0.f;
+    if (tid < TERMS) {
+      s = red[tid];
 #pragma unroll
-    for (int q = 1; q < SAB_WAVES; ++q) v += red[q * 12 + tid];
+      for (int q = 1; q < SAB_WAVES; ++q) s += red[q * SLOTS + tid];
+    }
     const size_t tile = (size_t)blockIdx.y * gridDim.x + blockIdx.x, tiles = (size_t)gridDim.x * gridDim.y;
-    ws[((size_t)in * tiles + tile) * 12 + tid] = v;
+    ws[((size_t)in * tiles + tile) * SLOTS + tid] = s;
   }
 }
 
@@ -272,11 +278,11 @@ inline dim3 sa_grid(const SaParams& P) {
   return dim3((unsigned)((P.w + SA_TILE - 1) / SA_TILE), (unsigned)((P.h + SA_TILE - 1) / SA_TILE), (unsigned)P.n);
 }
 
-// bytes of the tile partials of sa_fold12, one 12-float partial per workgroup of sa_grid (a multiple of 48, so what follows
-// them in a workspace stays 16-byte aligned)
-inline size_t sa_partial_bytes(int n, int h, int w) {
+// bytes of the tile partials of sa_fold<TERMS, slots>, one partial of `slots` floats per workgroup of sa_grid (slots = 12: a
+// multiple of 48, so what follows them in a workspace stays 16-byte aligned)
+inline size_t sa_partial_bytes(int n, int h, int w, int slots) {
   const size_t tiles = (size_t)((w + SA_TILE - 1) / SA_TILE) * (size_t)((h + SA_TILE - 1) / SA_TILE);
-  return (size_t)n * tiles * 12 * sizeof(float);
+  return (size_t)n * tiles * slots * sizeof(float);
 }
 
 }  // namespace

@@ -17,7 +17,7 @@
 // MI355X shape of the work: as the forward and its backward, one 256-thread workgroup = a 16x16 pixel tile of ONE slice, the PSF
 // and the per-axis products r_ij * tap_offset in LDS.  The kernel only GATHERS: g' (and vol, vol_mask) are read under the PSF
 // straight from global memory, grad_slices is one plain store per thread, and the transform gradients go through the fixed-order
-// fold of fsg_sa.h (shuffle tree per wave, waves in order through LDS, one 12-float partial per workgroup, tiles added in index
+// fold of fsg_sa.h (sa_fold<12>: shuffle tree per wave, waves in order through LDS, one 12-float partial per workgroup, tiles added in index
 // order by sa_bwd_reduce_kernel).  No atomics anywhere: both outputs are pure functions of the inputs.
 //
 // Every range test is written in ACCEPTING form, `if (!(x >= 0 && x < hx ...)) continue;`: a NaN or Inf coordinate (non-finite
@@ -144,7 +144,7 @@ __global__ __launch_bounds__(SA_TILE* SA_TILE) void sa_adjoint_backward_kernel(S
   if (GT) {
 #pragma unroll
     for (int k = 0; k < 12; ++k) g[k] = kept ? g[k] / weight : 0.f;
-    sa_fold12(g, red, ws, in);
+    sa_fold<12>(g, red, ws, in);
   }
 }
 
@@ -173,7 +173,7 @@ extern "C" {
 
 size_t fsg_slice_acq_adjoint_backward_ws_bytes(int D, int H, int W, int n, int h, int w, int equalize, int want_transforms) {
   if (D <= 0 || H <= 0 || W <= 0 || n <= 0 || h <= 0 || w <= 0) return 0;
-  return (want_transforms ? sa_partial_bytes(n, h, w) : 0) + (equalize ? (size_t)D * H * W * sizeof(float) : 0);
+  return (want_transforms ? sa_partial_bytes(n, h, w, 12) : 0) + (equalize ? (size_t)D * H * W * sizeof(float) : 0);
 }
 
 int fsg_slice_acq_adjoint_backward_f32(const float* transforms, const float* grad_vol, const float* vol_weight, const float* vol,
@@ -199,7 +199,7 @@ int fsg_slice_acq_adjoint_backward_f32(const float* transforms, const float* gra
   float* partials = static_cast<float*>(ws);
   const float* G = grad_vol;
   if (eq) {
-    float* ge = reinterpret_cast<float*>(static_cast<char*>(ws) + (gt ? sa_partial_bytes(n, h, w) : 0));
+    float* ge = reinterpret_cast<float*>(static_cast<char*>(ws) + (gt ? sa_partial_bytes(n, h, w, 12) : 0));
     const size_t nv = (size_t)D * H * W;
     size_t blocks = (nv + 255) / 256;
     if (blocks > 8192) blocks = 8192;

@@ -1,7 +1,7 @@
 // fsg_slice_acq_bwd.hip -- backward of the slice-acquisition FORWARD operator: gradients of `slices` with respect to the
 // volume and to the (n,3,4) slice transforms (reference SliceAcqFunction.backward, slice_acq_cuda_kernel.cu:173-470,
-// host side :993-1030).  The backward of the adjoint is fsg_slice_acq_adjoint_bwd.hip; the fold of the 12 transform sums and
-// sa_bwd_reduce_kernel, which both units use, are in fsg_sa.h.
+// host side :993-1030).  The backward of the adjoint is fsg_slice_acq_adjoint_bwd.hip; the fold of the 12 transform sums (sa_fold<12>)
+// and sa_bwd_reduce_kernel, which both units use, are in fsg_sa.h.
 //
 // The rule (include/fsg_hip.h), per pixel inside slices_mask with grad_slices != 0:
 //   pass 1  weight = sum over the in-volume taps of the PSF value (FSG_SA_NEAREST_PSF: re-interpolated at the rounded voxel,
@@ -170,7 +170,7 @@ __device__ __forceinline__ void sa_backward_body(const SaParams P, const float* 
   }
 
   // the fold of fsg_sa.h: shuffle tree per wave, waves in order through LDS, one partial per workgroup
-  if (GT) sa_fold12(g, red, ws, in);
+  if (GT) sa_fold<12>(g, red, ws, in);
 }
 
 // The kernels: the body with each accumulator.  A kernel takes its destination as a __restrict__ argument of its own and builds
@@ -247,7 +247,7 @@ int sa_backward_run(const SaParams& P, size_t lds, const float* vol, const float
 extern "C" {
 
 size_t fsg_slice_acq_backward_ws_bytes(int n, int h, int w) {
-  return n <= 0 || h <= 0 || w <= 0 ? 0 : sa_partial_bytes(n, h, w);
+  return n <= 0 || h <= 0 || w <= 0 ? 0 : sa_partial_bytes(n, h, w, 12);
 }
 
 int fsg_slice_acq_backward_f32(const float* transforms, const float* vol, const uint8_t* vol_mask, const float* psf, int pd,

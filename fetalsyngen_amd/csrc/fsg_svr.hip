@@ -10,43 +10,20 @@
 //
 // MI355X shape of the work: as the backward of the forward, one 256-thread workgroup = a 16x16 pixel tile of ONE slice, the PSF
 // and the per-axis tap products in LDS (sa_fill_lds), the slice's 72 jac entries beside them.  No atomics: each lane keeps its
-// 30 terms in registers, a wave folds them with a fixed shuffle tree, the four waves meet in LDS and are added in wave order,
+// 30 terms in registers, a wave folds them with a fixed shuffle tree, the four waves meet in LDS and are added in wave order
+// (sa_fold<30, 32> of fsg_sa.h, the fold of the two backward units at another width),
 // the workgroup stores ONE 32-float partial at ws[slice][tile], and svr_reduce_kernel adds a slice's tiles in double in
 // tile-index order.  The result is a pure function of one slice's inputs.
 //
 // Every range test is in ACCEPTING form, so a NaN or Inf coordinate skips the tap and no address is formed from a value that
-// was not proven to be inside its array.
+// was not proven to be inside its array.  The iteration cap and the width of a row are the header's (FSG_SOLVER_MAX_ITER,
+// FSG_SVR_SLOTS); the overlap and finite tests are fsg_common.h's.
 #include "fsg_sa.h"
 
 namespace {
 
-constexpr int SVR_TERMS = 30;   // 21 + 6 + 1 + 1 + 1
-constexpr int SVR_SLOTS = 32;   // a partial and a row of `stats`; slots 30, 31 are 0
-constexpr int SVR_MAX_ITER = 4096;
-
-// The 30-value fold: sa_fold12's scheme at another width.  Every thread of the workgroup calls it (a pixel that takes no part
-// carries thirty zeros).  red: [SAB_WAVES][SVR_SLOTS].
-__device__ __forceinline__ void svr_fold30(const float (&v)[SVR_TERMS], float* red, float* __restrict__ ws, int in) {
-  const int tid = sa_tid(), lane = tid & (FSG_WAVE - 1), wave = tid / FSG_WAVE;
-#pragma unroll
-  for (int k = 0; k < SVR_TERMS; ++k) {
-    float s = v[k];
-#pragma unroll
-    for (int o = FSG_WAVE / 2; o > 0; o >>= 1) s += __shfl_down(s, o, FSG_WAVE);
-    if (lane == 0) red[wave * SVR_SLOTS + k] = s;
-  }
-  __syncthreads();
-  if (tid < SVR_SLOTS) {
-    float s = 0.f;
-    if (tid < SVR_TERMS) {
-      s = red[tid];
-#pragma unroll
-      for (int q = 1; q < SAB_WAVES; ++q) s += red[q * SVR_SLOTS + tid];
-    }
-    const size_t tile = (size_t)blockIdx.y * gridDim.x + blockIdx.x, tiles = (size_t)gridDim.x * gridDim.y;
-    ws[((size_t)in * tiles + tile) * SVR_SLOTS + tid] = s;  // all 32 slots: the workspace needs no zeroing
-  }
-}
+constexpr int SVR_TERMS = 30;  // 21 + 6 + 1 + 1 + 1
+// a partial and a row of `stats` are FSG_SVR_SLOTS = 32 wide; slots 30, 31 are 0
 
 __global__ __launch_bounds__(SA_TILE* SA_TILE) void svr_normal_kernel(SaParams P, const float* __restrict__ vol,
                                                                       const float* __restrict__ jac,
@@ -58,7 +35,7 @@ __global__ __launch_bounds__(SA_TILE* SA_TILE) void svr_normal_kernel(SaParams P
   const float* __restrict__ T = P.tr + (size_t)in * 12;
   const SaLds L = sa_lds_layout(smem, P);
   float* jl = L.tz + 3 * P.pd;  // [12][6]
-  float* red = jl + 72;         // [SAB_WAVES][SVR_SLOTS]
+  float* red = jl + 72;         // [SAB_WAVES][FSG_SVR_SLOTS]
   sa_fill_lds(L, P, T, sa_tid(), SA_TILE * SA_TILE);
   if (sa_tid() < 72) jl[sa_tid()] = jac[(size_t)in * 72 + sa_tid()];
   __syncthreads();
@@ -162,25 +139,20 @@ __global__ __launch_bounds__(SA_TILE* SA_TILE) void svr_normal_kernel(SaParams P
       out[29] = 1.f;
     }
   }
-  svr_fold30(out, red, ws, in);
+  sa_fold<SVR_TERMS, FSG_SVR_SLOTS>(out, red, ws, in);  // all 32 slots: the workspace needs no zeroing
 }
 
 // stats[slice][k] = the slice's tile partials added in double in tile-index order.  One wave per slice, 32 lanes busy.
 __global__ __launch_bounds__(FSG_WAVE) void svr_reduce_kernel(const float* __restrict__ ws, int tiles, double* __restrict__ stats) {
   const int in = blockIdx.x, k = threadIdx.x;
-  if (k >= SVR_SLOTS) return;
-  const float* p = ws + (size_t)in * tiles * SVR_SLOTS + k;
+  if (k >= FSG_SVR_SLOTS) return;
+  const float* p = ws + (size_t)in * tiles * FSG_SVR_SLOTS + k;
   double v = 0.0;
-  for (int t = 0; t < tiles; ++t) v = v + (double)p[(size_t)t * SVR_SLOTS];
-  stats[(size_t)in * SVR_SLOTS + k] = k < SVR_TERMS ? v : 0.0;
+  for (int t = 0; t < tiles; ++t) v = v + (double)p[(size_t)t * FSG_SVR_SLOTS];
+  stats[(size_t)in * FSG_SVR_SLOTS + k] = k < SVR_TERMS ? v : 0.0;
 }
 
-inline size_t svr_ws_bytes(int n, int h, int w) {
-  const size_t tiles = (size_t)((w + SA_TILE - 1) / SA_TILE) * (size_t)((h + SA_TILE - 1) / SA_TILE);
-  return (size_t)n * tiles * SVR_SLOTS * sizeof(float);
-}
-
-// ---- the state block of a solve (layout in fsg_hip.h) ----
+// ---- the state block of a solve (layout in fsg_hip.h): svr_state is its one statement here, svr_state_bytes measures it ----
 struct SvrState {
   double* stats_cur;   // [n][32]
   double* lambda;      // [n]
@@ -191,18 +163,14 @@ struct SvrState {
   int32_t* frozen;     // [n]
   int32_t* accepted_h; // [K+1][n]
   int32_t* frozen_h;   // [K+1][n]
+  void* end;           // one past frozen_h
 };
-
-__host__ __device__ inline size_t svr_state_bytes(size_t n, int K) {
-  const size_t s = (size_t)K + 1;
-  return (8 * (SVR_SLOTS * n + 2 * n + 2 * s * n) + 4 * (6 * n + n + 2 * s * n) + 7) & ~(size_t)7;
-}
 
 __host__ __device__ inline SvrState svr_state(void* p, size_t n, int K) {
   const size_t s = (size_t)K + 1;
   SvrState S;
   S.stats_cur = (double*)p;
-  S.lambda = S.stats_cur + SVR_SLOTS * n;
+  S.lambda = S.stats_cur + FSG_SVR_SLOTS * n;
   S.m0 = S.lambda + n;
   S.cost_h = S.m0 + n;
   S.lambda_h = S.cost_h + s * n;
@@ -210,14 +178,15 @@ __host__ __device__ inline SvrState svr_state(void* p, size_t n, int K) {
   S.frozen = (int32_t*)(S.theta_cur + 6 * n);
   S.accepted_h = S.frozen + n;
   S.frozen_h = S.accepted_h + s * n;
+  S.end = S.frozen_h + s * n;
   return S;
 }
+
+inline size_t svr_state_bytes(size_t n, int K) { return fsg_carved_bytes(fsg_origin, svr_state(fsg_origin, n, K).end); }
 
 struct SvrOpts {
   double lambda0, factor, lambda_min, lambda_max, min_overlap, tol;
 };
-
-__device__ __forceinline__ bool svr_finite(double x) { return fabs(x) <= 1.7976931348623157e308; }  // NaN fails
 
 // One thread per slice; double, + - * / only (the factorisation is Cholesky's square-root-free form A = L D L^T, whose pivots
 // are the squares of Cholesky's own, so `pivot > 0` is the same test and every operation is correctly rounded).
@@ -226,18 +195,18 @@ __global__ __launch_bounds__(256) void svr_update_kernel(const double* __restric
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   const SvrState S = svr_state(state, (size_t)n, K);
-  const double* tr = stats_trial + (size_t)i * SVR_SLOTS;
-  double* cur = S.stats_cur + (size_t)i * SVR_SLOTS;
+  const double* tr = stats_trial + (size_t)i * FSG_SVR_SLOTS;
+  double* cur = S.stats_cur + (size_t)i * FSG_SVR_SLOTS;
   float* th_t = theta_trial + (size_t)i * 6;
   float* th_c = S.theta_cur + (size_t)i * 6;
   bool fin = true;
-  for (int j = 0; j < SVR_TERMS; ++j) fin = fin && svr_finite(tr[j]);
+  for (int j = 0; j < SVR_TERMS; ++j) fin = fin && fsg_finite(tr[j]);
   const double cost_t = tr[27] / tr[28], m_t = tr[29];
   bool frozen;
   int accepted = 0;
   double lambda;
   if (k == 0) {
-    for (int j = 0; j < SVR_SLOTS; ++j) cur[j] = tr[j];
+    for (int j = 0; j < FSG_SVR_SLOTS; ++j) cur[j] = tr[j];
     for (int j = 0; j < 6; ++j) th_c[j] = th_t[j];
     S.m0[i] = m_t;
     lambda = O.lambda0;
@@ -249,7 +218,7 @@ __global__ __launch_bounds__(256) void svr_update_kernel(const double* __restric
       const double cost_old = cur[27] / cur[28];
       if (fin && m_t >= O.min_overlap * S.m0[i] && cost_t < cost_old) {
         accepted = 1;
-        for (int j = 0; j < SVR_SLOTS; ++j) cur[j] = tr[j];
+        for (int j = 0; j < FSG_SVR_SLOTS; ++j) cur[j] = tr[j];
         for (int j = 0; j < 6; ++j) th_c[j] = th_t[j];
         lambda = fmax(lambda / O.factor, O.lambda_min);
         if (cost_old - cost_t <= O.tol * cost_old) frozen = true;
@@ -332,17 +301,11 @@ __global__ __launch_bounds__(256) void svr_update_kernel(const double* __restric
   S.frozen_h[h] = frozen ? 1 : 0;
 }
 
-bool svr_overlap(const void* p, size_t bytes, const void* q, size_t qbytes) {
-  if (!p || !q) return false;
-  const uintptr_t a = (uintptr_t)p, b = (uintptr_t)q;
-  return a < b + qbytes && b < a + bytes;
-}
-
 }  // namespace
 
 extern "C" {
 
-size_t fsg_svr_ws_bytes(int n, int h, int w) { return n <= 0 || h <= 0 || w <= 0 ? 0 : svr_ws_bytes(n, h, w); }
+size_t fsg_svr_ws_bytes(int n, int h, int w) { return n <= 0 || h <= 0 || w <= 0 ? 0 : sa_partial_bytes(n, h, w, FSG_SVR_SLOTS); }
 
 int fsg_svr_normal_f32(const float* transforms, const float* jac, const float* vol, const float* psf, int pd, int ph, int pw,
                        const float* slices, const uint8_t* slices_mask, const float* slices_weight, double* stats, int D, int H,
@@ -358,7 +321,7 @@ int fsg_svr_normal_f32(const float* transforms, const float* jac, const float* v
   if (rc) return rc;
   if (!ws || ws_bytes < fsg_svr_ws_bytes(n, h, w)) return FSG_E_BADARG;
   if (((uintptr_t)ws & 7) || ((uintptr_t)stats & 7)) return FSG_E_ALIGN;
-  lds += (size_t)(72 + SAB_WAVES * SVR_SLOTS) * sizeof(float);
+  lds += (size_t)(72 + SAB_WAVES * FSG_SVR_SLOTS) * sizeof(float);
   const dim3 grid = sa_grid(P);
   hipStream_t st = fsg_stream(stream);
   hipLaunchKernelGGL(svr_normal_kernel, grid, dim3(SA_TILE, SA_TILE), lds, st, P, vol, jac, slices, slices_weight, min_weight,
@@ -371,22 +334,22 @@ int fsg_svr_normal_f32(const float* transforms, const float* jac, const float* v
 }
 
 size_t fsg_svr_state_bytes(int n, int n_iter) {
-  if (n <= 0 || n_iter < 1 || n_iter > SVR_MAX_ITER) return 0;
+  if (n <= 0 || n_iter < 1 || n_iter > FSG_SOLVER_MAX_ITER) return 0;
   return svr_state_bytes((size_t)n, n_iter);
 }
 
 int fsg_svr_update_f32(const double* stats_trial, float* theta_trial, void* state, size_t state_bytes, int n, int k, int n_iter,
                        double lambda0, double factor, double lambda_min, double lambda_max, double min_overlap, double tol,
                        void* stream) {
-  if (n <= 0 || n_iter < 1 || n_iter > SVR_MAX_ITER || k < 0 || k > n_iter) return FSG_E_BADARG;
+  if (n <= 0 || n_iter < 1 || n_iter > FSG_SOLVER_MAX_ITER || k < 0 || k > n_iter) return FSG_E_BADARG;
   if (!stats_trial || !theta_trial || !state || state_bytes < fsg_svr_state_bytes(n, n_iter)) return FSG_E_BADARG;
   if (!(lambda0 > 0.0) || !(factor > 1.0) || !(lambda_min > 0.0) || !(lambda_max >= lambda_min) || !(min_overlap >= 0.0) ||
       !(tol >= 0.0))
     return FSG_E_BADARG;
   if (((uintptr_t)state & 7) || ((uintptr_t)stats_trial & 7) || ((uintptr_t)theta_trial & 3)) return FSG_E_ALIGN;
-  const size_t sb = (size_t)n * SVR_SLOTS * sizeof(double), tb = (size_t)n * 6 * sizeof(float);
-  if (svr_overlap(state, state_bytes, stats_trial, sb) || svr_overlap(state, state_bytes, theta_trial, tb) ||
-      svr_overlap(theta_trial, tb, stats_trial, sb))
+  const size_t sb = (size_t)n * FSG_SVR_SLOTS * sizeof(double), tb = (size_t)n * 6 * sizeof(float);
+  if (fsg_overlap(state, state_bytes, stats_trial, sb) || fsg_overlap(state, state_bytes, theta_trial, tb) ||
+      fsg_overlap(theta_trial, tb, stats_trial, sb))
     return FSG_E_BADARG;
   const SvrOpts O{lambda0, factor, lambda_min, lambda_max, min_overlap, tol};
   hipLaunchKernelGGL(svr_update_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, fsg_stream(stream), stats_trial,

@@ -3,7 +3,7 @@
 // L is the weighted graph Laplacian of the 6-neighbour grid restricted to the voxels of the mask; include/fsg_hip.h states which
 // edges take part, the edge weight and the order of the fp32 operations.  A gather: every thread reads p (and the guide, the
 // mask) around its four voxels and writes those four alone, so there are no atomics, no LDS, no allocation and no host
-// synchronisation, and the result is the same bits whichever of the load paths ran.
+// synchronisation, and the result is the same bits whichever of the load paths ran.  The overlap test is fsg_common.h's.
 #include "fsg_common.h"
 #include <cmath>
 
@@ -146,12 +146,6 @@ __global__ __launch_bounds__(TK_THREADS) void tk1_apply_kernel(const float* __re
   }
 }
 
-bool tk1_overlap(const void* p, size_t bytes, const void* q, size_t qbytes) {
-  if (!p || !q) return false;
-  const uintptr_t a = (uintptr_t)p, b = (uintptr_t)q;
-  return a < b + qbytes && b < a + bytes;
-}
-
 }  // namespace
 
 extern "C" int fsg_tk1_apply_f32(const float* p, const float* t, const uint8_t* mask, const float* guide, float delta, float lam,
@@ -162,8 +156,8 @@ extern "C" int fsg_tk1_apply_f32(const float* p, const float* t, const uint8_t* 
   const size_t n = (size_t)D * H * W;
   if (n > (size_t)0x7FFFFFFF) return FSG_E_TOOBIG;
   const size_t nb = n * sizeof(float);
-  if (tk1_overlap(out, nb, p, nb) || tk1_overlap(out, nb, guide, nb) || tk1_overlap(out, nb, mask, n)) return FSG_E_BADARG;
-  if (out != t && tk1_overlap(out, nb, t, nb)) return FSG_E_BADARG;
+  if (fsg_overlap(out, nb, p, nb) || fsg_overlap(out, nb, guide, nb) || fsg_overlap(out, nb, mask, n)) return FSG_E_BADARG;
+  if (out != t && fsg_overlap(out, nb, t, nb)) return FSG_E_BADARG;
   const dim3 grid((unsigned)((((n + 3) >> 2) + TK_THREADS - 1) / TK_THREADS)), block(TK_THREADS);
   const bool vec = ((((uintptr_t)p | (uintptr_t)t | (uintptr_t)guide | (uintptr_t)out) & 15) == 0) && ((uintptr_t)mask & 3) == 0;
   const uint32_t h = (uint32_t)H, w = (uint32_t)W, nn = (uint32_t)n;

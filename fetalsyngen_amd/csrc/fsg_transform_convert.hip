@@ -42,6 +42,7 @@
 // Every output element is written by every call: the translation column / elements are copied, and each of the four branches
 // of the mat2axisangle backward stores all nine rotation entries of grad_mat.  Outputs need no zeroing.
 // The reference's DEGREE macro is never defined there; there is no degree mode here.
+// The overlap test in front of the launches is fsg_common.h's fsg_overlap.
 #include "fsg_common.h"
 
 namespace {
@@ -286,12 +287,6 @@ __global__ __launch_bounds__(TC_THREADS) void tc_mat2axisangle_backward_kernel(c
   gm[3] = ga[3]; gm[7] = ga[4]; gm[11] = ga[5];
 }
 
-// [p, p + bytes) and [q, q + qbytes) share a byte
-bool tc_overlap(const void* p, size_t bytes, const void* q, size_t qbytes) {
-  const uintptr_t a = (uintptr_t)p, b = (uintptr_t)q;
-  return a < b + qbytes && b < a + bytes;
-}
-
 // What the four entries refuse, before any launch: 0 = go on, 1 = nothing to do (n == 0), < 0 = the refusal.
 // `out` has out_w floats per row, in0 / in1 (in1 may be absent: in1_w == 0) in0_w / in1_w; the kernels declare all three
 // __restrict__, so an output that shares a byte with an input is refused.
@@ -301,8 +296,8 @@ int tc_check(const void* out, int out_w, const void* in0, int in0_w, const void*
   if (!out || !in0 || (in1_w && !in1)) return FSG_E_BADARG;
   if ((long long)n * 12 > 0x7FFFFFFFLL) return FSG_E_TOOBIG;
   const size_t row = (size_t)n * sizeof(float);
-  if (tc_overlap(out, row * out_w, in0, row * in0_w)) return FSG_E_BADARG;
-  if (in1_w && tc_overlap(out, row * out_w, in1, row * in1_w)) return FSG_E_BADARG;
+  if (fsg_overlap(out, row * out_w, in0, row * in0_w)) return FSG_E_BADARG;
+  if (in1_w && fsg_overlap(out, row * out_w, in1, row * in1_w)) return FSG_E_BADARG;
   return 0;
 }
 

@@ -17,17 +17,9 @@ import math
 import torch
 
 from .... import kernels as K
+from ._solver import no_grad_inputs, prep
 
 DEFAULTS = dict(min_weight=0.5, n_em=5, c0=0.9, sigma_floor=0.04, slice_floor=0.025, min_pixels=4, level="slice")
-
-
-def _no_grad_inputs(**tensors):
-    if not torch.is_grad_enabled():
-        return
-    for name, t in tensors.items():
-        if isinstance(t, torch.Tensor) and t.requires_grad:
-            raise NotImplementedError(f"robust_weights is not differentiable: `{name}` requires grad.  Detach it, or call "
-                                      "under torch.no_grad()")
 
 
 def check_options(opts):
@@ -64,7 +56,7 @@ def robust_weights(slices, simulated, *, slices_mask=None, sim_weight=None, min_
     min_pixels: a slice with fewer pixels gets weight 0.  level: "slice" = the slice weight on every pixel of the slice, "both"
     = times the pixel posterior.  return_info: also the device histories sigma, c, mu1, mu2 (float64), frozen (int32), each
     n_em + 1 slots, ws (n_em + 1, n) and u (n)."""
-    _no_grad_inputs(slices=slices, simulated=simulated, sim_weight=sim_weight)
+    no_grad_inputs("robust_weights", slices=slices, simulated=simulated, sim_weight=sim_weight)
     o = check_options(dict(min_weight=min_weight, n_em=n_em, c0=c0, sigma_floor=sigma_floor, slice_floor=slice_floor,
                            min_pixels=min_pixels, level=level))
     K._need_gpu(slices, simulated)
@@ -72,12 +64,8 @@ def robust_weights(slices, simulated, *, slices_mask=None, sim_weight=None, min_
     h, w = (int(v) for v in slices.shape[-2:])
     n = int(slices.shape[0])
 
-    def prep(t, dtype=torch.float32):
-        if t is None or t.numel() == 0:
-            return None
-        return t.detach().to(device=dev, dtype=dtype).reshape(n, h, w).contiguous()
-
-    y, s, sm, wg = prep(slices), prep(simulated), prep(slices_mask, torch.bool), prep(sim_weight)
+    y, s, wg = (prep(t, (n, h, w), dev) for t in (slices, simulated, sim_weight))
+    sm = prep(slices_mask, (n, h, w), dev, torch.bool)
     st = K.robust_state(n, int(o["n_em"]), dev, (h, w))
     for t in range(st.n_em + 1):
         K.robust_estep(st, t, y, s, sm, wg, o["min_weight"])

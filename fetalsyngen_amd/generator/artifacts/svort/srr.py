@@ -35,16 +35,8 @@ import torch
 
 from .... import kernels as K
 from .... import rng as _rng
+from ._solver import no_grad_inputs, prep
 from .outlier import check_options as _robust_options, robust_weights
-
-
-def _no_grad_inputs(**tensors):
-    if not torch.is_grad_enabled():
-        return
-    for name, t in tensors.items():
-        if isinstance(t, torch.Tensor) and t.requires_grad:
-            raise NotImplementedError(f"srr is not differentiable: `{name}` requires grad.  Detach it, or call under "
-                                      "torch.no_grad(); gradients through the solve are not implemented")
 
 
 def srr(transforms, slices, psf, vol_shape, res_slice, *, interp_psf=False, slices_mask=None, vol_mask=None,
@@ -67,7 +59,7 @@ def srr(transforms, slices, psf, vol_shape, res_slice, *, interp_psf=False, slic
     the complete solve (all `n_outer` rounds) again from `x0`; the relu is applied in the very last solve only.  robust: a
     dict of `robust_weights`' options (n_em, c0, sigma_floor, slice_floor, min_pixels, level, min_weight).  With n_robust > 0
     the info dict gains "robust": the list of the EM histories, one dict per rejection round."""
-    _no_grad_inputs(transforms=transforms, slices=slices, psf=psf, slices_weight=slices_weight, x0=x0, z=z, guide=guide)
+    no_grad_inputs("srr", transforms=transforms, slices=slices, psf=psf, slices_weight=slices_weight, x0=x0, z=z, guide=guide)
     lam, n_outer = float(lam), int(n_outer)
     if not (math.isfinite(lam) and lam >= 0):
         raise ValueError(f"lam must be finite and >= 0, got {lam}")
@@ -97,20 +89,15 @@ def srr(transforms, slices, psf, vol_shape, res_slice, *, interp_psf=False, slic
     n = int(transforms.shape[0])
     nvox = D * H * W
 
-    def prep(t, shape, dtype=torch.float32):
-        if t is None or t.numel() == 0:
-            return None
-        return t.detach().to(device=dev, dtype=dtype).reshape(shape).contiguous()
-
-    tr = prep(transforms, (n, 3, 4))
-    ps = prep(psf, tuple(psf.shape))
-    y = prep(slices, (n, h, w))
-    sm = prep(slices_mask, (n, h, w), torch.bool)
-    vm = prep(vol_mask, (D, H, W), torch.bool)
-    wt = wt_given = prep(slices_weight, (n, h, w))
-    zz = prep(z, (D, H, W))
-    xs = prep(x0, (D, H, W))
-    gd = prep(guide, (D, H, W))
+    tr = prep(transforms, (n, 3, 4), dev)
+    ps = prep(psf, tuple(psf.shape), dev)
+    y = prep(slices, (n, h, w), dev)
+    sm = prep(slices_mask, (n, h, w), dev, torch.bool)
+    vm = prep(vol_mask, (D, H, W), dev, torch.bool)
+    wt = wt_given = prep(slices_weight, (n, h, w), dev)
+    zz = prep(z, (D, H, W), dev)
+    xs = prep(x0, (D, H, W), dev)
+    gd = prep(guide, (D, H, W), dev)
 
     def normal(v):
         """A^T P W A v"""

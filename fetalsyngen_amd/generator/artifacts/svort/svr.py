@@ -24,15 +24,7 @@ from __future__ import annotations
 import torch
 
 from .... import kernels as K
-
-
-def _no_grad_inputs(**tensors):
-    if not torch.is_grad_enabled():
-        return
-    for name, t in tensors.items():
-        if isinstance(t, torch.Tensor) and t.requires_grad:
-            raise NotImplementedError(f"svr is not differentiable: `{name}` requires grad.  Detach it, or call under "
-                                      "torch.no_grad(); gradients through the solve are not implemented")
+from ._solver import no_grad_inputs, prep
 
 
 def svr(poses, slices, vol, psf, res_slice, *, slices_mask=None, slices_weight=None, n_iter=10, lambda0=1e-3, factor=10.0,
@@ -51,24 +43,19 @@ def svr(poses, slices, vol, psf, res_slice, *, slices_mask=None, slices_weight=N
     the cost.  A slice with no pixel, no weight or non-finite sums keeps the pose it came with, bit for bit.
     return_info: also a dict of the device histories cost, lambda (float64), accepted, frozen (int32), each
     (n_iter + 1, n), row k for round k."""
-    _no_grad_inputs(poses=poses, slices=slices, vol=vol, psf=psf, slices_weight=slices_weight)
+    no_grad_inputs("svr", poses=poses, slices=slices, vol=vol, psf=psf, slices_weight=slices_weight)
     n_iter = int(n_iter)
     dev = slices.device
     h, w = (int(v) for v in slices.shape[-2:])
     D, H, W = (int(v) for v in vol.shape[-3:])
     n = int(poses.shape[0])
 
-    def prep(t, shape, dtype=torch.float32):
-        if t is None or t.numel() == 0:
-            return None
-        return t.detach().to(device=dev, dtype=dtype).reshape(shape).contiguous()
-
-    theta = prep(poses, (n, 6)).clone()  # the trial; overwritten by every update
-    ps = prep(psf, tuple(psf.shape))
-    y = prep(slices, (n, h, w))
-    x = prep(vol, (D, H, W))
-    sm = prep(slices_mask, (n, h, w), torch.bool)
-    wt = prep(slices_weight, (n, h, w))
+    theta = prep(poses, (n, 6), dev).clone()  # the trial; overwritten by every update
+    ps = prep(psf, tuple(psf.shape), dev)
+    y = prep(slices, (n, h, w), dev)
+    x = prep(vol, (D, H, W), dev)
+    sm = prep(slices_mask, (n, h, w), dev, torch.bool)
+    wt = prep(slices_weight, (n, h, w), dev)
 
     # everything the loop needs, made before it
     state = K.svr_state(n, n_iter, dev)
@@ -95,7 +82,7 @@ class SVR:
         self.n_iter, self.options = n_iter, options
 
     def __call__(self, transforms, slices, volume, psf, res_slice, slices_mask=None, slices_weight=None):
-        _no_grad_inputs(transforms=transforms)
+        no_grad_inputs("svr", transforms=transforms)
         mat = transforms.detach().to(device=slices.device, dtype=torch.float32).reshape(-1, 3, 4).contiguous()
         poses = svr(K.mat2axisangle(mat), slices, volume, psf, res_slice, slices_mask=slices_mask, slices_weight=slices_weight,
                     n_iter=self.n_iter, **self.options)

@@ -61,6 +61,76 @@ def _dims3(t):
     return int(t.shape[0]), int(t.shape[1]), int(t.shape[2])
 
 
+# ---- argument checks the slice-acquisition entries and the reconstruction solvers share ----
+def _mask(m, name, shape, device=None):
+    """A bool/uint8 contiguous device mask of `shape` (leading dimensions of 1 aside; an int: that many elements in any
+    shape), on `device` where one is given.  None stays None."""
+    if m is None:
+        return None
+    _need_gpu(m)
+    if m.dtype not in (torch.bool, torch.uint8):
+        raise TypeError(f"{name} must be bool/uint8, got {m.dtype}")
+    if isinstance(shape, int):
+        fits = m.numel() == shape
+    else:
+        fits = tuple(m.shape[-len(shape):]) == tuple(shape) and m.numel() == math.prod(shape)
+    if not fits:
+        raise ValueError(f"{name} shape {tuple(m.shape)} does not match {shape}")
+    _same_device(device, "its operands", (name, m))
+    return m
+
+
+def _same_device(device, what, *named):
+    """every (name, tensor or None) is on `device`, the device of `what` (None: nothing to hold them to)"""
+    for name, t in named:
+        if device is not None and t is not None and t.device != device:
+            raise ValueError(f"{name} is on {t.device}, {what} on {device}")
+
+
+def _nhw(t, name, n):
+    """`t` is (n,h,w); returns (h, w)"""
+    if t.dim() != 3 or int(t.shape[0]) != n:
+        raise ValueError(f"{name} must be (n,h,w) with n={n}, got {tuple(t.shape)}")
+    return int(t.shape[1]), int(t.shape[2])
+
+
+def _pow2_scale(v, name):
+    """the scale of a fixed-point accumulation: a power of two in [2^-20, 2^20]"""
+    m, e = math.frexp(float(v))
+    if m != 0.5 or not -20 <= e - 1 <= 20:
+        raise ValueError(f"{name} must be a power of two in [2^-20, 2^20], got {v!r}")
+
+
+class _StateBlock:
+    """A device block whose layout include/fsg_hip.h states: `buf` (int64, `nbytes` bytes as the library counts them) and one
+    attribute per field, a view of `buf`, carved in the header's order from a table of (name, dtype, shape)."""
+
+    def _carve(self, entry, args, device, fields):
+        self.nbytes = int(getattr(_lib.load(), entry)(*args))
+        self.buf = torch.empty(self.nbytes // 8, dtype=torch.int64, device=device)
+        raw, off = self.buf.view(torch.uint8), 0
+        for name, dtype, shape in fields:
+            size = math.prod(shape) * dtype.itemsize
+            setattr(self, name, raw[off:off + size].view(dtype).view(shape))
+            off += size
+        if (off + 7) // 8 * 8 != self.nbytes:
+            raise RuntimeError(f"{entry}{args} = {self.nbytes}, the layout of fsg_hip.h needs {off}")
+
+
+def _slice_count(n):
+    n = int(n)
+    if n < 1:
+        raise ValueError(f"n must be at least 1, got {n}")
+    return n
+
+
+def _iterations(name, v):
+    v = int(v)
+    if not 1 <= v <= _lib.SOLVER_MAX_ITER:
+        raise ValueError(f"{name} must be in 1..{_lib.SOLVER_MAX_ITER}, got {v}")
+    return v
+
+
 _DEV_TABLES: dict = {}  # (device, id(host table)) -> (device bytes, host table kept alive)
 _DEV_TABLES_MAX = 2048
 
@@ -665,15 +735,9 @@ def _sa_mode(semantics: str, interp_psf: bool) -> int:
     return SA_MODES["nearest_psf"] if interp_psf else SA_MODES["linear"]
 
 
-def _sa_mask(m, shape, name):
-    if m is None or m.numel() == 0:
-        return None
-    _need_gpu(m)
-    if m.dtype not in (torch.bool, torch.uint8):
-        raise TypeError(f"{name} must be bool/uint8, got {m.dtype}")
-    if tuple(m.shape[-len(shape):]) != tuple(shape) or m.numel() != int(np.prod(shape)):
-        raise ValueError(f"{name} shape {tuple(m.shape)} does not match {tuple(shape)}")
-    return m
+def _sa_mask(m, shape, name, device=None):
+    """`_mask`, for the entries whose callers hand an empty tensor for "no mask" as the reference's do"""
+    return None if m is None or m.numel() == 0 else _mask(m, name, tuple(shape), device)
 
 
 def _sa_common(transforms, psf):
@@ -713,18 +777,14 @@ def slice_acq_backward(transforms, vol, vol_mask, slices_mask, psf, grad_slices,
     order; grad_transforms has the same bits either way.  grad_scale: a power of two in [2^-20, 2^20] the contributions are
     divided by before they are quantised (1 for gradients of about unit size)."""
     if deterministic:
-        m, e = math.frexp(float(grad_scale))
-        if m != 0.5 or not -20 <= e - 1 <= 20:
-            raise ValueError(f"grad_scale must be a power of two in [2^-20, 2^20], got {grad_scale!r}")
+        _pow2_scale(grad_scale, "grad_scale")
     if not (need_vol_grad or need_transforms_grad):
         return None, None
     n, (pd, ph, pw) = _sa_common(transforms, psf)
     _need_gpu(vol, grad_slices)
     D, H, W = _dims3(_f32(vol, "vol"))
     _f32(grad_slices, "grad_slices")
-    if grad_slices.dim() != 3 or int(grad_slices.shape[0]) != n:
-        raise ValueError(f"grad_slices must be (n,h,w) with n={n}, got {tuple(grad_slices.shape)}")
-    h, w = int(grad_slices.shape[1]), int(grad_slices.shape[2])
+    h, w = _nhw(grad_slices, "grad_slices", n)
     vm, sm = _sa_mask(vol_mask, (D, H, W), "vol_mask"), _sa_mask(slices_mask, (n, h, w), "slices_mask")
     gvol = torch.empty((D, H, W), dtype=F32, device=vol.device) if need_vol_grad else None
     gtr = torch.empty((n, 3, 4), dtype=F32, device=vol.device) if need_transforms_grad else None
@@ -761,9 +821,7 @@ def slice_acq_adjoint_backward(transforms, grad_vol, psf, slices, slices_mask, v
     _need_gpu(grad_vol, slices)
     D, H, W = _dims3(_f32(grad_vol, "grad_vol"))
     _f32(slices, "slices")
-    if slices.dim() != 3 or int(slices.shape[0]) != n:
-        raise ValueError(f"slices must be (n,h,w) with n={n}, got {tuple(slices.shape)}")
-    h, w = int(slices.shape[1]), int(slices.shape[2])
+    h, w = _nhw(slices, "slices", n)
     vm, sm = _sa_mask(vol_mask, (D, H, W), "vol_mask"), _sa_mask(slices_mask, (n, h, w), "slices_mask")
     if equalize:
         _need_gpu(vol, vol_weight)
@@ -796,15 +854,12 @@ def slice_acq_adjoint(transforms, psf, slices, slices_mask, vol_mask, vol_shape,
     if deterministic and semantics == "torch":
         raise ValueError("the deterministic adjoint follows the CUDA semantics only (semantics='cuda')")
     if deterministic:
-        m, e = math.frexp(float(value_scale))
-        if m != 0.5 or not -20 <= e - 1 <= 20:
-            raise ValueError(f"value_scale must be a power of two in [2^-20, 2^20], got {value_scale!r}")
+        _pow2_scale(value_scale, "value_scale")
     n, (pd, ph, pw) = _sa_common(transforms, psf)
     _need_gpu(slices)
     _f32(slices, "slices")
     ns = int(slices.shape[0])
-    if slices.dim() != 3 or (slice_ids is None and ns != n):
-        raise ValueError(f"slices must be (n,h,w) with n={n}, got {tuple(slices.shape)}")
+    h, w = _nhw(slices, "slices", n if slice_ids is None else ns)
     if slice_ids is not None:
         # host tensor on purpose: the ids index device memory, so they are range-checked here before a kernel sees them
         if slice_ids.is_cuda or slice_ids.numel() != n:
@@ -813,7 +868,6 @@ def slice_acq_adjoint(transforms, psf, slices, slices_mask, vol_mask, vol_shape,
         if n and (int(ids.min()) < 0 or int(ids.max()) >= ns):
             raise IndexError(f"slice_ids out of range for {ns} slices")
         slice_ids = _upload(ids.to(torch.int32).contiguous(), slices.device)
-    h, w = int(slices.shape[1]), int(slices.shape[2])
     D, H, W = (int(v) for v in vol_shape)
     vm, sm = _sa_mask(vol_mask, (D, H, W), "vol_mask"), _sa_mask(slices_mask, (ns, h, w), "slices_mask")
     vol = torch.empty((D, H, W), dtype=F32, device=slices.device)
@@ -853,8 +907,7 @@ def _tc_same(n, m, a, b, ta, tb):
     """both tensors of a backward call: as many rows, and on ONE device (the output and the stream follow the second)"""
     if n != m:
         raise ValueError(f"{a} has {n} rows, {b} has {m}")
-    if ta.device != tb.device:
-        raise ValueError(f"{a} is on {ta.device}, {b} on {tb.device}")
+    _same_device(tb.device, b, (a, ta))
 
 
 def axisangle2mat(axisangle) -> torch.Tensor:
@@ -897,30 +950,19 @@ def mat2axisangle_backward(mat, grad_axisangle) -> torch.Tensor:
 
 # ---- conjugate gradients around the slice-acquisition operators (fsg_cg.hip) ------------------------------------
 CG_RELU = _lib.CG_RELU
-CG_MAX_ITER = 4096
+CG_MAX_ITER = _lib.SOLVER_MAX_ITER
 
 
-class CGWorkspace:
+class CGWorkspace(_StateBlock):
     """The device block of a solve's scalars (include/fsg_hip.h, fsg_cg_*): `buf` (int64) and, as views of it, the histories
     rr, pq (float64), alpha, beta (float32), frozen (int32), each of n_iter + 1 slots indexed by iteration."""
 
     def __init__(self, n: int, n_iter: int, device):
-        n, n_iter = int(n), int(n_iter)
-        if not 1 <= n_iter <= CG_MAX_ITER:
-            raise ValueError(f"n_iter must be in 1..{CG_MAX_ITER}, got {n_iter}")
-        self.n, self.n_iter = n, n_iter
-        self.nbytes = int(_lib.load().fsg_cg_ws_bytes(n, n_iter))
-        self.buf = torch.empty(self.nbytes // 8, dtype=torch.int64, device=device)
-        s, b = n_iter + 1, min(max((n + 1023) // 1024, 1), 1024)
-        raw, off = self.buf.view(torch.uint8), 0
-        for name, dtype, count in (("rr", torch.float64, s), ("pq", torch.float64, s), ("partial_rr", torch.float64, b),
-                                   ("partial_pq", torch.float64, b), ("alpha", F32, s), ("beta", F32, s),
-                                   ("frozen", torch.int32, s)):
-            size = count * torch.empty((), dtype=dtype).element_size()
-            setattr(self, name, raw[off:off + size].view(dtype))
-            off += size
-        if (off + 7) // 8 * 8 != self.nbytes:
-            raise RuntimeError(f"fsg_cg_ws_bytes({n}, {n_iter}) = {self.nbytes}, the layout of fsg_hip.h needs {off}")
+        self.n, self.n_iter = n, n_iter = int(n), _iterations("n_iter", n_iter)
+        s, b = (n_iter + 1,), (min(max((n + 1023) // 1024, 1), 1024),)
+        self._carve("fsg_cg_ws_bytes", (n, n_iter), device,
+                    (("rr", torch.float64, s), ("pq", torch.float64, s), ("partial_rr", torch.float64, b),
+                     ("partial_pq", torch.float64, b), ("alpha", F32, s), ("beta", F32, s), ("frozen", torch.int32, s)))
 
     def info(self):
         return {k: getattr(self, k) for k in ("rr", "pq", "alpha", "beta", "frozen")}
@@ -939,19 +981,11 @@ def _cg_vectors(ws, *named):
         _f32(t, name)
         if t.numel() != ws.n:
             raise ValueError(f"{name} has {t.numel()} elements, the workspace was made for {ws.n}")
-        if t.device != ws.buf.device:
-            raise ValueError(f"{name} is on {t.device}, the workspace on {ws.buf.device}")
+    _same_device(ws.buf.device, "the workspace", *named)
 
 
 def _cg_mask(ws, mask):
-    if mask is None:
-        return None
-    _need_gpu(mask)
-    if mask.dtype not in (torch.bool, torch.uint8):
-        raise TypeError(f"mask must be bool/uint8, got {mask.dtype}")
-    if mask.numel() != ws.n or mask.device != ws.buf.device:
-        raise ValueError(f"mask must have {ws.n} elements on {ws.buf.device}")
-    return mask
+    return _mask(mask, "mask", ws.n, ws.buf.device)
 
 
 def cg_init(ws: CGWorkspace, b, r, p, x, mask=None, mu=0.0, z=None, x0=None, t0=None):
@@ -1005,14 +1039,8 @@ def tk1_apply(p, t, shape, lam, mask=None, guide=None, delta=None, out=None):
         _f32(v, name)
         if v.numel() != n:
             raise ValueError(f"{name} has {v.numel()} elements, shape {(D, H, W)} has {n}")
-        if v.device != p.device:
-            raise ValueError(f"{name} is on {v.device}, p on {p.device}")
-    if mask is not None:
-        _need_gpu(mask)
-        if mask.dtype not in (torch.bool, torch.uint8):
-            raise TypeError(f"mask must be bool/uint8, got {mask.dtype}")
-        if mask.numel() != n or mask.device != p.device or not mask.is_contiguous():
-            raise ValueError(f"mask must be contiguous with {n} elements on {p.device}")
+    _same_device(p.device, "p", ("t", t), ("guide", guide), ("out", out))
+    mask = _mask(mask, "mask", n, p.device)
     if (guide is None) != (delta is None):
         raise ValueError("guide and delta are given together")
     rc = _lib.load().fsg_tk1_apply_f32(_p(p), _p(t), _p(mask), _p(guide), 0.0 if delta is None else float(delta), float(lam),
@@ -1022,8 +1050,8 @@ def tk1_apply(p, t, shape, lam, mask=None, guide=None, delta=None, out=None):
 
 
 # ---- per-slice Levenberg-Marquardt slice-to-volume registration (fsg_svr.hip) -----------------------------------
-SVR_MAX_ITER = 4096
-SVR_SLOTS = 32  # doubles per slice in `stats`: H (21, upper triangle), g (6), sum w e^2, sum w, m, two zeros
+SVR_MAX_ITER = _lib.SOLVER_MAX_ITER
+SVR_SLOTS = _lib.SVR_SLOTS  # doubles per slice in `stats`: H (21, upper triangle), g (6), sum w e^2, sum w, m, two zeros
 
 
 def svr_ws_bytes(n: int, h: int, w: int) -> int:
@@ -1042,9 +1070,7 @@ def svr_normal(transforms, jac, vol, psf, slices, slices_mask, slices_weight, re
     _f32(jac, "jac"), _f32(slices, "slices")
     if tuple(jac.shape) != (n, 12, 6):
         raise ValueError(f"jac must be (n,12,6) with n={n}, got {tuple(jac.shape)}")
-    if slices.dim() != 3 or int(slices.shape[0]) != n:
-        raise ValueError(f"slices must be (n,h,w) with n={n}, got {tuple(slices.shape)}")
-    h, w = int(slices.shape[1]), int(slices.shape[2])
+    h, w = _nhw(slices, "slices", n)
     sm = _sa_mask(slices_mask, (n, h, w), "slices_mask")
     if slices_weight is not None:
         _f32(slices_weight, "slices_weight")
@@ -1052,10 +1078,8 @@ def svr_normal(transforms, jac, vol, psf, slices, slices_mask, slices_weight, re
             raise ValueError(f"slices_weight shape {tuple(slices_weight.shape)} does not match {(n, h, w)}")
     if not float(min_weight) >= 0.0:
         raise ValueError(f"min_weight must be >= 0, got {min_weight!r}")
-    for t, name in ((jac, "jac"), (slices, "slices"), (psf, "psf"), (transforms, "transforms"), (sm, "slices_mask"),
-                    (slices_weight, "slices_weight"), (out, "out"), (ws, "ws")):
-        if t is not None and t.device != vol.device:
-            raise ValueError(f"{name} is on {t.device}, vol on {vol.device}")
+    _same_device(vol.device, "vol", ("jac", jac), ("slices", slices), ("psf", psf), ("transforms", transforms),
+                 ("slices_mask", sm), ("slices_weight", slices_weight), ("out", out), ("ws", ws))
     need = svr_ws_bytes(n, h, w)
     if ws is None:
         ws = torch.empty(need // 8, dtype=torch.int64, device=vol.device)  # 128 bytes per tile
@@ -1072,32 +1096,18 @@ def svr_normal(transforms, jac, vol, psf, slices, slices_mask, slices_weight, re
     return out
 
 
-class SVRState:
+class SVRState(_StateBlock):
     """The device block of a registration's per-slice state (include/fsg_hip.h, fsg_svr_update_f32): `buf` (int64) and, as views
     of it, stats_cur (n,32), lam (n), m0 (n) float64, theta_cur (n,6) float32, frozen_now (n) int32 and the histories cost,
     lambda (float64), accepted, frozen (int32), each (n_iter + 1, n), row k for iteration slot k."""
 
     def __init__(self, n: int, n_iter: int, device):
-        n, n_iter = int(n), int(n_iter)
-        if n < 1:
-            raise ValueError(f"n must be at least 1, got {n}")
-        if not 1 <= n_iter <= SVR_MAX_ITER:
-            raise ValueError(f"n_iter must be in 1..{SVR_MAX_ITER}, got {n_iter}")
-        self.n, self.n_iter = n, n_iter
-        self.nbytes = int(_lib.load().fsg_svr_state_bytes(n, n_iter))
-        self.buf = torch.empty(self.nbytes // 8, dtype=torch.int64, device=device)
+        self.n, self.n_iter = n, n_iter = _slice_count(n), _iterations("n_iter", n_iter)
         s = n_iter + 1
-        raw, off = self.buf.view(torch.uint8), 0
-        for name, dtype, shape in (("stats_cur", torch.float64, (n, SVR_SLOTS)), ("lam", torch.float64, (n,)),
-                                   ("m0", torch.float64, (n,)), ("cost", torch.float64, (s, n)),
-                                   ("lambda_hist", torch.float64, (s, n)), ("theta_cur", F32, (n, 6)),
-                                   ("frozen_now", torch.int32, (n,)), ("accepted", torch.int32, (s, n)),
-                                   ("frozen", torch.int32, (s, n))):
-            size = int(np.prod(shape)) * torch.empty((), dtype=dtype).element_size()
-            setattr(self, name, raw[off:off + size].view(dtype).view(shape))
-            off += size
-        if (off + 7) // 8 * 8 != self.nbytes:
-            raise RuntimeError(f"fsg_svr_state_bytes({n}, {n_iter}) = {self.nbytes}, the layout of fsg_hip.h needs {off}")
+        self._carve("fsg_svr_state_bytes", (n, n_iter), device,
+                    (("stats_cur", torch.float64, (n, SVR_SLOTS)), ("lam", torch.float64, (n,)), ("m0", torch.float64, (n,)),
+                     ("cost", torch.float64, (s, n)), ("lambda_hist", torch.float64, (s, n)), ("theta_cur", F32, (n, 6)),
+                     ("frozen_now", torch.int32, (n,)), ("accepted", torch.int32, (s, n)), ("frozen", torch.int32, (s, n))))
 
     def info(self):
         return {"cost": self.cost, "lambda": self.lambda_hist, "accepted": self.accepted, "frozen": self.frozen}
@@ -1118,9 +1128,7 @@ def svr_update(state: SVRState, k: int, stats_trial, theta_trial, lambda0=1e-3, 
         raise ValueError(f"stats_trial must be float64 ({state.n},{SVR_SLOTS}), got {stats_trial.dtype} {tuple(stats_trial.shape)}")
     if tuple(theta_trial.shape) != (state.n, 6):
         raise ValueError(f"theta_trial must be ({state.n},6), got {tuple(theta_trial.shape)}")
-    for t, name in ((stats_trial, "stats_trial"), (theta_trial, "theta_trial")):
-        if t.device != state.buf.device:
-            raise ValueError(f"{name} is on {t.device}, the state on {state.buf.device}")
+    _same_device(state.buf.device, "the state", ("stats_trial", stats_trial), ("theta_trial", theta_trial))
     rc = _lib.load().fsg_svr_update_f32(_p(stats_trial), _p(theta_trial), _p(state.buf), state.nbytes, state.n, int(k),
                                         state.n_iter, float(lambda0), float(factor), float(lambda_min), float(lambda_max),
                                         float(min_overlap), float(tol), _stream(theta_trial))
@@ -1128,37 +1136,25 @@ def svr_update(state: SVRState, k: int, stats_trial, theta_trial, lambda0=1e-3, 
 
 
 # ---- outlier weights: robust-statistics EM over the residual of a reconstruction (fsg_robust.hip) -----------------
-ROBUST_MAX_EM = 4096
+ROBUST_MAX_EM = _lib.SOLVER_MAX_ITER
 ROBUST_LEVELS = {"slice": _lib.ROBUST_SLICE, "both": _lib.ROBUST_BOTH}
-ROBUST_ROW = 6  # doubles of a slice's row: N, sum p, sum p e^2, sum (1-p)^2, min y, max y
+ROBUST_ROW = _lib.ROBUST_ROW  # doubles of a slice's row: N, sum p, sum p e^2, sum (1-p)^2, min y, max y
 
 
-class RobustState:
+class RobustState(_StateBlock):
     """The device blocks of one EM (include/fsg_hip.h, fsg_robust_*): `buf` (int64), the state, and as views of it consts (4:
     R, m, sigma_min, 0), rows (n,6), u (n), the histories sigma, c, mu1, mu2 (float64), frozen (int32), each of n_em + 1 slots,
     ws (n_em + 1, n) float64 and scal (2 float32: kappa, inv2var); `part` (int64) is the workspace of the per-workgroup
     partials for (h, w) slices."""
 
     def __init__(self, n: int, n_em: int, device, slice_shape=None):
-        n, n_em = int(n), int(n_em)
-        if n < 1:
-            raise ValueError(f"n must be at least 1, got {n}")
-        if not 1 <= n_em <= ROBUST_MAX_EM:
-            raise ValueError(f"n_em must be in 1..{ROBUST_MAX_EM}, got {n_em}")
-        self.n, self.n_em = n, n_em
-        self.nbytes = int(_lib.load().fsg_robust_state_bytes(n, n_em))
-        self.buf = torch.empty(self.nbytes // 8, dtype=torch.int64, device=device)
+        self.n, self.n_em = n, n_em = _slice_count(n), _iterations("n_em", n_em)
         s = n_em + 1
-        raw, off = self.buf.view(torch.uint8), 0
-        for name, dtype, shape in (("consts", torch.float64, (4,)), ("rows", torch.float64, (n, ROBUST_ROW)),
-                                   ("u", torch.float64, (n,)), ("sigma", torch.float64, (s,)), ("c", torch.float64, (s,)),
-                                   ("mu1", torch.float64, (s,)), ("mu2", torch.float64, (s,)), ("ws", torch.float64, (s, n)),
-                                   ("scal", F32, (2,)), ("frozen", torch.int32, (s,))):
-            size = int(np.prod(shape)) * torch.empty((), dtype=dtype).element_size()
-            setattr(self, name, raw[off:off + size].view(dtype).view(shape))
-            off += size
-        if (off + 7) // 8 * 8 != self.nbytes:
-            raise RuntimeError(f"fsg_robust_state_bytes({n}, {n_em}) = {self.nbytes}, the layout of fsg_hip.h needs {off}")
+        self._carve("fsg_robust_state_bytes", (n, n_em), device,
+                    (("consts", torch.float64, (4,)), ("rows", torch.float64, (n, ROBUST_ROW)), ("u", torch.float64, (n,)),
+                     ("sigma", torch.float64, (s,)), ("c", torch.float64, (s,)), ("mu1", torch.float64, (s,)),
+                     ("mu2", torch.float64, (s,)), ("ws", torch.float64, (s, n)), ("scal", F32, (2,)),
+                     ("frozen", torch.int32, (s,))))
         self.part, self.slice_shape = None, None
         if slice_shape is not None:
             self.reserve(slice_shape)
@@ -1185,20 +1181,16 @@ def robust_state(n: int, n_em: int, device, slice_shape=None) -> RobustState:
 def _robust_pixels(state, y, s, slices_mask, sim_weight, min_weight, out=None):
     """(n,h,w) fp32 contiguous device arrays on the state's device -> (h, w, mask as bytes)"""
     _need_gpu(y, s, slices_mask, sim_weight, out)
-    if y.dim() != 3 or int(y.shape[0]) != state.n:
-        raise ValueError(f"slices must be (n,h,w) with n={state.n}, got {tuple(y.shape)}")
-    shape = tuple(int(v) for v in y.shape)
-    for name, v in (("slices", y), ("simulated", s), ("sim_weight", sim_weight), ("out", out)):
+    shape = (state.n, *_nhw(y, "slices", state.n))
+    named = (("slices", y), ("simulated", s), ("sim_weight", sim_weight), ("out", out))
+    for name, v in named:
         if v is None:
             continue
         _f32(v, name)
         if tuple(v.shape) != shape:
             raise ValueError(f"{name} shape {tuple(v.shape)} does not match {shape}")
-        if v.device != state.buf.device:
-            raise ValueError(f"{name} is on {v.device}, the state on {state.buf.device}")
-    sm = _sa_mask(slices_mask, shape, "slices_mask")
-    if sm is not None and sm.device != state.buf.device:
-        raise ValueError(f"slices_mask is on {sm.device}, the state on {state.buf.device}")
+    _same_device(state.buf.device, "the state", *named)
+    sm = _sa_mask(slices_mask, shape, "slices_mask", state.buf.device)
     if not float(min_weight) >= 0.0:
         raise ValueError(f"min_weight must be >= 0, got {min_weight!r}")
     return shape[1], shape[2], sm

@@ -551,7 +551,7 @@ int fsg_mat2axisangle_backward_f32(const float* mat /*(n,12)*/, const float* gra
  * Element-wise arithmetic is fp32, one rounding per operation (no contraction); V is a selection (a masked element is +0).
  * Scalars: ws holds, 8-byte aligned and in this order, with s = K + 1 and B = clamp(ceil(n / 1024), 1, 1024):
  *     double rr[s], double pq[s], double partial_rr[B], double partial_pq[B], float alpha[s], float beta[s], int32 frozen[s]
- * = fsg_cg_ws_bytes(n, K) bytes (rounded up to 8; 0 for K outside 1..4096).  Slot k belongs to iteration k (slot 0 of pq, alpha,
+ * = fsg_cg_ws_bytes(n, K) bytes (rounded up to 8; 0 for K outside 1..FSG_SOLVER_MAX_ITER).  Slot k belongs to iteration k (slot 0 of pq, alpha,
  * beta is 0).  It needs no initialisation: q(1) writes rr[0], frozen[0] and the zero slots, step(k) writes pq[k] and alpha[k], dir(k) writes
  * rr[k], beta[k] and frozen[k], each from workgroup 0; a launch reads only slots and partials that an EARLIER launch wrote.
  * Dot products <r,r> and <p,q>: every launch has B workgroups of 256 threads.  Elements are dealt in groups of four: group
@@ -569,11 +569,12 @@ int fsg_mat2axisangle_backward_f32(const float* mat /*(n,12)*/, const float* gra
  * as the only thing the launch does when the solve is frozen by then.  For k < K the flag is ignored.
  * Loads and stores are 16 bytes per lane when every float pointer of the call is 16-byte aligned and mask is 4-byte aligned;
  * otherwise scalars, same values and same sums.
- * Refusals, all before any launch and with nothing written: K outside 1..4096 or k outside 1..K (FSG_E_BADARG); n == 0 is
+ * Refusals, all before any launch and with nothing written: K outside 1..FSG_SOLVER_MAX_ITER or k outside 1..K (FSG_E_BADARG); n == 0 is
  * success without a launch; a null vector or ws with n > 0, x0 without t0, ws_bytes < fsg_cg_ws_bytes(n, K), an unknown flag
  * (FSG_E_BADARG); ws not 8-byte aligned (FSG_E_ALIGN); an output that shares a byte with an input, another output or ws
  * (FSG_E_BADARG; q over t is the one in-place pair). */
 #define FSG_CG_RELU 1
+#define FSG_SOLVER_MAX_ITER 4096 /* the most iterations of one solve: K of fsg_cg_* and fsg_svr_update_f32, T of fsg_robust_* */
 size_t fsg_cg_ws_bytes(size_t n, int n_iter);
 int fsg_cg_init_f32(const float* b, const float* z, const float* t0, const float* x0, const uint8_t* mask, float mu, size_t n,
                     int n_iter, float* r, float* p, float* x, void* ws, size_t ws_bytes, void* stream);
@@ -613,7 +614,7 @@ int fsg_tk1_apply_f32(const float* p, const float* t, const uint8_t* mask, const
  *   transforms (n,12), jac (n,12,6): row k of a slice = the derivative of transform entry k with respect to the 6 pose
  *   parameters; vol (D,H,W); psf (pd,ph,pw), limits as the forward; slices (n,h,w) = y; slices_mask (n,h,w) bytes or NULL;
  *   slices_weight (n,h,w) non-negative or NULL (w = 1); min_weight >= 0 (negative or NaN: FSG_E_BADARG).
- *   stats (n,32) DOUBLE, 8-byte aligned: [0..20] H = sum w J J^T, upper triangle row-major (00 01 .. 05 11 12 .. 55);
+ *   stats (n,32) DOUBLE (a row is FSG_SVR_SLOTS wide), 8-byte aligned: [0..20] H = sum w J J^T, upper triangle row-major (00 01 .. 05 11 12 .. 55);
  *   [21..26] g = sum w e J; [27] sum w e^2; [28] sum w; [29] m, the number of pixels that took part; [30], [31] = 0.
  * Per pixel inside slices_mask:
  *   pass 1  weight = the raw PSF sum over the non-zero taps with 0 <= p < size - 1 on every axis, exactly as
@@ -638,7 +639,7 @@ int fsg_tk1_apply_f32(const float* p, const float* t, const uint8_t* mask, const
  *
  * fsg_svr_update_f32: the damped step and the accept / reject decision for slot k of 0..K, one thread per slice, double
  * arithmetic with + - * / only and no contraction.  `state` is a DEVICE block of fsg_svr_state_bytes(n, K) bytes (0 for n < 1
- * or K outside 1..4096), 8-byte aligned, in this order with s = K + 1:
+ * or K outside 1..FSG_SOLVER_MAX_ITER), 8-byte aligned, in this order with s = K + 1:
  *     double stats_cur[n][32], double lambda[n], double m0[n], double cost[s][n], double lambda_hist[s][n],
  *     float theta_cur[n][6], int32 frozen[n], int32 accepted[s][n], int32 frozen_hist[s][n]
  * rounded up to 8 bytes.  It needs no initialisation: update(0) writes every per-slice field, update(k) row k of the histories.
@@ -658,10 +659,11 @@ int fsg_tk1_apply_f32(const float* p, const float* t, const uint8_t* mask, const
  *           A frozen slice, or k = K: theta_trial = theta_cur, so every later launch runs on valid data.
  *   histories, row k: cost[k] = the cost of cur after the decision, lambda_hist[k], accepted[k] (0 for k = 0), frozen_hist[k]
  *           (after the pivot test).
- * Refusals, before any launch and with nothing written: n < 1, K outside 1..4096, k outside 0..K, a null pointer, a short
+ * Refusals, before any launch and with nothing written: n < 1, K outside 1..FSG_SOLVER_MAX_ITER, k outside 0..K, a null pointer, a short
  * state, !(lambda0 > 0), !(factor > 1), !(lambda_min > 0), !(lambda_max >= lambda_min), !(min_overlap >= 0), !(tol >= 0)
  * (FSG_E_BADARG); state or stats_trial not 8-byte aligned, theta_trial not 4-byte aligned (FSG_E_ALIGN); state, stats_trial
  * and theta_trial sharing a byte (FSG_E_BADARG). */
+#define FSG_SVR_SLOTS 32 /* doubles of a slice's row of stats, floats of a tile's partial: the 30 sums and two zeros */
 size_t fsg_svr_ws_bytes(int n, int h, int w);
 int fsg_svr_normal_f32(const float* transforms, const float* jac, const float* vol, const float* psf, int pd, int ph, int pw,
                        const float* slices, const uint8_t* slices_mask, const float* slices_weight, double* stats, int D, int H,
@@ -712,7 +714,7 @@ int fsg_svr_update_f32(const double* stats_trial, float* theta_trial, void* stat
  *   freeze     R == 0 or not finite, Nw == 0, S0 == 0, var == 0 or any scalar above not finite: the solve is frozen from this
  *              slot on.  Frozen: ws[t][k] = 1 for every ok slice, kappa = inv2var = 0 (so p = 1), sigma, c, mu1, mu2 of the
  *              slot are 0, frozen[t] = 1, and every later slot repeats this.  No NaN is ever stored.
- * state: one DEVICE block of fsg_robust_state_bytes(n, T) bytes (0 for n < 1 or T outside 1..4096), 8-byte aligned, in this
+ * state: one DEVICE block of fsg_robust_state_bytes(n, T) bytes (0 for n < 1 or T outside 1..FSG_SOLVER_MAX_ITER), 8-byte aligned, in this
  * order with s = T + 1:
  *     double consts[4] (R, m, sigma_min, 0), double rows[n][6] (N, sum p, sum p e2, sum q^2, min y, max y: the LAST estep's),
  *     double u[n], double sigma[s], double c[s], double mu1[s], double mu2[s], double ws[s][n], float kappa, float inv2var,
@@ -726,13 +728,14 @@ int fsg_svr_update_f32(const double* stats_trial, float* theta_trial, void* stat
  * Determinism: no atomics and every order fixed, so the same bits in any run and on any stream.  sigma and c are GLOBAL sums
  * in slice-index order, so permuting the slices permutes the result only up to rounding (unlike fsg_svr_normal_f32, whose
  * rows do not see the other slices).
- * Refusals, all before any launch and with nothing written: n, h or w < 1, T outside 1..4096, t outside 0..T, a null y, s,
+ * Refusals, all before any launch and with nothing written: n, h or w < 1, T outside 1..FSG_SOLVER_MAX_ITER, t outside 0..T, a null y, s,
  * state, ws or out, a short state or ws, min_weight negative or NaN, c0 outside (0, 1] or NaN, sigma_floor or slice_floor
  * negative, NaN or Inf, min_pixels < 0, an unknown level (FSG_E_BADARG); n > 65535 or n * h * w > 2^31 - 1 (FSG_E_TOOBIG);
  * state or ws not 8-byte aligned, a float pointer not 4-byte aligned (FSG_E_ALIGN); ws sharing a byte with an input or the
  * state, out sharing a byte with an input or the state (FSG_E_BADARG). */
 #define FSG_ROBUST_SLICE 0
 #define FSG_ROBUST_BOTH 1
+#define FSG_ROBUST_ROW 6 /* doubles of a slice's entry of rows[n][6] in the state */
 size_t fsg_robust_ws_bytes(int n, int h, int w);
 size_t fsg_robust_state_bytes(int n, int n_em);
 int fsg_robust_estep_f32(const float* y, const float* s, const uint8_t* slices_mask, const float* sim_weight, float min_weight,

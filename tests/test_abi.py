@@ -209,3 +209,59 @@ def test_no_restated_header_numbers():
     for rel in ("fetalsyngen_amd/generator/model.py", "fetalsyngen_amd/keyed.py", "tools/host_phases.py"):
         hits = [ln for ln in (REPO / rel).read_text().splitlines() if slot.search(ln)]
         assert not hits, f"{rel}: {hits[:3]}"
+    # the solvers' iteration cap and row widths are the header's: kernels.py binds its names to them and restates no number
+    kernels = (REPO / "fetalsyngen_amd" / "kernels.py").read_text().splitlines()
+    bare = re.compile(r"\b\w*(MAX_ITER|MAX_EM|SLOTS|ROW)\s*=\s*\d")
+    hits = [ln for ln in kernels if bare.search(ln) or ("4096" in ln and "_DT_CACHE" not in ln)]
+    assert not hits, f"fetalsyngen_amd/kernels.py: {hits[:3]}"
+    # one overlap test and one finite test for every unit
+    csrc = "".join(p.read_text() for p in sorted((REPO / "fetalsyngen_amd" / "csrc").iterdir()))
+    for name in ("_overlap(", "_finite("):
+        defs = re.findall(r"^[\w \t]*\bbool\s+(\w*" + re.escape(name[:-1]) + r")\(", csrc, flags=re.M)
+        assert defs == ["fsg" + name[:-1]], f"{name} is defined as {defs}"
+
+
+def test_solver_constants_are_the_headers():
+    from fetalsyngen_amd import kernels as K
+
+    assert (_lib.SOLVER_MAX_ITER, _lib.SVR_SLOTS, _lib.ROBUST_ROW) == (4096, 32, 6)  # the contracts' figures
+    assert K.CG_MAX_ITER == K.SVR_MAX_ITER == K.ROBUST_MAX_EM == _lib.SOLVER_MAX_ITER
+    assert K.SVR_SLOTS == _lib.SVR_SLOTS and K.ROBUST_ROW == _lib.ROBUST_ROW
+
+
+# the layout paragraphs of include/fsg_hip.h, field by field in their order: (attribute, dtype name, shape); s = iterations + 1
+def _cg_fields(n, k):
+    s, b = k + 1, min(max(-(-n // 1024), 1), 1024)
+    return [("rr", "float64", (s,)), ("pq", "float64", (s,)), ("partial_rr", "float64", (b,)), ("partial_pq", "float64", (b,)),
+            ("alpha", "float32", (s,)), ("beta", "float32", (s,)), ("frozen", "int32", (s,))]
+
+
+def _svr_fields(n, k):
+    s = k + 1
+    return [("stats_cur", "float64", (n, 32)), ("lam", "float64", (n,)), ("m0", "float64", (n,)), ("cost", "float64", (s, n)),
+            ("lambda_hist", "float64", (s, n)), ("theta_cur", "float32", (n, 6)), ("frozen_now", "int32", (n,)),
+            ("accepted", "int32", (s, n)), ("frozen", "int32", (s, n))]
+
+
+def _robust_fields(n, t):
+    s = t + 1
+    return [("consts", "float64", (4,)), ("rows", "float64", (n, 6)), ("u", "float64", (n,)), ("sigma", "float64", (s,)),
+            ("c", "float64", (s,)), ("mu1", "float64", (s,)), ("mu2", "float64", (s,)), ("ws", "float64", (s, n)),
+            ("scal", "float32", (2,)), ("frozen", "int32", (s,))]
+
+
+@pytest.mark.parametrize("make,fields,n,k", [("cg_workspace", _cg_fields, 2049, 4), ("svr_state", _svr_fields, 5, 3),
+                                             ("robust_state", _robust_fields, 3, 4)])
+def test_state_views_tile_the_block_in_the_headers_order(make, fields, n, k):
+    """on the host (the classes take device="cpu"): the views follow one another from byte 0 of `buf` with no gap and no
+    overlap, and end within the rounding to 8 of the size the library counts"""
+    from fetalsyngen_amd import kernels as K
+
+    st = getattr(K, make)(n, k, "cpu")
+    off = 0
+    for name, dtype, shape in fields(n, k):
+        v = getattr(st, name)
+        assert (str(v.dtype), tuple(v.shape)) == ("torch." + dtype, shape) and v.is_contiguous(), name
+        assert v.data_ptr() - st.buf.data_ptr() == off, name
+        off += v.numel() * v.element_size()
+    assert -(-off // 8) * 8 == st.nbytes == st.buf.numel() * st.buf.element_size()

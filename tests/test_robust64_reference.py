@@ -320,6 +320,18 @@ def test_entries_refuse_before_any_launch():
     assert _weights(lib, out=(7 << 24) + 2) == ALIGN
 
 
+@pytest.mark.parametrize("T", (1, 2, 12, 4096))
+@pytest.mark.parametrize("n", (1, 5, 1024, 1025))
+def test_state_bytes_is_the_headers_formula(n, T):
+    """fsg_robust_state_bytes against the layout paragraph of include/fsg_hip.h, written out; s = T + 1 takes both parities,
+    so the rounding to 8 is exercised"""
+    from fetalsyngen_amd import _lib
+
+    lib, s = _lib.load(), T + 1
+    assert lib.fsg_robust_state_bytes(n, T) == (8 * (4 + 6 * n + n + 4 * s + s * n) + 4 * (2 + s) + 7) // 8 * 8
+    assert lib.fsg_robust_state_bytes(n, 0) == 0 and lib.fsg_robust_state_bytes(n, 4096 + 1) == 0
+
+
 def test_front_ends_refuse_cpu_tensors_and_bad_arguments():
     import torch
 

@@ -310,6 +310,19 @@ def test_entries_refuse_before_any_launch():
             assert _calls(lib, n, 1, K, ws, need, ptrs=ptrs)[name]() == _lib.E_BADARG, (name, out, "ws")
 
 
+@pytest.mark.parametrize("K", (1, 2, 12, 4096))
+@pytest.mark.parametrize("n", (1, 5, 1024, 1025, 2**20 + 1, 2**20 + 1025))
+def test_ws_bytes_is_the_headers_formula(n, K):
+    """fsg_cg_ws_bytes against the layout paragraph of include/fsg_hip.h, written out: rr, pq (double[s]), the two partial
+    arrays (double[B]), alpha, beta, frozen (4 bytes, [s]), rounded up to 8; s = K + 1 takes both parities, B its clamp"""
+    from fetalsyngen_amd import _lib
+
+    s, B = K + 1, min(max(-(-n // 1024), 1), 1024)
+    assert B == (1024 if n > 2**20 else {1: 1, 5: 1, 1024: 1, 1025: 2}[n])
+    assert _lib.load().fsg_cg_ws_bytes(n, K) == -(-(16 * s + 16 * B + 12 * s) // 8) * 8
+    assert _lib.load().fsg_cg_ws_bytes(n, 0) == 0 and _lib.load().fsg_cg_ws_bytes(n, 4096 + 1) == 0
+
+
 def test_front_ends_refuse_cpu_tensors():
     import torch
 

@@ -303,6 +303,18 @@ def test_entries_refuse_before_any_launch():
         assert _update_call(lib, **kw) == ALIGN, kw
 
 
+@pytest.mark.parametrize("K", (1, 2, 12, 4096))
+@pytest.mark.parametrize("n", (1, 5, 1024, 1025))
+def test_state_bytes_is_the_headers_formula(n, K):
+    """fsg_svr_state_bytes against the layout paragraph of include/fsg_hip.h, written out; s = K + 1 and n take both parities,
+    so the rounding to 8 is exercised"""
+    from fetalsyngen_amd import _lib
+
+    lib, s = _lib.load(), K + 1
+    assert lib.fsg_svr_state_bytes(n, K) == (8 * (32 * n + 2 * n + 2 * s * n) + 4 * (6 * n + n + 2 * s * n) + 7) // 8 * 8
+    assert lib.fsg_svr_state_bytes(n, 0) == 0 and lib.fsg_svr_state_bytes(n, 4096 + 1) == 0
+
+
 def test_front_ends_refuse_cpu_tensors_and_bad_arguments():
     import torch
 
