@@ -79,6 +79,41 @@ __device__ __forceinline__ float fsg_wave_max(float v) {
   return v;
 }
 
+// The fold of the streaming pixel passes (fsg_robust.hip, fsg_imatch.hip): every thread of the THREADS-wide workgroup calls it
+// with its NS sums and its min / max (a thread without a pixel carries zeros, +Inf and -Inf).  Lanes of a wave: a fixed
+// shuffle-down tree; waves: LDS (`red`), combined in wave order; one partial of SLOTS floats at `out`: the NS sums, min, max,
+// then zeros.  All SLOTS are stored, so the workspace needs no zeroing.
+template <int NS, int SLOTS, int THREADS>
+__device__ __forceinline__ void fsg_fold_sums_minmax(float (&v)[NS], float mn, float mx, float (*red)[SLOTS],
+                                                     float* __restrict__ out) {
+  static_assert(NS + 2 <= SLOTS, "a partial holds the sums, min and max");
+  const int tid = threadIdx.x, lane = tid & (FSG_WAVE - 1), wave = tid / FSG_WAVE;
+#pragma unroll
+  for (int o = FSG_WAVE / 2; o > 0; o >>= 1) {
+#pragma unroll
+    for (int j = 0; j < NS; ++j) v[j] += __shfl_down(v[j], o, FSG_WAVE);
+    mn = fminf(mn, __shfl_down(mn, o, FSG_WAVE));
+    mx = fmaxf(mx, __shfl_down(mx, o, FSG_WAVE));
+  }
+  if (lane == 0) {
+#pragma unroll
+    for (int j = 0; j < NS; ++j) red[wave][j] = v[j];
+    red[wave][NS] = mn;
+    red[wave][NS + 1] = mx;
+  }
+  __syncthreads();
+  if (tid < SLOTS) {
+    float s = 0.f;
+    if (tid < NS + 2) {
+      s = red[0][tid];
+#pragma unroll
+      for (int q = 1; q < THREADS / FSG_WAVE; ++q)
+        s = tid < NS ? s + red[q][tid] : (tid == NS ? fminf(s, red[q][tid]) : fmaxf(s, red[q][tid]));
+    }
+    out[tid] = s;
+  }
+}
+
 // ---------------------------------------------------------------------------------------------
 // Philox4x32-10 + Box-Muller: element e of stream (seed, stream_id) is lane e%4 of block e/4
 // ---------------------------------------------------------------------------------------------

@@ -13,7 +13,8 @@
 // VGPRs: occupancy is not the limit, HBM is.  No atomics: fixed shuffle tree per wave, waves in order, one 8-float partial per
 // workgroup in a workspace that needs no zeroing, a slice's partials added in double in index order by the update.
 // The iteration cap and the width of a slice's row are the header's (FSG_SOLVER_MAX_ITER, FSG_ROBUST_ROW); the overlap and
-// finite tests and the measuring of the state block are fsg_common.h's.
+// finite tests, the measuring of the state block and the workgroup fold (fsg_fold_sums_minmax, shared with fsg_imatch.hip) are
+// fsg_common.h's.
 #include "fsg_common.h"
 #include <math.h>
 
@@ -117,7 +118,7 @@ template <bool VEC>
 __global__ __launch_bounds__(RB_THREADS) void rb_estep_kernel(RbIn I, int n, int T, int first, const void* state,
                                                               float* __restrict__ ws) {
   __shared__ float red[RB_THREADS / FSG_WAVE][RB_SLOTS];
-  const int k = blockIdx.y, tid = threadIdx.x, lane = tid & (FSG_WAVE - 1), wave = tid / FSG_WAVE;
+  const int k = blockIdx.y, tid = threadIdx.x;
   const int e0 = (blockIdx.x * RB_THREADS + tid) * 4;
   float v[4] = {0.f, 0.f, 0.f, 0.f};
   float mn = INFINITY, mx = -INFINITY;
@@ -142,30 +143,7 @@ __global__ __launch_bounds__(RB_THREADS) void rb_estep_kernel(RbIn I, int n, int
       mx = fmaxf(mx, y[j]);
     }
   }
-#pragma unroll
-  for (int o = FSG_WAVE / 2; o > 0; o >>= 1) {
-#pragma unroll
-    for (int j = 0; j < 4; ++j) v[j] += __shfl_down(v[j], o, FSG_WAVE);
-    mn = fminf(mn, __shfl_down(mn, o, FSG_WAVE));
-    mx = fmaxf(mx, __shfl_down(mx, o, FSG_WAVE));
-  }
-  if (lane == 0) {
-#pragma unroll
-    for (int j = 0; j < 4; ++j) red[wave][j] = v[j];
-    red[wave][4] = mn;
-    red[wave][5] = mx;
-  }
-  __syncthreads();
-  if (tid < RB_SLOTS) {
-    float s = 0.f;
-    if (tid < FSG_ROBUST_ROW) {
-      s = red[0][tid];
-#pragma unroll
-      for (int q = 1; q < RB_THREADS / FSG_WAVE; ++q)
-        s = tid < 4 ? s + red[q][tid] : (tid == 4 ? fminf(s, red[q][tid]) : fmaxf(s, red[q][tid]));
-    }
-    ws[((size_t)k * gridDim.x + blockIdx.x) * RB_SLOTS + tid] = s;  // all 8 slots: the workspace needs no zeroing
-  }
+  fsg_fold_sums_minmax<FSG_ROBUST_ROW - 2, RB_SLOTS, RB_THREADS>(v, mn, mx, red, ws + ((size_t)k * gridDim.x + blockIdx.x) * RB_SLOTS);
 }
 
 struct RbOpts {

@@ -7,6 +7,7 @@ from .scan import (get_PSF, get_trajectory, interleave_index, random_stack, reso
                    set_trajectory_bank, synthetic_trajectory_bank)
 from .slice_acq import get_semantics, set_semantics, slice_acquisition, slice_acquisition_adjoint  # noqa: F401
 from .outlier import robust_weights  # noqa: F401
+from .intensity import intensity_match  # noqa: F401
 from .srr import SRR, srr  # noqa: F401
 from .svr import SVR, svr  # noqa: F401
 # the device-resident, differentiable conversions live in their module: `axisangle2mat`, `mat2axisangle` and `RigidTransform`

@@ -26,6 +26,11 @@ With `n_robust > 0` the solve rejects outliers: after the
 its x, `outlier.robust_weights` turns the residual into per-pixel weights, they multiply the caller's `slices_weight`, the
 right-hand side is rebuilt and the whole solve runs again from `x0` as given, `n_robust` times.  With `n_robust == 0`, the
 default, none of this is launched.
+
+With `n_match > 0` the solve matches the slices' intensities: after a complete solve
+`intensity.intensity_match` fits one scale and, with `bias_sigma`, one smooth bias field per slice against the slices simulated
+from its x, and the next solve takes the corrected slices in place of y.  The refinement loop runs max(n_robust, n_match) rounds;
+a round first takes the robust weights, then the match under them.  With `n_match == 0`, the default, none of it is launched.
 """
 from __future__ import annotations
 
@@ -36,13 +41,14 @@ import torch
 from .... import kernels as K
 from .... import rng as _rng
 from ._solver import no_grad_inputs, prep
+from .intensity import check_options as _match_options, intensity_match
 from .outlier import check_options as _robust_options, robust_weights
 
 
 def srr(transforms, slices, psf, vol_shape, res_slice, *, interp_psf=False, slices_mask=None, vol_mask=None,
         slices_weight=None, x0=None, mu=0.0, z=None, n_iter=10, tol=0.0, output_relu=True, deterministic=None,
         value_scale=1.0, return_info=False, lam=0.0, huber_delta=None, n_outer=1, guide=None,
-        n_robust=0, robust=None):
+        n_robust=0, robust=None, n_match=0, match=None):
     """transforms (n,3,4), slices (n,1,h,w) or (n,h,w), psf (pd,ph,pw) -> volume (1,1,D,H,W) after `n_iter` CG iterations.
 
     slices_mask (n,[1,]h,w) bool: pixels that take part.  vol_mask (D,H,W)-shaped bool: the voxels solved for, the rest is 0.
@@ -58,7 +64,13 @@ def srr(transforms, slices, psf, vol_shape, res_slice, *, interp_psf=False, slic
     n_robust: that many outlier-rejection rounds: weights from `robust_weights(slices, A x, ...)` times `slices_weight`, then
     the complete solve (all `n_outer` rounds) again from `x0`; the relu is applied in the very last solve only.  robust: a
     dict of `robust_weights`' options (n_em, c0, sigma_floor, slice_floor, min_pixels, level, min_weight).  With n_robust > 0
-    the info dict gains "robust": the list of the EM histories, one dict per rejection round."""
+    the info dict gains "robust": the list of the EM histories, one dict per rejection round.
+    n_match: that many intensity-matching rounds, run beside the rejection rounds (max(n_robust, n_match) refinement rounds in
+    all): round r < n_match calls `intensity_match(slices, A x, weights=<the weights the next solve takes>, bias0=<the bias of
+    the round before>)` on the slices AS GIVEN, and the next solve (and the next round's `robust_weights`) takes its `corrected`
+    in place of `slices`.  match: a dict of `intensity_match`'s options (bias_sigma, log_floor, min_pixels, min_weight).  With
+    n_match > 0 the info dict gains "match": per round a dict of the device arrays scale, ok, frozen; and "match_bias", the bias
+    (n,h,w) of the last round."""
     no_grad_inputs("srr", transforms=transforms, slices=slices, psf=psf, slices_weight=slices_weight, x0=x0, z=z, guide=guide)
     lam, n_outer = float(lam), int(n_outer)
     if not (math.isfinite(lam) and lam >= 0):
@@ -79,6 +91,13 @@ def srr(transforms, slices, psf, vol_shape, res_slice, *, interp_psf=False, slic
     if robust is not None and n_robust == 0:
         raise ValueError("robust sets the options of the outlier rejection: it needs n_robust > 0")
     ropts = {k: v for k, v in _robust_options(dict(robust or {})).items() if robust and k in robust}
+    n_match = int(n_match)
+    if n_match < 0:
+        raise ValueError(f"n_match must be >= 0, got {n_match}")
+    if match is not None and n_match == 0:
+        raise ValueError("match sets the options of the intensity matching: it needs n_match > 0")
+    mopts = {k: v for k, v in _match_options(dict(match or {})).items() if match and k in match}
+    n_refine = max(n_robust, n_match)
     if deterministic is None:
         deterministic = _rng.in_keyed_scope()
     det = bool(deterministic)
@@ -114,9 +133,10 @@ def srr(transforms, slices, psf, vol_shape, res_slice, *, interp_psf=False, slic
             K.tk1_apply(v, t, (D, H, W), lam, mask=vm, guide=g, delta=None if g is None else huber_delta, out=t)
         return t
 
-    robust_info = []
+    robust_info, match_info = [], []
     xs0, gd0 = xs, gd
-    for rb in range(n_robust + 1):
+    y_given, bias = y, None
+    for rb in range(n_refine + 1):
         xs, gd = xs0, gd0  # every robust round solves from x0 as given: a warm start keeps the outliers' imprint
         rounds = []
         for o in range(n_outer):
@@ -131,35 +151,44 @@ def srr(transforms, slices, psf, vol_shape, res_slice, *, interp_psf=False, slic
             t0 = None if xs is None else apply(xs, gd)
             r, p, x = (torch.empty((D, H, W), dtype=torch.float32, device=dev) for _ in range(3))
             K.cg_init(ws, b, r, p, x, mask=vm, mu=mu, z=zz, x0=xs, t0=t0)
-            relu = bool(output_relu) and o == n_outer - 1 and rb == n_robust
+            relu = bool(output_relu) and o == n_outer - 1 and rb == n_refine
             for k in range(1, n_iter + 1):
                 q = apply(p, gd)
                 K.cg_q(ws, k, p, q, mask=vm, mu=mu, tol=tol)
                 K.cg_step(ws, k, p, q, x, r, relu=relu)
                 K.cg_dir(ws, k, r, p, tol=tol)
             rounds.append(ws.info())
-        if rb < n_robust:
+        if rb < n_refine:
             s, wgt = K.slice_acq_forward(tr, x, None, sm, ps, (h, w), res_slice, need_weight=True, interp_psf=interp_psf,
                                          semantics="cuda")
+        if rb < n_robust:
             rw = robust_weights(y, s, slices_mask=sm, sim_weight=wgt, return_info=True, **ropts)
             robust_info.append(rw[1])
             wt = rw[0] if wt_given is None else K.mul(rw[0], wt_given)
+        if rb < n_match:
+            y, _, bias, mi = intensity_match(y_given, s, weights=wt, slices_mask=sm, sim_weight=wgt, bias0=bias, return_info=True,
+                                             **mopts)
+            match_info.append({k: mi[k] for k in ("scale", "ok", "frozen")})
     out = x.view(1, 1, D, H, W)
     if not return_info:
         return out
     info = dict(rounds[-1], rounds=rounds) if lam > 0 else rounds[-1]  # lam == 0: the dict it has always been
-    return out, (dict(info, robust=robust_info) if n_robust > 0 else info)
+    if n_robust > 0:
+        info = dict(info, robust=robust_info)
+    return out, (dict(info, match=match_info, match_bias=bias) if n_match > 0 else info)
 
 
 class SRR:
     """`srr` behind the call shape of `PSFreconstruction`: `params` carries psf, interp_psf, res_s, res_r, s_thick and
     volume_shape."""
 
-    def __init__(self, n_iter=10, tol=0.0, output_relu=True, lam=0.0, huber_delta=None, n_outer=1, n_robust=0, robust=None):
+    def __init__(self, n_iter=10, tol=0.0, output_relu=True, lam=0.0, huber_delta=None, n_outer=1, n_robust=0, robust=None, n_match=0,
+                 match=None):
         self.n_iter, self.tol, self.output_relu = n_iter, tol, output_relu
-        # the regulariser and the outlier rejection of `srr`, handed on only when set
+        # the regulariser, the outlier rejection and the intensity matching of `srr`, handed on only when set
         self.reg = {k: v for k, v, unset in (("lam", lam, 0.0), ("huber_delta", huber_delta, None), ("n_outer", n_outer, 1),
-                                             ("n_robust", n_robust, 0), ("robust", robust, None))
+                                             ("n_robust", n_robust, 0), ("robust", robust, None),
+                                             ("n_match", n_match, 0), ("match", match, None))
                     if v != unset}
 
     def __call__(self, transforms, slices, volume, params, p=None, mu=0, z=None, vol_mask=None, slices_mask=None):

@@ -1178,11 +1178,11 @@ def robust_state(n: int, n_em: int, device, slice_shape=None) -> RobustState:
     return RobustState(n, n_em, device, slice_shape)
 
 
-def _robust_pixels(state, y, s, slices_mask, sim_weight, min_weight, out=None):
-    """(n,h,w) fp32 contiguous device arrays on the state's device -> (h, w, mask as bytes)"""
-    _need_gpu(y, s, slices_mask, sim_weight, out)
-    shape = (state.n, *_nhw(y, "slices", state.n))
-    named = (("slices", y), ("simulated", s), ("sim_weight", sim_weight), ("out", out))
+def _pixel_arrays(state, named, slices_mask=None, min_weight=0.0):
+    """named: (name, (n,h,w) fp32 contiguous device array or None), the first one present; all on the device of `state`, the
+    block of a robust EM or an intensity matching -> (h, w, mask as bytes)"""
+    _need_gpu(slices_mask, *(v for _, v in named))
+    shape = (state.n, *_nhw(named[0][1], named[0][0], state.n))
     for name, v in named:
         if v is None:
             continue
@@ -1194,6 +1194,10 @@ def _robust_pixels(state, y, s, slices_mask, sim_weight, min_weight, out=None):
     if not float(min_weight) >= 0.0:
         raise ValueError(f"min_weight must be >= 0, got {min_weight!r}")
     return shape[1], shape[2], sm
+
+
+def _robust_pixels(state, y, s, slices_mask, sim_weight, min_weight, out=None):
+    return _pixel_arrays(state, (("slices", y), ("simulated", s), ("sim_weight", sim_weight), ("out", out)), slices_mask, min_weight)
 
 
 def robust_estep(state: RobustState, t: int, y, s, slices_mask=None, sim_weight=None, min_weight=0.5):
@@ -1230,6 +1234,113 @@ def robust_weights(state: RobustState, y, s, slices_mask=None, sim_weight=None, 
                                             ROBUST_LEVELS[level], _p(state.buf), state.nbytes, _p(out), _stream(y))
     _lib.check(rc, "fsg_robust_weights_f32")
     return out
+
+
+# ---- slice intensity matching: per-slice scale and smooth bias field (fsg_imatch.hip) ------------------------------
+IMATCH_ROW = _lib.IMATCH_ROW  # doubles of a slice's row: N, sum omega c s, sum omega c c, min y, max y
+IMATCH_MAX_RADIUS = _lib.IMATCH_MAX_RADIUS  # the largest ceil(3 sigma)
+
+
+class ImatchState(_StateBlock):
+    """The device blocks of one matching (include/fsg_hip.h, fsg_imatch_*): `buf` (int64), the state, and as views of it consts
+    (4: R, floor, g, the number of ok slices), rows (n,5), raw (n), mean (n) float64, scale (n) float32, ok (n) and frozen (1)
+    int32; `part` (int64) is the workspace of the per-workgroup partials and `planes` (float32, made on first use) that of the
+    bias field's two passes, both for (h, w) slices."""
+
+    def __init__(self, n: int, device, slice_shape=None):
+        self.n = n = _slice_count(n)
+        self._carve("fsg_imatch_state_bytes", (n,), device,
+                    (("consts", torch.float64, (4,)), ("rows", torch.float64, (n, IMATCH_ROW)), ("raw", torch.float64, (n,)),
+                     ("mean", torch.float64, (n,)), ("scale", F32, (n,)), ("ok", torch.int32, (n,)),
+                     ("frozen", torch.int32, (1,))))
+        self.part, self.planes, self.slice_shape = None, None, None
+        if slice_shape is not None:
+            self.reserve(slice_shape)
+
+    def reserve(self, slice_shape):
+        """the workspace for (h, w) slices"""
+        h, w = (int(v) for v in slice_shape)
+        if self.slice_shape != (h, w):
+            need = int(_lib.load().fsg_imatch_ws_bytes(self.n, h, w))
+            if need == 0:
+                raise ValueError(f"no workspace for {self.n} slices of {(h, w)}")
+            self.part = torch.empty(need // 8, dtype=torch.int64, device=self.buf.device)
+            self.planes, self.slice_shape = None, (h, w)
+        return self.part
+
+    def reserve_planes(self):
+        """the planes between the row and the column pass, for the slices `reserve` was given"""
+        if self.planes is None:
+            need = int(_lib.load().fsg_imatch_plane_bytes(self.n, *self.slice_shape))
+            self.planes = torch.empty(need // 4, dtype=F32, device=self.buf.device)
+        return self.planes
+
+    def info(self):
+        return {k: getattr(self, k) for k in ("scale", "ok", "frozen", "raw", "rows", "mean", "consts")}
+
+
+def imatch_state(n: int, device, slice_shape=None) -> ImatchState:
+    return ImatchState(n, device, slice_shape)
+
+
+def imatch_sums(state: ImatchState, y, s, slices_mask=None, sim_weight=None, min_weight=0.5, weights=None, bias0=None):
+    """The pixel pass (fsg_imatch_sums_f32): one partial of the per-slice sums N, sum omega c s, sum omega c c, min y, max y per
+    workgroup, into state.part; c = expf(-bias0) * y, omega = `weights` (None: 1)."""
+    named = (("slices", y), ("simulated", s), ("sim_weight", sim_weight), ("weights", weights), ("bias0", bias0))
+    h, w, sm = _pixel_arrays(state, named, slices_mask, min_weight)
+    part = state.reserve((h, w))
+    rc = _lib.load().fsg_imatch_sums_f32(_p(y), _p(s), _p(sm), _p(sim_weight), float(min_weight), _p(weights), _p(bias0), state.n,
+                                         h, w, _p(part), part.numel() * 8, _stream(y))
+    _lib.check(rc, "fsg_imatch_sums_f32")
+
+
+def imatch_scale(state: ImatchState, log_floor=0.01, min_pixels=4):
+    """The scalar pass (fsg_imatch_scale_f32): the slices' rows, their gains raw, the gauge g, scale = raw / g, ok, the floor
+    log_floor * (max y - min y) and frozen.  After imatch_sums(state, ...), on the same stream."""
+    if state.part is None:
+        raise ValueError("imatch_scale follows imatch_sums: the state has no partials yet")
+    h, w = state.slice_shape
+    rc = _lib.load().fsg_imatch_scale_f32(_p(state.buf), state.nbytes, _p(state.part), state.part.numel() * 8, state.n, h, w,
+                                          float(log_floor), int(min_pixels), _stream(state.buf))
+    _lib.check(rc, "fsg_imatch_scale_f32")
+
+
+def imatch_bias(state: ImatchState, y, s, sigma, slices_mask=None, sim_weight=None, min_weight=0.5, weights=None, bias0=None,
+                out=None):
+    """out (n,h,w) fp32 = b1, bias0 plus the normalised Gaussian blur (sigma, in pixels) of omega * log(scale c / s) over the
+    pixels above the floor, and state.mean, its weighted mean per slice (fsg_imatch_bias_f32: the row pass, the column pass and
+    the means).  After imatch_scale(state), on the same stream, with the arrays imatch_sums was given."""
+    if state.part is None:
+        raise ValueError("imatch_bias follows imatch_sums and imatch_scale: the state has no partials yet")
+    if out is None and isinstance(y, torch.Tensor):
+        out = torch.empty_like(y)
+    named = (("slices", y), ("simulated", s), ("sim_weight", sim_weight), ("weights", weights), ("bias0", bias0), ("out", out))
+    h, w, sm = _pixel_arrays(state, named, slices_mask, min_weight)
+    if (h, w) != state.slice_shape:
+        raise ValueError(f"slices are {(h, w)}, the sums were taken over {state.slice_shape}")
+    planes = state.reserve_planes()
+    rc = _lib.load().fsg_imatch_bias_f32(_p(y), _p(s), _p(sm), _p(sim_weight), float(min_weight), _p(weights), _p(bias0),
+                                         float(sigma), state.n, h, w, _p(state.buf), state.nbytes, _p(planes), planes.numel() * 4,
+                                         _p(state.part), state.part.numel() * 8, _p(out), _stream(y))
+    _lib.check(rc, "fsg_imatch_bias_f32")
+    return out
+
+
+def imatch_apply(state: ImatchState, y, bias=None, bias0=None, corrected=None):
+    """-> (corrected, bias), both (n,h,w) fp32 (fsg_imatch_apply_f32).  `bias` given: it is imatch_bias's b1 and becomes
+    b1 - mean on the ok slices, in place.  `bias` None (scale only): a new array, bias0 or zeros.  corrected =
+    scale * expf(-bias) * y on every pixel."""
+    with_bias = bias is not None
+    if isinstance(y, torch.Tensor):
+        bias = torch.empty_like(y) if bias is None else bias
+        corrected = torch.empty_like(y) if corrected is None else corrected
+    named = (("slices", y), ("bias", bias), ("bias0", bias0), ("corrected", corrected))
+    h, w, _ = _pixel_arrays(state, named)
+    rc = _lib.load().fsg_imatch_apply_f32(_p(y), _p(None if with_bias else bias0), _lib.IMATCH_WITH_BIAS if with_bias else
+                                          _lib.IMATCH_SCALE_ONLY, state.n, h, w, _p(state.buf), state.nbytes, _p(bias),
+                                          _p(corrected), _stream(y))
+    _lib.check(rc, "fsg_imatch_apply_f32")
+    return corrected, bias
 
 
 # ---- SR-artifact volumetric helpers (fsg_artifacts.hip) ----------------------------------------------------

@@ -40,7 +40,8 @@ extern "C" {
                                  and with fsg_cg_ws_bytes / fsg_cg_init_f32 / _q_f32 / _step_f32 / _dir_f32, and with
                                  fsg_svr_ws_bytes / fsg_svr_normal_f32 / fsg_svr_state_bytes / fsg_svr_update_f32, and with
                                  fsg_tk1_apply_f32, and with fsg_robust_ws_bytes / _state_bytes / _estep_f32 / _update_f32 /
-                                 _weights_f32: entries added, nothing older changed */
+                                 _weights_f32, and with fsg_imatch_ws_bytes / _state_bytes / _plane_bytes / _sums_f32 /
+                                 _scale_f32 / _bias_f32 / _apply_f32: entries added, nothing older changed */
 
 #define FSG_E_BADARG (-1)   /* null pointer / non-positive size / bad enum */
 #define FSG_E_TOOBIG (-2)   /* size exceeds what the kernel indexes (2^31-1 voxels per volume) */
@@ -746,6 +747,103 @@ int fsg_robust_update_f32(void* state, size_t state_bytes, const void* ws, size_
 int fsg_robust_weights_f32(const float* y, const float* s, const uint8_t* slices_mask, const float* sim_weight, float min_weight,
                            int n, int h, int w, int n_em, int level, const void* state, size_t state_bytes, float* out,
                            void* stream);
+
+/* ---- slice intensity matching for the reconstruction: per-slice scale and smooth bias field (fsg_imatch.hip; DESIGN.md
+ * section 28) ----------------------------------------------------------------------------------------------------------------
+ * The third part of the slice-to-volume method (Kuklisova-Murgasova et al. 2012) beside the solve and the robust statistics:
+ * every acquired slice gets one multiplicative scale and one smooth multiplicative bias field exp(bias), both estimated from the
+ * slice and its simulation s = A x and both removed before the next solve.  One matching is the launch sequence, on one stream:
+ *     sums;  scale;  (sigma > 0: bias = three launches, rows, columns, means;)  apply
+ * and it is the same sequence whatever the data: nothing returns early, nothing is read back.
+ *   y (n,h,w) the acquired slices, s (n,h,w) the simulated ones, fp32; slices_mask (n,h,w) bytes or NULL; sim_weight (n,h,w) fp32
+ *   or NULL with min_weight >= 0, as fsg_robust_*; pix_weight (n,h,w) fp32 or NULL, the robust weights omega (NULL: omega = 1);
+ *   bias0 (n,h,w) fp32 or NULL, the log-bias carried from an earlier matching (NULL: 0); sigma, a double, in pixels.
+ * c = fl(expf(-bias0) * y), and c = y without bias0: the slice with the carried bias removed.
+ * Omega: a pixel takes part iff it is inside slices_mask, (with sim_weight) weight > 0 && weight >= min_weight, y, s and c are
+ * finite, and (with pix_weight) omega is finite and > 0.  A NaN or Inf in any array leaves the pixel out and reaches no sum.
+ *
+ * fsg_imatch_sums_f32.  Per pixel of Omega, fp32 with one rounding per operation (no contraction), expf the library's:
+ *     t = fl(omega * c) (t = c without pix_weight);  the terms 1, fl(t * s), fl(t * c)
+ * Per-slice sums: N (the count), A = sum omega c s, B = sum omega c c, and min y, max y.  Reduction exactly as
+ * fsg_robust_estep_f32: pixel i of a slice belongs to thread (i / 4) mod 256 of workgroup i / 1024 of that slice; a thread adds
+ * its four pixels in increasing i from +0; the 64 lanes of a wave fold by v[i] += v[i + o], o = 32..1 (shuffle-down; min / max by
+ * fminf / fmaxf from +Inf / -Inf); the four waves are added in wave order; the workgroup stores one partial of 8 floats (N, A, B,
+ * min, max, 0, 0, 0) at ws[slice][workgroup].  Loads are 16 bytes per lane when h * w is a multiple of 4, every float pointer is
+ * 16-byte aligned and slices_mask 4-byte aligned; scalars otherwise, same values and same sums.
+ *
+ * fsg_imatch_scale_f32: one workgroup, double arithmetic.  A slice's row = its partials added in DOUBLE in workgroup order from
+ * +0.0 (min / max by fmin / fmax; a slice without a pixel stores min = max = 0): rows[k] = (N, A, B, min y, max y).
+ *     R = max y - min y over all of Omega;  floor = log_floor * R
+ *     own_k = N_k >= min_pixels && N_k > 0 && A_k, B_k finite and > 0 && A_k / B_k finite;  raw_k = A_k / B_k (0 for a slice
+ *         that is not own_k; its A and B are stored as 0 when either is not finite): the least-squares gain that takes c to s,
+ *         the minimiser of sum omega (raw c - s)^2
+ *     gauge: g = (sum of raw_k over the own_k slices in index order from +0.0) / (their number): a common gain of all slices is
+ *         the volume's, not a slice's, so the scales have arithmetic mean 1 over the slices that have one
+ *     scale_k = (float)(raw_k / g);  a slice that is not own_k keeps scale_k = 1
+ *     freeze: R == 0 or not finite, no slice own_k, g not finite or not > 0, or a scale_k that is not finite or not > 0:
+ *         frozen = 1, every scale_k = 1 and every ok_k = 0.  Otherwise ok_k = own_k.  No NaN is ever stored.
+ *     mean_k = 0 (fsg_imatch_bias_f32 overwrites it).
+ * A slice with ok_k == 0 keeps scale 1 and its bias as given, in every later launch.
+ *
+ * fsg_imatch_bias_f32, only for sigma > 0 (sigma == 0 is scale only: the entry is not called and refuses).  Rr = ceil(3 sigma),
+ * taps g[t] = (float)exp(-(t * t) / (2 sigma^2)), t = 0..Rr, computed on the host in double and NOT normalised: only a quotient
+ * of two sums under the same taps is formed.
+ *   Omega_b: a pixel of Omega whose slice is ok, with d = fl(scale_k * c) > (float)floor and s > (float)floor.
+ *   r = logf(fl(d / s)) (the division correctly rounded, logf the library's); a pixel whose r is not finite is not in Omega_b.
+ *   Planes: P = fl(omega * r) and Q = omega on Omega_b (r and 1 without pix_weight), 0 elsewhere.
+ *   rows     for both planes, per pixel (row i, column j): acc = +0; for t = -Rr..Rr in increasing t, the taps with
+ *            0 <= j + t < w only (a tap outside the slice is skipped; one inside the slice and outside Omega_b runs with its
+ *            zero): acc = fmaf(g[|t|], plane[i][j + t], acc).  -> P1, Q1.
+ *   columns  the same along i over P1 and Q1: t = -Rr..Rr increasing, 0 <= i + t < h, acc = fmaf(g[|t|], plane1[i + t][j], acc),
+ *            from +0.  -> P2, Q2.  inc = Q2 >= FLT_MIN ? fl(P2 / Q2) : 0;  b1 = fl(bias0 + inc) (b1 = inc without bias0),
+ *            written to `bias`.  A pixel all of whose taps miss Omega_b has Q2 == 0 and inc == 0 exactly.
+ *   means    per ok slice m_k = sum over Omega_b of fl(omega * b1) / sum over Omega_b of omega (0 when the denominator is 0, and
+ *            for a slice that is not ok): a thread of the column pass adds its pixels in increasing row from +0, the 256 threads
+ *            of a tile fold as in fsg_svr_normal_f32 (shuffle-down, waves in order), one partial of two floats per tile at
+ *            ws[slice][tile], tile = tile_y * tiles_x + tile_x, tiles of 64 rows by 32 columns; the third launch adds a slice's
+ *            partials in DOUBLE in tile order from +0.0 and stores mean_k.  The smooth field takes no part of the scale's work.
+ *   planes: DEVICE workspace of fsg_imatch_plane_bytes(n, h, w) = 12 bytes a pixel (P1, Q1 and Q, each (n,h,w) fp32), 16-byte
+ *   aligned; it needs no initialisation.
+ *
+ * fsg_imatch_apply_f32.  mode FSG_IMATCH_WITH_BIAS: `bias` holds b1; bias = fl(b1 - (float)mean_k) on every pixel of an ok
+ * slice, b1 unchanged on the others.  mode FSG_IMATCH_SCALE_ONLY: bias = bias0, or 0 without it.  Then on EVERY pixel
+ *     corrected = fl(scale_k * fl(expf(-bias) * y))
+ * so a NaN in y stays a NaN in corrected, at that pixel only.  16-byte loads and stores as above.
+ *
+ * state: one DEVICE block of fsg_imatch_state_bytes(n) bytes (0 for n < 1 or n > 65535), 8-byte aligned, in this order:
+ *     double consts[4] (R, floor, g, the number of ok slices), double rows[n][5] (N, A, B, min y, max y), double raw[n],
+ *     double mean[n], float scale[n], int32 ok[n], int32 frozen
+ * rounded up to 8 bytes.  It needs no initialisation: scale writes every field, bias overwrites mean; a launch reads only what
+ * an EARLIER launch wrote.  ws: DEVICE, 8-byte aligned, fsg_imatch_ws_bytes(n, h, w) = 32 bytes per 1024 pixels (rounded up) of
+ * every slice for the sums, followed by 8 bytes per tile of every slice for the means; it needs no initialisation.
+ *
+ * Determinism: no atomics and every order fixed, so the same bits in any run and on any stream.  A slice's row is a function of
+ * that slice alone; R, g and so every scale are GLOBAL sums in slice-index order (as sigma and c of fsg_robust_*).
+ * Refusals, all before any launch and with nothing written: n, h or w < 1, a null y, s, state, ws, planes, bias or corrected, a
+ * short state, ws or plane buffer, min_weight or log_floor negative or NaN (log_floor Inf too), min_pixels < 0, sigma negative,
+ * NaN, Inf or 0 in fsg_imatch_bias_f32, 3 sigma > FSG_IMATCH_MAX_RADIUS, an unknown mode (FSG_E_BADARG); n > 65535,
+ * n * h * w > 2^31 - 1, h * w > 2^31 - 1 - 1024 (a slice's pixels are counted in int, 1024 to a workgroup), or h > 65535 in
+ * fsg_imatch_bias_f32 (FSG_E_TOOBIG; the three fsg_imatch_*_bytes return 0 for the same sizes); state or ws not 8-byte aligned, planes not 16-byte aligned, a float pointer not 4-byte
+ * aligned (FSG_E_ALIGN); an output, the planes, ws or the state sharing a byte with an input or with one another (FSG_E_BADARG;
+ * `bias` of apply is in place by contract). */
+#define FSG_IMATCH_SCALE_ONLY 0
+#define FSG_IMATCH_WITH_BIAS 1
+#define FSG_IMATCH_ROW 5         /* doubles of a slice's entry of rows[n][5] in the state */
+#define FSG_IMATCH_MAX_RADIUS 48 /* the largest ceil(3 sigma): sigma up to 16 pixels, 12 mm at 0.75 mm */
+size_t fsg_imatch_ws_bytes(int n, int h, int w);
+size_t fsg_imatch_state_bytes(int n);
+size_t fsg_imatch_plane_bytes(int n, int h, int w);
+int fsg_imatch_sums_f32(const float* y, const float* s, const uint8_t* slices_mask, const float* sim_weight, float min_weight,
+                        const float* pix_weight, const float* bias0, int n, int h, int w, void* ws, size_t ws_bytes,
+                        void* stream);
+int fsg_imatch_scale_f32(void* state, size_t state_bytes, const void* ws, size_t ws_bytes, int n, int h, int w, double log_floor,
+                         int min_pixels, void* stream);
+int fsg_imatch_bias_f32(const float* y, const float* s, const uint8_t* slices_mask, const float* sim_weight, float min_weight,
+                        const float* pix_weight, const float* bias0, double sigma, int n, int h, int w, void* state,
+                        size_t state_bytes, void* planes, size_t plane_bytes, void* ws, size_t ws_bytes, float* bias,
+                        void* stream);
+int fsg_imatch_apply_f32(const float* y, const float* bias0, int mode, int n, int h, int w, const void* state,
+                         size_t state_bytes, float* bias, float* corrected, void* stream);
 
 /* ---- SR-artifact volumetric helpers, fsg_artifacts.hip ------------------------------------ */
 /* out = clamp(sum_g exp(-(((x-c0)/s0)^2 + ((y-c1)/s1)^2 + ((z-c2)/s2)^2) / 2), 0, 1) over a (D,H,W) grid with

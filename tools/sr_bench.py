@@ -25,6 +25,8 @@ launches of an iteration alone (srr_bench below).  --srr-lambda L > 0 adds the s
 beside the forward plus the grad_transforms-only backward, at n = 80 and 250 (svr_bench below).
 --robust runs INSTEAD of the legs above, on the same problem: one `svort.robust_weights` call (--robust-em EM iterations) beside
 one CG iteration of `svort.srr`, and its three kernels alone, at n = 80 and 250 (robust_bench below).
+--imatch runs INSTEAD of the legs above, on the same problem: one `svort.intensity_match` call at sigma = 16 and 4 pixels and
+scale only beside one CG iteration of `svort.srr`, and its entries alone, at n = 80 and 250 (imatch_bench below).
 """
 import argparse
 import json
@@ -372,6 +374,80 @@ def robust_bench(a, dev, vs, ss, psf, vol, res):
     return out
 
 
+def imatch_bench(a, dev, vs, ss, psf, vol, res):
+    """--imatch, n = 80 and 250.  One `svort.intensity_match` call at sigma = 16 and 4 pixels and scale only, beside ONE iteration
+    of the conjugate gradients of `svort.srr` (A, A^T in the float adjoint, q, step, dir; the operators as in robust_bench), by device events over
+    --reps calls, the legs alternated three times after a warm-up.  Then the entries alone, with their bytes from the shapes
+    (y, s and the forward's weight; no mask, robust weights or carried bias): sums reads 12 bytes a pixel; bias reads 12 and
+    writes 12 in the row pass, reads 12 and writes 4 in the column pass (28 + 12 = 40); apply reads 8 and writes 8.  bias at
+    sigma = 0.3 (radius 1) is the two passes with next to no taps: what remains of the other two is the taps' LDS work.  No
+    threshold is asserted: the figures are for DESIGN.md section 28."""
+    from fetalsyngen_amd.generator.artifacts.svort import intensity_match
+
+    rs = a.res_slice / res
+    out = {"volume": vs, "psf": list(psf.shape), "psf_taps": int((psf > 0).sum()),
+           "clock": f"device events around {a.reps} calls, legs alternated three times"}
+    nvox = int(np.prod(vs))
+    for n in (80, 250):
+        np.random.seed(0)
+        tr = random_stack(n, gap=a.size * res / n / res, max_angle=0.3).to(dev)
+        y = K.slice_acq_forward(tr, vol, None, None, psf, (ss, ss), rs, interp_psf=True)
+        gain = torch.exp(0.25 * torch.randn(n, 1, 1, device=dev))
+        y = y * gain + 0.02 * torch.randn_like(y)
+        s, wgt = K.slice_acq_forward(tr, 0.95 * vol, None, None, psf, (ss, ss), rs, need_weight=True, interp_psf=True)
+        ws = K.cg_workspace(nvox, 1, dev)
+        b = torch.rand(vs, device=dev)
+        r, p, x = torch.empty_like(b), torch.empty_like(b), torch.empty_like(b)
+
+        def cg_iteration():
+            K.cg_init(ws, b, r, p, x)
+            t = K.slice_acq_forward(tr, p, None, None, psf, (ss, ss), rs, interp_psf=True)
+            q = K.slice_acq_adjoint(tr, psf, t, None, None, vs, rs, interp_psf=True)
+            K.cg_q(ws, 1, p, q)
+            K.cg_step(ws, 1, p, q, x, r)
+            K.cg_dir(ws, 1, r, p)
+
+        legs = {"match_sigma16": lambda: intensity_match(y, s, sim_weight=wgt, bias_sigma=16.0),
+                "match_sigma4": lambda: intensity_match(y, s, sim_weight=wgt, bias_sigma=4.0),
+                "match_scale_only": lambda: intensity_match(y, s, sim_weight=wgt),
+                "cg_iteration": cg_iteration, "cg_init_alone": lambda: K.cg_init(ws, b, r, p, x)}
+        for fn in legs.values():
+            fn()
+        row = {k: [] for k in legs}
+        for _ in range(3):
+            for k, fn in legs.items():
+                row[k].append(round(timed(fn, a.reps), 4))
+        st = K.imatch_state(n, dev, (ss, ss))
+        K.imatch_sums(st, y, s, None, wgt), K.imatch_scale(st)
+        b1, cor = torch.empty_like(y), torch.empty_like(y)
+        alone = {"sums": lambda: K.imatch_sums(st, y, s, None, wgt), "scale": lambda: K.imatch_scale(st),
+                 "bias_sigma16": lambda: K.imatch_bias(st, y, s, 16.0, None, wgt, out=b1),
+                 "bias_sigma4": lambda: K.imatch_bias(st, y, s, 4.0, None, wgt, out=b1),
+                 "bias_sigma0.3": lambda: K.imatch_bias(st, y, s, 0.3, None, wgt, out=b1),
+                 "apply_scale_only": lambda: K.imatch_apply(st, y, None, None, corrected=cor)}
+        for k, fn in alone.items():
+            fn()
+            row[k] = [round(timed(fn, a.reps), 4) for _ in range(3)]
+        npix = n * ss * ss
+        row["sums_GB_per_s"] = round(12 * npix / min(row["sums"]) / 1e6, 1)
+        row["apply_GB_per_s"] = round(12 * npix / min(row["apply_scale_only"]) / 1e6, 1)  # no bias read: y in, bias and corrected out
+        for k in ("bias_sigma16", "bias_sigma4", "bias_sigma0.3"):
+            row[k + "_GB_per_s"] = round(40 * npix / min(row[k]) / 1e6, 1)
+        it = min(row["cg_iteration"]) - min(row["cg_init_alone"])
+        row["cg_iteration_without_init"] = round(it, 4)
+        for k in ("match_sigma16", "match_sigma4", "match_scale_only"):
+            row[k + "_over_cg_iteration"] = round(min(row[k]) / it, 4)
+        row["slices"] = [n, ss, ss]
+        m1 = intensity_match(y, s, sim_weight=wgt, bias_sigma=4.0, return_info=True)
+        m2 = intensity_match(y, s, sim_weight=wgt, bias_sigma=4.0)
+        row["twice_equal"] = all(bool(torch.equal(u, v)) for u, v in zip(m1[:3], m2))
+        row["frozen"] = int(m1[3]["frozen"].item())
+        row["scale_against_gain_corr"] = round(float(torch.corrcoef(torch.stack([m1[1], 1 / gain.reshape(-1)]))[0, 1].item()), 4)
+        out[f"n{n}_ms"] = row
+        del y, s, wgt, st, b1, cor, m1, m2
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--size", type=int, default=384)
@@ -393,6 +469,7 @@ def main():
     ap.add_argument("--svr-iters", type=int, default=5, help="iterations per --svr solve (iters + 1 rounds)")
     ap.add_argument("--robust", action="store_true", help="time svort.robust_weights beside one CG iteration instead")
     ap.add_argument("--robust-em", type=int, default=5, help="EM iterations per --robust call (n_em)")
+    ap.add_argument("--imatch", action="store_true", help="time svort.intensity_match beside one CG iteration instead")
     a = ap.parse_args()
     dev, res = "cuda:0", 0.5
     vs = (a.size,) * 3
@@ -407,6 +484,9 @@ def main():
         return
     if a.robust:
         print(json.dumps(robust_bench(a, dev, vs, ss, psf, torch.rand(vs, device=dev), res)))
+        return
+    if a.imatch:
+        print(json.dumps(imatch_bench(a, dev, vs, ss, psf, torch.rand(vs, device=dev), res)))
         return
     delta = get_PSF(0).to(dev)
     np.random.seed(0)
