@@ -10,6 +10,7 @@ from .outlier import robust_weights  # noqa: F401
 from .intensity import intensity_match  # noqa: F401
 from .srr import SRR, srr  # noqa: F401
 from .svr import SVR, svr  # noqa: F401
+from .align import align_stacks  # noqa: F401
 # the device-resident, differentiable conversions live in their module: `axisangle2mat`, `mat2axisangle` and `RigidTransform`
 # of this namespace stay rigid.py's detaching host versions, which the generator relies on
 from . import transform_convert  # noqa: F401,E402

@@ -1135,6 +1135,58 @@ def svr_update(state: SVRState, k: int, stats_trial, theta_trial, lambda0=1e-3, 
     _lib.check(rc, "fsg_svr_update_f32")
 
 
+def _i32_rows(t, name, numel):
+    """`t` is a contiguous int32 device vector of `numel` elements"""
+    _need_gpu(t)
+    if t.dtype != torch.int32 or t.dim() != 1 or t.numel() != numel:
+        raise ValueError(f"{name} must be int32 of {numel} elements, got {t.dtype} {tuple(t.shape)}")
+    return t
+
+
+def svr_compose(group_mat, group_jac, base, group, out=None):
+    """Slices that move with their group (fsg_svr_compose_f32): group_mat (G,3,4) = [Q | d], group_jac (G,12,6) its Jacobian,
+    base (n,3,4), group (n) int32 (an id outside [0, G), -1 by convention: the slice is fixed) -> transforms (n,3,4) with
+    R' = Q R, t' = t + R'^T d, and jac (n,12,6) = d transforms / d the GROUP's 6 parameters (0 for a fixed slice): the operands
+    of svr_normal.  `out` = (transforms, jac) may be passed to keep a loop free of allocations."""
+    G = _tc_rows(group_mat, "group_mat", (3, 4))
+    n = _tc_rows(base, "base", (3, 4))
+    if _tc_rows(group_jac, "group_jac", (12, 6)) != G:
+        raise ValueError(f"group_jac must be (G,12,6) with G={G}, got {tuple(group_jac.shape)}")
+    _i32_rows(group, "group", n)
+    if out is None:
+        out = (torch.empty((n, 3, 4), dtype=F32, device=base.device), torch.empty((n, 12, 6), dtype=F32, device=base.device))
+    tr, jac = out
+    if _tc_rows(tr, "out[0]", (3, 4)) != n or _tc_rows(jac, "out[1]", (12, 6)) != n:
+        raise ValueError(f"out must be ((n,3,4), (n,12,6)) with n={n}, got {tuple(tr.shape)}, {tuple(jac.shape)}")
+    _same_device(base.device, "base", ("group_mat", group_mat), ("group_jac", group_jac), ("group", group), ("out[0]", tr),
+                 ("out[1]", jac))
+    rc = _lib.load().fsg_svr_compose_f32(_p(group_mat), _p(group_jac), _p(base), _p(group), _p(tr), _p(jac), n, G, _stream(base))
+    _lib.check(rc, "fsg_svr_compose_f32")
+    return tr, jac
+
+
+def svr_group_reduce(stats, members, offsets, out=None):
+    """A group's normal equations = the sum of its slices' (fsg_svr_group_reduce_f64): stats (n,32) float64, members int32
+    slice indices, offsets (G+1) int32 into members -> gstats (G,32) float64, a group's members added in the listed order from
+    +0.0 (an empty group: zeros).  No atomics: a group's row is a pure function of its members' rows."""
+    _need_gpu(stats, members, offsets, out)
+    if stats.dtype != torch.float64 or stats.dim() != 2 or int(stats.shape[1]) != SVR_SLOTS:
+        raise ValueError(f"stats must be float64 (n,{SVR_SLOTS}), got {stats.dtype} {tuple(stats.shape)}")
+    n, G = int(stats.shape[0]), int(offsets.numel()) - 1
+    _i32_rows(members, "members", members.numel()), _i32_rows(offsets, "offsets", G + 1)
+    if G < 1:
+        raise ValueError("offsets must have G + 1 >= 2 elements")
+    if out is None:
+        out = torch.empty((G, SVR_SLOTS), dtype=torch.float64, device=stats.device)
+    elif out.dtype != torch.float64 or tuple(out.shape) != (G, SVR_SLOTS):
+        raise ValueError(f"out must be float64 ({G},{SVR_SLOTS}), got {out.dtype} {tuple(out.shape)}")
+    _same_device(stats.device, "stats", ("members", members), ("offsets", offsets), ("out", out))
+    rc = _lib.load().fsg_svr_group_reduce_f64(_p(stats), _p(members), _p(offsets), _p(out), n, int(members.numel()), G,
+                                              _stream(stats))
+    _lib.check(rc, "fsg_svr_group_reduce_f64")
+    return out
+
+
 # ---- outlier weights: robust-statistics EM over the residual of a reconstruction (fsg_robust.hip) -----------------
 ROBUST_MAX_EM = _lib.SOLVER_MAX_ITER
 ROBUST_LEVELS = {"slice": _lib.ROBUST_SLICE, "both": _lib.ROBUST_BOTH}

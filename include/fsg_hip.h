@@ -41,7 +41,8 @@ extern "C" {
                                  fsg_svr_ws_bytes / fsg_svr_normal_f32 / fsg_svr_state_bytes / fsg_svr_update_f32, and with
                                  fsg_tk1_apply_f32, and with fsg_robust_ws_bytes / _state_bytes / _estep_f32 / _update_f32 /
                                  _weights_f32, and with fsg_imatch_ws_bytes / _state_bytes / _plane_bytes / _sums_f32 /
-                                 _scale_f32 / _bias_f32 / _apply_f32: entries added, nothing older changed */
+                                 _scale_f32 / _bias_f32 / _apply_f32, and with fsg_svr_compose_f32 / fsg_svr_group_reduce_f64:
+                                 entries added, nothing older changed */
 
 #define FSG_E_BADARG (-1)   /* null pointer / non-positive size / bad enum */
 #define FSG_E_TOOBIG (-2)   /* size exceeds what the kernel indexes (2^31-1 voxels per volume) */
@@ -674,6 +675,49 @@ size_t fsg_svr_state_bytes(int n, int n_iter);
 int fsg_svr_update_f32(const double* stats_trial, float* theta_trial, void* state, size_t state_bytes, int n, int k, int n_iter,
                        double lambda0, double factor, double lambda_min, double lambda_max, double min_overlap, double tol,
                        void* stream);
+
+/* ---- grouped registration: several slices share one pose increment (fsg_svr_group.hip) --------------
+ * A group of slices (a stack, a package) moves as one rigid body.  Its increment phi = [rotation vector q | translation d] is a
+ * rigid motion of the VOLUME frame about the volume centre, x' = Q x + d with [Q | d] = fsg_axisangle2mat_f32(phi).  A slice's
+ * matrix [R | t] maps pixel p to the volume-centred point R (p + t), so under the increment
+ *     R' = Q R,   t' = t + R'^T d,   dR'/dphi_a = dQ_a R,   dt'/dphi_a = (dQ_a R)^T d + R'^T dd_a
+ * with dQ_a, dd_a column a of the (12,6) Jacobian of fsg_axisangle2mat_f32 at phi (fsg_axisangle2mat_backward_f32 on the 12
+ * one-hot matrices).  One grouped solve is the launch sequence, for k = 0..K on one stream, G the number of groups:
+ *     [Q | d] = axisangle2mat(phi_trial);  its Jacobian;  compose;  fsg_svr_normal_f32 (as it is);  group_reduce;
+ *     fsg_svr_update_f32 with n := G on gstats and phi_trial
+ * and one compose at the state's theta_cur after the loop.
+ *
+ * fsg_svr_compose_f32: group_mat (G,12) = [Q | d] row-major 3 x 4, group_jac (G,12,6) row k = d entry k / d phi, base (n,12),
+ * group (n) int32 -> transforms (n,12) and jac (n,12,6), the operands of fsg_svr_normal_f32.  One thread per slice and
+ * parameter; fp32, one rounding per operation, no contraction, every three-term sum as ((x0 y0) + (x1 y1)) + (x2 y2):
+ *     R'[r][c]      = ((Q[r][0] R[0][c]) + (Q[r][1] R[1][c])) + (Q[r][2] R[2][c])
+ *     t'[c]         = t[c] + (((R'[0][c] d[0]) + (R'[1][c] d[1])) + (R'[2][c] d[2]))
+ *     jac[4r+c][a]  = dR_a[r][c] = ((dQ_a[r][0] R[0][c]) + (dQ_a[r][1] R[1][c])) + (dQ_a[r][2] R[2][c])
+ *     jac[4c+3][a]  = (((dR_a[0][c] d[0]) + (dR_a[1][c] d[1])) + (dR_a[2][c] d[2]))
+ *                   + (((R'[0][c] dd_a[0]) + (R'[1][c] dd_a[1])) + (R'[2][c] dd_a[2]))
+ * with dQ_a[r][m] = group_jac[g][4r+m][a] and dd_a[r] = group_jac[g][4r+3][a].  It holds no pose arithmetic of its own.
+ *   group[k] outside [0, G) (-1 by convention) means FIXED: transforms[k] = base[k] bit for bit and jac[k] = 0.  The id is
+ *   range-tested before it selects a row and never becomes an address otherwise.
+ *   phi = 0: the conversion's small-angle branch gives Q = identity exactly and d = 0, and 1 r + 0 r' + 0 r'' is exact, so
+ *   transforms = base bit for bit for finite base (the sign of a zero entry apart: it is the sum's, +0 unless all three
+ *   products are -0).  Round 0 of a solve therefore evaluates the poses as given.
+ * Refusals, before any launch and with nothing written: a null pointer, n < 1, G < 1 (FSG_E_BADARG); n or G > 65535
+ * (FSG_E_TOOBIG); a pointer not 4-byte aligned (FSG_E_ALIGN); transforms or jac sharing a byte with an input or with each
+ * other (FSG_E_BADARG).
+ *
+ * fsg_svr_group_reduce_f64: stats (n,32) DOUBLE, members (n_members) int32 slice indices, offsets (G+1) int32 into members
+ * -> gstats (G,32) DOUBLE: gstats[g][k] = stats[members[j]][k] added in double for j = offsets[g] .. offsets[g+1] - 1 in that
+ * order from +0.0.  One thread per group and slot; all 32 slots are written; an empty group (offsets[g] == offsets[g+1]) gets
+ * zeros; no atomics: a group's row is a pure function of its members' rows, the same bits in any run, on any stream, for any
+ * number of other groups.  A member index outside [0, n) adds nothing, and a group whose range is not inside [0, n_members]
+ * gets zeros: neither becomes an address.
+ * Refusals, before any launch and with nothing written: a null pointer, n < 1, G < 1, n_members < 1 (FSG_E_BADARG); n, G or
+ * n_members > 65535 (FSG_E_TOOBIG); stats or gstats not 8-byte aligned, members or offsets not 4-byte aligned (FSG_E_ALIGN);
+ * gstats sharing a byte with an input (FSG_E_BADARG). */
+int fsg_svr_compose_f32(const float* group_mat, const float* group_jac, const float* base, const int32_t* group, float* transforms,
+                        float* jac, int n, int G, void* stream);
+int fsg_svr_group_reduce_f64(const double* stats, const int32_t* members, const int32_t* offsets, double* gstats, int n,
+                             int n_members, int G, void* stream);
 
 /* ---- outlier weights for the two solves above: robust-statistics EM (fsg_robust.hip) ----------------
  * The W of fsg_cg_* / fsg_svr_normal_f32 from the residual of a reconstruction (Kuklisova-Murgasova et al. 2012): per pixel a

@@ -27,6 +27,9 @@ beside the forward plus the grad_transforms-only backward, at n = 80 and 250 (sv
 one CG iteration of `svort.srr`, and its three kernels alone, at n = 80 and 250 (robust_bench below).
 --imatch runs INSTEAD of the legs above, on the same problem: one `svort.intensity_match` call at sigma = 16 and 4 pixels and
 scale only beside one CG iteration of `svort.srr`, and its entries alone, at n = 80 and 250 (imatch_bench below).
+
+--svr-groups runs INSTEAD of the legs above, on the same problem: a round of `svort.svr` with 3 groups beside today's per-slice
+round, and the two launches the grouped round adds alone, at n = 80 and 250 (svr_groups_bench below).
 """
 import argparse
 import json
@@ -311,6 +314,65 @@ def svr_bench(a, dev, vs, ss, psf, vol, res):
     return out
 
 
+def svr_groups_bench(a, dev, vs, ss, psf, vol, res):
+    """--svr-groups, n = 80 and 250, 3 groups of consecutive slices.  A round of `svort.svr(groups=)` (axisangle2mat and its
+    Jacobian on 3 rows, svr_compose, fsg_svr_normal_f32, svr_group_reduce, fsg_svr_update_f32 on 3 rows) beside a round of the
+    per-slice `svort.svr` (the conversions and the update on n rows): device events around one solve of --svr-iters iterations,
+    divided by its iters + 1 rounds, the two legs alternated three times after a warm-up.  Then fsg_svr_compose_f32 and
+    fsg_svr_group_reduce_f64 alone, by device events over --reps launches.  The expectation: a grouped round is the per-slice
+    round plus the two launches (the conversions and the update shrink from n rows to 3, which is below the clock's
+    resolution either way); `grouped_minus_per_slice` against `compose_plus_reduce` and the legs' own spread says whether it
+    holds."""
+    from fetalsyngen_amd.generator.artifacts.svort import rigid, svr
+
+    rs, n_iter, G = a.res_slice / res, a.svr_iters, 3
+    out = {"volume": vs, "psf": list(psf.shape), "psf_taps": int((psf > 0).sum()), "iters": n_iter, "rounds": n_iter + 1, "groups": G,
+           "clock": f"rounds: device events around one solve / rounds, legs alternated three times; launches: device events around {a.reps}"}
+    for n in (80, 250):
+        np.random.seed(0)
+        tr = random_stack(n, gap=a.size * res / n / res, max_angle=0.3)
+        ax = rigid.mat2axisangle(tr).to(dev).float().contiguous()
+        y = K.slice_acq_forward(K.axisangle2mat(ax), vol, None, None, psf, (ss, ss), rs)
+        start = (ax + 0.01 * torch.randn_like(ax)).contiguous()
+        groups = (np.arange(n) * G // n).tolist()
+
+        def solve(g):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            torch.cuda.synchronize()
+            e0.record()
+            p = svr(start, y, vol, psf, rs, n_iter=n_iter, groups=g)
+            e1.record()
+            torch.cuda.synchronize()
+            return p, round(e0.elapsed_time(e1) / (n_iter + 1), 4)
+
+        solve(groups), solve(None)  # warm-up
+        row = {"grouped_round": [], "per_slice_round": []}
+        for _ in range(3):
+            row["grouped_round"].append(solve(groups)[1])
+            row["per_slice_round"].append(solve(None)[1])
+        base = K.axisangle2mat(start)
+        phi = 0.01 * torch.randn(G, 6, device=dev)
+        onehot = torch.eye(12, device=dev).repeat(G, 1).view(12 * G, 3, 4)
+        gm, gj = K.axisangle2mat(phi), K.axisangle2mat_backward(onehot, phi.repeat_interleave(12, 0).contiguous()).view(G, 12, 6)
+        gd = torch.tensor(groups, dtype=torch.int32, device=dev)
+        members = torch.arange(n, dtype=torch.int32, device=dev)
+        offsets = torch.tensor(np.searchsorted(groups, np.arange(G + 1)), dtype=torch.int32, device=dev)
+        buf = (torch.empty(n, 3, 4, device=dev), torch.empty(n, 12, 6, device=dev))
+        stats, gstats = torch.rand(n, K.SVR_SLOTS, dtype=torch.float64, device=dev), torch.empty(G, K.SVR_SLOTS, dtype=torch.float64, device=dev)
+        row["compose"] = [round(timed(lambda: K.svr_compose(gm, gj, base, gd, out=buf), a.reps), 4) for _ in range(3)]
+        row["group_reduce"] = [round(timed(lambda: K.svr_group_reduce(stats, members, offsets, out=gstats), a.reps), 4) for _ in range(3)]
+        best = {k: min(v) for k, v in row.items()}
+        row["slices"] = [n, ss, ss]
+        row["grouped_over_per_slice"] = round(best["grouped_round"] / best["per_slice_round"], 4)
+        row["grouped_minus_per_slice"] = round(best["grouped_round"] - best["per_slice_round"], 4)
+        row["compose_plus_reduce"] = round(best["compose"] + best["group_reduce"], 4)
+        row["spread_of_the_rounds"] = round(max(max(row[k]) - min(row[k]) for k in ("grouped_round", "per_slice_round")), 4)
+        p1, p2 = solve(groups)[0], solve(groups)[0]
+        row["poses_twice_equal"] = bool(torch.equal(p1, p2))
+        out[f"n{n}_ms"] = row
+    return out
+
+
 def robust_bench(a, dev, vs, ss, psf, vol, res):
     """--robust, n = 80 and 250.  One `svort.robust_weights` call (T = --robust-em: T + 1 pixel passes, T + 1 scalar passes, the
     weights) beside ONE iteration of the conjugate gradients of `svort.srr` (A, A^T in the float adjoint, q, step, dir), both by
@@ -467,6 +529,7 @@ def main():
     ap.add_argument("--srr-outer", type=int, default=1, help="rounds of the guided solve (n_outer)")
     ap.add_argument("--svr", action="store_true", help="time a round of svort.svr against a pose-fit iteration through autograd instead")
     ap.add_argument("--svr-iters", type=int, default=5, help="iterations per --svr solve (iters + 1 rounds)")
+    ap.add_argument("--svr-groups", action="store_true", help="time a round of svort.svr with 3 groups beside the per-slice round instead")
     ap.add_argument("--robust", action="store_true", help="time svort.robust_weights beside one CG iteration instead")
     ap.add_argument("--robust-em", type=int, default=5, help="EM iterations per --robust call (n_em)")
     ap.add_argument("--imatch", action="store_true", help="time svort.intensity_match beside one CG iteration instead")
@@ -481,6 +544,9 @@ def main():
         return
     if a.svr:
         print(json.dumps(svr_bench(a, dev, vs, ss, psf, torch.rand(vs, device=dev), res)))
+        return
+    if a.svr_groups:
+        print(json.dumps(svr_groups_bench(a, dev, vs, ss, psf, torch.rand(vs, device=dev), res)))
         return
     if a.robust:
         print(json.dumps(robust_bench(a, dev, vs, ss, psf, torch.rand(vs, device=dev), res)))
