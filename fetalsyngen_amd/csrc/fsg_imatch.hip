@@ -11,27 +11,26 @@
 //   fsg_imatch_apply_f32  the last pass: bias = b1 - mean, corrected = scale * expf(-bias) * y.
 //
 // MI355X shape of the work.  sums and apply are pure streaming: 256 threads that each own FOUR consecutive pixels of one slice,
-// 16-byte loads where the pointers allow, the workgroup fold of fsg_common.h.  The row pass is a workgroup per 256 pixels of one
-// row: its 256 + 2 Rr planes' values are formed once into 3 KiB of LDS (1.4 times the pixels at Rr = 48, 1.05 at Rr = 6), then
+// 16-byte loads where the pointers allow, the workgroup fold of fsg_common.h; their geometry, shape check, loads, stores and gate
+// and the fold of a slice's partials (N, A, B, min y, max y, 0, 0, 0) are fsg_pixels.h's, shared with fsg_robust.hip.
+// The row pass is a workgroup per 256 pixels of one row: its 256 + 2 Rr planes' values are formed once into 3 KiB of LDS (1.4 times the pixels at Rr = 48, 1.05 at Rr = 6), then
 // 2 Rr + 1 LDS reads and fmafs per plane and pixel.  The column pass is a tile of 64 rows by 32 columns (a wave reads two runs of
 // 128 bytes) with an Rr halo above and below over both planes in dynamic LDS, (64 + 2 Rr) * 32 * 8 bytes: 19 KiB at Rr = 6, 28 KiB
 // at 24, 40 KiB at 48, so three to eight workgroups share a CU's 160 KiB; a thread walks 8 rows of its column.  Fusing the two
 // passes would need a (T + 2 Rr)^2 tile of both planes: 128 KiB for T = 32 at Rr = 48, one workgroup a CU that computes nine
 // times the pixels it keeps, hence two launches and 12 bytes a pixel of planes between them.  No atomics anywhere.
+#include "fsg_pixels.h"
 #include "fsg_sa.h"
 #include <float.h>
 #include <math.h>
 
 namespace {
 
-constexpr int IM_THREADS = 256;
-constexpr int IM_CHUNK = 4 * IM_THREADS;  // pixels of one slice per workgroup of the streaming passes
-constexpr int IM_SLOTS = 8;               // floats of a partial of the sums: N, A, B, min y, max y, 0, 0, 0
+constexpr int IM_THREADS = PX_THREADS;    // of the bias field's kernels too
 constexpr int IM_MEAN_SLOTS = 2;          // floats of a partial of the means: sum omega b1, sum omega
 constexpr int IM_ROW_W = 256;             // pixels of one row per workgroup of the row pass
 constexpr int IM_TH = 64, IM_TW = 32;     // tile of the column pass
 constexpr int IM_TROWS = IM_THREADS / IM_TW;  // thread rows of the column pass: a thread walks IM_TH / IM_TROWS rows
-constexpr float IM_FLT_MAX = 3.402823466e+38f;
 static_assert(IM_THREADS == SA_TILE * SA_TILE, "the column pass folds with sa_fold");
 
 struct ImState {  // pointers into the state block for n slices; layout in fsg_hip.h, stated here once and measured by im_state_bytes
@@ -59,10 +58,9 @@ __host__ __device__ inline ImState im_state(void* p, size_t n) {
 }
 
 inline size_t im_state_bytes(size_t n) { return fsg_carved_bytes(fsg_origin, im_state(fsg_origin, n).end); }
-inline int im_chunks(int h, int w) { return (int)(((size_t)h * (size_t)w + IM_CHUNK - 1) / IM_CHUNK); }
 inline int im_tiles_x(int w) { return (w + IM_TW - 1) / IM_TW; }
 inline int im_tiles_y(int h) { return (h + IM_TH - 1) / IM_TH; }
-inline size_t im_sums_bytes(int n, int h, int w) { return (size_t)n * (size_t)im_chunks(h, w) * IM_SLOTS * sizeof(float); }
+inline size_t im_sums_bytes(int n, int h, int w) { return (size_t)n * (size_t)px_chunks(h, w) * PX_SLOTS * sizeof(float); }
 inline size_t im_means_bytes(int n, int h, int w) {
   return (size_t)n * (size_t)im_tiles_x(w) * (size_t)im_tiles_y(h) * IM_MEAN_SLOTS * sizeof(float);
 }
@@ -93,10 +91,9 @@ __device__ __forceinline__ ImPix im_pixel(const ImIn& I, float y, float s, bool 
   ImPix p;
   p.c = I.b0 ? expf(-b0) * y : y;
   p.om = I.pw ? pw : 1.f;
-  bool ok = mk;
-  if (I.sw) ok = ok && sw > 0.f && sw >= I.min_weight;  // a NaN weight takes no part
-  ok = ok && fabsf(y) <= IM_FLT_MAX && fabsf(s) <= IM_FLT_MAX && fabsf(p.c) <= IM_FLT_MAX;
-  if (I.pw) ok = ok && pw > 0.f && pw <= IM_FLT_MAX;
+  bool ok = px_gate(mk, I.sw != nullptr, sw, I.min_weight);
+  ok = ok && fabsf(y) <= PX_FLT_MAX && fabsf(s) <= PX_FLT_MAX && fabsf(p.c) <= PX_FLT_MAX;
+  if (I.pw) ok = ok && pw > 0.f && pw <= PX_FLT_MAX;
   p.part = ok;
   return p;
 }
@@ -107,30 +104,8 @@ __device__ __forceinline__ ImPix im_pixel_at(const ImIn& I, size_t a, float& s) 
 }
 
 template <bool VEC>
-__device__ __forceinline__ void im_load4(const float* __restrict__ p, size_t a, int cnt, float (&v)[4]) {
-  if (VEC) {
-    const float4 t = *reinterpret_cast<const float4*>(p + a);
-    v[0] = t.x; v[1] = t.y; v[2] = t.z; v[3] = t.w;
-  } else {
-#pragma unroll
-    for (int j = 0; j < 4; ++j) v[j] = j < cnt ? p[a + j] : 0.f;  // no address is formed past the end of the slice
-  }
-}
-
-template <bool VEC>
-__device__ __forceinline__ void im_store4(float* __restrict__ p, size_t a, int cnt, const float (&v)[4]) {
-  if (VEC) {
-    *reinterpret_cast<float4*>(p + a) = make_float4(v[0], v[1], v[2], v[3]);
-  } else {
-#pragma unroll
-    for (int j = 0; j < 4; ++j)
-      if (j < cnt) p[a + j] = v[j];
-  }
-}
-
-template <bool VEC>
 __global__ __launch_bounds__(IM_THREADS) void im_sums_kernel(ImIn I, float* __restrict__ ws) {
-  __shared__ float red[IM_THREADS / FSG_WAVE][IM_SLOTS];
+  __shared__ float red[IM_THREADS / FSG_WAVE][PX_SLOTS];
   const int k = blockIdx.y, tid = threadIdx.x;
   const int e0 = (blockIdx.x * IM_THREADS + tid) * 4;
   float v[FSG_IMATCH_ROW - 2] = {0.f, 0.f, 0.f};
@@ -140,26 +115,16 @@ __global__ __launch_bounds__(IM_THREADS) void im_sums_kernel(ImIn I, float* __re
     const int cnt = I.hw - e0 < 4 ? I.hw - e0 : 4;
     const size_t a = (size_t)k * I.hw + e0;
     float y[4], s[4], sw[4] = {0.f, 0.f, 0.f, 0.f}, pw[4] = {0.f, 0.f, 0.f, 0.f}, b0[4] = {0.f, 0.f, 0.f, 0.f};
-    uint32_t mk = 0x01010101u;
-    im_load4<VEC>(I.y, a, cnt, y);
-    im_load4<VEC>(I.s, a, cnt, s);
-    if (I.sw) im_load4<VEC>(I.sw, a, cnt, sw);
-    if (I.pw) im_load4<VEC>(I.pw, a, cnt, pw);
-    if (I.b0) im_load4<VEC>(I.b0, a, cnt, b0);
-    if (I.mask) {
-      if (VEC) {
-        mk = *reinterpret_cast<const uint32_t*>(I.mask + a);
-      } else {
-        mk = 0;
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-          if (j < cnt && I.mask[a + j] != 0) mk |= 1u << (8 * j);
-      }
-    }
+    px_load4<VEC>(I.y, a, cnt, y);
+    px_load4<VEC>(I.s, a, cnt, s);
+    if (I.sw) px_load4<VEC>(I.sw, a, cnt, sw);
+    if (I.pw) px_load4<VEC>(I.pw, a, cnt, pw);
+    if (I.b0) px_load4<VEC>(I.b0, a, cnt, b0);
+    const uint32_t mk = px_mask4<VEC>(I.mask, a, cnt);
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
       if (j >= cnt) continue;
-      const ImPix p = im_pixel(I, y[j], s[j], ((mk >> (8 * j)) & 255u) != 0, sw[j], pw[j], b0[j]);
+      const ImPix p = im_pixel(I, y[j], s[j], px_mask_bit(mk, j), sw[j], pw[j], b0[j]);
       if (!p.part) continue;
       const float t = I.pw ? p.om * p.c : p.c;
       v[0] += 1.f;
@@ -169,7 +134,7 @@ __global__ __launch_bounds__(IM_THREADS) void im_sums_kernel(ImIn I, float* __re
       mx = fmaxf(mx, y[j]);
     }
   }
-  fsg_fold_sums_minmax<FSG_IMATCH_ROW - 2, IM_SLOTS, IM_THREADS>(v, mn, mx, red, ws + ((size_t)k * gridDim.x + blockIdx.x) * IM_SLOTS);
+  fsg_fold_sums_minmax<FSG_IMATCH_ROW - 2, PX_SLOTS, IM_THREADS>(v, mn, mx, red, ws + ((size_t)k * gridDim.x + blockIdx.x) * PX_SLOTS);
 }
 
 // One workgroup.  Phase A, a thread per slice: the row, own_k and raw_k.  Phase B, wave 0: R, the gauge (the wave-walk of
@@ -180,22 +145,15 @@ __global__ __launch_bounds__(IM_THREADS) void im_scale_kernel(void* state, const
   const ImState S = im_state(state, (size_t)n);
   const int tid = threadIdx.x;
   for (int k = tid; k < n; k += IM_THREADS) {
-    const float* p = ws + (size_t)k * chunks * IM_SLOTS;
-    double r[3] = {0.0, 0.0, 0.0}, mn = INFINITY, mx = -INFINITY;
-    for (int b = 0; b < chunks; ++b) {
-#pragma unroll
-      for (int j = 0; j < 3; ++j) r[j] = r[j] + (double)p[(size_t)b * IM_SLOTS + j];
-      mn = fmin(mn, (double)p[(size_t)b * IM_SLOTS + 3]);
-      mx = fmax(mx, (double)p[(size_t)b * IM_SLOTS + 4]);
-    }
-    const bool any = r[0] > 0.0;  // a slice without a pixel stores no Inf
+    double r[FSG_IMATCH_ROW - 2], mn, mx;
+    const bool any = px_fold_slice(ws + (size_t)k * chunks * PX_SLOTS, chunks, r, mn, mx);
     double* row = S.rows + (size_t)k * FSG_IMATCH_ROW;
     const bool sums_ok = fsg_finite(r[1]) && fsg_finite(r[2]);
     row[0] = r[0];
     row[1] = sums_ok ? r[1] : 0.0;
     row[2] = sums_ok ? r[2] : 0.0;
-    row[3] = any ? mn : 0.0;
-    row[4] = any ? mx : 0.0;
+    row[3] = mn;
+    row[4] = mx;
     const double q = r[1] / r[2];
     const bool own = r[0] >= (double)min_pixels && any && sums_ok && r[1] > 0.0 && r[2] > 0.0 && fsg_finite(q);
     S.raw[k] = own ? q : 0.0;
@@ -203,16 +161,8 @@ __global__ __launch_bounds__(IM_THREADS) void im_scale_kernel(void* state, const
   }
   __syncthreads();
   if (tid < FSG_WAVE) {
-    double mn = INFINITY, mx = -INFINITY;  // min and max do not depend on the order
-    for (int k = tid; k < n; k += FSG_WAVE) {
-      const double* row = S.rows + (size_t)k * FSG_IMATCH_ROW;
-      if (row[0] > 0.0) { mn = fmin(mn, row[3]); mx = fmax(mx, row[4]); }
-    }
-#pragma unroll
-    for (int o = FSG_WAVE / 2; o > 0; o >>= 1) {
-      mn = fmin(mn, __shfl_xor(mn, o, FSG_WAVE));
-      mx = fmax(mx, __shfl_xor(mx, o, FSG_WAVE));
-    }
+    double mn, mx;
+    px_wave_range<FSG_IMATCH_ROW>(S.rows, n, mn, mx);
     const double R = mx - mn, floor_ = log_floor * R;
     double sum = 0.0, nok = 0.0;
     for (int base = 0; base < n; base += FSG_WAVE) {
@@ -233,7 +183,7 @@ __global__ __launch_bounds__(IM_THREADS) void im_scale_kernel(void* state, const
     if (!frozen)
       for (int k = tid; k < n; k += FSG_WAVE) {
         const float sc = (float)(S.raw[k] / g);
-        if (S.ok[k] != 0 && !(sc > 0.f && sc <= IM_FLT_MAX)) bad = 1;
+        if (S.ok[k] != 0 && !(sc > 0.f && sc <= PX_FLT_MAX)) bad = 1;
       }
 #pragma unroll
     for (int o = FSG_WAVE / 2; o > 0; o >>= 1) bad |= __shfl_xor(bad, o, FSG_WAVE);
@@ -280,7 +230,7 @@ __global__ __launch_bounds__(IM_THREADS) void im_rows_kernel(ImIn I, ImTaps T, i
       const float d = scale * x.c;
       if (x.part && d > floor_ && s > floor_) {
         const float r = logf(d / s);
-        if (fabsf(r) <= IM_FLT_MAX) {
+        if (fabsf(r) <= PX_FLT_MAX) {
           p = I.pw ? x.om * r : r;
           q = x.om;
         }
@@ -382,31 +332,17 @@ __global__ __launch_bounds__(IM_THREADS) void im_apply_kernel(const float* __res
   const int cnt = hw - e0 < 4 ? hw - e0 : 4;
   const size_t a = (size_t)k * hw + e0;
   float yy[4], b[4] = {0.f, 0.f, 0.f, 0.f}, o[4];
-  im_load4<VEC>(y, a, cnt, yy);
-  if (with_bias) im_load4<VEC>(bias, a, cnt, b);
-  else if (b0) im_load4<VEC>(b0, a, cnt, b);
+  px_load4<VEC>(y, a, cnt, yy);
+  if (with_bias) px_load4<VEC>(bias, a, cnt, b);
+  else if (b0) px_load4<VEC>(b0, a, cnt, b);
 #pragma unroll
   for (int j = 0; j < 4; ++j) {
     if (shift) b[j] = b[j] - m;
     const float c = expf(-b[j]) * yy[j];
     o[j] = scale * c;
   }
-  im_store4<VEC>(bias, a, cnt, b);
-  im_store4<VEC>(corrected, a, cnt, o);
-}
-
-bool im_vec(int hw, const void* a, const void* b, const void* c, const void* d, const void* e, const void* f, const uint8_t* mask) {
-  return hw % 4 == 0 && !(((uintptr_t)a | (uintptr_t)b | (uintptr_t)c | (uintptr_t)d | (uintptr_t)e | (uintptr_t)f) & 15) &&
-         !((uintptr_t)mask & 3);
-}
-
-int im_check_shape(int n, int h, int w) {
-  if (n <= 0 || h <= 0 || w <= 0) return FSG_E_BADARG;
-  if (n > 65535 || (size_t)n * (size_t)h * (size_t)w > (size_t)0x7FFFFFFF) return FSG_E_TOOBIG;
-  // the streaming passes count a slice's pixels in int, a workgroup of IM_CHUNK at a time: the last workgroup's first index stays
-  // representable
-  if ((size_t)h * (size_t)w > (size_t)0x7FFFFFFF - IM_CHUNK) return FSG_E_TOOBIG;
-  return 0;
+  px_store4<VEC>(bias, a, cnt, b);
+  px_store4<VEC>(corrected, a, cnt, o);
 }
 
 // what sums and bias share: sizes, the pixel arrays and their alignment
@@ -414,17 +350,15 @@ int im_check_pixels(const float* y, const float* s, const float* sw, float min_w
                     int h, int w) {
   if (n <= 0 || h <= 0 || w <= 0 || !y || !s) return FSG_E_BADARG;
   if (!(min_weight >= 0.f)) return FSG_E_BADARG;  // negative or NaN
-  const int rc = im_check_shape(n, h, w);
+  const int rc = px_check_shape(n, h, w);
   if (rc) return rc;
   if (((uintptr_t)y | (uintptr_t)s | (uintptr_t)sw | (uintptr_t)pw | (uintptr_t)b0) & 3) return FSG_E_ALIGN;
   return 0;
 }
 
 // `p` shares a byte with one of the six pixel arrays of a call
-bool im_hits_inputs(const void* p, size_t bytes, const float* y, const float* s, const uint8_t* mask, const float* sw,
-                    const float* pw, const float* b0, size_t pix) {
-  return fsg_overlap(p, bytes, y, pix * 4) || fsg_overlap(p, bytes, s, pix * 4) || fsg_overlap(p, bytes, mask, pix) ||
-         fsg_overlap(p, bytes, sw, pix * 4) || fsg_overlap(p, bytes, pw, pix * 4) || fsg_overlap(p, bytes, b0, pix * 4);
+bool im_hits_inputs(const void* p, size_t bytes, const ImIn& I, size_t pix) {
+  return px_hits(p, bytes, {{I.y, pix * 4}, {I.s, pix * 4}, {I.mask, pix}, {I.sw, pix * 4}, {I.pw, pix * 4}, {I.b0, pix * 4}});
 }
 
 }  // namespace
@@ -432,7 +366,7 @@ bool im_hits_inputs(const void* p, size_t bytes, const float* y, const float* s,
 extern "C" {
 
 size_t fsg_imatch_ws_bytes(int n, int h, int w) {
-  if (im_check_shape(n, h, w)) return 0;
+  if (px_check_shape(n, h, w)) return 0;
   return im_sums_bytes(n, h, w) + im_means_bytes(n, h, w);
 }
 
@@ -442,7 +376,7 @@ size_t fsg_imatch_state_bytes(int n) {
 }
 
 size_t fsg_imatch_plane_bytes(int n, int h, int w) {
-  if (im_check_shape(n, h, w)) return 0;
+  if (px_check_shape(n, h, w)) return 0;
   return (size_t)n * (size_t)h * (size_t)w * 3 * sizeof(float);
 }
 
@@ -454,12 +388,11 @@ int fsg_imatch_sums_f32(const float* y, const float* s, const uint8_t* slices_ma
   if (rc) return rc;
   if (!ws || ws_bytes < fsg_imatch_ws_bytes(n, h, w)) return FSG_E_BADARG;
   if ((uintptr_t)ws & 7) return FSG_E_ALIGN;
-  const size_t pix = (size_t)n * h * w;
-  if (im_hits_inputs(ws, fsg_imatch_ws_bytes(n, h, w), y, s, slices_mask, sim_weight, pix_weight, bias0, pix)) return FSG_E_BADARG;
   const ImIn I{y, s, slices_mask, sim_weight, pix_weight, bias0, min_weight, h * w};
-  const dim3 grid((unsigned)im_chunks(h, w), (unsigned)n);
+  if (im_hits_inputs(ws, fsg_imatch_ws_bytes(n, h, w), I, (size_t)n * h * w)) return FSG_E_BADARG;
+  const dim3 grid((unsigned)px_chunks(h, w), (unsigned)n);
   hipStream_t st = fsg_stream(stream);
-  if (im_vec(h * w, y, s, sim_weight, pix_weight, bias0, nullptr, slices_mask))
+  if (px_vec(h * w, {y, s, sim_weight, pix_weight, bias0}, slices_mask))
     hipLaunchKernelGGL(im_sums_kernel<true>, grid, dim3(IM_THREADS), 0, st, I, (float*)ws);
   else
     hipLaunchKernelGGL(im_sums_kernel<false>, grid, dim3(IM_THREADS), 0, st, I, (float*)ws);
@@ -469,13 +402,13 @@ int fsg_imatch_sums_f32(const float* y, const float* s, const uint8_t* slices_ma
 int fsg_imatch_scale_f32(void* state, size_t state_bytes, const void* ws, size_t ws_bytes, int n, int h, int w, double log_floor,
                          int min_pixels, void* stream) {
   if (n <= 0 || h <= 0 || w <= 0 || !state || !ws) return FSG_E_BADARG;
-  const int rc = im_check_shape(n, h, w);
+  const int rc = px_check_shape(n, h, w);
   if (rc) return rc;
   if (state_bytes < im_state_bytes((size_t)n) || ws_bytes < fsg_imatch_ws_bytes(n, h, w)) return FSG_E_BADARG;
   if (!(log_floor >= 0.0 && log_floor <= 1.7976931348623157e308) || min_pixels < 0) return FSG_E_BADARG;
   if (((uintptr_t)state & 7) || ((uintptr_t)ws & 7)) return FSG_E_ALIGN;
   if (fsg_overlap(state, im_state_bytes((size_t)n), ws, fsg_imatch_ws_bytes(n, h, w))) return FSG_E_BADARG;
-  hipLaunchKernelGGL(im_scale_kernel, dim3(1), dim3(IM_THREADS), 0, fsg_stream(stream), state, (const float*)ws, im_chunks(h, w), n,
+  hipLaunchKernelGGL(im_scale_kernel, dim3(1), dim3(IM_THREADS), 0, fsg_stream(stream), state, (const float*)ws, px_chunks(h, w), n,
                      log_floor, min_pixels);
   FSG_RETURN_LAUNCH();
 }
@@ -492,10 +425,11 @@ int fsg_imatch_bias_f32(const float* y, const float* s, const uint8_t* slices_ma
   const size_t pix = (size_t)n * h * w, stb = im_state_bytes((size_t)n), wsb = fsg_imatch_ws_bytes(n, h, w), plb = pix * 12;
   if (state_bytes < stb || ws_bytes < wsb || plane_bytes < plb) return FSG_E_BADARG;
   if (((uintptr_t)state & 7) || ((uintptr_t)ws & 7) || ((uintptr_t)planes & 15) || ((uintptr_t)bias & 3)) return FSG_E_ALIGN;
+  const ImIn I{y, s, slices_mask, sim_weight, pix_weight, bias0, min_weight, h * w};
   const void* outs[4] = {state, planes, ws, bias};
   const size_t outb[4] = {stb, plb, wsb, pix * 4};
   for (int a = 0; a < 4; ++a) {
-    if (im_hits_inputs(outs[a], outb[a], y, s, slices_mask, sim_weight, pix_weight, bias0, pix)) return FSG_E_BADARG;
+    if (im_hits_inputs(outs[a], outb[a], I, pix)) return FSG_E_BADARG;
     for (int b = a + 1; b < 4; ++b)
       if (fsg_overlap(outs[a], outb[a], outs[b], outb[b])) return FSG_E_BADARG;
   }
@@ -503,7 +437,6 @@ int fsg_imatch_bias_f32(const float* y, const float* s, const uint8_t* slices_ma
   T.R = (int)ceil(3.0 * sigma);
   T.g[0] = 1.f;  // exp(-0), also for a sigma whose square underflows
   for (int t = 1; t <= FSG_IMATCH_MAX_RADIUS; ++t) T.g[t] = t <= T.R ? (float)exp(-(double)(t * t) / (2.0 * sigma * sigma)) : 0.f;
-  const ImIn I{y, s, slices_mask, sim_weight, pix_weight, bias0, min_weight, h * w};
   float* P1 = (float*)planes;
   float* Q1 = P1 + pix;
   float* Q0 = Q1 + pix;
@@ -523,22 +456,19 @@ int fsg_imatch_apply_f32(const float* y, const float* bias0, int mode, int n, in
                          size_t state_bytes, float* bias, float* corrected, void* stream) {
   if (n <= 0 || h <= 0 || w <= 0 || !y || !state || !bias || !corrected) return FSG_E_BADARG;
   if (mode != FSG_IMATCH_SCALE_ONLY && mode != FSG_IMATCH_WITH_BIAS) return FSG_E_BADARG;
-  const int rc = im_check_shape(n, h, w);
+  const int rc = px_check_shape(n, h, w);
   if (rc) return rc;
   const size_t pix = (size_t)n * h * w, stb = im_state_bytes((size_t)n);
   if (state_bytes < stb) return FSG_E_BADARG;
   if (((uintptr_t)y | (uintptr_t)bias0 | (uintptr_t)bias | (uintptr_t)corrected) & 3) return FSG_E_ALIGN;
   if ((uintptr_t)state & 7) return FSG_E_ALIGN;
-  const void* outs[2] = {bias, corrected};
-  for (int a = 0; a < 2; ++a)
-    if (fsg_overlap(outs[a], pix * 4, y, pix * 4) || fsg_overlap(outs[a], pix * 4, bias0, pix * 4) ||
-        fsg_overlap(outs[a], pix * 4, state, stb))
-      return FSG_E_BADARG;
+  for (const void* out : {(const void*)bias, (const void*)corrected})
+    if (px_hits(out, pix * 4, {{y, pix * 4}, {bias0, pix * 4}, {state, stb}})) return FSG_E_BADARG;
   if (fsg_overlap(bias, pix * 4, corrected, pix * 4)) return FSG_E_BADARG;
-  const dim3 grid((unsigned)im_chunks(h, w), (unsigned)n);
+  const dim3 grid((unsigned)px_chunks(h, w), (unsigned)n);
   hipStream_t st = fsg_stream(stream);
   const int with_bias = mode == FSG_IMATCH_WITH_BIAS ? 1 : 0;
-  if (im_vec(h * w, y, bias0, bias, corrected, nullptr, nullptr, nullptr))
+  if (px_vec(h * w, {y, bias0, bias, corrected}, nullptr))
     hipLaunchKernelGGL(im_apply_kernel<true>, grid, dim3(IM_THREADS), 0, st, y, bias0, with_bias, h * w, n, state, bias, corrected);
   else
     hipLaunchKernelGGL(im_apply_kernel<false>, grid, dim3(IM_THREADS), 0, st, y, bias0, with_bias, h * w, n, state, bias, corrected);

@@ -13,17 +13,13 @@
 // VGPRs: occupancy is not the limit, HBM is.  No atomics: fixed shuffle tree per wave, waves in order, one 8-float partial per
 // workgroup in a workspace that needs no zeroing, a slice's partials added in double in index order by the update.
 // The iteration cap and the width of a slice's row are the header's (FSG_SOLVER_MAX_ITER, FSG_ROBUST_ROW); the overlap and
-// finite tests, the measuring of the state block and the workgroup fold (fsg_fold_sums_minmax, shared with fsg_imatch.hip) are
-// fsg_common.h's.
-#include "fsg_common.h"
+// finite tests, the measuring of the state block and the workgroup fold are fsg_common.h's; the streaming geometry, the shape
+// check, the 4-pixel loads and stores, the gate and the fold of a slice's partials (N, sum p, sum p e^2, sum (1-p)^2, min y,
+// max y, 0, 0) are fsg_pixels.h's, shared with fsg_imatch.hip.
+#include "fsg_pixels.h"
 #include <math.h>
 
 namespace {
-
-constexpr int RB_THREADS = 256;
-constexpr int RB_CHUNK = 4 * RB_THREADS;  // pixels of one slice per workgroup
-constexpr int RB_SLOTS = 8;               // floats of a partial: N, sum p, sum p e^2, sum (1-p)^2, min y, max y, 0, 0
-constexpr float RB_FLT_MAX = 3.402823466e+38f;
 
 struct RbState {  // pointers into the state block for (n, T); layout in fsg_hip.h, stated here once by rb_state and measured by rb_state_bytes
   double* consts;   // [4] R, m, sigma_min, 0
@@ -58,8 +54,6 @@ __host__ __device__ inline RbState rb_state(void* p, size_t n, int T) {
 
 inline size_t rb_state_bytes(size_t n, int T) { return fsg_carved_bytes(fsg_origin, rb_state(fsg_origin, n, T).end); }
 
-inline int rb_chunks(int h, int w) { return (int)(((size_t)h * (size_t)w + RB_CHUNK - 1) / RB_CHUNK); }
-
 struct RbIn {
   const float* y;
   const float* s;
@@ -74,52 +68,32 @@ struct RbIn {
 template <bool VEC>
 __device__ __forceinline__ void rb_load(const RbIn& I, size_t base, int e0, float (&y)[4], float (&e)[4], bool (&part)[4]) {
   const int cnt = I.hw - e0 < 4 ? I.hw - e0 : 4;  // >= 1 for a thread that is called
-  float s[4], wg[4];
-  uint32_t mk = 0x01010101u;
-  if (VEC) {  // hw % 4 == 0, so cnt == 4
-    const float4 ty = *reinterpret_cast<const float4*>(I.y + base + e0);
-    const float4 ts = *reinterpret_cast<const float4*>(I.s + base + e0);
-    y[0] = ty.x; y[1] = ty.y; y[2] = ty.z; y[3] = ty.w;
-    s[0] = ts.x; s[1] = ts.y; s[2] = ts.z; s[3] = ts.w;
-    if (I.mask) mk = *reinterpret_cast<const uint32_t*>(I.mask + base + e0);
-    if (I.sw) {
-      const float4 tw = *reinterpret_cast<const float4*>(I.sw + base + e0);
-      wg[0] = tw.x; wg[1] = tw.y; wg[2] = tw.z; wg[3] = tw.w;
-    }
-  } else {
-    mk = 0;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const bool in = j < cnt;
-      const size_t a = base + e0 + (in ? j : 0);
-      y[j] = in ? I.y[a] : 0.f;
-      s[j] = in ? I.s[a] : 0.f;
-      wg[j] = (in && I.sw) ? I.sw[a] : 0.f;
-      const uint32_t b = !in ? 0u : (I.mask ? (I.mask[a] != 0 ? 1u : 0u) : 1u);
-      mk |= b << (8 * j);
-    }
-  }
+  const size_t a = base + e0;
+  float s[4], wg[4] = {0.f, 0.f, 0.f, 0.f};
+  px_load4<VEC>(I.y, a, cnt, y);
+  px_load4<VEC>(I.s, a, cnt, s);
+  if (I.sw) px_load4<VEC>(I.sw, a, cnt, wg);
+  const uint32_t mk = px_mask4<VEC>(I.mask, a, cnt);
 #pragma unroll
   for (int j = 0; j < 4; ++j) {
     e[j] = y[j] - s[j];
-    bool ok = j < cnt && ((mk >> (8 * j)) & 255u) != 0;
-    if (I.sw) ok = ok && wg[j] > 0.f && wg[j] >= I.min_weight;  // a NaN weight takes no part
-    part[j] = ok && fabsf(e[j]) <= RB_FLT_MAX;                  // NaN and Inf fail
+    const bool ok = j < cnt && px_gate(px_mask_bit(mk, j), I.sw != nullptr, wg[j], I.min_weight);
+    part[j] = ok && fabsf(e[j]) <= PX_FLT_MAX;  // NaN and Inf fail
   }
 }
 
 // p = 1 / (1 + kappa * expf(e^2 * inv2var)), one rounding per operation; an overflowing expf gives 0
 __device__ __forceinline__ float rb_posterior(float e2, float kappa, float inv2var) {
   const float x = expf(e2 * inv2var);
-  return x <= RB_FLT_MAX ? 1.f / (1.f + kappa * x) : 0.f;
+  return x <= PX_FLT_MAX ? 1.f / (1.f + kappa * x) : 0.f;
 }
 
 template <bool VEC>
-__global__ __launch_bounds__(RB_THREADS) void rb_estep_kernel(RbIn I, int n, int T, int first, const void* state,
+__global__ __launch_bounds__(PX_THREADS) void rb_estep_kernel(RbIn I, int n, int T, int first, const void* state,
                                                               float* __restrict__ ws) {
-  __shared__ float red[RB_THREADS / FSG_WAVE][RB_SLOTS];
+  __shared__ float red[PX_THREADS / FSG_WAVE][PX_SLOTS];
   const int k = blockIdx.y, tid = threadIdx.x;
-  const int e0 = (blockIdx.x * RB_THREADS + tid) * 4;
+  const int e0 = (blockIdx.x * PX_THREADS + tid) * 4;
   float v[4] = {0.f, 0.f, 0.f, 0.f};
   float mn = INFINITY, mx = -INFINITY;
   // no thread leaves before the fold
@@ -143,7 +117,7 @@ __global__ __launch_bounds__(RB_THREADS) void rb_estep_kernel(RbIn I, int n, int
       mx = fmaxf(mx, y[j]);
     }
   }
-  fsg_fold_sums_minmax<FSG_ROBUST_ROW - 2, RB_SLOTS, RB_THREADS>(v, mn, mx, red, ws + ((size_t)k * gridDim.x + blockIdx.x) * RB_SLOTS);
+  fsg_fold_sums_minmax<FSG_ROBUST_ROW - 2, PX_SLOTS, PX_THREADS>(v, mn, mx, red, ws + ((size_t)k * gridDim.x + blockIdx.x) * PX_SLOTS);
 }
 
 struct RbOpts {
@@ -158,28 +132,21 @@ __device__ __forceinline__ double rb_normal_pdf(double u, double mu, double v) {
 
 // One workgroup.  Phase A, a thread per slice: the row and u.  Phase B, wave 0: every sum over the slices, in slice-index
 // order.  Phase C, a thread per slice: the new slice weight.
-__global__ __launch_bounds__(RB_THREADS) void rb_update_kernel(void* state, const float* __restrict__ ws, int chunks, int n, int t,
+__global__ __launch_bounds__(PX_THREADS) void rb_update_kernel(void* state, const float* __restrict__ ws, int chunks, int n, int t,
                                                                int T, RbOpts O) {
   __shared__ double sh[6];  // frozen, mu1, mu2, v1, v2, mix
   const RbState S = rb_state(state, (size_t)n, T);
   const int tid = threadIdx.x;
   const double* wold = t > 0 ? S.ws + (size_t)(t - 1) * n : nullptr;
   double* wnew = S.ws + (size_t)t * n;
-  for (int k = tid; k < n; k += RB_THREADS) {
-    const float* p = ws + (size_t)k * chunks * RB_SLOTS;
-    double r[4] = {0.0, 0.0, 0.0, 0.0}, mn = INFINITY, mx = -INFINITY;
-    for (int b = 0; b < chunks; ++b) {
-#pragma unroll
-      for (int j = 0; j < 4; ++j) r[j] = r[j] + (double)p[(size_t)b * RB_SLOTS + j];
-      mn = fmin(mn, (double)p[(size_t)b * RB_SLOTS + 4]);
-      mx = fmax(mx, (double)p[(size_t)b * RB_SLOTS + 5]);
-    }
-    const bool any = r[0] > 0.0;  // a slice without a pixel stores no Inf
+  for (int k = tid; k < n; k += PX_THREADS) {
+    double r[FSG_ROBUST_ROW - 2], mn, mx;
+    const bool any = px_fold_slice(ws + (size_t)k * chunks * PX_SLOTS, chunks, r, mn, mx);
     double* row = S.rows + (size_t)k * FSG_ROBUST_ROW;
 #pragma unroll
-    for (int j = 0; j < 4; ++j) row[j] = r[j];
-    row[4] = any ? mn : 0.0;
-    row[5] = any ? mx : 0.0;
+    for (int j = 0; j < FSG_ROBUST_ROW - 2; ++j) row[j] = r[j];
+    row[FSG_ROBUST_ROW - 2] = mn;
+    row[FSG_ROBUST_ROW - 1] = mx;
     const bool ok = r[0] >= (double)O.min_pixels && any;
     S.u[k] = ok ? sqrt(r[3] / r[0]) : 0.0;
   }
@@ -191,16 +158,8 @@ __global__ __launch_bounds__(RB_THREADS) void rb_update_kernel(void* state, cons
     bool frozen = t > 0 && S.frozen[t - 1] != 0;
     double m, smin;
     if (t == 0) {
-      double mn = INFINITY, mx = -INFINITY;  // min and max do not depend on the order
-      for (int k = tid; k < n; k += FSG_WAVE) {
-        const double* row = S.rows + (size_t)k * FSG_ROBUST_ROW;
-        if (row[0] > 0.0) { mn = fmin(mn, row[4]); mx = fmax(mx, row[5]); }
-      }
-#pragma unroll
-      for (int o = FSG_WAVE / 2; o > 0; o >>= 1) {
-        mn = fmin(mn, __shfl_xor(mn, o, FSG_WAVE));
-        mx = fmax(mx, __shfl_xor(mx, o, FSG_WAVE));
-      }
+      double mn, mx;
+      px_wave_range<FSG_ROBUST_ROW>(S.rows, n, mn, mx);
       const double R = mx - mn;
       const bool good = fsg_finite(R) && R > 0.0 && fsg_finite(1.0 / R);
       if (tid == 0) {
@@ -247,7 +206,7 @@ __global__ __launch_bounds__(RB_THREADS) void rb_update_kernel(void* state, cons
     const double kappa = ((1.0 - c) / c) * m * sqrt(6.283185307179586 * var), inv2var = 1.0 / (2.0 * var);
     const float kf = (float)kappa, vf = (float)inv2var;
     frozen = frozen || !(Nw > 0.0) || !(S0 > 0.0) || !fsg_finite(S2) || !fsg_finite(var) || !(var > 0.0) || !fsg_finite(c) ||
-             !(fabsf(kf) <= RB_FLT_MAX) || !(fabsf(vf) <= RB_FLT_MAX) || !(kf >= 0.f);
+             !(fabsf(kf) <= PX_FLT_MAX) || !(fabsf(vf) <= PX_FLT_MAX) || !(kf >= 0.f);
     double mu1 = 0.0, mu2 = 0.0, v1 = 0.0, v2 = 0.0, mix = 1.0;
     if (t > 0 && !frozen) {  // wave-uniform
       const double fl2 = O.slice_floor * O.slice_floor;
@@ -287,7 +246,7 @@ __global__ __launch_bounds__(RB_THREADS) void rb_update_kernel(void* state, cons
   __syncthreads();
   const bool frozen = sh[0] != 0.0;
   const double mu1 = sh[1], mu2 = sh[2], v1 = sh[3], v2 = sh[4], mix = sh[5];
-  for (int k = tid; k < n; k += RB_THREADS) {
+  for (int k = tid; k < n; k += PX_THREADS) {
     const double N = S.rows[(size_t)k * FSG_ROBUST_ROW];
     const bool ok = N >= (double)O.min_pixels && N > 0.0;
     double w = ok ? 1.0 : 0.0;
@@ -307,10 +266,10 @@ __global__ __launch_bounds__(RB_THREADS) void rb_update_kernel(void* state, cons
 }
 
 template <bool VEC>
-__global__ __launch_bounds__(RB_THREADS) void rb_weights_kernel(RbIn I, int n, int T, int both, const void* state,
+__global__ __launch_bounds__(PX_THREADS) void rb_weights_kernel(RbIn I, int n, int T, int both, const void* state,
                                                                 float* __restrict__ out) {
   const int k = blockIdx.y;
-  const int e0 = (blockIdx.x * RB_THREADS + threadIdx.x) * 4;
+  const int e0 = (blockIdx.x * PX_THREADS + threadIdx.x) * 4;
   if (e0 >= I.hw) return;
   const RbState S = rb_state(const_cast<void*>(state), (size_t)n, T);
   const float wk = (float)S.ws[(size_t)T * n + k], kappa = S.scal[0], inv2var = S.scal[1];
@@ -324,14 +283,7 @@ __global__ __launch_bounds__(RB_THREADS) void rb_weights_kernel(RbIn I, int n, i
     if (part[j]) v = both ? wk * rb_posterior(e[j] * e[j], kappa, inv2var) : wk;
     o[j] = v;
   }
-  if (VEC) {
-    *reinterpret_cast<float4*>(out + base + e0) = make_float4(o[0], o[1], o[2], o[3]);
-  } else {
-    const int cnt = I.hw - e0 < 4 ? I.hw - e0 : 4;
-#pragma unroll
-    for (int j = 0; j < 4; ++j)
-      if (j < cnt) out[base + e0 + j] = o[j];
-  }
+  px_store4<VEC>(out, base + e0, I.hw - e0 < 4 ? I.hw - e0 : 4, o);
 }
 
 // what estep and weights share: sizes, pointers, options, the state and its alignment
@@ -340,16 +292,17 @@ int rb_check_pixels(const float* y, const float* s, const float* sw, float min_w
   if (n <= 0 || h <= 0 || w <= 0 || n_em < 1 || n_em > FSG_SOLVER_MAX_ITER) return FSG_E_BADARG;
   if (!y || !s || !state) return FSG_E_BADARG;
   if (!(min_weight >= 0.f)) return FSG_E_BADARG;  // negative or NaN
-  if (n > 65535 || (size_t)n * (size_t)h * (size_t)w > (size_t)0x7FFFFFFF) return FSG_E_TOOBIG;
+  const int rc = px_check_shape(n, h, w);
+  if (rc) return rc;
   if (state_bytes < rb_state_bytes((size_t)n, n_em)) return FSG_E_BADARG;
   if (((uintptr_t)y & 3) || ((uintptr_t)s & 3) || ((uintptr_t)sw & 3)) return FSG_E_ALIGN;
   if ((uintptr_t)state & 7) return FSG_E_ALIGN;
   return 0;
 }
 
-bool rb_vec(const RbIn& I, const float* out) {
-  return I.hw % 4 == 0 && !((uintptr_t)I.y & 15) && !((uintptr_t)I.s & 15) && !((uintptr_t)I.sw & 15) && !((uintptr_t)I.mask & 3) &&
-         !((uintptr_t)out & 15);
+// `p` shares a byte with one of the pixel arrays of a call or with the state
+bool rb_hits_inputs(const void* p, size_t bytes, const RbIn& I, size_t pix, const void* state, size_t state_bytes) {
+  return px_hits(p, bytes, {{I.y, pix * 4}, {I.s, pix * 4}, {I.sw, pix * 4}, {I.mask, pix}, {state, state_bytes}});
 }
 
 }  // namespace
@@ -357,8 +310,8 @@ bool rb_vec(const RbIn& I, const float* out) {
 extern "C" {
 
 size_t fsg_robust_ws_bytes(int n, int h, int w) {
-  if (n <= 0 || h <= 0 || w <= 0 || (size_t)n * (size_t)h * (size_t)w > (size_t)0x7FFFFFFF) return 0;
-  return (size_t)n * (size_t)rb_chunks(h, w) * RB_SLOTS * sizeof(float);
+  if (px_check_shape(n, h, w)) return 0;
+  return (size_t)n * (size_t)px_chunks(h, w) * PX_SLOTS * sizeof(float);
 }
 
 size_t fsg_robust_state_bytes(int n, int n_em) {
@@ -375,24 +328,22 @@ int fsg_robust_estep_f32(const float* y, const float* s, const uint8_t* slices_m
   if (t < 0 || t > n_em) return FSG_E_BADARG;
   if (!ws || ws_bytes < fsg_robust_ws_bytes(n, h, w)) return FSG_E_BADARG;
   if ((uintptr_t)ws & 7) return FSG_E_ALIGN;
-  const size_t pix = (size_t)n * h * w, wsb = fsg_robust_ws_bytes(n, h, w), stb = rb_state_bytes((size_t)n, n_em);
-  if (fsg_overlap(ws, wsb, y, pix * 4) || fsg_overlap(ws, wsb, s, pix * 4) || fsg_overlap(ws, wsb, sim_weight, pix * 4) ||
-      fsg_overlap(ws, wsb, slices_mask, pix) || fsg_overlap(ws, wsb, state, stb))
-    return FSG_E_BADARG;
   const RbIn I{y, s, slices_mask, sim_weight, min_weight, h * w};
-  const dim3 grid((unsigned)rb_chunks(h, w), (unsigned)n);
+  if (rb_hits_inputs(ws, fsg_robust_ws_bytes(n, h, w), I, (size_t)n * h * w, state, rb_state_bytes((size_t)n, n_em))) return FSG_E_BADARG;
+  const dim3 grid((unsigned)px_chunks(h, w), (unsigned)n);
   hipStream_t st = fsg_stream(stream);
-  if (rb_vec(I, nullptr))
-    hipLaunchKernelGGL(rb_estep_kernel<true>, grid, dim3(RB_THREADS), 0, st, I, n, n_em, t == 0 ? 1 : 0, state, (float*)ws);
+  if (px_vec(I.hw, {y, s, sim_weight}, slices_mask))
+    hipLaunchKernelGGL(rb_estep_kernel<true>, grid, dim3(PX_THREADS), 0, st, I, n, n_em, t == 0 ? 1 : 0, state, (float*)ws);
   else
-    hipLaunchKernelGGL(rb_estep_kernel<false>, grid, dim3(RB_THREADS), 0, st, I, n, n_em, t == 0 ? 1 : 0, state, (float*)ws);
+    hipLaunchKernelGGL(rb_estep_kernel<false>, grid, dim3(PX_THREADS), 0, st, I, n, n_em, t == 0 ? 1 : 0, state, (float*)ws);
   FSG_RETURN_LAUNCH();
 }
 
 int fsg_robust_update_f32(void* state, size_t state_bytes, const void* ws, size_t ws_bytes, int n, int h, int w, int t, int n_em,
                           double c0, double sigma_floor, double slice_floor, int min_pixels, void* stream) {
   if (n <= 0 || h <= 0 || w <= 0 || n_em < 1 || n_em > FSG_SOLVER_MAX_ITER || t < 0 || t > n_em) return FSG_E_BADARG;
-  if (n > 65535 || (size_t)n * (size_t)h * (size_t)w > (size_t)0x7FFFFFFF) return FSG_E_TOOBIG;
+  const int rc = px_check_shape(n, h, w);
+  if (rc) return rc;
   if (!state || !ws || state_bytes < rb_state_bytes((size_t)n, n_em) || ws_bytes < fsg_robust_ws_bytes(n, h, w)) return FSG_E_BADARG;
   if (!(c0 > 0.0 && c0 <= 1.0) || !(sigma_floor >= 0.0 && sigma_floor <= 1.7976931348623157e308) ||
       !(slice_floor >= 0.0 && slice_floor <= 1.7976931348623157e308) || min_pixels < 0)
@@ -400,7 +351,7 @@ int fsg_robust_update_f32(void* state, size_t state_bytes, const void* ws, size_
   if (((uintptr_t)state & 7) || ((uintptr_t)ws & 7)) return FSG_E_ALIGN;
   if (fsg_overlap(state, rb_state_bytes((size_t)n, n_em), ws, fsg_robust_ws_bytes(n, h, w))) return FSG_E_BADARG;
   const RbOpts O{c0, sigma_floor, slice_floor, min_pixels};
-  hipLaunchKernelGGL(rb_update_kernel, dim3(1), dim3(RB_THREADS), 0, fsg_stream(stream), state, (const float*)ws, rb_chunks(h, w),
+  hipLaunchKernelGGL(rb_update_kernel, dim3(1), dim3(PX_THREADS), 0, fsg_stream(stream), state, (const float*)ws, px_chunks(h, w),
                      n, t, n_em, O);
   FSG_RETURN_LAUNCH();
 }
@@ -412,17 +363,15 @@ int fsg_robust_weights_f32(const float* y, const float* s, const uint8_t* slices
   if (rc) return rc;
   if (!out || (level != FSG_ROBUST_SLICE && level != FSG_ROBUST_BOTH)) return FSG_E_BADARG;
   if ((uintptr_t)out & 3) return FSG_E_ALIGN;
-  const size_t pix = (size_t)n * h * w, stb = rb_state_bytes((size_t)n, n_em);
-  if (fsg_overlap(out, pix * 4, y, pix * 4) || fsg_overlap(out, pix * 4, s, pix * 4) || fsg_overlap(out, pix * 4, sim_weight, pix * 4) ||
-      fsg_overlap(out, pix * 4, slices_mask, pix) || fsg_overlap(out, pix * 4, state, stb))
-    return FSG_E_BADARG;
   const RbIn I{y, s, slices_mask, sim_weight, min_weight, h * w};
-  const dim3 grid((unsigned)rb_chunks(h, w), (unsigned)n);
+  const size_t pix = (size_t)n * h * w;
+  if (rb_hits_inputs(out, pix * 4, I, pix, state, rb_state_bytes((size_t)n, n_em))) return FSG_E_BADARG;
+  const dim3 grid((unsigned)px_chunks(h, w), (unsigned)n);
   hipStream_t st = fsg_stream(stream);
-  if (rb_vec(I, out))
-    hipLaunchKernelGGL(rb_weights_kernel<true>, grid, dim3(RB_THREADS), 0, st, I, n, n_em, level == FSG_ROBUST_BOTH ? 1 : 0, state, out);
+  if (px_vec(I.hw, {y, s, sim_weight, out}, slices_mask))
+    hipLaunchKernelGGL(rb_weights_kernel<true>, grid, dim3(PX_THREADS), 0, st, I, n, n_em, level == FSG_ROBUST_BOTH ? 1 : 0, state, out);
   else
-    hipLaunchKernelGGL(rb_weights_kernel<false>, grid, dim3(RB_THREADS), 0, st, I, n, n_em, level == FSG_ROBUST_BOTH ? 1 : 0, state,
+    hipLaunchKernelGGL(rb_weights_kernel<false>, grid, dim3(PX_THREADS), 0, st, I, n, n_em, level == FSG_ROBUST_BOTH ? 1 : 0, state,
                        out);
   FSG_RETURN_LAUNCH();
 }

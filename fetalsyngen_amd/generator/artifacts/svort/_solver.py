@@ -2,6 +2,8 @@
 each brings its inputs to one device, dtype and shape before the first launch."""
 from __future__ import annotations
 
+import math
+
 import torch
 
 
@@ -20,3 +22,31 @@ def prep(t, shape, device, dtype=torch.float32):
     if t is None or t.numel() == 0:
         return None
     return t.detach().to(device=device, dtype=dtype).reshape(shape).contiguous()
+
+
+def check_options(kind, defaults, opts, nonneg):
+    """`opts` over `defaults` as a complete dict; ValueError for an unknown name, for one of `nonneg` that is not finite and
+    >= 0, and for min_pixels < 0.  What the options of `robust_weights` and `intensity_match` share."""
+    unknown = set(opts) - set(defaults)
+    if unknown:
+        raise ValueError(f"unknown {kind} option(s) {sorted(unknown)}; known: {sorted(defaults)}")
+    o = dict(defaults, **opts)
+    for name in nonneg:
+        v = float(o[name])
+        if not (math.isfinite(v) and v >= 0):
+            raise ValueError(f"{name} must be finite and >= 0, got {o[name]!r}")
+    if int(o["min_pixels"]) < 0:
+        raise ValueError(f"min_pixels must be >= 0, got {o['min_pixels']!r}")
+    return o
+
+
+def refinement(count_name, count, opts_name, opts, what, check):
+    """A refinement of `srr` that runs `count` rounds with the options `opts` (None: the defaults) -> (count, the options the
+    caller gave, checked by `check`)"""
+    count = int(count)
+    if count < 0:
+        raise ValueError(f"{count_name} must be >= 0, got {count}")
+    if opts is not None and count == 0:
+        raise ValueError(f"{opts_name} sets the options of the {what}: it needs {count_name} > 0")
+    full = check(dict(opts or {}))
+    return count, {k: full[k] for k in opts or ()}

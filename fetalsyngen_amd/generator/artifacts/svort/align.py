@@ -18,7 +18,7 @@ import torch
 
 from ._solver import no_grad_inputs, prep
 from .srr import srr as _srr
-from .svr import parse_groups, solve_groups
+from .svr import operands, parse_groups, solve_groups
 
 
 def align_stacks(transforms, slices, stack_ids, psf, vol_shape, res_slice, *, template=None, n_rounds=3,
@@ -60,10 +60,7 @@ def align_stacks(transforms, slices, stack_ids, psf, vol_shape, res_slice, *, te
     moving = [g for g in range(ids.size) if g != t]
 
     tr = prep(transforms, (n, 3, 4), dev)
-    ps = prep(psf, tuple(psf.shape), dev)
-    y = prep(slices, (n, h, w), dev)
-    sm = prep(slices_mask, (n, h, w), dev, torch.bool)
-    wt = prep(slices_weight, (n, h, w), dev)
+    ps, y, _, sm, wt = operands(n, slices, None, psf, slices_mask, slices_weight)  # the targets are reconstructed below
 
     # the index sets and the leave-out masks, made on the host and uploaded before the first launch
     stack_t = torch.from_numpy(stack.astype("int64"))

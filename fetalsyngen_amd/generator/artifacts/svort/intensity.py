@@ -17,23 +17,14 @@ import math
 import torch
 
 from .... import kernels as K
-from ._solver import no_grad_inputs, prep
+from ._solver import check_options as _check_options, no_grad_inputs, prep
 
 DEFAULTS = dict(min_weight=0.5, bias_sigma=None, log_floor=0.01, min_pixels=4)
 
 
 def check_options(opts):
     """the options of `intensity_match` as a complete dict; ValueError for an unknown name or a value the kernels refuse"""
-    unknown = set(opts) - set(DEFAULTS)
-    if unknown:
-        raise ValueError(f"unknown match option(s) {sorted(unknown)}; known: {sorted(DEFAULTS)}")
-    o = dict(DEFAULTS, **opts)
-    for name in ("min_weight", "log_floor"):
-        v = float(o[name])
-        if not (math.isfinite(v) and v >= 0):
-            raise ValueError(f"{name} must be finite and >= 0, got {o[name]!r}")
-    if int(o["min_pixels"]) < 0:
-        raise ValueError(f"min_pixels must be >= 0, got {o['min_pixels']!r}")
+    o = _check_options("match", DEFAULTS, opts, ("min_weight", "log_floor"))
     if o["bias_sigma"] is not None:
         v = float(o["bias_sigma"])
         if not (math.isfinite(v) and v >= 0 and 3 * v <= K.IMATCH_MAX_RADIUS):

@@ -12,32 +12,21 @@ order of summation fixed: bit-identical from run to run and on any stream.  Not 
 """
 from __future__ import annotations
 
-import math
-
 import torch
 
 from .... import kernels as K
-from ._solver import no_grad_inputs, prep
+from ._solver import check_options as _check_options, no_grad_inputs, prep
 
 DEFAULTS = dict(min_weight=0.5, n_em=5, c0=0.9, sigma_floor=0.04, slice_floor=0.025, min_pixels=4, level="slice")
 
 
 def check_options(opts):
     """the options of `robust_weights` as a complete dict; ValueError for an unknown name or a value the kernels refuse"""
-    unknown = set(opts) - set(DEFAULTS)
-    if unknown:
-        raise ValueError(f"unknown robust option(s) {sorted(unknown)}; known: {sorted(DEFAULTS)}")
-    o = dict(DEFAULTS, **opts)
-    for name in ("min_weight", "sigma_floor", "slice_floor"):
-        v = float(o[name])
-        if not (math.isfinite(v) and v >= 0):
-            raise ValueError(f"{name} must be finite and >= 0, got {o[name]!r}")
+    o = _check_options("robust", DEFAULTS, opts, ("min_weight", "sigma_floor", "slice_floor"))
     if not 0 < float(o["c0"]) <= 1:
         raise ValueError(f"c0 must be in (0, 1], got {o['c0']!r}")
     if not 1 <= int(o["n_em"]) <= K.ROBUST_MAX_EM:
         raise ValueError(f"n_em must be in 1..{K.ROBUST_MAX_EM}, got {o['n_em']!r}")
-    if int(o["min_pixels"]) < 0:
-        raise ValueError(f"min_pixels must be >= 0, got {o['min_pixels']!r}")
     if o["level"] not in K.ROBUST_LEVELS:
         raise ValueError(f"level must be one of {sorted(K.ROBUST_LEVELS)}, got {o['level']!r}")
     return o

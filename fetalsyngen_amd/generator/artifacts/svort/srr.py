@@ -40,7 +40,7 @@ import torch
 
 from .... import kernels as K
 from .... import rng as _rng
-from ._solver import no_grad_inputs, prep
+from ._solver import no_grad_inputs, prep, refinement
 from .intensity import check_options as _match_options, intensity_match
 from .outlier import check_options as _robust_options, robust_weights
 
@@ -85,18 +85,8 @@ def srr(transforms, slices, psf, vol_shape, res_slice, *, interp_psf=False, slic
         raise ValueError(f"n_outer must be >= 1, got {n_outer}")
     if huber_delta is None and (n_outer > 1 or guide is not None):
         raise ValueError("n_outer > 1 and guide reweight the edges by huber_delta: give it")
-    n_robust = int(n_robust)
-    if n_robust < 0:
-        raise ValueError(f"n_robust must be >= 0, got {n_robust}")
-    if robust is not None and n_robust == 0:
-        raise ValueError("robust sets the options of the outlier rejection: it needs n_robust > 0")
-    ropts = {k: v for k, v in _robust_options(dict(robust or {})).items() if robust and k in robust}
-    n_match = int(n_match)
-    if n_match < 0:
-        raise ValueError(f"n_match must be >= 0, got {n_match}")
-    if match is not None and n_match == 0:
-        raise ValueError("match sets the options of the intensity matching: it needs n_match > 0")
-    mopts = {k: v for k, v in _match_options(dict(match or {})).items() if match and k in match}
+    n_robust, ropts = refinement("n_robust", n_robust, "robust", robust, "outlier rejection", _robust_options)
+    n_match, mopts = refinement("n_match", n_match, "match", match, "intensity matching", _match_options)
     n_refine = max(n_robust, n_match)
     if deterministic is None:
         deterministic = _rng.in_keyed_scope()

@@ -67,36 +67,56 @@ def parse_groups(groups, n, what="groups"):
     return ids, group, members, offsets
 
 
-def solve_groups(base, groups, y, x, ps, sm, wt, res_slice, *, n_iter=10, lambda0=1e-3, factor=10.0, lambda_min=1e-9,
-                 lambda_max=1e10, min_weight=0.5, min_overlap=0.5, tol=0.0):
+def operands(n, slices, vol, psf, slices_mask, slices_weight):
+    """the operands of a registration of n slices, prepared on the device of `slices`: (psf, slices (n,h,w), vol (D,H,W) or
+    None when none is given yet, slices_mask, slices_weight)"""
+    dev = slices.device
+    nhw = (n, *(int(v) for v in slices.shape[-2:]))
+    x = None if vol is None else prep(vol, tuple(int(v) for v in vol.shape[-3:]), dev)
+    return (prep(psf, tuple(psf.shape), dev), prep(slices, nhw, dev), x, prep(slices_mask, nhw, dev, torch.bool),
+            prep(slices_weight, nhw, dev))
+
+
+def lm_rounds(par, stats_of, *, n_iter=10, lambda0=1e-3, factor=10.0, lambda_min=1e-9, lambda_max=1e10, min_overlap=0.5, tol=0.0):
+    """The n_iter + 1 rounds of both solves on par (rows,6), the trial that every update overwrites: axisangle2mat(par), the
+    Jacobian of its 12 entries, stats_of(mat, jac) -> the (rows, SVR_SLOTS) sums at the trial, svr_update.  -> (the state of
+    `rows` rows, the Jacobian of the last round)"""
+    rows, dev = int(par.shape[0]), par.device
+    # everything the loop needs, made before it
+    state = K.svr_state(rows, int(n_iter), dev)
+    onehot = torch.eye(12, dtype=torch.float32, device=dev).repeat(rows, 1).view(12 * rows, 3, 4)  # grad_mat of entry k, per row
+    rep = torch.empty((rows, 12, 6), dtype=torch.float32, device=dev)  # every row of par 12 times
+    for k in range(state.n_iter + 1):
+        mat = K.axisangle2mat(par)
+        rep.copy_(par.view(rows, 1, 6).expand(rows, 12, 6))
+        jac = K.axisangle2mat_backward(onehot, rep.view(12 * rows, 6)).view(rows, 12, 6)  # row k: d entry k / d parameter
+        K.svr_update(state, k, stats_of(mat, jac), par, lambda0=lambda0, factor=factor, lambda_min=lambda_min, lambda_max=lambda_max,
+                     min_overlap=min_overlap, tol=tol)
+    return state, jac
+
+
+def solve_groups(base, groups, y, x, ps, sm, wt, res_slice, *, min_weight=0.5, **lm):
     """The grouped solve on prepared device operands: base (n,3,4) -> (the composed transforms (n,3,4), the state of G rows, the
-    host ids, the slices' relabelled ids on the device)."""
-    n_iter = int(n_iter)
+    host ids, the slices' relabelled ids on the device).  lm: the keywords of `lm_rounds`."""
     dev = y.device
     n, h, w = (int(v) for v in y.shape)
     ids, group, members, offsets = parse_groups(groups, n)
     G = int(ids.size)
 
-    # everything the loop needs, made before it; the two index arrays and the slices' ids are uploaded once
+    # the two index arrays and the slices' ids are uploaded once, before the first launch
     group_d = torch.from_numpy(group).to(dev)
     members_d, offsets_d = torch.from_numpy(members).to(dev), torch.from_numpy(offsets).to(dev)
-    phi = torch.zeros((G, 6), dtype=torch.float32, device=dev)  # the trial; overwritten by every update
-    state = K.svr_state(G, n_iter, dev)
-    onehot = torch.eye(12, dtype=torch.float32, device=dev).repeat(G, 1).view(12 * G, 3, 4)
-    rep = torch.empty((G, 12, 6), dtype=torch.float32, device=dev)
     out = (torch.empty((n, 3, 4), dtype=torch.float32, device=dev), torch.empty((n, 12, 6), dtype=torch.float32, device=dev))
     stats = torch.empty((n, K.SVR_SLOTS), dtype=torch.float64, device=dev)
     gstats = torch.empty((G, K.SVR_SLOTS), dtype=torch.float64, device=dev)
     ws = torch.empty(K.svr_ws_bytes(n, h, w) // 8, dtype=torch.int64, device=dev)
-    for k in range(n_iter + 1):
-        gm = K.axisangle2mat(phi)
-        rep.copy_(phi.view(G, 1, 6).expand(G, 12, 6))
-        gj = K.axisangle2mat_backward(onehot, rep.view(12 * G, 6)).view(G, 12, 6)
+
+    def stats_of(gm, gj):
         tr, jac = K.svr_compose(gm, gj, base, group_d, out=out)
         K.svr_normal(tr, jac, x, ps, y, sm, wt, res_slice, min_weight, out=stats, ws=ws)
-        K.svr_group_reduce(stats, members_d, offsets_d, out=gstats)
-        K.svr_update(state, k, gstats, phi, lambda0=lambda0, factor=factor, lambda_min=lambda_min, lambda_max=lambda_max,
-                     min_overlap=min_overlap, tol=tol)
+        return K.svr_group_reduce(stats, members_d, offsets_d, out=gstats)
+
+    state, gj = lm_rounds(torch.zeros((G, 6), dtype=torch.float32, device=dev), stats_of, **lm)
     # the accepted increments; the Jacobian of the last round is only a valid operand here, the jac it gives is not used
     tr, _ = K.svr_compose(K.axisangle2mat(state.theta_cur), gj, base, group_d, out=out)
     return tr, state, ids, group_d
@@ -136,41 +156,27 @@ def svr(poses, slices, vol, psf, res_slice, *, slices_mask=None, slices_weight=N
     package (the slices acquired in one sweep of an interleaved stack), then `groups=None` for single slices once the volume
     is sharp enough to hold them.  No driver is shipped for the walk."""
     no_grad_inputs("svr", poses=poses, slices=slices, vol=vol, psf=psf, slices_weight=slices_weight)
-    n_iter = int(n_iter)
-    dev = slices.device
-    h, w = (int(v) for v in slices.shape[-2:])
-    D, H, W = (int(v) for v in vol.shape[-3:])
     n = int(poses.shape[0])
-
-    theta = prep(poses, (n, 6), dev).clone()  # the trial; overwritten by every update
-    ps = prep(psf, tuple(psf.shape), dev)
-    y = prep(slices, (n, h, w), dev)
-    x = prep(vol, (D, H, W), dev)
-    sm = prep(slices_mask, (n, h, w), dev, torch.bool)
-    wt = prep(slices_weight, (n, h, w), dev)
+    lm = dict(n_iter=n_iter, lambda0=lambda0, factor=factor, lambda_min=lambda_min, lambda_max=lambda_max, min_overlap=min_overlap,
+              tol=tol)
+    theta = prep(poses, (n, 6), slices.device).clone()  # the trial; overwritten by every update
+    ps, y, x, sm, wt = operands(n, slices, vol, psf, slices_mask, slices_weight)
 
     if groups is not None:
-        tr, state, ids, group_d = solve_groups(K.axisangle2mat(theta), groups, y, x, ps, sm, wt, res_slice, n_iter=n_iter,
-                                               lambda0=lambda0, factor=factor, lambda_min=lambda_min, lambda_max=lambda_max,
-                                               min_weight=min_weight, min_overlap=min_overlap, tol=tol)
+        tr, state, ids, group_d = solve_groups(K.axisangle2mat(theta), groups, y, x, ps, sm, wt, res_slice, min_weight=min_weight, **lm)
         # a slice moved iff its group's accepted increment is not 0 (selected on the device: nothing is read back)
         moved = (state.theta_cur != 0).any(dim=1)[group_d.clamp(min=0).long()] & (group_d >= 0)
         out = torch.where(moved[:, None], K.mat2axisangle(tr), theta)
         return (out, _group_info(state, ids)) if return_info else out
 
-    # everything the loop needs, made before it
-    state = K.svr_state(n, n_iter, dev)
-    onehot = torch.eye(12, dtype=torch.float32, device=dev).repeat(n, 1).view(12 * n, 3, 4)  # grad_mat of entry k, per slice
-    rep = torch.empty((n, 12, 6), dtype=torch.float32, device=dev)  # every pose 12 times
-    stats = torch.empty((n, K.SVR_SLOTS), dtype=torch.float64, device=dev)
-    ws = torch.empty(K.svr_ws_bytes(n, h, w) // 8, dtype=torch.int64, device=dev)
-    for k in range(n_iter + 1):
-        tr = K.axisangle2mat(theta)
-        rep.copy_(theta.view(n, 1, 6).expand(n, 12, 6))
-        jac = K.axisangle2mat_backward(onehot, rep.view(12 * n, 6)).view(n, 12, 6)  # row k: d entry k / d pose
-        K.svr_normal(tr, jac, x, ps, y, sm, wt, res_slice, min_weight, out=stats, ws=ws)
-        K.svr_update(state, k, stats, theta, lambda0=lambda0, factor=factor, lambda_min=lambda_min, lambda_max=lambda_max,
-                     min_overlap=min_overlap, tol=tol)
+    h, w = (int(v) for v in slices.shape[-2:])
+    stats = torch.empty((n, K.SVR_SLOTS), dtype=torch.float64, device=slices.device)
+    ws = torch.empty(K.svr_ws_bytes(n, h, w) // 8, dtype=torch.int64, device=slices.device)
+
+    def stats_of(tr, jac):
+        return K.svr_normal(tr, jac, x, ps, y, sm, wt, res_slice, min_weight, out=stats, ws=ws)
+
+    state, _ = lm_rounds(theta, stats_of, **lm)
     out = state.theta_cur.clone()
     return (out, state.info()) if return_info else out
 
@@ -193,11 +199,6 @@ class SVR:
                         n_iter=self.n_iter, return_info=return_info, **self.options)
             return (K.axisangle2mat(poses[0]), poses[1]) if return_info else K.axisangle2mat(poses)
         no_grad_inputs("svr", slices=slices, vol=volume, psf=psf, slices_weight=slices_weight)
-        dev = slices.device
-        n = int(mat.shape[0])
-        h, w = (int(v) for v in slices.shape[-2:])
-        D, H, W = (int(v) for v in volume.shape[-3:])
-        tr, state, ids, _ = solve_groups(mat, groups, prep(slices, (n, h, w), dev), prep(volume, (D, H, W), dev),
-                                         prep(psf, tuple(psf.shape), dev), prep(slices_mask, (n, h, w), dev, torch.bool),
-                                         prep(slices_weight, (n, h, w), dev), res_slice, n_iter=self.n_iter, **self.options)
+        ps, y, x, sm, wt = operands(int(mat.shape[0]), slices, volume, psf, slices_mask, slices_weight)
+        tr, state, ids, _ = solve_groups(mat, groups, y, x, ps, sm, wt, res_slice, n_iter=self.n_iter, **self.options)
         return (tr, _group_info(state, ids)) if return_info else tr

@@ -117,6 +117,28 @@ class _StateBlock:
             raise RuntimeError(f"{entry}{args} = {self.nbytes}, the layout of fsg_hip.h needs {off}")
 
 
+class _PixelState(_StateBlock):
+    """A state block for n slices plus `part` (int64), the workspace of the per-workgroup partials for (h, w) slices, sized
+    by the library's entry `ws_entry`(n, h, w)."""
+
+    def _carve_pixels(self, entry, ws_entry, args, device, fields, slice_shape):
+        self._carve(entry, args, device, fields)
+        self._ws_entry, self.part, self.slice_shape = ws_entry, None, None
+        if slice_shape is not None:
+            self.reserve(slice_shape)
+
+    def reserve(self, slice_shape):
+        """the workspace for (h, w) slices"""
+        h, w = (int(v) for v in slice_shape)
+        if self.slice_shape != (h, w):
+            need = int(getattr(_lib.load(), self._ws_entry)(self.n, h, w))
+            if need == 0:
+                raise ValueError(f"no workspace for {self.n} slices of {(h, w)}")
+            self.part = torch.empty(need // 8, dtype=torch.int64, device=self.buf.device)
+            self.slice_shape = (h, w)
+        return self.part
+
+
 def _slice_count(n):
     n = int(n)
     if n < 1:
@@ -1193,7 +1215,7 @@ ROBUST_LEVELS = {"slice": _lib.ROBUST_SLICE, "both": _lib.ROBUST_BOTH}
 ROBUST_ROW = _lib.ROBUST_ROW  # doubles of a slice's row: N, sum p, sum p e^2, sum (1-p)^2, min y, max y
 
 
-class RobustState(_StateBlock):
+class RobustState(_PixelState):
     """The device blocks of one EM (include/fsg_hip.h, fsg_robust_*): `buf` (int64), the state, and as views of it consts (4:
     R, m, sigma_min, 0), rows (n,6), u (n), the histories sigma, c, mu1, mu2 (float64), frozen (int32), each of n_em + 1 slots,
     ws (n_em + 1, n) float64 and scal (2 float32: kappa, inv2var); `part` (int64) is the workspace of the per-workgroup
@@ -1202,25 +1224,11 @@ class RobustState(_StateBlock):
     def __init__(self, n: int, n_em: int, device, slice_shape=None):
         self.n, self.n_em = n, n_em = _slice_count(n), _iterations("n_em", n_em)
         s = n_em + 1
-        self._carve("fsg_robust_state_bytes", (n, n_em), device,
-                    (("consts", torch.float64, (4,)), ("rows", torch.float64, (n, ROBUST_ROW)), ("u", torch.float64, (n,)),
-                     ("sigma", torch.float64, (s,)), ("c", torch.float64, (s,)), ("mu1", torch.float64, (s,)),
-                     ("mu2", torch.float64, (s,)), ("ws", torch.float64, (s, n)), ("scal", F32, (2,)),
-                     ("frozen", torch.int32, (s,))))
-        self.part, self.slice_shape = None, None
-        if slice_shape is not None:
-            self.reserve(slice_shape)
-
-    def reserve(self, slice_shape):
-        """the workspace for (h, w) slices"""
-        h, w = (int(v) for v in slice_shape)
-        if self.slice_shape != (h, w):
-            need = int(_lib.load().fsg_robust_ws_bytes(self.n, h, w))
-            if need == 0:
-                raise ValueError(f"no workspace for {self.n} slices of {(h, w)}")
-            self.part = torch.empty(need // 8, dtype=torch.int64, device=self.buf.device)
-            self.slice_shape = (h, w)
-        return self.part
+        self._carve_pixels("fsg_robust_state_bytes", "fsg_robust_ws_bytes", (n, n_em), device,
+                           (("consts", torch.float64, (4,)), ("rows", torch.float64, (n, ROBUST_ROW)), ("u", torch.float64, (n,)),
+                            ("sigma", torch.float64, (s,)), ("c", torch.float64, (s,)), ("mu1", torch.float64, (s,)),
+                            ("mu2", torch.float64, (s,)), ("ws", torch.float64, (s, n)), ("scal", F32, (2,)),
+                            ("frozen", torch.int32, (s,))), slice_shape)
 
     def info(self):
         return {k: getattr(self, k) for k in ("sigma", "c", "mu1", "mu2", "frozen", "ws", "u")}
@@ -1248,14 +1256,11 @@ def _pixel_arrays(state, named, slices_mask=None, min_weight=0.0):
     return shape[1], shape[2], sm
 
 
-def _robust_pixels(state, y, s, slices_mask, sim_weight, min_weight, out=None):
-    return _pixel_arrays(state, (("slices", y), ("simulated", s), ("sim_weight", sim_weight), ("out", out)), slices_mask, min_weight)
-
-
 def robust_estep(state: RobustState, t: int, y, s, slices_mask=None, sim_weight=None, min_weight=0.5):
     """Slot t of the EM, the pixel pass (fsg_robust_estep_f32): the posteriors p of e = y - s under the scalars update(t - 1)
     stored (p = 1 at t == 0) and one partial of the per-slice sums per workgroup, into state.part."""
-    h, w, sm = _robust_pixels(state, y, s, slices_mask, sim_weight, min_weight)
+    named = (("slices", y), ("simulated", s), ("sim_weight", sim_weight))
+    h, w, sm = _pixel_arrays(state, named, slices_mask, min_weight)
     part = state.reserve((h, w))
     rc = _lib.load().fsg_robust_estep_f32(_p(y), _p(s), _p(sm), _p(sim_weight), float(min_weight), state.n, h, w, int(t),
                                           state.n_em, _p(state.buf), state.nbytes, _p(part), part.numel() * 8, _stream(y))
@@ -1281,7 +1286,8 @@ def robust_weights(state: RobustState, y, s, slices_mask=None, sim_weight=None, 
         raise ValueError(f"level must be one of {sorted(ROBUST_LEVELS)}, got {level!r}")
     if out is None and isinstance(y, torch.Tensor):
         out = torch.empty_like(y)
-    h, w, sm = _robust_pixels(state, y, s, slices_mask, sim_weight, min_weight, out)
+    named = (("slices", y), ("simulated", s), ("sim_weight", sim_weight), ("out", out))
+    h, w, sm = _pixel_arrays(state, named, slices_mask, min_weight)
     rc = _lib.load().fsg_robust_weights_f32(_p(y), _p(s), _p(sm), _p(sim_weight), float(min_weight), state.n, h, w, state.n_em,
                                             ROBUST_LEVELS[level], _p(state.buf), state.nbytes, _p(out), _stream(y))
     _lib.check(rc, "fsg_robust_weights_f32")
@@ -1293,7 +1299,7 @@ IMATCH_ROW = _lib.IMATCH_ROW  # doubles of a slice's row: N, sum omega c s, sum 
 IMATCH_MAX_RADIUS = _lib.IMATCH_MAX_RADIUS  # the largest ceil(3 sigma)
 
 
-class ImatchState(_StateBlock):
+class ImatchState(_PixelState):
     """The device blocks of one matching (include/fsg_hip.h, fsg_imatch_*): `buf` (int64), the state, and as views of it consts
     (4: R, floor, g, the number of ok slices), rows (n,5), raw (n), mean (n) float64, scale (n) float32, ok (n) and frozen (1)
     int32; `part` (int64) is the workspace of the per-workgroup partials and `planes` (float32, made on first use) that of the
@@ -1301,24 +1307,19 @@ class ImatchState(_StateBlock):
 
     def __init__(self, n: int, device, slice_shape=None):
         self.n = n = _slice_count(n)
-        self._carve("fsg_imatch_state_bytes", (n,), device,
-                    (("consts", torch.float64, (4,)), ("rows", torch.float64, (n, IMATCH_ROW)), ("raw", torch.float64, (n,)),
-                     ("mean", torch.float64, (n,)), ("scale", F32, (n,)), ("ok", torch.int32, (n,)),
-                     ("frozen", torch.int32, (1,))))
-        self.part, self.planes, self.slice_shape = None, None, None
-        if slice_shape is not None:
-            self.reserve(slice_shape)
+        self.planes = None
+        self._carve_pixels("fsg_imatch_state_bytes", "fsg_imatch_ws_bytes", (n,), device,
+                           (("consts", torch.float64, (4,)), ("rows", torch.float64, (n, IMATCH_ROW)), ("raw", torch.float64, (n,)),
+                            ("mean", torch.float64, (n,)), ("scale", F32, (n,)), ("ok", torch.int32, (n,)),
+                            ("frozen", torch.int32, (1,))), slice_shape)
 
     def reserve(self, slice_shape):
-        """the workspace for (h, w) slices"""
-        h, w = (int(v) for v in slice_shape)
-        if self.slice_shape != (h, w):
-            need = int(_lib.load().fsg_imatch_ws_bytes(self.n, h, w))
-            if need == 0:
-                raise ValueError(f"no workspace for {self.n} slices of {(h, w)}")
-            self.part = torch.empty(need // 8, dtype=torch.int64, device=self.buf.device)
-            self.planes, self.slice_shape = None, (h, w)
-        return self.part
+        """the workspace for (h, w) slices; the planes of another shape go"""
+        was = self.slice_shape
+        part = super().reserve(slice_shape)
+        if self.slice_shape != was:
+            self.planes = None
+        return part
 
     def reserve_planes(self):
         """the planes between the row and the column pass, for the slices `reserve` was given"""

@@ -775,7 +775,9 @@ int fsg_svr_group_reduce_f64(const double* stats, const int32_t* members, const 
  * rows do not see the other slices).
  * Refusals, all before any launch and with nothing written: n, h or w < 1, T outside 1..FSG_SOLVER_MAX_ITER, t outside 0..T, a null y, s,
  * state, ws or out, a short state or ws, min_weight negative or NaN, c0 outside (0, 1] or NaN, sigma_floor or slice_floor
- * negative, NaN or Inf, min_pixels < 0, an unknown level (FSG_E_BADARG); n > 65535 or n * h * w > 2^31 - 1 (FSG_E_TOOBIG);
+ * negative, NaN or Inf, min_pixels < 0, an unknown level (FSG_E_BADARG); n > 65535, n * h * w > 2^31 - 1 or
+ * h * w > 2^31 - 1 - 1024 (a slice's pixels are counted in int, 1024 to a workgroup; FSG_E_TOOBIG, and fsg_robust_ws_bytes
+ * returns 0 for the same sizes);
  * state or ws not 8-byte aligned, a float pointer not 4-byte aligned (FSG_E_ALIGN); ws sharing a byte with an input or the
  * state, out sharing a byte with an input or the state (FSG_E_BADARG). */
 #define FSG_ROBUST_SLICE 0

@@ -318,6 +318,12 @@ def test_entries_refuse_before_any_launch():
                dict(out=(4 << 24) + 4), dict(out=(5 << 24) + 8)):
         assert _weights(lib, **kw) == BAD, kw
     assert _weights(lib, out=(7 << 24) + 2) == ALIGN
+    # a slice's pixels are counted in int, 1024 to a workgroup: the last workgroup's first index has to fit
+    edge = 2 ** 31 - 1 - 1024
+    for call in (_estep, _update, _weights):
+        assert call(lib, n=1, h=1, w=edge + 1, state_bytes=1 << 40, ws_bytes=1 << 40) == BIG, call.__name__
+    fn = lib.fsg_robust_ws_bytes
+    assert fn(1, 1, edge) > 0 and fn(1, edge, 1) > 0 and fn(1, 1, edge + 1) == 0 and fn(1, 2, edge // 2 + 1) == 0
 
 
 @pytest.mark.parametrize("T", (1, 2, 12, 4096))
