@@ -73,8 +73,9 @@ def rows(yy, ss, c, om, part, ft=F64):
 
 
 # ---- the scalar pass -------------------------------------------------------------------------------------------------------------
-def scale(r, log_floor=0.01, min_pixels=4, single=True):
-    """single: scale rounded to float32 (the device); False: kept in double (the float64 reference)"""
+def scale(r, log_floor=0.01, min_pixels=4, single=True, mutant=None):
+    """single: scale rounded to float32 (the device); False: kept in double (the float64 reference).  mutant: one of
+    util_robust64.ORDER_MUTANTS, the slices the sums over the slices visit and their order (util_robust64.slice_order)."""
     r = np.asarray(r, F64).copy()
     n = r.shape[0]
     bad = ~(np.isfinite(r[:, 1]) & np.isfinite(r[:, 2]))
@@ -85,11 +86,14 @@ def scale(r, log_floor=0.01, min_pixels=4, single=True):
         q = A / np.where(own, B, 1.0)
     own &= np.isfinite(q)
     raw = np.where(own, q, 0.0)
-    have = N > 0
+    order = RB.slice_order(n, mutant)
+    have = np.zeros(n, bool)
+    have[order] = True
+    have &= N > 0
     R = (r[have, 4].max() - r[have, 3].min()) if have.any() else math.nan
     floor = log_floor * R
     tot = nok = 0.0
-    for k in np.flatnonzero(own):
+    for k in (j for j in order if own[j]):
         tot, nok = tot + raw[k], nok + 1.0
     g = tot / nok if nok else math.nan
     frozen = not (math.isfinite(R) and R > 0 and math.isfinite(floor) and nok > 0 and math.isfinite(g) and g > 0)
@@ -292,6 +296,17 @@ E_CPU = {
     "scale": 1.26e-07,  # 1.256e-07
     "bias": 2.71e-06,  # 2.702e-06
     "corrected": 2.99e-07,  # 2.982e-07
+}
+
+# the groups in which a size case of tests/util_recon_counts.py (three slices, scale only) exceeds the figure above, measured by
+# the same procedure (util_recon_counts.measure_size_e_cpu); the tests of those cases use the larger of the two, times 4
+E_CPU_SIZES = {
+    "rows": 1.23e-07,  # 1.224e-07, set by imatch_size_case((2, 513)): 1026 pixels, the second chunk holds two
+    "scale": 2.62e-07,  # 2.614e-07, set by imatch_size_case((2, 513))
+}
+# the same for the one case of 257 slices of 5 x 7 with the bias field (util_recon_counts.imatch_means_case, sigma 4)
+E_CPU_N257 = {
+    "scale": 1.53e-07,  # 1.524e-07, set by imatch_means_case(): the gauge is a sum of 255 gains
 }
 
 

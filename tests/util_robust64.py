@@ -10,7 +10,7 @@ fsg_robust_*).  Test infrastructure, numpy only.
                          ft = float32: pixel operations in float32 one rounding each, rows_device, kappa and inv2var rounded
                          to float32: what the device computes, expf apart.  mutant (float64 only): "no_sigma_floor",
                          "new_ws_in_sums" (the pixel sums S0, S2, Nw under the NEW slice weights), "no_mu2_rule" (u > mu2 -> 0
-                         left out: the quotient of the densities is used there too).
+                         left out: the quotient of the densities is used there too); ORDER_MUTANTS: see slice_order.
 
 Margins: the slice weight is discontinuous at u = mu1 and u = mu2, so a comparison between two arithmetics needs every u_k
 away from both.  em() records the smallest distance (`margin`); `assert_margin` demands 1e-3.  A single slice is exempt by
@@ -132,16 +132,38 @@ def _fin(*xs):
     return all(math.isfinite(x) for x in xs)
 
 
-def _slice_scalars(u, ok, w, fl2):
+ORDER_MUTANTS = ("drop_ragged", "drop_256", "trip0_again", "reverse")
+
+
+def slice_order(n, mutant=None):
+    """the slice indices a sum over the slices visits, in its order: 0..n-1, the order of the wave walk (64 slices a trip) and
+    of the strided loops (256 threads).  The mutants are the ways such a walk goes wrong: "drop_ragged" leaves out the ragged
+    last trip where it is not the first (k >= 64 * (n // 64) for n > 64), "drop_256" the second thread stride (k >= 256),
+    "trip0_again" reads trip 0 once more in place of trip 1, "reverse" adds in decreasing index.  Any other mutant name
+    leaves the order alone."""
+    k = np.arange(n)
+    if mutant == "drop_ragged":
+        return k[:WAVE * (n // WAVE)] if n > WAVE else k
+    if mutant == "drop_256":
+        return k[:THREADS]
+    if mutant == "trip0_again":
+        return np.where((k >= WAVE) & (k < 2 * WAVE), k - WAVE, k)
+    if mutant == "reverse":
+        return k[::-1]
+    return k
+
+
+def _slice_scalars(u, ok, w, fl2, order=None):
     """mu1, v1, mu2, v2, mix under the weights w, sums in slice-index order"""
     sw = swu = so = sou = umax = nok = 0.0
-    for k in np.flatnonzero(ok):
+    visit = np.flatnonzero(ok) if order is None else [k for k in order if ok[k]]
+    for k in visit:
         sw, swu, so, sou = sw + w[k], swu + w[k] * u[k], so + (1.0 - w[k]), sou + (1.0 - w[k]) * u[k]
         umax, nok = max(umax, u[k]), nok + 1.0
     mu1 = swu / sw if sw != 0 else math.nan
     mu2 = sou / so if so > 0 else (umax + mu1) / 2.0
     a1 = a2 = 0.0
-    for k in np.flatnonzero(ok):
+    for k in visit:
         a1 = a1 + w[k] * ((u[k] - mu1) * (u[k] - mu1))
         a2 = a2 + (1.0 - w[k]) * ((u[k] - mu2) * (u[k] - mu2))
     v1 = max(a1 / sw, fl2) if sw != 0 else math.nan
@@ -183,8 +205,11 @@ def update(S, t, rows, c0=0.9, sigma_floor=0.04, slice_floor=0.025, min_pixels=4
         u = np.where(ok, np.sqrt(rows[:, 3] / np.where(ok, N, 1.0)), 0.0)
     S["u"] = u
     frozen = bool(t > 0 and S["frozen"][t - 1])
+    order = slice_order(n, mutant)
     if t == 0:
-        have = N > 0
+        have = np.zeros(n, bool)
+        have[order] = True
+        have &= N > 0
         R = (rows[have, 5].max() - rows[have, 4].min()) if have.any() else math.nan
         good = _fin(R) and R > 0 and _fin(1.0 / R)
         S["consts"] = np.array([R, 1.0 / R, (0.0 if mutant == "no_sigma_floor" else sigma_floor) * R, 0.0]) if good else np.zeros(4)
@@ -195,11 +220,11 @@ def update(S, t, rows, c0=0.9, sigma_floor=0.04, slice_floor=0.025, min_pixels=4
     sl = None
     wsum = wold
     if t > 0 and not frozen:
-        sl = _slice_scalars(u, ok, wold, fl2)
+        sl = _slice_scalars(u, ok, wold, fl2, order)
         if mutant == "new_ws_in_sums" and _fin(*sl):
             wsum = _slice_weights(dict(S, margin=math.inf), u, ok, *sl)
     S0 = S2 = Nw = 0.0
-    for k in range(n):
+    for k in order:
         S0, S2, Nw = S0 + wsum[k] * rows[k, 1], S2 + wsum[k] * rows[k, 2], Nw + wsum[k] * rows[k, 0]
     kappa = inv2var = var = c = math.nan
     if S0 > 0 and Nw > 0 and _fin(S2):
