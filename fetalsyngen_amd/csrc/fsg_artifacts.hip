@@ -110,6 +110,8 @@ __global__ __launch_bounds__(256) void perlin_kernel(PerlinArgs A, float* __rest
     for (int q = 0; q < A.noct; ++q) v += A.o[q].amp * perlin_octave(A.o[q], A.n0, A.n1, i, j, k);
     out[((size_t)i * A.n1 + j) * A.n2 + k] = v;
   }
+  // (not fsg_block_minmax: the workgroup is blockDim.x >> 6 waves wide here, and with the wave count as an argument of the
+  // shared fold the compiler arranges this kernel's tail differently)
   float lo = fsg_wave_min(live ? v : INFINITY), hi = fsg_wave_max(live ? v : -INFINITY);
   __shared__ float red[2][4];
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
@@ -427,9 +429,8 @@ int fsg_blend_f32(const float* a, const float* b, const float* w, size_t n, int 
   if (w_mode == 1 && !w_mm) return FSG_E_BADARG;
   if (b_mode == 1 && (!b_mm || !a_mm)) return FSG_E_BADARG;
   BlendArgs B{a, b, w, w_mm, increase, seg, w_mode, b_mode, b_mm, a_mm, std, out, w_out, n};
-  size_t blocks = (n + 255) / 256;
-  if (blocks > 16384) blocks = 16384;
-  hipLaunchKernelGGL(blend_kernel, dim3((unsigned)blocks), dim3(256), 0, fsg_stream(stream), B);
+  const unsigned blocks = fsg_blocks(n, 256, 16384);
+  hipLaunchKernelGGL(blend_kernel, dim3(blocks), dim3(256), 0, fsg_stream(stream), B);
   FSG_RETURN_LAUNCH();
 }
 
@@ -437,9 +438,8 @@ int fsg_slice_noise_f32(float* slices, size_t n, float threshold, float sigma, c
                         uint64_t seed, uint64_t stream_id, void* stream) {
   if (n == 0) return 0;  // nothing to do: no launch, pointers may be null
   if (!slices || ((noise1 == nullptr) != (noise2 == nullptr))) return FSG_E_BADARG;
-  size_t blocks = (n + 255) / 256;
-  if (blocks > 16384) blocks = 16384;
-  hipLaunchKernelGGL(slice_noise_kernel, dim3((unsigned)blocks), dim3(256), 0, fsg_stream(stream), slices, n, threshold, sigma,
+  const unsigned blocks = fsg_blocks(n, 256, 16384);
+  hipLaunchKernelGGL(slice_noise_kernel, dim3(blocks), dim3(256), 0, fsg_stream(stream), slices, n, threshold, sigma,
                      noise1, noise2, seed, stream_id);
   FSG_RETURN_LAUNCH();
 }
@@ -448,10 +448,8 @@ int fsg_slice_void_f32(float* slices, int h, int w, const int32_t* slice_ids, co
                        const float* ylin, const float* xlin, void* stream) {
   if (!slices || !slice_ids || !params || !ylin || !xlin || h <= 0 || w <= 0 || nvoid <= 0 || nvoid > 65535)
     return FSG_E_BADARG;
-  int bx = (h * w + 255) / 256;
-  if (bx > 1024) bx = 1024;
-  hipLaunchKernelGGL(slice_void_kernel, dim3((unsigned)bx, (unsigned)nvoid), dim3(256), 0, fsg_stream(stream), slices, h, w,
-                     slice_ids, params, ylin, xlin);
+  const dim3 grid(fsg_blocks((size_t)(h * w), 256, 1024), (unsigned)nvoid);
+  hipLaunchKernelGGL(slice_void_kernel, grid, dim3(256), 0, fsg_stream(stream), slices, h, w, slice_ids, params, ylin, xlin);
   FSG_RETURN_LAUNCH();
 }
 
@@ -505,9 +503,8 @@ int fsg_ewise_f32(const float* a, const float* b, size_t n, int op, float value,
   if (n == 0) return 0;  // nothing to do: no launch, pointers may be null
   if (!a || !out || op < 0 || op > 7) return FSG_E_BADARG;
   if ((op == 0 || (op >= 3 && op <= 6)) && !b) return FSG_E_BADARG;
-  size_t blocks = (n + 255) / 256;
-  if (blocks > 16384) blocks = 16384;
-  hipLaunchKernelGGL(ewise_kernel, dim3((unsigned)blocks), dim3(256), 0, fsg_stream(stream), a, b, n, op, value, out);
+  const unsigned blocks = fsg_blocks(n, 256, 16384);
+  hipLaunchKernelGGL(ewise_kernel, dim3(blocks), dim3(256), 0, fsg_stream(stream), a, b, n, op, value, out);
   FSG_RETURN_LAUNCH();
 }
 
@@ -528,9 +525,8 @@ int fsg_boundary_mask_f32(const float* image, const float* mask, const float* ma
   if (n == 0) return 0;  // nothing to do: no launch, pointers may be null
   if (!mask || !mask_modif || !mog || !dist || n_dilate <= 0 || (!out && !mask_out) || (out && !image))
     return FSG_E_BADARG;
-  size_t blocks = (n + 255) / 256;
-  if (blocks > 16384) blocks = 16384;
-  hipLaunchKernelGGL(boundary_mask_kernel, dim3((unsigned)blocks), dim3(256), 0, fsg_stream(stream), image, mask, mask_modif,
+  const unsigned blocks = fsg_blocks(n, 256, 16384);
+  hipLaunchKernelGGL(boundary_mask_kernel, dim3(blocks), dim3(256), 0, fsg_stream(stream), image, mask, mask_modif,
                      mog, dist, n_dilate, n, out, mask_out);
   FSG_RETURN_LAUNCH();
 }
@@ -538,9 +534,8 @@ int fsg_boundary_mask_f32(const float* image, const float* mask, const float* ma
 int fsg_bernoulli_keep_f32(const float* a, size_t n, float p, uint64_t seed, uint64_t stream_id, float* out, void* stream) {
   if (n == 0) return 0;  // nothing to do: no launch, pointers may be null
   if (!a || !out) return FSG_E_BADARG;
-  size_t blocks = (n + 255) / 256;
-  if (blocks > 16384) blocks = 16384;
-  hipLaunchKernelGGL(bernoulli_kernel, dim3((unsigned)blocks), dim3(256), 0, fsg_stream(stream), a, n, p, seed, stream_id, out);
+  const unsigned blocks = fsg_blocks(n, 256, 16384);
+  hipLaunchKernelGGL(bernoulli_kernel, dim3(blocks), dim3(256), 0, fsg_stream(stream), a, n, p, seed, stream_id, out);
   FSG_RETURN_LAUNCH();
 }
 

@@ -98,6 +98,8 @@ __global__ __launch_bounds__(256) void blur_contig_lds(const float* __restrict__
       reinterpret_cast<float4*>(row + RP + nz)[lane] = make_float4(0.f, 0.f, 0.f, 0.f);
     }
     for (int q = lane; q < nz4; q += 64) reinterpret_cast<float4*>(row + RP)[q] = s4[q];
+    // Not fsg_wave_lds_sync() (fsg_common.h), here and in blur_contig_long: a bare wave barrier and an explicit wait, no
+    // fences.  A different construct with a different schedule; these kernels are timed and keep it.
     __builtin_amdgcn_wave_barrier();
     __builtin_amdgcn_s_waitcnt(0xC07F);  // lgkmcnt(0): this wave's LDS writes have landed
     for (int q = lane; q < nz4; q += 64) {
@@ -309,8 +311,7 @@ template <int R>
 int launch_contig(const float* src, float* dst, int rows, int nz, const Taps& T, hipStream_t st) {
   constexpr int RP = (R + 3) & ~3;
   const size_t lds = (size_t)4 * (nz + 2 * RP) * sizeof(float);
-  int grid = (rows + 3) / 4;
-  if (grid > 8192) grid = 8192;
+  const unsigned grid = fsg_blocks((size_t)rows, 4, 8192);
   hipLaunchKernelGGL((blur_contig_lds<R>), dim3(grid), dim3(256), lds, st, src, dst, rows, nz, T);
   FSG_RETURN_LAUNCH();
 }
@@ -328,9 +329,8 @@ extern "C" int fsg_blur_axis_f32(const float* src, float* dst, int nx, int ny, i
   else if (axis == 1) { outer = nx; len = ny; inner = nz; }
   else { outer = nx * ny; len = nz; inner = 1; }
   const size_t total = (size_t)nx * ny * nz;
-  size_t blocks = (total + 255) / 256;
-  if (blocks > 16384) blocks = 16384;
-  hipLaunchKernelGGL(blur_generic_kernel, dim3((unsigned)blocks), dim3(256), 0, st, src, dst, outer, len, inner, taps,
+  const unsigned blocks = fsg_blocks(total, 256, 16384);
+  hipLaunchKernelGGL(blur_generic_kernel, dim3(blocks), dim3(256), 0, st, src, dst, outer, len, inner, taps,
                      ntaps);
   FSG_RETURN_LAUNCH();
 }
@@ -363,8 +363,7 @@ extern "C" int fsg_blur_axis_taps_host_f32(const float* src, float* dst, int nx,
     }
     if (aligned && (nz & 3) == 0 && R > 8 && nz + 2 * ((R + 3) & ~3) + 4 <= 4096) {  // 4 staged rows within 64 KB of LDS
       const int RP = (R + 3) & ~3;
-      int grid = (rows + 3) / 4;
-      if (grid > 8192) grid = 8192;
+      const unsigned grid = fsg_blocks((size_t)rows, 4, 8192);
       hipLaunchKernelGGL(blur_contig_long, dim3(grid), dim3(256), (size_t)4 * (nz + 2 * RP + 4) * sizeof(float), st, src, dst,
                          rows, nz, R, T);
       FSG_RETURN_LAUNCH();

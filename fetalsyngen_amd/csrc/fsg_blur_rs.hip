@@ -35,13 +35,6 @@
 namespace {
 
 constexpr int RS_MAXR = 8;
-
-__device__ __forceinline__ void rs_wave_sync() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
 constexpr int RS_KCAP = 2 * RS_MAXR + 1;
 struct TapsK { float w[RS_KCAP + 3]; };
 
@@ -306,7 +299,7 @@ __global__ __launch_bounds__(64 * RSY_NW) void blur_rs_yz_kernel(const float4* _
       }
     }
   }
-  rs_wave_sync();
+  fsg_wave_lds_sync();
   // ---- per output row: z blur in place (every lane reads its windows, then the row is overwritten; taps ascending, fmaf),
   //      then z resampling + noise + clamp of the lane's quads (one Philox block per aligned quad of the FLAT output index:
   //      a row that does not start on a multiple of 4 takes its normals from two neighbouring blocks) ----
@@ -337,7 +330,7 @@ __global__ __launch_bounds__(64 * RSY_NW) void blur_rs_yz_kernel(const float4* _
         if (qi == 0 && inner4 <= 64) break;  // uniform: one float4 per lane and row
       }
     }
-    rs_wave_sync();
+    fsg_wave_lds_sync();
 #pragma unroll
     for (int p = 0; p < 2; ++p) {
       if (r0 + p < nrows) {
@@ -347,7 +340,7 @@ __global__ __launch_bounds__(64 * RSY_NW) void blur_rs_yz_kernel(const float4* _
           if (tx + 64 * qi < inner4) reinterpret_cast<float4*>(row + RP)[tx + 64 * qi] = make_float4(o[p][qi][0], o[p][qi][1], o[p][qi][2], o[p][qi][3]);
       }
     }
-    rs_wave_sync();
+    fsg_wave_lds_sync();
 #pragma unroll
     for (int p = 0; p < 2; ++p) {
       if (r0 + p >= nrows) break;  // uniform

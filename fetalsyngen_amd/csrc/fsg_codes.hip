@@ -170,17 +170,10 @@ int fsg_seed_codes_build(const uint8_t* const* parts, int nparts, size_t n, int 
   P.slot_code = (int32_t*)(w + (size_t)SC_SLOTS * sizeof(int32_t));
   P.slot_col = (uint32_t*)(w + (size_t)SC_SLOTS * 2 * sizeof(int32_t));
   P.count = count_dev;
-  size_t blocks = (n + 255) / 256;
-  if (blocks > 4096) blocks = 4096;
   bool quad = (n & 3) == 0 && (((uintptr_t)codes) & 7) == 0;
   for (int j = 0; j < nparts; ++j) quad = quad && (((uintptr_t)parts[j]) & 3) == 0;
-  if (quad) {
-    blocks = (n / 4 + 255) / 256;
-    if (blocks > 4096) blocks = 4096;
-    hipLaunchKernelGGL(seed_codes_kernel<4>, dim3((unsigned)blocks), dim3(256), 0, st, P);
-  } else {
-    hipLaunchKernelGGL(seed_codes_kernel<1>, dim3((unsigned)blocks), dim3(256), 0, st, P);
-  }
+  if (quad) hipLaunchKernelGGL(seed_codes_kernel<4>, dim3(fsg_blocks(n / 4, 256, 4096)), dim3(256), 0, st, P);
+  else hipLaunchKernelGGL(seed_codes_kernel<1>, dim3(fsg_blocks(n, 256, 4096)), dim3(256), 0, st, P);
   FSG_RETURN_LAUNCH();
 }
 

@@ -22,6 +22,25 @@ extern int g_tuning_flags;
 
 static inline hipStream_t fsg_stream(void* s) { return (hipStream_t)s; }
 
+// Workgroups of a grid-stride launch: ceil(n / per_block), at most `cap`, and at least one where the site launches for n = 0 too.
+// Divisor, cap and lower bound are the site's own (measured) choices.
+static inline unsigned fsg_blocks(size_t n, size_t per_block, size_t cap, bool at_least_one = false) {
+  size_t b = (n + per_block - 1) / per_block;
+  if (b > cap) b = cap;
+  if (at_least_one && b < 1) b = 1;
+  return (unsigned)b;
+}
+
+// The instantiations of a fused-warp kernel family: LAUNCH(HAS_LIN, HAS_NN, FAST) for both sources / the trilinear one alone,
+// each with fast or precise epilogue math, and the labels alone (no epilogue: one instantiation).
+#define FSG_WARP_LADDER(LAUNCH, lin, nn, fast)                                                             \
+  do {                                                                                                     \
+    const bool lin_ = (lin), nn_ = (nn), fast_ = (fast); /* each argument evaluated once */                \
+    if (lin_ && nn_) { if (fast_) LAUNCH(true, true, true); else LAUNCH(true, true, false); }              \
+    else if (lin_)   { if (fast_) LAUNCH(true, false, true); else LAUNCH(true, false, false); }            \
+    else             { LAUNCH(false, true, true); }                                                        \
+  } while (0)
+
 // [p, p + bytes) and [q, q + qbytes) share a byte; an absent (null) array shares none.  The one overlap test of the library:
 // it stands in front of every kernel whose arguments are declared __restrict__ or whose state block must not be an operand.
 static inline bool fsg_overlap(const void* p, size_t bytes, const void* q, size_t qbytes) {
@@ -77,6 +96,47 @@ __device__ __forceinline__ float fsg_wave_max(float v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, FSG_WAVE));
   return v;
+}
+
+// Workgroup min / max for 256-thread workgroups of four waves (the zoom kernels, minmax_kernel; perlin_kernel, whose wave count
+// is the launch's, keeps its own): every thread calls it with its lo, hi and the workgroup's red[2][4].  `first` in thread 0 alone, whose lo / hi
+// are then the workgroup's; the caller writes the keys its own way.  (fsg_regrid.hip folds six integers and keeps its own.)
+// `wave` is the caller's wave index, so that a kernel which holds it in a scalar register (readfirstlane) keeps it there.
+// By value and by return on purpose: with lo / hi passed by reference the compiler orders the callers' loops differently.
+struct FsgMinMax {
+  float lo, hi;
+  bool first;  // thread 0: lo / hi are the workgroup's
+};
+__device__ __forceinline__ FsgMinMax fsg_block_minmax(float lo, float hi, float (*red)[4], int wave) {
+  const int lane = threadIdx.x & 63;
+  lo = fsg_wave_min(lo);
+  hi = fsg_wave_max(hi);
+  if (lane == 0) { red[0][wave] = lo; red[1][wave] = hi; }
+  __syncthreads();
+  const bool first = threadIdx.x == 0;
+  if (first) {
+    for (int w = 1; w < 4; ++w) { lo = fminf(lo, red[0][w]); hi = fmaxf(hi, red[1][w]); }
+  }
+  return FsgMinMax{lo, hi, first};
+}
+
+// Hand-over of LDS data between the lanes of ONE wave (a wave-private row or plate): the writes before it are visible to every
+// lane after it.  No workgroup barrier.  (fsg_blur.hip keeps a different construct, see there.)
+__device__ __forceinline__ void fsg_wave_lds_sync() {
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+// table entry idx, idx wave-uniform: broadcast through SGPRs so the 16-byte load is issued once
+__device__ __forceinline__ fsg_tap fsg_uniform_tap(const fsg_tap* t, int idx) {
+  const int4 v = *reinterpret_cast<const int4*>(t + idx);
+  fsg_tap r;
+  r.lo = __builtin_amdgcn_readfirstlane(v.x);
+  r.hi = __builtin_amdgcn_readfirstlane(v.y);
+  r.w_lo = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(v.z));
+  r.w_hi = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(v.w));
+  return r;
 }
 
 // The fold of the streaming pixel passes (fsg_robust.hip, fsg_imatch.hip): every thread of the THREADS-wide workgroup calls it

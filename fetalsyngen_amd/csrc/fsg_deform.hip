@@ -113,12 +113,6 @@ __device__ __forceinline__ T sample_nearest(const T* __restrict__ s, const FsgDe
 // =================================================================================================
 constexpr int ROWCAP = 512;  // floats of LDS per wave (3*f2 + b2 must fit; else per-voxel fallback)
 
-__device__ __forceinline__ void wave_lds_sync() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
 // x/y part of the separable interpolation for one row: dst[c*s2 + zs], c < NCH
 template <int NCH>
 __device__ __forceinline__ void fill_row_xy(const float* __restrict__ grid, int s1, int s2, const fsg_tap a,
@@ -134,17 +128,6 @@ __device__ __forceinline__ void fill_row_xy(const float* __restrict__ grid, int 
     const float t1 = fsg_mix(a.w_lo, p01[o], a.w_hi, p11[o]);  // y = b.hi
     dst[e] = fsg_mix(b.w_lo, t0, b.w_hi, t1);
   }
-}
-
-__device__ __forceinline__ fsg_tap uniform_tap(const fsg_tap* t, int idx) {
-  // idx is wave-uniform: broadcast through SGPRs so the 16-byte load is issued once
-  const int4 v = *reinterpret_cast<const int4*>(t + idx);
-  fsg_tap r;
-  r.lo = __builtin_amdgcn_readfirstlane(v.x);
-  r.hi = __builtin_amdgcn_readfirstlane(v.y);
-  r.w_lo = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(v.z));
-  r.w_hi = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(v.w));
-  return r;
 }
 
 // position of voxel (i,j,k) from the row's LDS slot (same op order as fsg_position)
@@ -169,10 +152,6 @@ __device__ __forceinline__ void row_position(const FsgDeformK& D, const float* s
 }
 
 typedef float float2_u __attribute__((ext_vector_type(2), aligned(4)));
-
-// logical tile id: hardware deals consecutive workgroups round-robin over the 8 XCDs; give every XCD a
-// contiguous range of tiles (= a slab of x planes) so the source planes it gathers from stay in ITS L2.
-// Speed only: any mapping gives the same result.
 
 // ---- per-row coarse values, precomputed once per deformation ------------------------------------------
 // rows[(i*n1 + j)*stride + e]: e < 3*f2 -> x/y-interpolated displacement (channel-major, then z index of
@@ -242,13 +221,13 @@ __device__ __forceinline__ void deform_rows_block(const FsgDeformK& D, const Epi
     if (E.bias) S.by[tid] = *reinterpret_cast<const int4*>(E.by + j0 + tid);
   }
   if (D.field) {
-    const fsg_tap a = uniform_tap(D.tx, i);
+    const fsg_tap a = fsg_uniform_tap(D.tx, i);
     const float* g0 = D.field + (size_t)a.lo * slab_f;
     const float* g1 = D.field + (size_t)a.hi * slab_f;
     for (int t = tid; t < slab_f; t += 256) S.sf[t] = fsg_mix(a.w_lo, g0[t], a.w_hi, g1[t]);
   }
   if (E.bias) {
-    const fsg_tap a = uniform_tap(E.bx, i);
+    const fsg_tap a = fsg_uniform_tap(E.bx, i);
     const float* g0 = E.bias + (size_t)a.lo * slab_b;
     const float* g1 = E.bias + (size_t)a.hi * slab_b;
     for (int t = tid; t < slab_b; t += 256) S.sb[t] = fsg_mix(a.w_lo, g0[t], a.w_hi, g1[t]);
@@ -550,8 +529,8 @@ __device__ __forceinline__ void stage_row(const FsgDeformK& D, const EpiK& E, in
     const float* r = D.rows + ((size_t)i * D.n1 + j) * D.row_stride;
     for (int e = lane; e < need; e += FSG_WAVE) sm[e] = r[e];
   } else {
-    if (D.field) fill_row_xy<3>(D.field, D.f1, D.f2, ax, uniform_tap(D.ty, j), sm, lane);
-    if (E.bias) fill_row_xy<1>(E.bias, E.b1, E.b2, abx, uniform_tap(E.by, j), sm + nf, lane);
+    if (D.field) fill_row_xy<3>(D.field, D.f1, D.f2, ax, fsg_uniform_tap(D.ty, j), sm, lane);
+    if (E.bias) fill_row_xy<1>(E.bias, E.b1, E.b2, abx, fsg_uniform_tap(E.by, j), sm + nf, lane);
   }
 }
 
@@ -593,8 +572,8 @@ __global__ __launch_bounds__(256) void warp_rows_kernel(FsgDeformK D, const int3
   const int need = nf + (E.bias ? E.b2 : 0);
   const fsg_tap none = fsg_tap{0, 0, 0.f, 0.f};
   const bool onfly = D.rows == nullptr;
-  const fsg_tap ax = (onfly && D.field) ? uniform_tap(D.tx, i) : none;
-  const fsg_tap abx = (onfly && E.bias) ? uniform_tap(E.bx, i) : none;
+  const fsg_tap ax = (onfly && D.field) ? fsg_uniform_tap(D.tx, i) : none;
+  const fsg_tap abx = (onfly && E.bias) ? fsg_uniform_tap(E.bx, i) : none;
   // the z tables are the same for every row: keep this lane's entries in registers (n2 <= 256)
   const bool cached = D.n2 <= 256;
   fsg_tap ck[4], cbk[4];
@@ -610,7 +589,7 @@ __global__ __launch_bounds__(256) void warp_rows_kernel(FsgDeformK D, const int3
     const int j = jbase + r * jstep;
     if (j >= D.n1) break;
     const float* sm = sm_all[wave][r & 1];
-    wave_lds_sync();
+    fsg_wave_lds_sync();
     // prefetch the next row's coarse values into the other buffer while this row's gathers are in flight
     if (r + 1 < WARP_ROWS_PER_WAVE && j + jstep < D.n1 && need)
       stage_row(D, E, i, j + jstep, nf, need, ax, abx, sm_all[wave][(r + 1) & 1], lane);
@@ -678,8 +657,8 @@ __global__ __launch_bounds__(1024, 8) void warp_patch_kernel(FsgDeformK D, const
   float* sm = sm_all[wave];
   if (need) {
     const bool onfly = D.rows == nullptr;
-    const fsg_tap ax = (onfly && D.field) ? uniform_tap(D.tx, i) : none;
-    const fsg_tap abx = (onfly && E.bias) ? uniform_tap(E.bx, i) : none;
+    const fsg_tap ax = (onfly && D.field) ? fsg_uniform_tap(D.tx, i) : none;
+    const fsg_tap abx = (onfly && E.bias) ? fsg_uniform_tap(E.bx, i) : none;
     stage_row(D, E, i, j, nf, need, ax, abx, sm, lane);
   }
   __syncthreads();  // rows are wave-private, the z taps were written by every wave
@@ -753,9 +732,9 @@ __device__ __forceinline__ void coords_minmax_rows_body(const FsgDeformK& D, int
       const float* rr = D.rows + (size_t)r * D.row_stride;
       for (int e = lane; e < 3 * D.f2; e += FSG_WAVE) sm[e] = rr[e];
     } else if (D.field) {
-      fill_row_xy<3>(D.field, D.f1, D.f2, uniform_tap(D.tx, i), uniform_tap(D.ty, j), sm, lane);
+      fill_row_xy<3>(D.field, D.f1, D.f2, fsg_uniform_tap(D.tx, i), fsg_uniform_tap(D.ty, j), sm, lane);
     }
-    wave_lds_sync();
+    fsg_wave_lds_sync();
     if (cached) {
 #pragma unroll
       for (int q = 0; q < 4; ++q) {
@@ -777,7 +756,7 @@ __device__ __forceinline__ void coords_minmax_rows_body(const FsgDeformK& D, int
         lo[2] = fminf(lo[2], z); hi[2] = fmaxf(hi[2], z);
       }
     }
-    wave_lds_sync();
+    fsg_wave_lds_sync();
   }
 #pragma unroll
   for (int a = 0; a < 3; ++a) {
@@ -820,22 +799,41 @@ __global__ __launch_bounds__(256) void warp_kernel(FsgDeformK D, const int32_t* 
   }
 }
 
-template <typename LT>
-int launch_warp(const fsg_deform* d, const int32_t* mm6, const float* src_lin, float* out_lin, const LT* src_nn,
-                LT* out_nn, const fsg_epilogue* epi, void* stream) {
-  FsgDeformK D;
-  int rc = fsg_fill_deform(d, D);
+// ---- operand checks of the fused-warp entry points ----------------------------------------------------------------------------
+// What fsg_warp_f32 / _u8 (launch_warp), fsg_warp_f32_u8_to_f32 and fsg_warp_dual_f32 all refuse, before any launch: a bad
+// deformation (fsg_fill_deform's own code, FSG_E_TOOBIG included, first in all three), then with FSG_E_BADARG a null mm6, one of
+// a source / destination pair without the other, no source at all (the dual entry point needs src_lin, so it refuses that too)
+// and a bad epilogue.  Every refusal after the deformation's is FSG_E_BADARG, so their order among themselves shows nowhere.
+static int warp_operands(const fsg_deform* d, const fsg_epilogue* epi, const int32_t* mm6, const void* src_lin,
+                         const void* out_lin, const void* src_nn, const void* out_nn, FsgDeformK& D, EpiK& E) {
+  const int rc = fsg_fill_deform(d, D);
   if (rc) return rc;
   if (!mm6) return FSG_E_BADARG;
   if ((src_lin == nullptr) != (out_lin == nullptr)) return FSG_E_BADARG;
   if ((src_nn == nullptr) != (out_nn == nullptr)) return FSG_E_BADARG;
   if (!src_lin && !src_nn) return FSG_E_BADARG;
-  if ((const void*)src_lin == (const void*)out_lin && src_lin) return FSG_E_BADARG;
-  EpiK E;
-  rc = fill_epilogue(epi, E);
-  if (rc) return rc;
+  return fill_epilogue(epi, E);
+}
+
+// Two more that launch_warp and fsg_warp_dual_f32 make and fsg_warp_f32_u8_to_f32 does NOT: the trilinear source warped onto
+// itself, and precomputed rows narrower than the coarse values of a row.  (_u8_to_f32 launches the first as it is, and for the
+// second gets FSG_E_ALIGN from the lean launcher where the other two answer FSG_E_BADARG.  Not unified here.)
+static int warp_alias_rows(const FsgDeformK& D, const EpiK& E, const void* src_lin, const void* out_lin) {
+  if (src_lin && src_lin == out_lin) return FSG_E_BADARG;
   const int need = (D.field ? 3 * D.f2 : 0) + (E.bias ? E.b2 : 0);
   if (D.rows && D.row_stride < need) return FSG_E_BADARG;
+  return 0;
+}
+
+template <typename LT>
+int launch_warp(const fsg_deform* d, const int32_t* mm6, const float* src_lin, float* out_lin, const LT* src_nn,
+                LT* out_nn, const fsg_epilogue* epi, void* stream) {
+  FsgDeformK D;
+  EpiK E;
+  int rc = warp_operands(d, epi, mm6, src_lin, out_lin, src_nn, out_nn, D, E);
+  if (!rc) rc = warp_alias_rows(D, E, src_lin, out_lin);
+  if (rc) return rc;
+  const int need = (D.field ? 3 * D.f2 : 0) + (E.bias ? E.b2 : 0);
   if (!(g_tuning_flags & (FSG_TUNE_GENERIC_WARP | FSG_TUNE_NO_PATCH | FSG_TUNE_NO_LEAN))) {
     // default: the lean body (fsg_warp_lean.hip); FSG_E_ALIGN = configuration outside its domain
     rc = fsg_launch_warp_lean(D, E, mm6, src_lin, out_lin, src_nn, out_nn, (int)sizeof(LT), (int)sizeof(LT),
@@ -849,9 +847,7 @@ int launch_warp(const fsg_deform* d, const int32_t* mm6, const float* src_lin, f
     hipStream_t st = fsg_stream(stream);
 #define FSG_LAUNCH_PATCH(L, N, F) \
   hipLaunchKernelGGL((warp_patch_kernel<LT, L, N, F>), grid, block, 0, st, D, mm6, src_lin, out_lin, src_nn, out_nn, E)
-    if (src_lin && src_nn) { if (fast) FSG_LAUNCH_PATCH(true, true, true); else FSG_LAUNCH_PATCH(true, true, false); }
-    else if (src_lin)      { if (fast) FSG_LAUNCH_PATCH(true, false, true); else FSG_LAUNCH_PATCH(true, false, false); }
-    else                   { FSG_LAUNCH_PATCH(false, true, true); }
+    FSG_WARP_LADDER(FSG_LAUNCH_PATCH, src_lin, src_nn, fast);
 #undef FSG_LAUNCH_PATCH
     FSG_RETURN_LAUNCH();
   }
@@ -868,9 +864,7 @@ int launch_warp(const fsg_deform* d, const int32_t* mm6, const float* src_lin, f
     hipStream_t st = fsg_stream(stream);
 #define FSG_LAUNCH_WARP(L, N, F) \
   hipLaunchKernelGGL((warp_rows_kernel<LT, L, N, F>), grid, block, 0, st, D, mm6, src_lin, out_lin, src_nn, out_nn, E)
-    if (src_lin && src_nn) { if (fast) FSG_LAUNCH_WARP(true, true, true); else FSG_LAUNCH_WARP(true, true, false); }
-    else if (src_lin)      { if (fast) FSG_LAUNCH_WARP(true, false, true); else FSG_LAUNCH_WARP(true, false, false); }
-    else                   { FSG_LAUNCH_WARP(false, true, true); }
+    FSG_WARP_LADDER(FSG_LAUNCH_WARP, src_lin, src_nn, fast);
 #undef FSG_LAUNCH_WARP
     FSG_RETURN_LAUNCH();
   }
@@ -960,7 +954,7 @@ int fsg_coords_minmax_f32(const fsg_deform* d, int32_t* mm6, void* stream) {
   if (!mm6) return FSG_E_BADARG;
   const int rows = D.n0 * D.n1;
   if ((D.field ? 3 * D.f2 : 0) <= ROWCAP && !(g_tuning_flags & FSG_TUNE_GENERIC_WARP)) {
-    int grid = (rows + 7) / 8 < 2048 ? (rows + 7) / 8 : 2048;
+    int grid = (int)fsg_blocks((size_t)rows, 8, 2048);
     const int rpb = (rows + grid - 1) / grid;
     grid = (rows + rpb - 1) / rpb;
     hipLaunchKernelGGL(coords_minmax_rows_kernel<false>, dim3(grid), dim3(256), 0, fsg_stream(stream), D, mm6, rpb);
@@ -978,14 +972,12 @@ int fsg_coords_floormin_f32(const fsg_deform* d, int32_t* mm3, void* stream) {
   if (!mm3) return FSG_E_BADARG;
   hipStream_t st = fsg_stream(stream);
   const int faces = faces_total(D.n0, D.n1, D.n2);
-  int g1 = (faces + 255) / 256;
-  if (g1 > 1024) g1 = 1024;
-  hipLaunchKernelGGL(coords_faces_min_kernel, dim3(g1), dim3(256), 0, st, D, mm3);
+  hipLaunchKernelGGL(coords_faces_min_kernel, dim3(fsg_blocks((size_t)faces, 256, 1024)), dim3(256), 0, st, D, mm3);
   const int rows = D.n0 * D.n1;
   if ((D.field ? 3 * D.f2 : 0) <= ROWCAP) {
     // 512 workgroups: in the usual case every one of them exits on its first instruction, and fewer of them
     // exit sooner; the rare full pass runs at a quarter of the parallelism, which is fine
-    int grid = (rows + 7) / 8 < 512 ? (rows + 7) / 8 : 512;
+    int grid = (int)fsg_blocks((size_t)rows, 8, 512);
     const int rpb = (rows + grid - 1) / grid;
     grid = (rows + rpb - 1) / rpb;
     hipLaunchKernelGGL(coords_minmax_rows_kernel<true>, dim3(grid), dim3(256), 0, st, D, mm3, rpb);
@@ -1003,7 +995,7 @@ int fsg_coords_floormin_rest_f32(const fsg_deform* d, int32_t* mm3, void* stream
   if (!mm3) return FSG_E_BADARG;
   if ((D.field ? 3 * D.f2 : 0) > ROWCAP) return FSG_E_TOOBIG;
   const int rows = D.n0 * D.n1;
-  int grid = (rows + 7) / 8 < 512 ? (rows + 7) / 8 : 512;
+  int grid = (int)fsg_blocks((size_t)rows, 8, 512);
   const int rpb = (rows + grid - 1) / grid;
   grid = (rows + rpb - 1) / rpb;
   hipLaunchKernelGGL(coords_minmax_rows_kernel<true>, dim3(grid), dim3(256), 0, fsg_stream(stream), D, mm3, rpb);
@@ -1085,12 +1077,10 @@ static int launch_sample_head(const HeadGmm& G, size_t n, const fsg_deform* d, c
   const int rows_gx = need > 0 ? (D.n1 + RB_J - 1) / RB_J : 0;
   const long long nrows = (long long)rows_gx * D.n0;
   const int faces = faces_total(D.n0, D.n1, D.n2);
-  int nfaces = (faces + 255) / 256;
-  if (nfaces > 1024) nfaces = 1024;
-  size_t ngmm = ((n + 3) / 4 + 255) / 256;
-  if (!G.out) ngmm = 0;  // fsg_internal_head_no_gmm
-  if (ngmm > 4096) ngmm = 4096;  // 4 groups per thread: 33.8 us (8 192: 34.8, 16 384: 39.0); codes mode, 2 x 8 voxels per thread: 30.5 us
-                                 // (1 024: 34.7, 2 048: 37.0, 8 192: 33.6)
+  const int nfaces = (int)fsg_blocks((size_t)faces, 256, 1024);
+  // No GMM job without an output (fsg_internal_head_no_gmm).  Cap 4 096, 4 groups per thread: 33.8 us (8 192: 34.8,
+  // 16 384: 39.0); codes mode, 2 x 8 voxels per thread: 30.5 us (1 024: 34.7, 2 048: 37.0, 8 192: 33.6)
+  const unsigned ngmm = G.out ? fsg_blocks((n + 3) / 4, 256, 4096) : 0u;
   if (nrows > 1000000) return FSG_E_TOOBIG;
   static const fsg_ride::DrawK no_draw = {};
   hipLaunchKernelGGL(sample_head_kernel, dim3((unsigned)(nrows + nfaces + ngmm) + draw_blocks), dim3(256), 0, fsg_stream(stream), G,
@@ -1122,15 +1112,10 @@ int fsg_warp_f32_u8(const fsg_deform* d, const int32_t* mm6, const float* src_li
 int fsg_warp_f32_u8_to_f32(const fsg_deform* d, const int32_t* mm6, const float* src_lin, float* out_lin,
                            const uint8_t* src_nn, float* out_nn, const fsg_epilogue* epi, void* stream) {
   FsgDeformK D;
-  int rc = fsg_fill_deform(d, D);
-  if (rc) return rc;
-  if (!mm6) return FSG_E_BADARG;
-  if ((src_lin == nullptr) != (out_lin == nullptr)) return FSG_E_BADARG;
-  if ((src_nn == nullptr) != (out_nn == nullptr)) return FSG_E_BADARG;
-  if (!src_lin && !src_nn) return FSG_E_BADARG;
   EpiK E;
-  rc = fill_epilogue(epi, E);
+  const int rc = warp_operands(d, epi, mm6, src_lin, out_lin, src_nn, out_nn, D, E);
   if (rc) return rc;
+  // (no warp_alias_rows here: see there)
   if (g_tuning_flags & (FSG_TUNE_GENERIC_WARP | FSG_TUNE_NO_PATCH | FSG_TUNE_NO_LEAN)) return FSG_E_ALIGN;
   // served by the lean kernel alone (the uint8 -> uint8 case reaches it through launch_warp)
   return fsg_launch_warp_lean(D, E, mm6, src_lin, out_lin, src_nn, out_nn, 1, 4, !(g_tuning_flags & FSG_TUNE_PRECISE_MATH),
@@ -1141,22 +1126,18 @@ int fsg_warp_dual_f32(const fsg_deform* d, const int32_t* mm6, const float* src_
                       float* out_img, size_t img_voxels, const void* src_nn, void* out_nn, int label_dtype_in, int label_dtype_out,
                       const fsg_epilogue* epi, void* stream) {
   FsgDeformK D;
-  int rc = fsg_fill_deform(d, D);
+  EpiK E;
+  int rc = warp_operands(d, epi, mm6, src_lin, out_lin, src_nn, out_nn, D, E);
+  if (!rc) rc = warp_alias_rows(D, E, src_lin, out_lin);
   if (rc) return rc;
-  if (!mm6 || !src_lin || !out_lin || src_lin == out_lin) return FSG_E_BADARG;
+  if (!src_lin) return FSG_E_BADARG;  // the labels alone are fsg_warp_f32 / _u8's
   if ((src_img == nullptr) != (out_img == nullptr)) return FSG_E_BADARG;
   if (src_img && (img_voxels != (size_t)D.n0 * D.n1 * D.n2 || out_img == src_img || out_img == src_lin || out_img == out_lin ||
                   out_lin == src_img))  // an output over a source other lanes still gather from
     return FSG_E_BADARG;
-  if ((src_nn == nullptr) != (out_nn == nullptr)) return FSG_E_BADARG;
   const int lin = label_dtype_in == FSG_LABEL_F32 ? 4 : label_dtype_in == FSG_LABEL_U8 ? 1 : 0;
   const int lout = label_dtype_out == FSG_LABEL_F32 ? 4 : label_dtype_out == FSG_LABEL_U8 ? 1 : 0;
   if (src_nn && (!lin || !lout || (lin == 4 && lout == 1))) return FSG_E_BADARG;
-  EpiK E;
-  rc = fill_epilogue(epi, E);
-  if (rc) return rc;
-  const int need = (D.field ? 3 * D.f2 : 0) + (E.bias ? E.b2 : 0);
-  if (D.rows && D.row_stride < need) return FSG_E_BADARG;
   if (g_tuning_flags & (FSG_TUNE_GENERIC_WARP | FSG_TUNE_NO_PATCH | FSG_TUNE_NO_LEAN)) return FSG_E_ALIGN;
   return fsg_launch_warp_lean(D, E, mm6, src_lin, out_lin, src_nn, out_nn, src_nn ? lin : 4, src_nn ? lout : 4,
                               !(g_tuning_flags & FSG_TUNE_PRECISE_MATH), stream, src_img, out_img);
@@ -1168,9 +1149,7 @@ int fsg_interp3d_f32(const float* src, int sx, int sy, int sz, const float* ii, 
   if (mode != 0 && mode != 1) return FSG_E_BADARG;
   if ((size_t)sx * sy * sz > (size_t)0x7FFFFFFF) return FSG_E_TOOBIG;
   if (npts == 0) return 0;
-  size_t blocks = (npts + 255) / 256;
-  if (blocks > 8192) blocks = 8192;
-  hipLaunchKernelGGL(interp_kernel, dim3((unsigned)blocks), dim3(256), 0, fsg_stream(stream), src, sx, sy, sz, ii,
+  hipLaunchKernelGGL(interp_kernel, dim3(fsg_blocks(npts, 256, 8192)), dim3(256), 0, fsg_stream(stream), src, sx, sy, sz, ii,
                      jj, kk, npts, mode, defval, dst);
   FSG_RETURN_LAUNCH();
 }

@@ -163,15 +163,11 @@ extern "C" int fsg_internal_sample_run(const fsg_sample_plan* p, const fsg_sampl
     int rw = FSG_E_ALIGN;
     bool image_done = false;
     if (image_in) {  // the real image in the same launch (same label sources as below); FSG_E_ALIGN: the two-launch form
-      if (p->seg_out_u8)
-        rw = fsg_warp_dual_f32(&d, p->mm8, cur, other, image_in, image_out, n, p->seg_in_u8, p->seg_out_u8, FSG_LABEL_U8,
-                               FSG_LABEL_U8, &p->epi, stream);
-      else if (p->seg_in_u8)
-        rw = fsg_warp_dual_f32(&d, p->mm8, cur, other, image_in, image_out, n, p->seg_in_u8, p->seg_out, FSG_LABEL_U8,
-                               FSG_LABEL_F32, &p->epi, stream);
-      else
-        rw = fsg_warp_dual_f32(&d, p->mm8, cur, other, image_in, image_out, n, p->seg_in, p->seg_out, FSG_LABEL_F32,
-                               FSG_LABEL_F32, &p->epi, stream);
+      const bool in_u8 = p->seg_out_u8 || p->seg_in_u8;
+      const void* src_nn = in_u8 ? (const void*)p->seg_in_u8 : (const void*)p->seg_in;
+      void* out_nn = p->seg_out_u8 ? (void*)p->seg_out_u8 : (void*)p->seg_out;
+      rw = fsg_warp_dual_f32(&d, p->mm8, cur, other, image_in, image_out, n, src_nn, out_nn, in_u8 ? FSG_LABEL_U8 : FSG_LABEL_F32,
+                             p->seg_out_u8 ? FSG_LABEL_U8 : FSG_LABEL_F32, &p->epi, stream);
       image_done = rw == 0;
     }
     if (image_done) {

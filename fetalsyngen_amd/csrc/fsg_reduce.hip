@@ -24,15 +24,10 @@ __global__ __launch_bounds__(256) void minmax_kernel(const float* __restrict__ x
     for (size_t g = e; g < n; g += stride) { lo = fminf(lo, x[g]); hi = fmaxf(hi, x[g]); }
   }
   __shared__ float red[2][4];
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  lo = fsg_wave_min(lo);
-  hi = fsg_wave_max(hi);
-  if (lane == 0) { red[0][wave] = lo; red[1][wave] = hi; }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    for (int w = 1; w < 4; ++w) { lo = fminf(lo, red[0][w]); hi = fmaxf(hi, red[1][w]); }
-    fsg_atomic_min_key(&mm[0], lo);
-    fsg_atomic_max_key(&mm[1], hi);
+  const FsgMinMax m = fsg_block_minmax(lo, hi, red, threadIdx.x >> 6);
+  if (m.first) {
+    fsg_atomic_min_key(&mm[0], m.lo);
+    fsg_atomic_max_key(&mm[1], m.hi);
   }
 }
 
@@ -85,38 +80,32 @@ extern "C" {
 int fsg_cast_f32_to_f16(const float* x, size_t n, void* out_f16, void* stream) {
   if (n == 0) return 0;  // nothing to do: no launch, pointers may be null
   if (!x || !out_f16) return FSG_E_BADARG;
-  size_t blocks = (n / 8 + 255) / 256;
-  if (blocks > 4096) blocks = 4096;
-  if (blocks < 1) blocks = 1;
-  hipLaunchKernelGGL(cast_f16_kernel, dim3((unsigned)blocks), dim3(256), 0, fsg_stream(stream), x, n, (_Float16*)out_f16);
+  const unsigned blocks = fsg_blocks(n / 8, 256, 4096, true);
+  hipLaunchKernelGGL(cast_f16_kernel, dim3(blocks), dim3(256), 0, fsg_stream(stream), x, n, (_Float16*)out_f16);
   FSG_RETURN_LAUNCH();
 }
 
 int fsg_copy_bytes(void* dst, const void* src, size_t nbytes, void* stream) {
   if (!dst || !src || nbytes == 0 || (nbytes & 15) || (((uintptr_t)dst | (uintptr_t)src) & 15)) return FSG_E_BADARG;
   const size_t n16 = nbytes >> 4;
-  size_t blocks = (n16 + 255) / 256;
-  if (blocks > 1024) blocks = 1024;
-  hipLaunchKernelGGL(copy16_kernel, dim3((unsigned)blocks), dim3(256), 0, fsg_stream(stream), (uint4*)dst, (const uint4*)src, n16);
+  const unsigned blocks = fsg_blocks(n16, 256, 1024);
+  hipLaunchKernelGGL(copy16_kernel, dim3(blocks), dim3(256), 0, fsg_stream(stream), (uint4*)dst, (const uint4*)src, n16);
   FSG_RETURN_LAUNCH();
 }
 
 int fsg_reduce_minmax_f32(const float* x, size_t n, int32_t* mm, void* stream) {
   if (n == 0) return 0;  // nothing to do: no launch, pointers may be null
   if (!x || !mm) return FSG_E_BADARG;
-  size_t blocks = (n / 4 + 255) / 256;
-  if (blocks < 1) blocks = 1;
-  if (blocks > 2048) blocks = 2048;
-  hipLaunchKernelGGL(minmax_kernel, dim3((unsigned)blocks), dim3(256), 0, fsg_stream(stream), x, n, mm);
+  const unsigned blocks = fsg_blocks(n / 4, 256, 2048, true);
+  hipLaunchKernelGGL(minmax_kernel, dim3(blocks), dim3(256), 0, fsg_stream(stream), x, n, mm);
   FSG_RETURN_LAUNCH();
 }
 
 int fsg_scale_f32(const float* x, size_t n, const int32_t* mm, int mode, float* out, void* stream) {
   if (n == 0) return 0;  // nothing to do: no launch, pointers may be null
   if (!x || !mm || !out || mode < 0 || mode > 2) return FSG_E_BADARG;
-  size_t blocks = (n + 255) / 256;
-  if (blocks > 8192) blocks = 8192;
-  hipLaunchKernelGGL(scale_kernel, dim3((unsigned)blocks), dim3(256), 0, fsg_stream(stream), x, n, mm, mode, out);
+  const unsigned blocks = fsg_blocks(n, 256, 8192);
+  hipLaunchKernelGGL(scale_kernel, dim3(blocks), dim3(256), 0, fsg_stream(stream), x, n, mm, mode, out);
   FSG_RETURN_LAUNCH();
 }
 

@@ -236,11 +236,6 @@ __global__ __launch_bounds__(SA_TILE* SA_TILE) void sa_forward_linear_fast_kerne
 // ---------------------------------------------------------------------------------------------------------
 constexpr int SAP_CAP = 2048;  // floats of plate per wave
 
-__device__ __forceinline__ void sap_wave_sync() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
 __device__ __forceinline__ float sap_uni(float v) { return __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, v))); }
 
 __global__ __launch_bounds__(256) void sa_forward_plate_kernel(SaParams P, const float* __restrict__ vol,
@@ -359,7 +354,7 @@ __global__ __launch_bounds__(256) void sa_forward_plate_kernel(SaParams P, const
               if (r < nrow) box[r * pitch + xl] = v[u];
             }
           }
-          sap_wave_sync();
+          fsg_wave_lds_sync();
         }
         const int py = pitch, pz = pitch * ey, org = Z0 * pz + Y0 * py + X0;
         for (int t = t_beg + phase; t < t_end; t += 8) {  // two taps of this phase per trip
@@ -411,7 +406,7 @@ __global__ __launch_bounds__(256) void sa_forward_plate_kernel(SaParams P, const
             weight += pvv[u];
           }
         }
-        if (plate && t_end > t_beg) sap_wave_sync();  // the next chunk's copy overwrites the plate
+        if (plate && t_end > t_beg) fsg_wave_lds_sync();  // the next chunk's copy overwrites the plate
         kz = kz1;
       }
     }
@@ -1182,9 +1177,8 @@ int fsg_slice_acq_adjoint_det_f32(const float* transforms, const float* psf, int
     hipError_t el = hipGetLastError();
     if (el != hipSuccess) return (int)el;
   }
-  size_t blocks = (nvox + 255) / 256;
-  if (blocks > 8192) blocks = 8192;
-  hipLaunchKernelGGL(sa_det_finalize_kernel, dim3((unsigned)blocks), dim3(256), 0, st, (const long long*)acc, limbs, vol,
+  const unsigned blocks = fsg_blocks(nvox, 256, 8192);
+  hipLaunchKernelGGL(sa_det_finalize_kernel, dim3(blocks), dim3(256), 0, st, (const long long*)acc, limbs, vol,
                      vol_weight, ex - 1 - SA_DET_HI_BITS, -SA_DET_HI_BITS, nvox);
   FSG_RETURN_LAUNCH();
 }
@@ -1199,9 +1193,8 @@ int fsg_slice_acq_set_tuning(int cap_cells, int z_chunk, int t16_extent) {
 
 int fsg_equalize_f32(float* vol, const float* vol_weight, const uint8_t* vol_mask, float threshold, size_t n, void* stream) {
   if (!vol || n == 0 || (!vol_weight && !vol_mask)) return FSG_E_BADARG;
-  size_t blocks = (n + 255) / 256;
-  if (blocks > 8192) blocks = 8192;
-  hipLaunchKernelGGL(sa_equalize_kernel, dim3((unsigned)blocks), dim3(256), 0, fsg_stream(stream), vol, vol_weight, vol_mask,
+  const unsigned blocks = fsg_blocks(n, 256, 8192);
+  hipLaunchKernelGGL(sa_equalize_kernel, dim3(blocks), dim3(256), 0, fsg_stream(stream), vol, vol_weight, vol_mask,
                      threshold, n);
   FSG_RETURN_LAUNCH();
 }

@@ -201,9 +201,8 @@ int fsg_slice_acq_adjoint_backward_f32(const float* transforms, const float* gra
   if (eq) {
     float* ge = reinterpret_cast<float*>(static_cast<char*>(ws) + (gt ? sa_partial_bytes(n, h, w, 12) : 0));
     const size_t nv = (size_t)D * H * W;
-    size_t blocks = (nv + 255) / 256;
-    if (blocks > 8192) blocks = 8192;
-    hipLaunchKernelGGL(saa_equalize_grad_kernel, dim3((unsigned)blocks), dim3(256), 0, st, grad_vol, vol_weight, ge, nv);
+    const unsigned blocks = fsg_blocks(nv, 256, 8192);
+    hipLaunchKernelGGL(saa_equalize_grad_kernel, dim3(blocks), dim3(256), 0, st, grad_vol, vol_weight, ge, nv);
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return (int)e;
     G = ge;

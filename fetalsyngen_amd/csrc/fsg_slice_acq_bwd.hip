@@ -234,9 +234,8 @@ int sa_backward_run(const SaParams& P, size_t lds, const float* vol, const float
   if (acc) {
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return (int)e;
-    size_t blocks = (nvox + 255) / 256;
-    if (blocks > 8192) blocks = 8192;
-    hipLaunchKernelGGL(sa_det_finalize_kernel, dim3((unsigned)blocks), dim3(256), 0, st, (const long long*)acc, 2, grad_vol,
+    const unsigned blocks = fsg_blocks(nvox, 256, 8192);
+    hipLaunchKernelGGL(sa_det_finalize_kernel, dim3(blocks), dim3(256), 0, st, (const long long*)acc, 2, grad_vol,
                        (float*)nullptr, ex - SA_DET_HI_BITS, -SA_DET_HI_BITS, nvox);
   }
   FSG_RETURN_LAUNCH();

@@ -342,9 +342,7 @@ int launch_lean(const FsgDeformK& D, const EpiK& E, const int32_t* mm6, const fl
     if (src_nn) { if (fast) FSG_LEAN_IMG(true, true); else FSG_LEAN_IMG(true, false); }
     else        { if (fast) FSG_LEAN_IMG(false, true); else FSG_LEAN_IMG(false, false); }
   }
-  else if (src_lin && src_nn) { if (fast) FSG_LEAN(true, true, true); else FSG_LEAN(true, true, false); }
-  else if (src_lin)      { if (fast) FSG_LEAN(true, false, true); else FSG_LEAN(true, false, false); }
-  else                   { FSG_LEAN(false, true, true); }
+  else FSG_WARP_LADDER(FSG_LEAN, src_lin, src_nn, fast);
 #undef FSG_LEAN_IMG
 #undef FSG_LEAN
   FSG_RETURN_LAUNCH();

@@ -84,6 +84,13 @@ __device__ __forceinline__ void zoom_mm_read(const EpiZ& E, float& mn, float& mx
   }
 }
 
+// end of an EPI_MINMAX workgroup: fold its threads' lo / hi, thread 0 updates the keys.  `update` is false only in a -DFSG_DIAG
+// build's timing ablation of the slab kernel (results are wrong there); the shipped library has no caller that passes it.
+__device__ __forceinline__ void zoom_mm_fold(const EpiZ& E, float lo, float hi, float (*red)[4], int wave, bool update = true) {
+  const FsgMinMax m = fsg_block_minmax(lo, hi, red, wave);
+  if (m.first && update) zoom_mm_update(E, m.lo, m.hi);
+}
+
 // the same in two halves, so that the loads are in flight while the caller does other work (slab kernel: behind its x stage)
 __device__ __forceinline__ void zoom_mm_issue(const EpiZ& E, int& kmin, int& kmax) {
   const int lane = threadIdx.x & 63;
@@ -109,88 +116,34 @@ __device__ __forceinline__ void zoom_mm_finish(int kmin, int kmax, float& mn, fl
   mx = fsg_key2f(__builtin_amdgcn_readfirstlane(kmax));
 }
 
+// What EPI_NORM needs of the keys: the maximum, and minimum and range of the values already divided by it.
+struct ZoomNorm {
+  float mx = 1.f, mnq = 0.f, den = 1.f;
+};
+__device__ __forceinline__ ZoomNorm zoom_norm_of(float mn, float mx) {
+  ZoomNorm N;
+  N.mx = mx;
+  N.mnq = mn / mx;       // min(y/max) == min(y)/max: IEEE division is monotone
+  N.den = 1.0f - N.mnq;  // max(y/max) == max/max == 1
+  return N;
+}
+__device__ __forceinline__ ZoomNorm zoom_norm_read(const EpiZ& E) {
+  float mn, mx;
+  zoom_mm_read(E, mn, mx);
+  return zoom_norm_of(mn, mx);
+}
+// v / max, and with norm_mode 1 scaled to [0, 1] (a flat image -> arr * minv)
+__device__ __forceinline__ float zoom_normalise(float v, const ZoomNorm& N, int norm_mode) {
+  float t = v / N.mx;
+  // den == 1 (min == 0: K8 clamps at 0, so this is the usual case): x / 1.0f == x exactly, the division is skipped
+  if (norm_mode == 1) t = (N.mnq == 1.0f) ? t * 0.0f : (N.den == 1.0f ? t - N.mnq : (t - N.mnq) / N.den);
+  return t;
+}
+
+// what becomes of output o's interpolated value v (the scalar kernels; the tile and slab kernels emit four at a time)
 template <int EPI>
-__global__ __launch_bounds__(256) void zoom1_kernel(ZoomK Z, EpiZ E) {
-  float lo = INFINITY, hi = -INFINITY;
-  float inv_max = 0.f, mnq = 0.f, den = 1.f, mx = 1.f;
-  if (EPI == EPI_NORM) {
-    float mn;
-    zoom_mm_read(E, mn, mx);
-    mnq = mn / mx;         // min(y/max) == min(y)/max: IEEE division is monotone
-    den = 1.0f - mnq;      // max(y/max) == max/max == 1
-    (void)inv_max;
-  }
-  const int rows = Z.dx * Z.dy;
-  for (int r = blockIdx.x; r < rows; r += gridDim.x) {
-    const int i = r / Z.dy, j = r - i * Z.dy;
-    const fsg_tap a = Z.tx[i], b = Z.ty[j];
-    const bool okr = a.lo >= 0 && b.lo >= 0;
-    for (int k = threadIdx.x; k < Z.dz; k += blockDim.x) {
-      const fsg_tap c = Z.tz[k];
-      float v = 0.f;
-      if (okr && c.lo >= 0) v = fsg_tab_interp<1>(Z.src, Z.sy, Z.sz, 0, a, b, c);
-      const size_t o = (size_t)r * Z.dz + k;
-      if (EPI == EPI_STORE) {
-        Z.dst[o] = v;
-      } else if (EPI == EPI_NOISE_PTR) {
-        v = v + E.noise_std * E.noise[o];
-        Z.dst[o] = v < 0.f ? 0.f : v;
-      } else if (EPI == EPI_NOISE_PHILOX) {
-        v = v + E.noise_std * fsg_randn1(E.seed, E.stream_id, (uint64_t)o);
-        Z.dst[o] = v < 0.f ? 0.f : v;
-      } else if (EPI == EPI_MINMAX) {
-        lo = fminf(lo, v);
-        hi = fmaxf(hi, v);
-      } else {  // EPI_NORM
-        float t = v / mx;
-        if (E.norm_mode == 1) t = (mnq == 1.0f) ? t * 0.0f : (t - mnq) / den;  // flat image -> arr*minv
-        Z.dst[o] = t;
-      }
-    }
-  }
-  if (EPI == EPI_MINMAX) {
-    __shared__ float red[2][4];
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    lo = fsg_wave_min(lo);
-    hi = fsg_wave_max(hi);
-    if (lane == 0) { red[0][wave] = lo; red[1][wave] = hi; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-      for (int w = 1; w < 4; ++w) { lo = fminf(lo, red[0][w]); hi = fmaxf(hi, red[1][w]); }
-      zoom_mm_update(E, lo, hi);
-    }
-  }
-}
-
-// ---- row-wise variant (tuned path) ------------------------------------------------------------------
-// One wave per output row (i, j, :): the x- and y-interpolation of the four source rows it depends on
-// is done once, coalesced, into a wave-private LDS row of sz floats; each output voxel is then one lerp
-// of two LDS values.  Global traffic per output row: 4 coalesced source rows (L1/L2 hits for the
-// neighbouring output rows that share them) + one coalesced store.  Same fp32 operation order as
-// fsg_tab_interp<1>, so results are bit-identical to the per-voxel kernel.
-constexpr int ZROWCAP = 1024;  // max source z extent handled by the row kernel
-
-__device__ __forceinline__ void zwave_sync() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
-__device__ __forceinline__ fsg_tap zuniform_tap(const fsg_tap* t, int idx) {
-  const int4 v = *reinterpret_cast<const int4*>(t + idx);
-  fsg_tap r;
-  r.lo = __builtin_amdgcn_readfirstlane(v.x);
-  r.hi = __builtin_amdgcn_readfirstlane(v.y);
-  r.w_lo = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(v.z));
-  r.w_hi = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(v.w));
-  return r;
-}
-
-template <int EPI>
-__device__ __forceinline__ void zoom_emit(const ZoomK& Z, const EpiZ& E, const float* sm, bool okr, const fsg_tap& c,
-                                          size_t o, float mx, float mnq, float den, float& lo, float& hi) {
-  float v = 0.f;
-  if (okr && c.lo >= 0) v = fsg_mix(c.w_lo, sm[c.lo], c.w_hi, sm[c.hi]);
+__device__ __forceinline__ void zoom_epilogue(const ZoomK& Z, const EpiZ& E, float v, size_t o, const ZoomNorm& N, float& lo,
+                                              float& hi) {
   if (EPI == EPI_STORE) {
     Z.dst[o] = v;
   } else if (EPI == EPI_NOISE_PTR) {
@@ -203,11 +156,48 @@ __device__ __forceinline__ void zoom_emit(const ZoomK& Z, const EpiZ& E, const f
     lo = fminf(lo, v);
     hi = fmaxf(hi, v);
   } else {
-    float t = v / mx;
-    // den == 1 (min == 0: K8 clamps at 0, so this is the usual case): x / 1.0f == x exactly, the division is skipped
-    if (E.norm_mode == 1) t = (mnq == 1.0f) ? t * 0.0f : (den == 1.0f ? t - mnq : (t - mnq) / den);
-    Z.dst[o] = t;
+    Z.dst[o] = zoom_normalise(v, N, E.norm_mode);
   }
+}
+
+template <int EPI>
+__global__ __launch_bounds__(256) void zoom1_kernel(ZoomK Z, EpiZ E) {
+  float lo = INFINITY, hi = -INFINITY;
+  ZoomNorm N;
+  if (EPI == EPI_NORM) N = zoom_norm_read(E);
+  const int rows = Z.dx * Z.dy;
+  for (int r = blockIdx.x; r < rows; r += gridDim.x) {
+    const int i = r / Z.dy, j = r - i * Z.dy;
+    const fsg_tap a = Z.tx[i], b = Z.ty[j];
+    const bool okr = a.lo >= 0 && b.lo >= 0;
+    for (int k = threadIdx.x; k < Z.dz; k += blockDim.x) {
+      const fsg_tap c = Z.tz[k];
+      float v = 0.f;
+      if (okr && c.lo >= 0) v = fsg_tab_interp<1>(Z.src, Z.sy, Z.sz, 0, a, b, c);
+      zoom_epilogue<EPI>(Z, E, v, (size_t)r * Z.dz + k, N, lo, hi);
+    }
+  }
+  if (EPI == EPI_MINMAX) {
+    __shared__ float red[2][4];
+    zoom_mm_fold(E, lo, hi, red, threadIdx.x >> 6);
+  }
+}
+
+// ---- row-wise variant (tuned path) ------------------------------------------------------------------
+// One wave per output row (i, j, :): the x- and y-interpolation of the four source rows it depends on
+// is done once, coalesced, into a wave-private LDS row of sz floats; each output voxel is then one lerp
+// of two LDS values.  Global traffic per output row: 4 coalesced source rows (L1/L2 hits for the
+// neighbouring output rows that share them) + one coalesced store.  Same fp32 operation order as
+// fsg_tab_interp<1>, so results are bit-identical to the per-voxel kernel.
+constexpr int ZROWCAP = 1024;  // max source z extent handled by the row kernel
+
+// z-lerp of the wave's x/y-blended LDS row, then the epilogue
+template <int EPI>
+__device__ __forceinline__ void zoom_emit(const ZoomK& Z, const EpiZ& E, const float* sm, bool okr, const fsg_tap& c,
+                                          size_t o, const ZoomNorm& N, float& lo, float& hi) {
+  float v = 0.f;
+  if (okr && c.lo >= 0) v = fsg_mix(c.w_lo, sm[c.lo], c.w_hi, sm[c.hi]);
+  zoom_epilogue<EPI>(Z, E, v, o, N, lo, hi);
 }
 
 template <int EPI>
@@ -217,13 +207,10 @@ __global__ __launch_bounds__(256) void zoom1_rows_kernel(ZoomK Z, EpiZ E, int ro
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
   float* sm = sm_all[wave];
   float lo = INFINITY, hi = -INFINITY;
-  float mnq = 0.f, den = 1.f, mx = 1.f;
-  if (EPI == EPI_NORM) {
-    float mn;
-    zoom_mm_read(E, mn, mx);
-    mnq = mn / mx;
-    den = 1.0f - mnq;
-  }
+  ZoomNorm N;
+  if (EPI == EPI_NORM) N = zoom_norm_read(E);
+  // xcd_tile()'s order, written out here and in the two kernels below: on the unsigned blockIdx.x the id's shift is logical,
+  // xcd_tile(int, int) makes it arithmetic -- one instruction of the timed kernels would change.  The mapping is the same.
   const int nb = gridDim.x;
   const int tile = (nb & 7) == 0 ? (blockIdx.x & 7) * (nb >> 3) + (blockIdx.x >> 3) : blockIdx.x;
   const int rows = Z.dx * Z.dy;
@@ -240,7 +227,7 @@ __global__ __launch_bounds__(256) void zoom1_rows_kernel(ZoomK Z, EpiZ E, int ro
   }
   for (int r = r_begin + wave; r < r_end; r += 4) {
     const int i = r / Z.dy, j = r - i * Z.dy;
-    const fsg_tap a = zuniform_tap(Z.tx, i), b = zuniform_tap(Z.ty, j);
+    const fsg_tap a = fsg_uniform_tap(Z.tx, i), b = fsg_uniform_tap(Z.ty, j);
     const bool okr = a.lo >= 0 && b.lo >= 0;
     if (okr) {
       const float* p00 = Z.src + ((size_t)a.lo * Z.sy + b.lo) * Z.sz;
@@ -253,30 +240,21 @@ __global__ __launch_bounds__(256) void zoom1_rows_kernel(ZoomK Z, EpiZ E, int ro
         sm[zs] = fsg_mix(b.w_lo, t0, b.w_hi, t1);
       }
     }
-    zwave_sync();
+    fsg_wave_lds_sync();
     const size_t row = (size_t)r * Z.dz;
     if (cached) {
 #pragma unroll
       for (int q = 0; q < 4; ++q) {
         const int k = lane + 64 * q;
-        if (k < Z.dz) zoom_emit<EPI>(Z, E, sm, okr, ck[q], row + k, mx, mnq, den, lo, hi);
+        if (k < Z.dz) zoom_emit<EPI>(Z, E, sm, okr, ck[q], row + k, N, lo, hi);
       }
     } else {
       for (int k = lane; k < Z.dz; k += FSG_WAVE)
-        zoom_emit<EPI>(Z, E, sm, okr, Z.tz[k], row + k, mx, mnq, den, lo, hi);
+        zoom_emit<EPI>(Z, E, sm, okr, Z.tz[k], row + k, N, lo, hi);
     }
-    zwave_sync();
+    fsg_wave_lds_sync();
   }
-  if (EPI == EPI_MINMAX) {
-    lo = fsg_wave_min(lo);
-    hi = fsg_wave_max(hi);
-    if (lane == 0) { red[0][wave] = lo; red[1][wave] = hi; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-      for (int w = 1; w < 4; ++w) { lo = fminf(lo, red[0][w]); hi = fmaxf(hi, red[1][w]); }
-      zoom_mm_update(E, lo, hi);
-    }
-  }
+  if (EPI == EPI_MINMAX) zoom_mm_fold(E, lo, hi, red, wave);
 }
 
 // Software-pipelined variant for sz <= 256 and dz <= 256 (every low-res / full-res size of the 256^3
@@ -289,13 +267,8 @@ __global__ __launch_bounds__(256, 8) void zoom1_rows_pf_kernel(ZoomK Z, EpiZ E, 
   __shared__ float red[2][4];
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
   float lo = INFINITY, hi = -INFINITY;
-  float mnq = 0.f, den = 1.f, mx = 1.f;
-  if (EPI == EPI_NORM) {
-    float mn;
-    zoom_mm_read(E, mn, mx);
-    mnq = mn / mx;
-    den = 1.0f - mnq;
-  }
+  ZoomNorm N;
+  if (EPI == EPI_NORM) N = zoom_norm_read(E);
   const int nb = gridDim.x;
   const int tile = (nb & 7) == 0 ? (blockIdx.x & 7) * (nb >> 3) + (blockIdx.x >> 3) : blockIdx.x;
   const int rows = Z.dx * Z.dy;
@@ -361,12 +334,12 @@ __global__ __launch_bounds__(256, 8) void zoom1_rows_pf_kernel(ZoomK Z, EpiZ E, 
           }
         }
       }
-      zwave_sync();
+      fsg_wave_lds_sync();
       const size_t row = (size_t)(base + 4 * t) * Z.dz;
 #pragma unroll
       for (int q = 0; q < 4; ++q) {
         const int k = lane + 64 * q;
-        if (k < Z.dz) zoom_emit<EPI>(Z, E, sm, okr, ck[q], row + k, mx, mnq, den, lo, hi);
+        if (k < Z.dz) zoom_emit<EPI>(Z, E, sm, okr, ck[q], row + k, N, lo, hi);
       }
       a = an;
       b = bn;
@@ -375,18 +348,9 @@ __global__ __launch_bounds__(256, 8) void zoom1_rows_pf_kernel(ZoomK Z, EpiZ E, 
 #pragma unroll
         for (int c = 0; c < 4; ++c) cur[u][c] = nxt[u][c];
     }
-    zwave_sync();
+    fsg_wave_lds_sync();
   }
-  if (EPI == EPI_MINMAX) {
-    lo = fsg_wave_min(lo);
-    hi = fsg_wave_max(hi);
-    if (lane == 0) { red[0][wave] = lo; red[1][wave] = hi; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-      for (int w = 1; w < 4; ++w) { lo = fminf(lo, red[0][w]); hi = fmaxf(hi, red[1][w]); }
-      zoom_mm_update(E, lo, hi);
-    }
-  }
+  if (EPI == EPI_MINMAX) zoom_mm_fold(E, lo, hi, red, wave);
 }
 
 
@@ -412,18 +376,13 @@ __global__ __launch_bounds__(256) void zoom_tile_kernel(ZoomK Z, EpiZ E, int TY,
   __shared__ fsg_tap tb[ZT_MAX_TY];
   __shared__ int win[2];
   __shared__ float red[2][4];
-  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+  const int tid = threadIdx.x, wave = tid >> 6;
   const int tiles_y = (Z.dy + TY - 1) / TY;
   const int i = blockIdx.x / tiles_y, jt = blockIdx.x - i * tiles_y;
   const int j0 = jt * TY, nj = min(TY, Z.dy - j0);
   float lo = INFINITY, hi = -INFINITY;
-  float mnq = 0.f, den = 1.f, mx = 1.f;
-  if (EPI == EPI_NORM) {
-    float mn;
-    zoom_mm_read(E, mn, mx);
-    mnq = mn / mx;
-    den = 1.0f - mnq;
-  }
+  ZoomNorm N;
+  if (EPI == EPI_NORM) N = zoom_norm_read(E);
   // y taps of the tile and the window of source rows they reference
   if (tid < 64) {
     fsg_tap t = fsg_tap{-1, 0, 0.f, 0.f};
@@ -441,7 +400,7 @@ __global__ __launch_bounds__(256) void zoom_tile_kernel(ZoomK Z, EpiZ E, int TY,
     if (tid == 0) { win[0] = smin; win[1] = smax; }
   }
   __syncthreads();
-  const fsg_tap a = zuniform_tap(Z.tx, i);
+  const fsg_tap a = fsg_uniform_tap(Z.tx, i);
   const int smin = win[0], nrows = win[1] - win[0] + 1;
   const bool okx = a.lo >= 0 && nrows > 0;
   const bool fits = nrows * Z.sz <= cap_floats;  // uniform
@@ -502,11 +461,7 @@ __global__ __launch_bounds__(256) void zoom_tile_kernel(ZoomK Z, EpiZ E, int TY,
       for (int u = 0; u < 4; ++u) v[u] = v[u] < 0.f ? 0.f : v[u];
     } else if (EPI == EPI_NORM) {
 #pragma unroll
-      for (int u = 0; u < 4; ++u) {
-        float t = v[u] / mx;
-        if (E.norm_mode == 1) t = (mnq == 1.0f) ? t * 0.0f : (den == 1.0f ? t - mnq : (t - mnq) / den);
-        v[u] = t;
-      }
+      for (int u = 0; u < 4; ++u) v[u] = zoom_normalise(v[u], N, E.norm_mode);
     }
     if (EPI == EPI_MINMAX) {
 #pragma unroll
@@ -520,16 +475,7 @@ __global__ __launch_bounds__(256) void zoom_tile_kernel(ZoomK Z, EpiZ E, int TY,
         if (live[u]) Z.dst[o0 + u] = v[u];
     }
   }
-  if (EPI == EPI_MINMAX) {
-    lo = fsg_wave_min(lo);
-    hi = fsg_wave_max(hi);
-    if (lane == 0) { red[0][wave] = lo; red[1][wave] = hi; }
-    __syncthreads();
-    if (tid == 0) {
-      for (int w = 1; w < 4; ++w) { lo = fminf(lo, red[0][w]); hi = fmaxf(hi, red[1][w]); }
-      zoom_mm_update(E, lo, hi);
-    }
-  }
+  if (EPI == EPI_MINMAX) zoom_mm_fold(E, lo, hi, red, wave);
 }
 
 // Correctly rounded v / d for a divisor that is uniform over the launch (K9b divides 16.8 M voxels by the same maximum).
@@ -585,10 +531,13 @@ __device__ __forceinline__ void zoom_slab_body(const ZoomK& Z, const EpiZ& E, co
   const int tid = threadIdx.x, wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
   const int tiles_y = (Z.dy + TY - 1) / TY;
   const int nb = (int)nbk;
+  // (xcd_tile()'s order, written out: see zoom1_rows_kernel)
   const int tile = (nb & 7) == 0 ? (int)(bid & 7) * (nb >> 3) + (int)(bid >> 3) : (int)bid;  // XCD-contiguous x slabs
   const int i = tile / tiles_y, jt = tile - i * tiles_y;
   const int j0 = jt * TY, nj = min(TY, Z.dy - j0);
   float lo = INFINITY, hi = -INFINITY;
+  // plain floats, not a ZoomNorm built by zoom_norm_of(): as a struct the normalising instantiation takes two more vector and
+  // nine more scalar registers
   float mnq = 0.f, den = 1.f, mx = 1.f;
   int kmin_l = 0, kmax_l = 0;
   if (EPI == EPI_NORM) zoom_mm_issue(E, kmin_l, kmax_l);  // consumed behind the x stage: the round trip hides under its loads
@@ -625,7 +574,7 @@ __device__ __forceinline__ void zoom_slab_body(const ZoomK& Z, const EpiZ& E, co
     }
     if (tid == 0) { win[0] = smin; win[1] = smax; }
   }
-  const fsg_tap a = zuniform_tap(Z.tx, i);
+  const fsg_tap a = fsg_uniform_tap(Z.tx, i);
   __syncthreads();
   const int smin = win[0], nrows = win[1] - win[0] + 1;
   const bool okx = a.lo >= 0 && nrows > 0;
@@ -715,11 +664,7 @@ __device__ __forceinline__ void zoom_slab_body(const ZoomK& Z, const EpiZ& E, co
       }
       if (__builtin_expect(__ballot(bad) != 0ull, 0)) {
 #pragma unroll
-        for (int u = 0; u < 4; ++u) {
-          float tt = v[u] / mx;
-          if (E.norm_mode == 1) tt = (mnq == 1.0f) ? tt * 0.0f : (den == 1.0f ? tt - mnq : (tt - mnq) / den);
-          t[u] = tt;
-        }
+        for (int u = 0; u < 4; ++u) t[u] = zoom_normalise(v[u], ZoomNorm{mx, mnq, den}, E.norm_mode);
       }
 #pragma unroll
       for (int u = 0; u < 4; ++u) v[u] = t[u];
@@ -759,13 +704,13 @@ __device__ __forceinline__ void zoom_slab_body(const ZoomK& Z, const EpiZ& E, co
         }
 #pragma unroll
         for (int c = 0; c < 4; ++c) y[lane + 64 * c] = fsg_mix(b.w_lo, l4[c], b.w_hi, h4[c]);  // (columns >= sz: padding, never read)
-        zwave_sync();
+        fsg_wave_lds_sync();
 #pragma unroll
         for (int u = 0; u < 4; ++u) {
           const float t = fsg_mix(zwl[u], y[zlo[u]], zwh[u], y[zhi[u]]);
           v[u] = zok[u] ? t : 0.f;
         }
-        zwave_sync();  // the wave's row is rewritten by its next iteration
+        fsg_wave_lds_sync();  // the wave's row is rewritten by its next iteration
       }
       emit(jj, v);
     }
@@ -780,20 +725,11 @@ __device__ __forceinline__ void zoom_slab_body(const ZoomK& Z, const EpiZ& E, co
       emit(jj, v);
     }
   }
-  if (EPI == EPI_MINMAX) {
-    lo = fsg_wave_min(lo);
-    hi = fsg_wave_max(hi);
-    if (lane == 0) { red[0][wave] = lo; red[1][wave] = hi; }
-    __syncthreads();
 #ifdef FSG_DIAG
-    if (tid == 0 && E.norm_mode != 77) {
+  if (EPI == EPI_MINMAX) zoom_mm_fold(E, lo, hi, red, wave, E.norm_mode != 77);
 #else
-    if (tid == 0) {
+  if (EPI == EPI_MINMAX) zoom_mm_fold(E, lo, hi, red, wave);
 #endif
-      for (int w = 1; w < 4; ++w) { lo = fminf(lo, red[0][w]); hi = fmaxf(hi, red[1][w]); }
-      zoom_mm_update(E, lo, hi);
-    }
-  }
 }
 
 template <int EPI>
@@ -812,6 +748,9 @@ int check(const float* src, int sx, int sy, int sz, const fsg_tap* tx, const fsg
   return 0;
 }
 
+// floats of the x-blended source window of TY output rows: they advance sy/dy source rows each (+3 for the pair and rounding)
+long long zoom_window(const ZoomK& Z, int TY) { return ((long long)TY * Z.sy / Z.dy + 3) * Z.sz; }
+
 template <int EPI>
 int launch1(const ZoomK& Z, const EpiZ& E, void* stream) {
   const int rows = Z.dx * Z.dy;
@@ -825,10 +764,9 @@ int launch1(const ZoomK& Z, const EpiZ& E, void* stream) {
                          Z.dz <= 256;
   if ((EPI == EPI_NOISE_PHILOX || EPI == EPI_NOISE_PTR || (g_tuning_flags & FSG_TUNE_TILE_ZOOM)) && !noise_big &&
       !(g_tuning_flags & (FSG_TUNE_GENERIC_ZOOM | FSG_TUNE_ROW_ZOOM | FSG_TUNE_SLAB_ZOOM))) {
-    // window estimate for the tile kernel: TY rows advance sy/dy source rows each (+2 for the pair and rounding)
     int TY = g_zoom_ty < ZT_MAX_TY ? g_zoom_ty : ZT_MAX_TY;
     if (TY > Z.dy) TY = Z.dy;
-    const long long est = ((long long)TY * Z.sy / Z.dy + 3) * Z.sz;
+    const long long est = zoom_window(Z, TY);
     if (TY >= 1 && est <= g_zoom_cap && est + 4LL * Z.dz <= 16000) {  // window + z taps within the 64 KB dynamic-LDS limit
       const int tiles_y = (Z.dy + TY - 1) / TY;
       const size_t lds = ((size_t)est + 4 * (size_t)Z.dz) * sizeof(float);  // window + z taps: as many workgroups per CU as fit
@@ -854,7 +792,7 @@ int launch1(const ZoomK& Z, const EpiZ& E, void* stream) {
     for (int mult = (EPI == EPI_MINMAX ? 4 : 2); mult >= 1; mult >>= 1) {
       TY = mult * g_zoom_ty < ZT_MAX_TY ? mult * g_zoom_ty : ZT_MAX_TY;
       if (TY > Z.dy) TY = Z.dy;
-      est = ((long long)TY * Z.sy / Z.dy + 3) * Z.sz;
+      est = zoom_window(Z, TY);
       total = est + 5LL * 256;  // window (+ 256 floats behind it: unclamped column reads) + the four waves' rows (256 each)
       if (est <= g_zoom_cap && total <= 16000) break;
     }
@@ -869,8 +807,7 @@ int launch1(const ZoomK& Z, const EpiZ& E, void* stream) {
   if (Z.sz <= ZROWCAP && !(g_tuning_flags & FSG_TUNE_GENERIC_ZOOM)) {
     // 2048 blocks when there is enough work: >= 8 rows per block keeps neighbouring rows (shared source
     // rows) on one CU, and the MINMAX variant issues only 2 atomics per block
-    int nblk = (rows + 7) / 8;
-    if (nblk > 2048) nblk = 2048;
+    int nblk = (int)fsg_blocks((size_t)rows, 8, 2048);
     if (nblk >= 8) nblk &= ~7;  // multiple of 8 for the XCD-contiguous tile order
     const int rpb = (rows + nblk - 1) / nblk;
     if (Z.sz <= 256 && Z.dz <= 256 && !(g_tuning_flags & FSG_TUNE_NO_PREFETCH))
@@ -928,19 +865,31 @@ int fsg_zoom_set_tuning(int y_rows, int cap_floats) {
   return 0;
 }
 
+// the min/max pass and the normalising pass over nslots slots of keys (1: the plain pair of the unsharded entry points)
+static int zoom_minmax(const ZoomK& Z, int32_t* mm, int nslots, bool diag, void* stream) {
+  EpiZ E{};
+  E.mm_out = mm;
+  E.mm_shards = nslots;
+  if (diag) E.norm_mode = 77;
+  return launch1<EPI_MINMAX>(Z, E, stream);
+}
+static int zoom_normalise_pass(const ZoomK& Z, const int32_t* mm, int nslots, int mode, void* stream) {
+  if (!Z.dst || !mm || Z.src == Z.dst || (mode != 0 && mode != 1)) return FSG_E_BADARG;
+  EpiZ E{};
+  E.mm_in = mm; E.norm_mode = mode; E.mm_shards = nslots;
+  return launch1<EPI_NORM>(Z, E, stream);
+}
+
 int fsg_zoom3d_minmax_f32(const float* src, int sx, int sy, int sz, const fsg_tap* tx, const fsg_tap* ty,
                           const fsg_tap* tz, int dx, int dy, int dz, int32_t* mm, void* stream) {
   int rc = check(src, sx, sy, sz, tx, ty, tz, dx, dy, dz);
   if (rc) return rc;
   if (!mm) return FSG_E_BADARG;
-  ZoomK Z{src, sx, sy, sz, tx, ty, tz, nullptr, dx, dy, dz};
-  EpiZ E{};
-  E.mm_out = mm;
-  E.mm_shards = 1;
+  bool diag = false;
 #ifdef FSG_DIAG  // timing ablation (results are wrong): only in a -DFSG_DIAG build, never in the shipped library
-  if (getenv("FSG_DIAG_NO_MM_ATOMICS")) E.norm_mode = 77;
+  if (getenv("FSG_DIAG_NO_MM_ATOMICS")) diag = true;
 #endif
-  return launch1<EPI_MINMAX>(Z, E, stream);
+  return zoom_minmax(ZoomK{src, sx, sy, sz, tx, ty, tz, nullptr, dx, dy, dz}, mm, 1, diag, stream);
 }
 
 int fsg_zoom3d_normalise_f32(const float* src, int sx, int sy, int sz, const fsg_tap* tx, const fsg_tap* ty,
@@ -948,11 +897,7 @@ int fsg_zoom3d_normalise_f32(const float* src, int sx, int sy, int sz, const fsg
                              void* stream) {
   int rc = check(src, sx, sy, sz, tx, ty, tz, dx, dy, dz);
   if (rc) return rc;
-  if (!dst || !mm || src == dst || (mode != 0 && mode != 1)) return FSG_E_BADARG;
-  ZoomK Z{src, sx, sy, sz, tx, ty, tz, dst, dx, dy, dz};
-  EpiZ E{};
-  E.mm_in = mm; E.norm_mode = mode; E.mm_shards = 1;
-  return launch1<EPI_NORM>(Z, E, stream);
+  return zoom_normalise_pass(ZoomK{src, sx, sy, sz, tx, ty, tz, dst, dx, dy, dz}, mm, 1, mode, stream);
 }
 
 int fsg_zoom3d_minmax_sharded_f32(const float* src, int sx, int sy, int sz, const fsg_tap* tx, const fsg_tap* ty,
@@ -960,11 +905,7 @@ int fsg_zoom3d_minmax_sharded_f32(const float* src, int sx, int sy, int sz, cons
   int rc = check(src, sx, sy, sz, tx, ty, tz, dx, dy, dz);
   if (rc) return rc;
   if (!slots || nslots < 2 || nslots > 64) return FSG_E_BADARG;
-  ZoomK Z{src, sx, sy, sz, tx, ty, tz, nullptr, dx, dy, dz};
-  EpiZ E{};
-  E.mm_out = slots;
-  E.mm_shards = nslots;
-  return launch1<EPI_MINMAX>(Z, E, stream);
+  return zoom_minmax(ZoomK{src, sx, sy, sz, tx, ty, tz, nullptr, dx, dy, dz}, slots, nslots, false, stream);
 }
 
 int fsg_zoom3d_normalise_sharded_f32(const float* src, int sx, int sy, int sz, const fsg_tap* tx, const fsg_tap* ty,
@@ -972,11 +913,8 @@ int fsg_zoom3d_normalise_sharded_f32(const float* src, int sx, int sy, int sz, c
                                      int mode, void* stream) {
   int rc = check(src, sx, sy, sz, tx, ty, tz, dx, dy, dz);
   if (rc) return rc;
-  if (!dst || !slots || src == dst || (mode != 0 && mode != 1) || nslots < 2 || nslots > 64) return FSG_E_BADARG;
-  ZoomK Z{src, sx, sy, sz, tx, ty, tz, dst, dx, dy, dz};
-  EpiZ E{};
-  E.mm_in = slots; E.norm_mode = mode; E.mm_shards = nslots;
-  return launch1<EPI_NORM>(Z, E, stream);
+  if (nslots < 2 || nslots > 64) return FSG_E_BADARG;
+  return zoom_normalise_pass(ZoomK{src, sx, sy, sz, tx, ty, tz, dst, dx, dy, dz}, slots, nslots, mode, stream);
 }
 
 }  // extern "C"

@@ -456,7 +456,8 @@ def test_interp3d(K):
 def test_bad_arguments(K):
     """The return codes of launch_warp (fsg_warp_f32, fsg_warp_f32_u8), fsg_warp_f32_u8_to_f32, fsg_warp_dual_f32,
     fsg_deform_rows_f32 and fsg_interp3d_f32 that are reached before any launch: the poisoned outputs stay as they were.  Each
-    entry point's unchanged argument list is accepted first, so that a refusal is the changed argument's."""
+    entry point's unchanged argument list is accepted first, so that a refusal is the changed argument's.  One call is no
+    refusal: fsg_warp_f32_u8_to_f32 with src_lin == out_lin launches (the other entry points refuse it), on scratch buffers."""
     from fetalsyngen_amd import _lib
     from tests.util_warp_cases import cases as table
 
@@ -540,6 +541,11 @@ def test_bad_arguments(K):
             refused(fn, good, (ALIGN if fn == "fsg_warp_f32_u8_to_f32" else BAD) if code is None else code, d=d)
     for fn in ("fsg_warp_f32", "fsg_warp_f32_u8"):
         refused(fn, warp[fn], BAD, out_lin=warp[fn]["src_lin"])  # in place
+    # ... which fsg_warp_f32_u8_to_f32 alone does not check (nor row_stride against the bias values, above): it launches.  Pinned so
+    # that the three entry points' shared operand checks keep the difference; on a scratch copy, whose contents are then anyone's.
+    scratch, scratch_nn = src["img"].clone(), torch.empty_like(o_nn)
+    in_place = dict(warp["fsg_warp_f32_u8_to_f32"], src_lin=P(scratch), out_lin=P(scratch), out_nn=P(scratch_nn))
+    assert lib.fsg_warp_f32_u8_to_f32(*in_place.values(), st) == 0
     # the u8 -> f32 entry is served by the lean kernel alone: FSG_E_ALIGN, nothing launched, under every flag that leaves it
     for flag in (_lib.TUNE.NO_LEAN, _lib.TUNE.NO_PATCH, _lib.TUNE.GENERIC_WARP):
         with tuning(flag):
@@ -549,6 +555,10 @@ def test_bad_arguments(K):
     refused("fsg_warp_dual_f32", dual, BAD, mm=N)
     refused("fsg_warp_dual_f32", dual, BAD, src_lin=N)
     refused("fsg_warp_dual_f32", dual, BAD, out_lin=N)
+    # no trilinear source at all: the entry point's own check (the pair checks above answer for half a pair; without src_img the
+    # lean launcher's "src_img needs src_lin" cannot answer in its place), then nothing to do at all
+    refused("fsg_warp_dual_f32", dual, BAD, src_lin=N, out_lin=N, src_img=N, out_img=N)
+    refused("fsg_warp_dual_f32", dual, BAD, src_lin=N, out_lin=N, src_img=N, out_img=N, src_nn=N, out_nn=N)
     refused("fsg_warp_dual_f32", dual, BAD, out_lin=dual["src_lin"])
     refused("fsg_warp_dual_f32", dual, BAD, src_img=N)
     refused("fsg_warp_dual_f32", dual, BAD, out_img=N)
@@ -602,4 +612,4 @@ def test_bad_arguments(K):
     torch.cuda.synchronize()
     for t in outs + (rows, dst):
         assert bool((torch.isnan(t) if t.dtype == torch.float32 else t == 255).all()), "a refused call wrote to an output"
-    assert ncalls == 3 * 17 + 2 + 6 + 18 + 8 + 6 + 14
+    assert ncalls == 3 * 17 + 2 + 6 + 20 + 8 + 6 + 14
