@@ -9,7 +9,7 @@ from pathlib import Path
 PKG = Path(__file__).resolve().parent
 CSRC = PKG / "csrc"
 LIB = PKG / "libfsg_hip.so"
-SOURCES = ["fsg_deform.hip", "fsg_warp_lean.hip", "fsg_zoom.hip", "fsg_intensity.hip", "fsg_blur.hip", "fsg_blur_rs.hip", "fsg_reduce.hip", "fsg_slice_acq.hip", "fsg_slice_acq_bwd.hip", "fsg_slice_acq_adjoint_bwd.hip", "fsg_transform_convert.hip", "fsg_cg.hip", "fsg_tk1.hip", "fsg_svr.hip", "fsg_svr_group.hip", "fsg_robust.hip", "fsg_imatch.hip", "fsg_artifacts.hip", "fsg_keyed.hip", "fsg_codes.hip", "fsg_seedgen.hip",
+SOURCES = ["fsg_deform.hip", "fsg_warp_lean.hip", "fsg_zoom.hip", "fsg_intensity.hip", "fsg_blur.hip", "fsg_blur_rs.hip", "fsg_reduce.hip", "fsg_slice_acq.hip", "fsg_slice_acq_bwd.hip", "fsg_slice_acq_adjoint_bwd.hip", "fsg_transform_convert.hip", "fsg_cg.hip", "fsg_tk1.hip", "fsg_svr.hip", "fsg_svr_group.hip", "fsg_robust.hip", "fsg_imatch.hip", "fsg_artifacts.hip", "fsg_keyed.hip", "fsg_codes.hip", "fsg_label_bricks.hip", "fsg_seedgen.hip",
            "fsg_regrid.hip", "fsg_pick.hip", "fsg_pipeline.cpp"]
 EXTRA = os.environ.get("FSG_EXTRA_FLAGS", "").split()
 # every header a translation unit may include: all of csrc/ (one added there cannot be missed) and the public one

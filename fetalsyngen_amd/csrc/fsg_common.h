@@ -434,6 +434,10 @@ int fsg_launch_warp_lean(const FsgDeformK& D, const EpiK& E, const int32_t* mm6,
                          const void* src_nn, void* out_nn, int label_in_bytes, int label_out_bytes, bool fast,
                          void* stream, const float* src_img = nullptr, float* out_img = nullptr);
 
+// The brick table attached (fsg_label_bricks_attach) to the uint8 label volume at `labels_u8`, if its registered shape is this
+// one and within the cap; else nullptr.  fsg_label_bricks.hip.
+const uint8_t* fsg_label_bricks_find(const void* labels_u8, int n0, int n1, int n2);
+
 // launch geometry: x = 64 lanes along z, y = 4 rows along y; grid (z chunks, y chunks, x)
 static inline dim3 fsg_block3() { return dim3(64, 4, 1); }
 static inline dim3 fsg_grid3(int n0, int n1, int n2) {

@@ -32,6 +32,7 @@ namespace {
 constexpr int LEAN_F2CAP = 32;   // coarse displacement entries along z
 constexpr int LEAN_B2CAP = 32;   // coarse bias entries along z
 constexpr int LEAN_TZCAP = 512;  // z extent whose taps are staged in LDS
+constexpr int LEAN_MAPCAP = FSG_LABEL_BRICKS_CAP;  // bricks of a label volume whose table is staged in LDS (one byte each)
 
 typedef float f2v __attribute__((ext_vector_type(2)));
 
@@ -61,19 +62,40 @@ template <> struct LeanImg<true> { const float* src; float* out; };
 // What a pending step keeps for the second source, and nothing without one (an empty base: the step's state is what it was).
 template <bool HAS_IMG> struct LeanPendImg {};
 template <> struct LeanPendImg<true> { unsigned o; };  // byte offset of the (x0, y0, z0) corner, for the gathers in finish()
+// The brick table of the label volume (fsg_label_bricks_u8) as a kernel argument, empty without one, and what a pending step
+// keeps of it: the label of a uniform brick, 0 where the gather decides.
+template <bool HAS_MAP> struct LeanMap {};
+template <> struct LeanMap<true> { const uint8_t* map; int nb, b2, b12; };  // bricks in all, along z, per x-plane of bricks
+template <bool HAS_MAP> struct LeanPendMap {};
+template <> struct LeanPendMap<true> { uint8_t fill; };
 
 // HAS_IMG (needs HAS_LIN): a second trilinear source, src_img -> out_img, sampled at the position (and with the weights and the
 // strict > 0 rule) the lane has for src_lin, stored without the gamma / bias epilogue -- the real image of a `load_image`
 // sample beside its synthetic channel.  Same operation sequence per output as a launch of its own, so the same bits.
-template <typename ST, typename DT, bool HAS_LIN, bool HAS_NN, bool FAST, int KZ, int WI, int ABL = 0, bool HAS_IMG = false>
+// HAS_MAP (uint8 labels, no second source): a label gather whose nearest source voxel lies in a brick of ONE label is sent
+// outside the descriptor's range -- the range check drops the lane without an access, and a quad of dropped lanes costs the
+// texture path next to nothing (profiles/r23_a_gather_dropped_quads.txt) -- and the table's entry is the label.  The load
+// itself stays where it is, issued on every trip, so the waits in front of the blends stay counted.
+template <typename ST, typename DT, bool HAS_LIN, bool HAS_NN, bool FAST, int KZ, int WI, int ABL = 0, bool HAS_IMG = false,
+          bool HAS_MAP = false>
 __global__ __launch_bounds__(1024, 8) void warp_lean_kernel(FsgDeformK D, const int32_t* __restrict__ mm6,
                                                          const float* __restrict__ src_lin, float* __restrict__ out_lin,
                                                          const ST* __restrict__ src_nn, DT* __restrict__ out_nn, EpiK E,
-                                                         int pace, LeanImg<HAS_IMG> I) {
+                                                         int pace, LeanImg<HAS_IMG> I, LeanMap<HAS_MAP> M) {
   const float* __restrict__ src_img = nullptr;
   float* __restrict__ out_img = nullptr;
   if constexpr (HAS_IMG) { src_img = I.src; out_img = I.out; }
   static_assert(!HAS_IMG || (HAS_LIN && ABL == 0), "the second source rides on the first one's positions");
+  static_assert(!HAS_MAP || (HAS_NN && !HAS_IMG && ABL == 0 && sizeof(ST) == 1), "the brick table serves the uint8 label gather");
+  const uint8_t* smap = nullptr;
+  if constexpr (HAS_MAP) {  // staged before the barrier below; 32 KB beside the 36 KB of the rest: two workgroups per CU still fit
+    __shared__ uint4 s_map[LEAN_MAPCAP / 16];
+    // the table is 16-byte aligned (fsg_label_bricks_attach checks); its last, partial 16 bytes go byte by byte
+    const int full = M.nb >> 4;
+    for (int t = threadIdx.x; t < full; t += 1024) s_map[t] = reinterpret_cast<const uint4*>(M.map)[t];
+    for (int t = (full << 4) + threadIdx.x; t < M.nb; t += 1024) reinterpret_cast<uint8_t*>(s_map)[t] = M.map[t];
+    smap = reinterpret_cast<const uint8_t*>(s_map);
+  }
   constexpr int RJ = 64 / KZ;  // rows (along j) per wave
   constexpr int WJ = 16 / WI;  // waves along j
   constexpr int PI = WI, PJ = WJ * RJ, NROW = PI * PJ;
@@ -130,6 +152,7 @@ __global__ __launch_bounds__(1024, 8) void warp_lean_kernel(FsgDeformK D, const 
   const int sxs = D.flip ? -sx : sx;
   const int base = D.flip ? (D.n0 - 1) * sx : 0;
   const int dxb = sxs * 4, oyb = sy * 4;  // byte strides towards the upper x / y neighbours
+  const int xflip = D.flip ? -1 : 1, xbase = D.flip ? D.n0 - 1 : 0;  // source x of an index before the flip (HAS_MAP)
   const float hx = (float)(D.n0 - 1), hy = (float)(D.n1 - 1), hz = (float)(D.n2 - 1);
   const float pxb = (float)i - D.cen[0], pyb = (float)j - D.cen[1];
   const unsigned orow = (unsigned)(((size_t)i * D.n1 + j) * D.n2);  // first output element of this lane's row
@@ -140,7 +163,7 @@ __global__ __launch_bounds__(1024, 8) void warp_lean_kernel(FsgDeformK D, const 
   // The arithmetic is written on register PAIRS (f2v) wherever two results share their operation sequence -- (y, z) of
   // the affine map, the two z-neighbours of every blend -- so that it lands on v_pk_mul_f32 / v_pk_add_f32 with the pairs
   // where the loads put them (no v_mov / v_pk_mov shuffles); each half is the reference's own operation order.
-  struct Pend : LeanPendImg<HAS_IMG> {
+  struct Pend : LeanPendImg<HAS_IMG>, LeanPendMap<HAS_MAP> {
     f2v p00, p10, p01, p11;
     float bx;
     f2v byz;
@@ -172,7 +195,16 @@ __global__ __launch_bounds__(1024, 8) void warp_lean_kernel(FsgDeformK D, const 
     P.lab = 0;
     if (HAS_NN) {
       const int xi = (int)rintf(x), yi = (int)rintf(yz.x), zi = (int)rintf(yz.y);  // round half to even; in range by construction
-      const unsigned e = (unsigned)(__mul24(xi, sxs) + (__mul24(yi, sy) + (zi + base)));
+      unsigned e = (unsigned)(__mul24(xi, sxs) + (__mul24(yi, sy) + (zi + base)));
+      if constexpr (HAS_MAP) {
+        // the source voxel's brick (x through the flip); the index is in range by construction, the min keeps the read in the table
+        const int xs = __mul24(xi, xflip) + xbase;
+        const unsigned bi = (unsigned)(__mul24(xs >> 3, M.b12) + (__mul24(yi >> 3, M.b2) + (zi >> 3)));
+        const unsigned b = smap[min(bi, (unsigned)(M.nb - 1))];
+        const bool mixed = b == 255u;
+        e = mixed ? e : 0x80000000u;  // past the descriptor's range (fewer than 2^30 voxels): reads 0 without an access
+        P.fill = (uint8_t)(mixed ? 0u : b);
+      }
       if (ABL != 1) P.lab = lean_load_label<ST>(r_nn, e);
       else if (mem) P.lab = lean_load_label<ST>(r_nn, e);
       else P.lab = (ST)(e & 7u);
@@ -252,6 +284,7 @@ __global__ __launch_bounds__(1024, 8) void warp_lean_kernel(FsgDeformK D, const 
         __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), r_olin, oelem * 4u, 0, 0);
       if (HAS_IMG && FAST) blend_img();
     }
+    if constexpr (HAS_MAP) P.lab = (ST)(P.lab | P.fill);  // a dropped gather read 0
     if (HAS_NN && live && (ABL != 1 || P.bx == 1.2345e30f)) lean_store_label(r_onn, oelem, (DT)P.lab);
   };
 
@@ -308,7 +341,8 @@ __global__ __launch_bounds__(1024, 8) void warp_lean_kernel(FsgDeformK D, const 
 
 template <typename ST, typename DT>
 int launch_lean(const FsgDeformK& D, const EpiK& E, const int32_t* mm6, const float* src_lin, float* out_lin,
-                const ST* src_nn, DT* out_nn, bool fast, hipStream_t st, const float* src_img = nullptr, float* out_img = nullptr) {
+                const ST* src_nn, DT* out_nn, bool fast, hipStream_t st, const float* src_img = nullptr, float* out_img = nullptr,
+                const LeanMap<true>* map = nullptr) {
   constexpr int KZ = 32, WI = 8;
   constexpr int PI = WI, PJ = (16 / WI) * (64 / KZ);
   const dim3 grid((unsigned)(((D.n0 + PI - 1) / PI) * ((D.n1 + PJ - 1) / PJ))), block(1024);
@@ -323,24 +357,33 @@ int launch_lean(const FsgDeformK& D, const EpiK& E, const int32_t* mm6, const fl
   const int pace = g_lean_pace >= 0 ? g_lean_pace : (src_img && slope < 0.27f ? 2 : 1);
 #define FSG_LEAN(L, N, F) \
   hipLaunchKernelGGL((warp_lean_kernel<ST, DT, L, N, F, KZ, WI>), grid, block, 0, st, D, mm6, src_lin, out_lin, src_nn, out_nn, E, \
-                     pace, LeanImg<false>{})
+                     pace, LeanImg<false>{}, LeanMap<false>{})
 #ifdef FSG_DIAG  // ablation instantiations (results are wrong; tools/kernel_bench.py --variant 8 / 9 on a -DFSG_DIAG build)
   if (src_lin && src_nn && fast && g_lean_ablate && sizeof(ST) == 4 && sizeof(DT) == 4) {
     if (g_lean_ablate == 1)
       hipLaunchKernelGGL((warp_lean_kernel<ST, DT, true, true, true, KZ, WI, 1>), grid, block, 0, st, D, mm6, src_lin, out_lin,
-                         src_nn, out_nn, E, pace, LeanImg<false>{});
+                         src_nn, out_nn, E, pace, LeanImg<false>{}, LeanMap<false>{});
     else
       hipLaunchKernelGGL((warp_lean_kernel<ST, DT, true, true, true, KZ, WI, 2>), grid, block, 0, st, D, mm6, src_lin, out_lin,
-                         src_nn, out_nn, E, pace, LeanImg<false>{});
+                         src_nn, out_nn, E, pace, LeanImg<false>{}, LeanMap<false>{});
     FSG_RETURN_LAUNCH();
   }
 #endif
 #define FSG_LEAN_IMG(N, F) \
   hipLaunchKernelGGL((warp_lean_kernel<ST, DT, true, N, F, KZ, WI, 0, true>), grid, block, 0, st, D, mm6, src_lin, out_lin, src_nn, \
-                     out_nn, E, pace, LeanImg<true>{src_img, out_img})
+                     out_nn, E, pace, LeanImg<true>{src_img, out_img}, LeanMap<false>{})
   if (src_img) {  // the dual-source family (checked by the entry point: src_lin given, out_img given)
     if (src_nn) { if (fast) FSG_LEAN_IMG(true, true); else FSG_LEAN_IMG(true, false); }
     else        { if (fast) FSG_LEAN_IMG(false, true); else FSG_LEAN_IMG(false, false); }
+  }
+  else if (map) {  // uint8 labels whose brick table is registered (decided by the entry point)
+    if constexpr (sizeof(ST) == 1) {
+#define FSG_LEAN_MAP(L, N, F) \
+  hipLaunchKernelGGL((warp_lean_kernel<ST, DT, L, true, F, KZ, WI, 0, false, true>), grid, block, 0, st, D, mm6, src_lin, out_lin, src_nn, \
+                     out_nn, E, pace, LeanImg<false>{}, *map)
+      FSG_WARP_LADDER(FSG_LEAN_MAP, src_lin, true, fast);
+#undef FSG_LEAN_MAP
+    }
   }
   else FSG_WARP_LADDER(FSG_LEAN, src_lin, src_nn, fast);
 #undef FSG_LEAN_IMG
@@ -365,10 +408,21 @@ int fsg_launch_warp_lean(const FsgDeformK& D, const EpiK& E, const int32_t* mm6,
   if (!src_nn) return launch_lean<float, float>(D, E, mm6, src_lin, out_lin, nullptr, nullptr, fast, st, src_img, out_img);
   if (label_in_bytes == 4 && label_out_bytes == 4)
     return launch_lean<float, float>(D, E, mm6, src_lin, out_lin, (const float*)src_nn, (float*)out_nn, fast, st, src_img, out_img);
+  // uint8 labels, one source: the brick table registered for this very volume and shape, if there is one (fsg_label_bricks_attach)
+  LeanMap<true> map{nullptr, 0, 0, 0};
+  if (label_in_bytes == 1 && !src_img && !(g_tuning_flags & FSG_TUNE_NO_LABEL_BRICKS)) {
+    map.map = fsg_label_bricks_find(src_nn, D.n0, D.n1, D.n2);
+    const int b1 = (D.n1 + 7) >> 3;
+    map.b2 = (D.n2 + 7) >> 3;
+    map.b12 = b1 * map.b2;
+    map.nb = ((D.n0 + 7) >> 3) * map.b12;
+  }
+  const LeanMap<true>* mp = map.map ? &map : nullptr;
   if (label_in_bytes == 1 && label_out_bytes == 1)
     return launch_lean<uint8_t, uint8_t>(D, E, mm6, src_lin, out_lin, (const uint8_t*)src_nn, (uint8_t*)out_nn, fast, st, src_img,
-                                         out_img);
+                                         out_img, mp);
   if (label_in_bytes == 1 && label_out_bytes == 4)
-    return launch_lean<uint8_t, float>(D, E, mm6, src_lin, out_lin, (const uint8_t*)src_nn, (float*)out_nn, fast, st, src_img, out_img);
+    return launch_lean<uint8_t, float>(D, E, mm6, src_lin, out_lin, (const uint8_t*)src_nn, (float*)out_nn, fast, st, src_img, out_img,
+                                       mp);
   return FSG_E_BADARG;
 }

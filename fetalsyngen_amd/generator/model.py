@@ -19,6 +19,7 @@ from __future__ import annotations
 
 import contextlib
 import ctypes as C
+import weakref
 from typing import Iterable
 
 import numpy as np
@@ -45,6 +46,40 @@ _MM_SLOTS_INIT = np.zeros((MM_NSLOTS, _lib.MM_SLOT_STRIDE), dtype=np.int32)
 _MM_SLOTS_INIT[:, 0], _MM_SLOTS_INIT[:, 1] = 0x7F800000, -2139095041
 _MM_SLOTS_INIT.setflags(write=False)
 _SEEN_ONCE, _NO_TWIN = object(), object()  # what `_twins` holds for a label volume that has no uint8 twin
+
+
+def _label_bricks_bytes(vol):
+    """Bytes of the brick table of the device label volume `vol` (one per 8x8x8 brick), 0 where the warp could not use one."""
+    shape = vol.shape
+    if vol.device.type != "cuda" or len(shape) != 3 or not _lib.load().fsg_label_bricks_usable(*[int(n) for n in shape]):
+        return 0
+    return ((shape[0] + 7) // 8) * ((shape[1] + 7) // 8) * ((shape[2] + 7) // 8)
+
+
+def _detach_label_bricks(ptr):
+    _lib.load().fsg_label_bricks_detach(ptr)
+
+
+def _attach_label_bricks(twin):
+    """Build the brick table of the uint8 label volume `twin` (csrc/fsg_label_bricks.hip: which 8x8x8 bricks hold one label)
+    and attach it, so that the fused warp drops the label gathers of those bricks.  The table lives as long as the twin (it
+    hangs on the tensor object) and is detached when the twin dies -- eviction, `invalidate_label_twins`, a new `_version`
+    and the death of the caller's volume all end there, before the memory can be reused.  Returns the table's bytes."""
+    nbytes = _label_bricks_bytes(twin) if twin.is_contiguous() else 0
+    if nbytes == 0:
+        return 0
+    lib = _lib.load()
+    table = torch.empty(nbytes, dtype=torch.uint8, device=twin.device)
+    stream = torch.cuda.current_stream(twin.device)
+    _lib.check(lib.fsg_label_bricks_u8(twin.data_ptr(), *[int(n) for n in twin.shape], table.data_ptr(), stream.cuda_stream),
+               "fsg_label_bricks_u8")
+    stream.synchronize()  # once per subject: the table is complete before a sample on any stream reads it
+    if lib.fsg_label_bricks_attach(twin.data_ptr(), *[int(n) for n in twin.shape], table.data_ptr()) != 0:
+        return 0  # registry full: this volume's labels are gathered as before
+    if getattr(twin, "_fsg_bricks", None) is None:
+        weakref.finalize(twin, _detach_label_bricks, twin.data_ptr())
+    twin._fsg_bricks = table
+    return nbytes
 
 
 class _Ctx:
@@ -223,7 +258,7 @@ class FetalSynthGen:
             raise ValueError("label twin must be a uint8 tensor of the segmentation's shape on its device")
         twins = self._cache("_twins")
         twins.drop(seg)
-        twins.put(seg, twin, twin.numel(), seg._version)
+        twins.put(seg, twin, twin.numel() + _attach_label_bricks(twin), seg._version)
 
     def invalidate_label_twins(self):
         """Forget every cached uint8 label twin.  The cache notices a new tensor object and an in-place torch write
@@ -248,8 +283,9 @@ class FetalSynthGen:
         if twin is _SEEN_ONCE:  # second sighting: check and convert (synchronises once per volume)
             twin, nbytes = _NO_TWIN, 0
             ok = bool(torch.equal(seg.round(), seg)) and float(seg.min()) >= 0 and float(seg.max()) <= 255
-            if ok and twins.make_room(seg.numel(), self.label_twin_budget_bytes):
-                twin, nbytes = seg.to(torch.uint8), seg.numel()
+            if ok and twins.make_room(seg.numel() + _label_bricks_bytes(seg), self.label_twin_budget_bytes):
+                twin = seg.to(torch.uint8)
+                nbytes = seg.numel() + _attach_label_bricks(twin)
             twins.put(seg, twin, nbytes, seg._version)  # (in the place of its first sighting)
         return None if twin is _NO_TWIN else twin
 

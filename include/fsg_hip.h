@@ -101,8 +101,30 @@ const char* fsg_error_string(int code);
 #define FSG_TUNE_NO_BLUR_RS 16384 /* fsg_sample_run: blur x3 + K7 as separate launches instead of the fused blur+resample pair */
 #define FSG_TUNE_NO_FLOORMIN_SKIP 524288 /* A/B: fsg_keyed_sample_run launches the conditional floor(min) pass even when the host has
                                           * proved it a no-op (same keys, same volumes) */
+#define FSG_TUNE_NO_LABEL_BRICKS 1048576 /* A/B: the fused warp gathers every label even where a brick table is attached
+                                          * (fsg_label_bricks_attach); same outputs bit for bit */
 /* Bits 16, 64 and 32768 are retired (kernel variants measured slower and removed): ignored by fsg_set_tuning, never reuse them. */
 int fsg_set_tuning(int flags);
+
+/* ---- brick table of a uint8 label volume (what lets the fused warp skip label gathers) -------- */
+/* One uint8 per 8x8x8 brick of the (n0,n1,n2) volume, partial bricks at the upper faces included, layout
+ * [ceil(n0/8)][ceil(n1/8)][ceil(n2/8)]: the brick's label if all of its voxels are equal and that label is not 255,
+ * else 255 ("mixed: gather"; a uniform brick of label 255 is mixed too, which stays correct).  Once per subject. */
+#define FSG_LABEL_BRICKS_CAP 32768 /* bricks of the largest volume whose table the warp can use (256^3 has exactly as many) */
+int fsg_label_bricks_u8(const uint8_t* labels_u8, int n0, int n1, int n2, uint8_t* map_out, void* stream);
+/* Process-wide registry (a few entries, guarded by a mutex): the table `map` (DEVICE, 16-byte aligned, written by
+ * fsg_label_bricks_u8) describes the (n0,n1,n2) uint8 volume at `labels_u8`.  The fused warp looks its label source up here
+ * and uses the table when the registered shape equals the launch's and fsg_label_bricks_usable holds; the caller keeps
+ * volume and table unchanged and alive until it detaches.  attach: 0, replacing an entry of the same volume; FSG_E_BADARG /
+ * FSG_E_ALIGN on bad arguments; FSG_E_TOOBIG when the registry is full (the volume is then simply gathered).  detach: 1 if
+ * there was an entry, else 0.  count: entries.  usable: 1 if a table of that shape is within the cap, else 0. */
+int fsg_label_bricks_attach(const void* labels_u8, int n0, int n1, int n2, const void* map);
+int fsg_label_bricks_detach(const void* labels_u8);
+int fsg_label_bricks_count(void);
+int fsg_label_bricks_usable(int n0, int n1, int n2);
+/* Test hook: the cap fsg_label_bricks_usable applies, 1..FSG_LABEL_BRICKS_CAP (0 = back to FSG_LABEL_BRICKS_CAP).  Returns the
+ * previous cap, or FSG_E_BADARG (setting unchanged). */
+int fsg_label_bricks_set_cap(int cap);
 /* Lockstep pacing of the lean warp kernel (speed only, results identical): 0 = chosen per launch, 5 = no barrier,
  * 6 = a barrier every second step, 7 = a barrier every step.  Returns the previous value, or FSG_E_BADARG (setting
  * unchanged) for any other value. */
