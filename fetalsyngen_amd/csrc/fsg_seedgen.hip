@@ -312,8 +312,11 @@ __global__ __launch_bounds__(SG_THREADS) void em_finalize_kernel(EmView V, int m
   if (threadIdx.x < k) {
     const int c = threadIdx.x;
     const double S0 = tot[c], S1 = tot[EM_KMAX + c], S2 = tot[2 * EM_KMAX + c];
-    const double nk = S0 + 10.0 * 2.220446049250313e-16;
-    const double dlt = S1 / nk;
+    const double eps10 = 10.0 * 2.220446049250313e-16;
+    const double nk = S0 + eps10;
+    // new mean - previous mean.  sum r x / nk with nk = S0 + 10 eps is (S1 + mu_prev S0) / nk = mu_prev + (S1 - mu_prev 10 eps) / nk:
+    // the second term is invisible for a live component and takes an empty one (S0 = 0) to mean 0, as sklearn's M-step does
+    const double dlt = (S1 - P[EM_KMAX + c] * eps10) / nk;
     const double mu = P[EM_KMAX + c] + dlt;
     // sum r (x - mu_new)^2 from the sums taken about the previous mean
     const double ss = fmax((S2 - 2.0 * dlt * S1) + dlt * dlt * S0, 0.0);

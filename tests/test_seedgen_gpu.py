@@ -118,7 +118,9 @@ def test_em_fixed_initialisation_fixed_iterations(sg, fx, iters):
         e = dict(mean=relerr(got["means"], ref["means"]), weight=relerr(got["weights"], ref["weights"]),
                  var=relerr(got["variances"], ref["variances"]))
         print(f"{name} iters={iters}: rel err means {e['mean']:.2e} weights {e['weight']:.2e} variances {e['var']:.2e} "
-              f"|lb diff| {abs(got['lower_bound'] - ref['lower_bound']):.2e}")
+              f"|lb diff| {abs(got['lower_bound'] - ref['lower_bound']):.2e} (bound {E.lb_bound(ref['lse_absmax']):.2e})")
+        # every sample's mx + logf(sum) is a float32 value built from float32 terms of at most max |lse|, averaged in float64
+        assert abs(got["lower_bound"] - ref["lower_bound"]) <= E.lb_bound(ref["lse_absmax"]), name
         for key in worst:
             worst[key] = max(worst[key], e[key])
         # labels of the product's own parameters through the assignment kernel vs the reference's labels
